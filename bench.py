@@ -6,7 +6,13 @@ One *step* = sample_blocks (3 layers) + feature gather + SAGE forward + backward
 Reddit-shaped synthetic graph, 3-layer SAGE, poisson-bandit sampler, fanouts 4096/2048/1024, batch 256.
 Synthetic data (no network): seeded Chung-Lu graph with Reddit's |V|, |E|, F, classes.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times K steps and prints the result line.  ``--full`` adds what else the benchmark measures
+after the timed steps: the ``roofline`` object (the same steps launched kernel by kernel, HIP events around the library
+kernels) and, on one GPU, the ``cpu_baseline`` (the oracle port of the step on the host).  ``--dump-outputs DIR`` writes what
+the timed path computed in its last step as DIR/<name>.npy (see ``write_outputs``); the inputs are seeded, so two builds can
+be compared array for array.
 
 N > 1: either launched under torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE in the environment, as the driver
 does), or started plainly -- then this process starts N fresh ranks itself (a child ``python -m torch.distributed.run``,
@@ -38,8 +44,13 @@ def parse():
     ap.add_argument("--sampler", default="poisson-bandit", choices=["poisson-bandit", "poisson-ladies"],
                     help="train_lightning.py:536-540; poisson-ladies = the static-weight baseline sampler (no EXP3 update)")
     ap.add_argument("--model", default="sage", choices=["sage", "gat"], help="gat = SURVEY config 4 (GATv2, heads 4/4/1, hidden 256)")
-    ap.add_argument("--cpu-baseline-steps", type=int, default=-1, help="-1: auto (bounded sample), 0: skip")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the roofline object and (one GPU) the CPU baseline; a plain run does neither")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step (loss, parameters, a fixed sample of the EXP3 rows, "
+                         "block sizes; inference: a fixed sample of the output rows) as DIR/<name>.npy, float32 / float64, <= 64 MB")
+    ap.add_argument("--cpu-baseline-steps", type=int, default=-1, help="with --full: -1: auto (bounded sample), 0: skip")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline object")
     ap.add_argument("--tune-gemm", type=int, default=1, help="1: TunableOp picks the library GEMM solutions during warm-up")
     ap.add_argument("--eager", action="store_true", help="launch kernel by kernel instead of replaying the step's HIP graph")
     ap.add_argument("--no-pipeline", action="store_true", help="one step per graph, sampling not overlapped with the backward pass")
@@ -53,10 +64,13 @@ def parse():
                          "the single-GPU step for --gpus 1.  With one GPU, shards = a world of one rank")
     ap.add_argument("--mode", default="train", choices=["train", "inference"],
                     help="inference: time SAGE.inference -- layer-wise full-neighbour evaluation of ALL nodes (model.py:335-383), the one "
-                         "whole-graph SpMM of the reference -- with its own roofline")
+                         "whole-graph SpMM of the reference -- with its own roofline (--full)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / rendezvous / reduction plumbing only (gloo, no GPU, no kernels): what a CPU-only box can check of --gpus N")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def relaunch_ranks(args):
@@ -113,6 +127,80 @@ def algorithmic_bytes(sizes, feat, dims):
     return dict(sampler=samp, gather=gather, spmm=spmm, bandit=bandit, total=samp + gather + spmm + bandit)
 
 
+def chung_lu_graph(num_nodes, num_edges, seed, device, sigma=1.0, chunk=1 << 26):
+    """bliss_gnn_amd.synth.chung_lu_csc's graph model (lognormal expected degrees, loops dropped, duplicates merged, one self
+    loop per node added last), drawn so that the same seed gives the same graph in every run: torch.multinomial on the GPU
+    goes through a float prefix sum whose rounding changes from run to run (torch lists CUDA cumsum among its nondeterministic
+    ops), and a few of the ~114 M Reddit-like edges came out differently each time.  Here the cumulative weights are summed once
+    on the host in float64 and seeded uniforms are inverted on the device; prepare_graph (csrc/prep.hip) builds the CSC with
+    chung_lu_csc's numbering (edge ids dst-major, the self loops last).  Returns (indptr, indices, eid)."""
+    from bliss_gnn_amd.prep import prepare_graph
+    gen = torch.Generator(device=device)
+    gen.manual_seed(seed)
+    V = int(num_nodes)
+    w = torch.exp(sigma * torch.randn(V, generator=gen, device=device, dtype=torch.float32)).double().cpu()
+    cdf = torch.cumsum(w, 0)
+    cdf = (cdf / cdf[-1]).to(device)
+    keys, left = [], int(num_edges)
+    while left > 0:
+        n = min(left, chunk)
+        dst, src = (torch.searchsorted(cdf, torch.rand(n, generator=gen, device=device, dtype=torch.float64), right=True).clamp_(max=V - 1)
+                    for _ in range(2))
+        m = src != dst
+        keys.append(dst[m] * V + src[m])
+        left -= n
+    key = torch.unique(torch.cat(keys))            # sorted: dst-major, src ascending, no duplicates
+    del keys
+    dst = torch.div(key, V, rounding_mode="floor")
+    g = prepare_graph(key - dst * V, dst, V)
+    return g.indptr, g.indices, g.eid
+
+
+DUMP_LIMIT = 64 << 20                      # bytes, all arrays of one --dump-outputs together
+
+
+def fixed_sample(n, k, device=None):
+    """Sorted distinct ids of a fixed, seeded sample of about ``k`` of ``range(n)`` (all of them when n <= k): the same ids in
+    every run with the same n."""
+    if n <= k:
+        return torch.arange(n, device=device)
+    draw = torch.randint(0, n, (k,), generator=torch.Generator().manual_seed(12345))
+    return torch.unique(draw).to(device)
+
+
+def write_outputs(path, arrays):
+    """--dump-outputs: each array as ``path/<name>.npy``, float64 where it is float64 or an integer (sizes, ids: exact), float32
+    otherwise (bf16 values are exact in float32).  More than DUMP_LIMIT bytes in all is an error, not a silent cut."""
+    import numpy as np
+    out = {}
+    for name, a in arrays.items():
+        t = torch.as_tensor(a).detach()
+        wide = t.dtype == torch.float64 or not (t.is_floating_point() or t.is_complex())
+        out[name] = t.to(torch.float64 if wide else torch.float32).cpu().numpy()
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (limit %d)" % (total, DUMP_LIMIT))
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def model_outputs(model, loss, sizes=None, sampler=None):
+    """What a caller of the train step holds after its last step: the loss, every parameter, the sampled block sizes (per
+    layer S, E, C, K, B) and, for the bandit samplers, the EXP3 rows at a fixed sample of edge ids."""
+    arrays = {"loss": torch.as_tensor(loss, dtype=torch.float32).reshape(1)}
+    for name, p in model.named_parameters():
+        arrays["param." + name] = p
+    if sizes:
+        arrays["block_sizes"] = torch.tensor([[s_.get(k, 0) for k in "SECKB"] for s_ in sizes], dtype=torch.float64)
+    w = getattr(sampler, "exp3_weights", None) if sampler is not None else None
+    if w is not None:
+        ids = fixed_sample(w.shape[1], 1 << 20, w.device)
+        arrays["exp3_weights_sample"] = w[:, ids]
+        arrays["exp3_sample_edge_ids"] = ids
+    return arrays
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -142,13 +230,13 @@ def main():
 
     import bliss_gnn_amd as bg
     from bliss_gnn_amd.model import SAGE
-    from bliss_gnn_amd.synth import CONFIGS, chung_lu_csc, node_data
+    from bliss_gnn_amd.synth import CONFIGS, node_data
     from bliss_gnn_amd.train import BatchLoader, GraphedTrainStep, PipelinedTrainStep, TrainStep
     from bliss_gnn_amd import dist as bdist
 
     cfg = CONFIGS[args.config]
     t0 = time.time()
-    ip, ix, ei = chung_lu_csc(cfg["num_nodes"], cfg["num_edges"], seed=0, device=dev)
+    ip, ix, ei = chung_lu_graph(cfg["num_nodes"], cfg["num_edges"], seed=0, device=dev)
     feats, labels, train_nid = node_data(cfg["num_nodes"], cfg["feat"], cfg["classes"], cfg["n_train"], seed=1, device=dev,
                                          multilabel=cfg["multilabel"], features=cfg.get("features", "normal"), nnz=cfg.get("nnz", 18))
     g = bg.Graph(ip, ix, ei, ndata={"features": feats, "labels": labels})
@@ -215,6 +303,7 @@ def main():
     if not graphed:
         step = TrainStep(g, sampler, model, lr=0.002, multilabel=cfg["multilabel"], grad_sync=grad_sync, exp3_sync=exp3_sync)
     pipelined = isinstance(step, PipelinedTrainStep)
+    last = {}                                                # the loss of the last step trained (for --dump-outputs)
 
     def advance(n, eager=False, pair_events=None):
         """Run exactly n train steps; returns the per-step block sizes (one list per sampled batch)."""
@@ -222,23 +311,24 @@ def main():
         while n > 0:
             if pipelined and n >= 2 and not eager:
                 got = step.run(loader, n // 2, pair_events=pair_events)
+                last["loss"] = step.losses[-1]
                 sizes += got
                 n -= max(len(got), n // 2 * 2)              # (a capacity regrow inside run() trains three batches more)
             elif pipelined and n >= 2:
-                step.eager_pair(loader)
+                last["loss"] = step.eager_pair(loader)[-1]
                 sizes += step.sizes2()
                 n -= 2
             elif pipelined:                          # an odd step: train the batch in flight, sample the next one
-                step.drain()
+                last["loss"] = step.drain()
                 step.prime(next(loader))
                 sizes.append(step.sizes())
                 n -= 1
             elif graphed:
-                (step.eager_step if eager else step)(next(loader))
+                last["loss"] = (step.eager_step if eager else step)(next(loader))
                 sizes.append(step.sizes())
                 n -= 1
             else:
-                step(next(loader))
+                last["loss"] = step(next(loader))
                 sizes.append([dict(S=b._counts.S, E=b._counts.E, C=b._counts.C, K=b._counts.K, B=b._counts.B) for b in step.last["mfgs"]])
                 n -= 1
         return sizes
@@ -282,10 +372,12 @@ def main():
         tmax = t.clone(); dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         tsum = t.clone(); dist.all_reduce(tsum, op=dist.ReduceOp.SUM)
         dt, n_edges, n_frontier = float(tmax[0]), float(tsum[1]), float(tsum[2])
+    if args.dump_outputs and rank == 0:                  # (before --full trains further steps)
+        write_outputs(args.dump_outputs, model_outputs(model, last["loss"], all_sizes[-1], sampler))
 
-    # ---- roofline: the same steps launched kernel by kernel, HIP events around the library kernels ----------------
+    # ---- roofline (--full): the same steps launched kernel by kernel, HIP events around the library kernels --------
     dominant, calib, dom_timing, alg_dom = None, {}, None, 0.0
-    if rank == 0 and world == 1 and not args.no_roofline:
+    if rank == 0 and world == 1 and args.full and not args.no_roofline:
         torch.cuda.synchronize()
         timer.enable("all")
         calib_sizes = advance(6, eager=True)
@@ -381,7 +473,7 @@ def main():
                                                "algorithmic_bytes_per_launch": round(v["alg_bytes_per_launch"]),
                                                "achieved_GBps": round(v["GBps"], 1), "frac": round(v["GBps"] / roofline.HBM_PEAK_GBPS, 5)}
                                            for k, v in sorted(hbm_kernels.items(), key=lambda kv: -kv[1]["total_ms"])}}
-    if rank == 0 and world == 1 and args.cpu_baseline_steps != 0:
+    if rank == 0 and world == 1 and args.full and args.cpu_baseline_steps != 0:
         out["cpu_baseline"] = cpu_baseline(g, feats, labels, train_nid, cfg, fan, eta, hidden, args.cpu_baseline_steps)
     if rank == 0:
         print(json.dumps(out), flush=True)
@@ -414,6 +506,7 @@ def bench_shards(args, ip, ix, ei, feats, labels, train_nid, cfg, hidden, dev, r
     loader = BatchLoader(mine, cfg["batch"], shuffle=True, drop_last=True, seed=2 + rank).forever()
     static = not args.eager
     edges_dev = torch.zeros(1, dtype=torch.int64, device=dev)
+    last = {}                                                      # the loss of the last step (for --dump-outputs)
     if static:
         caps = None
         if os.environ.get("BLISS_SHARD_CALIBRATE", "1") != "0":     # capacities from observed sizes (a throw-away model / EXP3 state)
@@ -439,7 +532,7 @@ def bench_shards(args, ip, ix, ei, feats, labels, train_nid, cfg, hidden, dev, r
             step.prime(next(loader))
 
         def one():
-            step(next(loader))
+            last["loss"] = step(next(loader))
             cnt = sampler._slot_bufs(step.slot if pipelined else 0)["counts"]
             if pipelined and step.graph is not None and (step.use_third or step.late_block):
                 # (the blocks just sampled are finished on another stream: the third one, or the backward stream for the last block)
@@ -453,7 +546,7 @@ def bench_shards(args, ip, ix, ei, feats, labels, train_nid, cfg, hidden, dev, r
         launch = "eager, routed exchanges (one host sync per exchange)"
 
         def one():
-            step(next(loader))
+            last["loss"] = step(next(loader))
             edges_dev.add_(sum(b.num_edges() for b in step.last["mfgs"]))
     for _ in range(args.warmup):
         one()
@@ -496,17 +589,20 @@ def bench_shards(args, ip, ix, ei, feats, labels, train_nid, cfg, hidden, dev, r
         tmax = t.clone(); dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         tsum = t.clone(); dist.all_reduce(tsum, op=dist.ReduceOp.SUM)
         dt, edges = float(tmax[0]), float(tsum[1])
+    sizes = None
     if static:
-        step.finish()                                              # (error words, capacity overflows, flag time-outs: a bad run raises here)
+        _, sizes = step.finish()                                   # (error words, capacity overflows, flag time-outs: a bad run raises here)
     else:
         sampler.check_errors()
+    if args.dump_outputs and rank == 0:                            # (before --full trains further steps)
+        write_outputs(args.dump_outputs, model_outputs(model, last["loss"], sizes))
     roof = None
-    if static and rank == 0 and not args.no_roofline:
+    if static and rank == 0 and args.full and not args.no_roofline:
         # the dominant library kernel of the sampler, timed with HIP events over a few steps launched kernel by kernel
         # (every rank must take part in the steps: the others run them too, below)
         timer = roofline.KernelTimer()
         timer.enable("k_bin_scatter")
-    n_roof = 0 if (not static or args.no_roofline) else 6
+    n_roof = 0 if (not static or args.no_roofline or not args.full) else 6
     if n_roof:
         saved, step.graph = step.graph, None
         alg = 0.0
@@ -562,19 +658,24 @@ def bench_inference(args, g, cfg, hidden, dev, t_setup):
     for _ in range(max(1, min(args.warmup, 2))):
         model.inference(g)
     torch.cuda.synchronize()
-    n = max(1, min(args.steps, 10))
+    n = args.steps
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(n + 1)]
     ev[0].record()
     for i in range(n):
-        model.inference(g)
+        h = model.inference(g)
         ev[i + 1].record()
     torch.cuda.synchronize()
     ms = [a.elapsed_time(b) for a, b in zip(ev[:-1], ev[1:])]
-    timer.enable("k_spmm_fwd")
-    model.inference(g)
-    torch.cuda.synchronize()
-    spmm = timer.read().get("k_spmm_fwd")
-    timer.enable("off")
+    if args.dump_outputs:                         # the output rows of the last pass at a fixed sample of node ids
+        rows = fixed_sample(V, max(1, (16 << 20) // (4 * h.shape[1])), h.device)
+        write_outputs(args.dump_outputs, {"inference_rows_sample": h[rows], "inference_sample_node_ids": rows})
+    spmm = None
+    if args.full and not args.no_roofline:        # one more pass, HIP events around the SpMM launches
+        timer.enable("k_spmm_fwd")
+        model.inference(g)
+        torch.cuda.synchronize()
+        spmm = timer.read().get("k_spmm_fwd")
+        timer.enable("off")
     dims = [hidden, hidden, cfg["classes"]]                       # SpMM widths (in > out: the Linear runs first), SURVEY.md m2
     # algorithmic HBM bytes of the aggregation per layer: CSC pointers + indices once, the feature rows in, the result out
     layer_bytes = [4 * (V + 1) + 4 * E + 2 * V * d * 2 for d in dims]
@@ -649,6 +750,10 @@ def cpu_baseline(g, feats, labels, train_nid, cfg, fan, eta, hidden, n_steps, bu
     except AttributeError:
         avail = logical
     threads = max(1, min(phys, avail))
+    try:                                                         # (a host shared with other jobs says how many CPUs are ours)
+        threads = min(threads, max(1, int(os.environ["OMP_NUM_THREADS"])))
+    except (KeyError, ValueError):
+        pass
     torch.set_num_threads(threads)
     og = bo.CSC(g.indptr.cpu(), g.indices.cpu(), g.eid.cpu())
     ref = RefTrainStep(og, feats.cpu(), labels.cpu(), fan, eta, cfg["feat"], hidden, cfg["classes"], multilabel=cfg["multilabel"])

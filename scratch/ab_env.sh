@@ -3,7 +3,7 @@
 K=$1; shift
 for round in 1 2; do for e in "$@"; do
   [ "$e" = "-" ] && ee="" || ee="$e"
-  env $ee timeout -k 10 300 python bench.py --steps 400 --warmup 40 --cpu-baseline-steps 0 2>/dev/null | python -c "
+  env $ee timeout -k 10 300 python bench.py --full --steps 400 --warmup 40 --cpu-baseline-steps 0 2>/dev/null | python -c "
 import sys,json
 o=json.loads(sys.stdin.read().strip().splitlines()[-1])
 ak=o['roofline'].get('all_kernels',{})

@@ -4,7 +4,7 @@ K=$1; shift
 cp bliss_gnn_amd/libbliss_gnn.so /tmp/base.so
 for round in 1 2; do for lib in "$@"; do
   if [ "$lib" = base ]; then cp /tmp/base.so bliss_gnn_amd/libbliss_gnn.so; else cp $lib bliss_gnn_amd/libbliss_gnn.so; fi
-  timeout -k 10 300 python bench.py --steps 400 --warmup 40 --cpu-baseline-steps 0 2>/dev/null | python -c "
+  timeout -k 10 300 python bench.py --full --steps 400 --warmup 40 --cpu-baseline-steps 0 2>/dev/null | python -c "
 import sys,json
 o=json.loads(sys.stdin.read().strip().splitlines()[-1])
 ak=o['roofline'].get('all_kernels',{})

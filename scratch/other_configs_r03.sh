@@ -4,7 +4,7 @@
 T=$1; O=gpurun_out/$T; mkdir -p $O
 one() {
   name=$1; shift
-  timeout -k 10 400 python bench.py --cpu-baseline-steps 0 "$@" > $O/bench_$name.json 2> $O/bench_$name.err || { echo "FAILED: $name"; tail -3 $O/bench_$name.err; return; }
+  timeout -k 10 400 python bench.py --full --cpu-baseline-steps 0 "$@" > $O/bench_$name.json 2> $O/bench_$name.err || { echo "FAILED: $name"; tail -3 $O/bench_$name.err; return; }
   python -c "
 import json
 o=json.loads(open('$O/bench_$name.json').read().strip().splitlines()[-1])

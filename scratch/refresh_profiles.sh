@@ -3,8 +3,8 @@
 set -o pipefail
 T=$1; O=gpurun_out/$T; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-echo "[1] bench default"; timeout -k 10 500 python bench.py > $O/bench_default.json 2> $O/bench_default.err || exit 1
-echo "[1b] bench inference"; timeout -k 10 300 python bench.py --mode inference --steps 5 --warmup 1 > $O/bench_inference.json 2> $O/bench_inference.err || exit 1
+echo "[1] bench default"; timeout -k 10 500 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err || exit 1
+echo "[1b] bench inference"; timeout -k 10 300 python bench.py --full --mode inference --steps 5 --warmup 1 > $O/bench_inference.json 2> $O/bench_inference.err || exit 1
 echo "[1c] bench force-dist"; timeout -k 10 300 python bench.py --steps 200 --warmup 40 --cpu-baseline-steps 0 --no-roofline --force-dist > $O/bench_force_dist.json 2> $O/bench_force_dist.err || exit 1
 echo "[2] kernel stats"; timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 bench.py --steps 100 --warmup 20 --cpu-baseline-steps 0 --tune-gemm 0 --no-roofline > $O/bench_under_rocprof.json 2> $O/rocprof.err || exit 1
 python scratch/timeline3.py $O/prof > $O/step_timeline.txt 2>&1
