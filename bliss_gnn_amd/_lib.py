@@ -46,7 +46,7 @@ class LayerWs(C.Structure):
                 ("n_bins", C.c_int32), ("bin_cap", C.c_int64), ("bin_cursor", C.c_void_p), ("bin_rec", C.c_void_p),
                 ("bitmap", C.c_void_p), ("word_prefix", C.c_void_p), ("touched_key", C.c_void_p), ("touched_sum", C.c_void_p),
                 ("span_seg", C.c_void_p), ("kept_rec", C.c_void_p), ("span_cnt", C.c_void_p), ("kept_rec_positions", C.c_int64),
-                ("kept_map", C.c_void_p), ("entry_flag", C.c_void_p), ("w_pend", C.c_void_p),
+                ("kept_map", C.c_void_p), ("entry_flag", C.c_void_p),
                 ("fs_ticket", C.c_void_p), ("fs_fanout", C.c_int32), ("fs_is_last", C.c_int32), ("fs_rng_cap", C.c_int32),
                 ("fs_reserved", C.c_int32), ("fs_eps", C.c_double), ("fs_rng_ctl", C.c_void_p), ("fs_layer_off", C.c_void_p),
                 ("block_ready_flag", C.c_void_p)]
@@ -56,8 +56,7 @@ class Exp3Block(C.Structure):
     _fields_ = [("w_pos", C.c_void_p), ("row_sum", C.c_void_p), ("scratch", C.c_void_p), ("norm_out", C.c_void_p),
                 ("blk_indptr", C.c_void_p), ("blk_src", C.c_void_p), ("blk_dst", C.c_void_p), ("blk_pos", C.c_void_p),
                 ("q_ij", C.c_void_p), ("node_prob", C.c_void_p), ("embed_norm", C.c_void_p), ("alpha_or_null", C.c_void_p),
-                ("dst_nid", C.c_void_p), ("n_edges_dev", C.c_void_p), ("rewards_out", C.c_void_p), ("edges_bound", C.c_int32),
-                ("norm_pend", C.c_void_p)]
+                ("dst_nid", C.c_void_p), ("n_edges_dev", C.c_void_p), ("rewards_out", C.c_void_p), ("edges_bound", C.c_int32)]
 
 
 EXP3_MAX_BLOCKS = 8
@@ -173,8 +172,6 @@ SIGNATURES = {
     "bliss_exp3_step": [C.POINTER(Graph), _P, C.POINTER(Exp3Block), _I32, _F, _P, _P],
     "bliss_exp3_normalize_global_rows": [C.POINTER(Exp3Block), _I32, _I64, _P, _I64, _P],
     "bliss_exp3_update_blocks": [C.POINTER(Graph), _P, C.POINTER(Exp3Block), _I32, _F, _P, _P],
-    "bliss_exp3_step_deferred": [C.POINTER(Graph), _P, C.POINTER(Exp3Block), _I32, _F, _P, _P, _P],
-    "bliss_exp3_normalize_pending": [C.POINTER(Exp3Block), _I32, _I64, _P],
     "bliss_exp3_apply": [_P, _P, _P, _P, _P, _I32, _P, _P],
     "bliss_exp3_normalize": [_P, _I64, _P, _P, _P, _P],
     "bliss_row_sum": [_P, _I64, _P, _P],

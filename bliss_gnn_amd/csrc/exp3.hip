@@ -164,16 +164,13 @@ struct Exp3Multi {
   bliss_exp3_block_t blk[BLISS_EXP3_MAX_BLOCKS];
   int grid_begin[BLISS_EXP3_MAX_BLOCKS + 1];
   int n;
-  int* done_flag;          // NORM_DECIDE: raised (bliss_flag_wait's protocol) once every row has been decided, or null
 };
 __global__ void __launch_bounds__(E3_TPB) k_exp3_update_multi(const int64_t* __restrict__ g_indptr, const bf16_t* __restrict__ edge_w,
                                                              const Exp3Multi m, float delta_f, int* err) {
   int b = 0;
   while (b + 1 < m.n && (int)blockIdx.x >= m.grid_begin[b + 1]) ++b;
   const bliss_exp3_block_t& k = m.blk[b];
-  int pend_unused;
-  bf16_t* w_row = norm_state_row((bf16_t*)k.w_pos, k.norm_pend, &pend_unused);        // (a pending pass has completed by now)
-  exp3_update_body(g_indptr, edge_w, w_row, k.row_sum, k.blk_indptr, k.blk_src, k.blk_dst, k.blk_pos, (const bf16_t*)k.q_ij,
+  exp3_update_body(g_indptr, edge_w, (bf16_t*)k.w_pos, k.row_sum, k.blk_indptr, k.blk_src, k.blk_dst, k.blk_pos, (const bf16_t*)k.q_ij,
                    (const bf16_t*)k.node_prob, (const bf16_t*)k.embed_norm, (const bf16_t*)k.alpha_or_null, k.dst_nid, k.n_edges_dev,
                    delta_f, (bf16_t*)k.rewards_out, nullptr, 1, err, (int)blockIdx.x - m.grid_begin[b], m.grid_begin[b + 1] - m.grid_begin[b],
                    k.edges_bound);
@@ -311,6 +308,10 @@ __global__ void __launch_bounds__(E3_TPB) k_row_sum(const bf16_t* __restrict__ w
 
 __global__ void k_zero_i64(int64_t* p, int n) { if ((int)threadIdx.x < n) p[threadIdx.x] = 0; }
 
+// F.normalize(row, p=1) element by element (bandit_sampler.py:249): x / max(norm, eps), rounded to bf16
+__device__ __forceinline__ float renorm_denom(bf16_t norm) { return rbf(fmaxf(bf2f(norm), 1e-12f)); }
+__device__ __forceinline__ bf16_t renorm_bf16(bf16_t x, float denom) { return f2bf(bf2f(x) / denom); }
+
 // F.normalize(row, p=1) in ONE launch.  scratch (int64[BLISS_NORM_SCRATCH], zero between calls): [0] = norm bits |
 // skip << 16 | err << 20 (for the host), [1] ticket, [2 ..] replicas of the renormalised row's exact sum.  Every workgroup
 // derives the norm from the (read-only) exact row sum; if it is 1.0 nothing is touched.  Otherwise the last workgroup to
@@ -332,44 +333,22 @@ __device__ __attribute__((noinline)) PairSlow renorm_pair_slow(uint32_t word, fl
   return r;
 }
 
-// mode NORM_NOW: decide and rewrite in this launch.  NORM_DECIDE (one workgroup per row): only derive the norm and leave
-// 0x10000 | norm bits in *pend when the row needs the pass (0 otherwise) -- the readers of the row apply the division on
-// the fly (renorm_pending, common.cuh) until NORM_APPLY (any number of workgroups, any later launch) rewrites the row from
-// *pend, installs the new exact sum and clears *pend.  DECIDE + APPLY leave the bits of NOW.
-enum { NORM_NOW = 0, NORM_DECIDE = 1, NORM_APPLY = 2 };
 __device__ __forceinline__ void normalize_row_body(bf16_t* w, int64_t n, int64_t* row_sum, int64_t* scratch, bf16_t* norm_out, int wg, int nwg,
-                                                   const int64_t* norm_src = nullptr, int mode = NORM_NOW, int* pend = nullptr) {
-  __shared__ int sh_norm, sh_last, sh_state;
+                                                   const int64_t* norm_src = nullptr) {
+  __shared__ int sh_norm, sh_last;
   if (threadIdx.x == 0) {
-    if (mode == NORM_APPLY) {
-      const int pd = __hip_atomic_load(pend, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      sh_state = pd;
-      sh_norm = (pd & 0x10000) ? (pd & 0xffff) : 0x3f80;       // nothing pending: leave like a row whose norm is 1.0
-    } else {
-      int bad = 0;
-      const bf16_t nb = limbs_to_bf16(norm_src ? norm_src : row_sum, &bad);
-      sh_norm = (int)nb | (bad << 20);
-      if (wg == 0) {
-        scratch[0] = (int64_t)nb | ((int64_t)(nb == 0x3f80) << 16) | ((int64_t)bad << 20);
-        if (norm_out) *norm_out = nb;
-        if (mode == NORM_DECIDE) {                             // (which buffer is current stays as it is)
-          const int cur = __hip_atomic_load(pend, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & NORM_CUR_ALT;
-          __hip_atomic_store(pend, cur | ((nb == 0x3f80) ? 0 : (0x10000 | (int)nb)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-      }
+    int bad = 0;
+    const bf16_t nb = limbs_to_bf16(norm_src ? norm_src : row_sum, &bad);
+    sh_norm = (int)nb | (bad << 20);
+    if (wg == 0) {
+      scratch[0] = (int64_t)nb | ((int64_t)(nb == 0x3f80) << 16) | ((int64_t)bad << 20);
+      if (norm_out) *norm_out = nb;
     }
   }
   __syncthreads();
   const bf16_t nb = (bf16_t)(sh_norm & 0xffff);
-  if (nb == 0x3f80 || mode == NORM_DECIDE) return;   // x / 1.0 == x : the row is already normalised, bit for bit
-  // NORM_APPLY works out of place: from the row's current buffer into the other one (the readers of the current one are
-  // not disturbed; they divide on the fly), and the last workgroup makes the other one current
-  const bf16_t* src = w;
-  if (mode == NORM_APPLY) {
-    const long long alt = *reinterpret_cast<const long long*>(pend + 2);
-    if (sh_state & NORM_CUR_ALT) src = w + alt; else w = w + alt;          // w = destination from here on
-  }
-  const float denom = renorm_denom((int)nb);       // F.normalize: norm.clamp_min(eps)
+  if (nb == 0x3f80) return;                        // x / 1.0 == x : the row is already normalised, bit for bit
+  const float denom = renorm_denom(nb);            // F.normalize: norm.clamp_min(eps)
   int bad = 0;
   int64_t dg[3] = {0, 0, 0};
   // The quotient without dividing.  Division by a fixed denominator commutes with powers of two as long as nothing leaves
@@ -413,17 +392,16 @@ __device__ __forceinline__ void normalize_row_body(bf16_t* w, int64_t n, int64_t
   const int64_t head = min(n, (int64_t)(((16 - ((uintptr_t)w & 15)) & 15) >> 1));
   const int64_t nvec = (n - head) / 8;
   const int64_t gtid = (int64_t)wg * E3_TPB + threadIdx.x, gsz = (int64_t)nwg * E3_TPB;
-  if (gtid < head) w[gtid] = one(src[gtid]);
-  for (int64_t i = head + nvec * 8 + gtid; i < n; i += gsz) w[i] = one(src[i]);
+  if (gtid < head) w[gtid] = one(w[gtid]);
+  for (int64_t i = head + nvec * 8 + gtid; i < n; i += gsz) w[i] = one(w[i]);
   typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
   u32x4* wv = reinterpret_cast<u32x4*>(w + head);
-  const u32x4* sv = reinterpret_cast<const u32x4*>(src + head);        // (both buffers share the 16-byte phase: alt % 8 == 0)
 #pragma unroll NORM_UNROLL
   for (int64_t i = gtid; i < nvec; i += gsz) {
 #if NORM_NT
-    u32x4 x = __builtin_nontemporal_load(sv + i);
+    u32x4 x = __builtin_nontemporal_load(wv + i);
 #else
-    u32x4 x = sv[i];
+    u32x4 x = wv[i];
 #endif
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -477,11 +455,7 @@ __device__ __forceinline__ void normalize_row_body(bf16_t* w, int64_t n, int64_t
       row_sum[k] = (int64_t)__hip_atomic_load((unsigned long long*)(scratch + 2 + k), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __hip_atomic_store((unsigned long long*)(scratch + 2 + k), 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    if (threadIdx.x == 0) {
-      __hip_atomic_store((unsigned long long*)(scratch + 1), 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      // (NORM_APPLY: the state word is flipped by k_norm_flip, a launch of its own behind this one -- the other workgroups'
-      // stores are only guaranteed to have left their XCD's L2 when this kernel has ended)
-    }
+    if (threadIdx.x == 0) __hip_atomic_store((unsigned long long*)(scratch + 1), 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 
@@ -497,29 +471,10 @@ __global__ void __launch_bounds__(E3_TPB) k_normalize_rows_global(const Exp3Mult
   normalize_row_body((bf16_t*)k.w_pos, n, k.row_sum, k.scratch, (bf16_t*)k.norm_out, (int)blockIdx.x - r * per_row, per_row, limbs + r * limb_stride);
 }
 // the rows of all layers in one launch: gridDim.x / n_rows workgroups per row
-__global__ void __launch_bounds__(E3_TPB) k_normalize_rows(const Exp3Multi m, int64_t n, int per_row, int mode) {
+__global__ void __launch_bounds__(E3_TPB) k_normalize_rows(const Exp3Multi m, int64_t n, int per_row) {
   const int r = blockIdx.x / per_row;
   const bliss_exp3_block_t& k = m.blk[r];
-  normalize_row_body((bf16_t*)k.w_pos, n, k.row_sum, k.scratch, (bf16_t*)k.norm_out, (int)blockIdx.x - r * per_row, per_row, nullptr, mode,
-                     k.norm_pend);
-  if (mode == NORM_DECIDE && m.done_flag && threadIdx.x == 0) {
-    // one workgroup per row here; the last one to have stored its row's state word tells the stream that runs the pass
-    // (row 0's pass ticket is idle during a decide launch and doubles as this one)
-    unsigned long long* ticket = (unsigned long long*)(m.blk[0].scratch + 1);
-    if (atomicAdd(ticket, 1ull) == (unsigned long long)m.n - 1) {
-      __hip_atomic_store(ticket, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(m.done_flag, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-}
-
-// after a NORM_APPLY launch: the rows that had a pass pending now live in their other buffer, nothing pending
-__global__ void k_norm_flip(const Exp3Multi m) {
-  const int r = threadIdx.x;
-  if (r >= m.n) return;
-  int* st = m.blk[r].norm_pend;
-  const int v = __hip_atomic_load(st, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (v & 0x10000) __hip_atomic_store(st, (v & NORM_CUR_ALT) ^ NORM_CUR_ALT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  normalize_row_body((bf16_t*)k.w_pos, n, k.row_sum, k.scratch, (bf16_t*)k.norm_out, (int)blockIdx.x - r * per_row, per_row);
 }
 
 // w_pos[p] = bf16(1 / bf16(indeg(dst(p))))          bandit_sampler.py:20-27
@@ -565,16 +520,15 @@ int bliss_exp3_update(const bliss_graph_t* g, const void* edge_w_pos, void* w_po
 }
 
 static int exp3_step(const bliss_graph_t* g, const void* edge_w_pos, const bliss_exp3_block_t* blocks, int32_t n_blocks,
-                     float delta_f, int32_t* err, void* stream, bool defer, int32_t* done_flag, bool normalize = true) {
+                     float delta_f, int32_t* err, void* stream, bool normalize) {
   if (!g || !blocks || n_blocks <= 0 || n_blocks > BLISS_EXP3_MAX_BLOCKS || !err) return BLISS_EINVAL;
   Exp3Multi m;
   m.n = n_blocks;
-  m.done_flag = done_flag;
   int total = 0;
   for (int i = 0; i < n_blocks; ++i) {
     const bliss_exp3_block_t& k = blocks[i];
     if (!k.w_pos || !k.row_sum || !k.scratch || !k.blk_indptr || !k.blk_src || !k.blk_dst || !k.blk_pos || !k.q_ij || !k.node_prob ||
-        !k.embed_norm || !k.dst_nid || !k.n_edges_dev || (!edge_w_pos && !k.alpha_or_null) || k.edges_bound < 0 || (defer && !k.norm_pend))
+        !k.embed_norm || !k.dst_nid || !k.n_edges_dev || (!edge_w_pos && !k.alpha_or_null) || k.edges_bound < 0)
       return BLISS_EINVAL;
     m.blk[i] = k;
     m.grid_begin[i] = total;
@@ -592,43 +546,18 @@ static int exp3_step(const bliss_graph_t* g, const void* edge_w_pos, const bliss
   // wants the whole chip: 1024 workgroups per row
   if (per_row > norm_wgs()) per_row = norm_wgs();
   if (per_row < 1) per_row = 1;
-  if (defer) per_row = 1;                              // only the decision: one workgroup per row
-  PROF_LAUNCH(BK_NORMALIZE, st, k_normalize_rows<<<(int)(per_row * n_blocks), E3_TPB, 0, st>>>(m, g->num_edges, (int)per_row, defer ? NORM_DECIDE : NORM_NOW));
+  PROF_LAUNCH(BK_NORMALIZE, st, k_normalize_rows<<<(int)(per_row * n_blocks), E3_TPB, 0, st>>>(m, g->num_edges, (int)per_row));
   return (int)hipGetLastError();
 }
 
 int bliss_exp3_step(const bliss_graph_t* g, const void* edge_w_pos, const bliss_exp3_block_t* blocks, int32_t n_blocks,
                     float delta_f, int32_t* err, void* stream) {
-  return exp3_step(g, edge_w_pos, blocks, n_blocks, delta_f, err, stream, false, nullptr);
+  return exp3_step(g, edge_w_pos, blocks, n_blocks, delta_f, err, stream, true);
 }
 
 int bliss_exp3_update_blocks(const bliss_graph_t* g, const void* edge_w_pos, const bliss_exp3_block_t* blocks, int32_t n_blocks,
                              float delta_f, int32_t* err, void* stream) {
-  return exp3_step(g, edge_w_pos, blocks, n_blocks, delta_f, err, stream, false, nullptr, false);
-}
-
-int bliss_exp3_step_deferred(const bliss_graph_t* g, const void* edge_w_pos, const bliss_exp3_block_t* blocks, int32_t n_blocks,
-                             float delta_f, int32_t* done_flag, int32_t* err, void* stream) {
-  return exp3_step(g, edge_w_pos, blocks, n_blocks, delta_f, err, stream, true, done_flag);
-}
-
-int bliss_exp3_normalize_pending(const bliss_exp3_block_t* rows, int32_t n_rows, int64_t num_edges, void* stream) {
-  if (!rows || n_rows <= 0 || n_rows > BLISS_EXP3_MAX_BLOCKS || num_edges < 0) return BLISS_EINVAL;
-  Exp3Multi m;
-  m.n = n_rows;
-  m.done_flag = nullptr;
-  for (int i = 0; i < n_rows; ++i) {
-    if (!rows[i].w_pos || !rows[i].row_sum || !rows[i].scratch || !rows[i].norm_pend) return BLISS_EINVAL;
-    m.blk[i] = rows[i];
-    m.grid_begin[i] = 0;
-  }
-  int64_t per_row = (num_edges + E3_TPB * 8 - 1) / (E3_TPB * 8);
-  if (per_row > norm_wgs()) per_row = norm_wgs();
-  if (per_row < 1) per_row = 1;
-  hipStream_t st = (hipStream_t)stream;
-  PROF_LAUNCH(BK_NORMALIZE, st, k_normalize_rows<<<(int)(per_row * n_rows), E3_TPB, 0, st>>>(m, num_edges, (int)per_row, NORM_APPLY));
-  k_norm_flip<<<1, 64, 0, st>>>(m);
-  return (int)hipGetLastError();
+  return exp3_step(g, edge_w_pos, blocks, n_blocks, delta_f, err, stream, false);
 }
 
 int bliss_exp3_apply(void* w_pos, int64_t* row_sum, const int32_t* pos, const void* factor, const int32_t* n_dev,
@@ -719,7 +648,6 @@ int bliss_exp3_normalize_global_rows(const bliss_exp3_block_t* rows, int32_t n_r
   if (!rows || n_rows <= 0 || n_rows > BLISS_EXP3_MAX_BLOCKS || num_edges <= 0 || !norm_limbs || limb_stride < 3 * ROWSUM_SLOTS) return BLISS_EINVAL;
   Exp3Multi m;
   m.n = n_rows;
-  m.done_flag = nullptr;
   for (int i = 0; i < n_rows; ++i) {
     if (!rows[i].w_pos || !rows[i].row_sum || !rows[i].scratch) return BLISS_EINVAL;
     m.blk[i] = rows[i];

@@ -347,7 +347,7 @@ class _HipShardOps:
             recs[i] = _lib.Exp3Block(self.w_pos[idx].data_ptr(), self.row_sum[idx].data_ptr(), self.scratch[idx].data_ptr(),
                                      self.norms[idx:].data_ptr(), blk.indptr.data_ptr(), blk.src.data_ptr(), blk.dst.data_ptr(),
                                      blk.pos.data_ptr(), blk._q.data_ptr(), blk._node_prob.data_ptr(), en.data_ptr(), 0, nid.data_ptr(),
-                                     blk._counts_dev.data_ptr() + 16, rewards.data_ptr(), B, 0)
+                                     blk._counts_dev.data_ptr() + 16, rewards.data_ptr(), B)
             blk.edata["rewards"] = rewards
         _lib.check(_lib.lib.bliss_exp3_update_blocks(C.byref(self.eng.c_graph), self.edge_w_pos.data_ptr(), recs, len(blks), delta_f,
                                                      self.err.data_ptr(), self._st()), "bliss_exp3_update_blocks")

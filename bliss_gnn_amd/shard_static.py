@@ -157,11 +157,10 @@ class DenseShardedSampler:
         outputs and NO host sync: safe inside HIP-graph capture.  The step number of the keyed draw lives on the device and
         advances by one per call / replay.  Returns this rank's blocks, input-most first; ``finish()`` reads sizes and errors.
 
-        ``part``: None = everything.  "select" = candidates, draw and kept lists of all layers without the blocks themselves
-        (``hook(n)`` is called behind layer n's kept list); "build" = only the blocks (generate_block, :269-339) of a preceding
-        "select" with the same slot (``hook(n)`` in front of layer n's block) -- for a loop that builds them on another stream.
+        ``part``: None = everything.  "build" = only the blocks (generate_block, :269-339) that a preceding call with the same slot
+        left out through ``defer`` (``hook(n)`` in front of layer n's block) -- for a loop that builds them on another stream.
         ``defer``: sampling layers whose block this call does NOT build; ``layers``: the only ones a "build" call builds (the loop
-        that leaves the input-most block to the backward stream: PipelinedShardedTrainStep; ``ready_flag``: device flag that
+        that leaves the blocks to the backward stream: PipelinedShardedTrainStep; ``ready_flag``: device flag that
         bliss_build_block raises once the blocks' forward arrays are final, BEFORE it sorts the by-source lists of the backward pass;
         ``sel_done_flag``: device flag raised by the last layer's bliss_shard_select_kept: all kept lists are final;
         ``layer_done_flags``: address of L consecutive device flags, flag n raised by layer n's select_kept: its kept list is final.
@@ -180,7 +179,9 @@ class DenseShardedSampler:
         st = torch.cuda.current_stream().cuda_stream
         lib, chk = _lib.lib, _lib.check
         V = eng.V
-        select, build = part in (None, "select"), part in (None, "build")
+        if part not in (None, "build"):
+            raise ValueError(f"enqueue: part must be None or 'build', not {part!r}")
+        select = part is None
         if (part is not None or defer) and eng.scratch_sets < L:
             raise RuntimeError("split enqueue needs one scratch set per layer (set ops.eng.scratch_sets before the first call)")
         if select:
@@ -223,20 +224,18 @@ class DenseShardedSampler:
                                                 c_ws.kept_map, cap["K"], V, V, cnt_ptr, nloc_ptr, b["scr_a"].data_ptr(), 1 if n == L - 1 else 0,
                                                 (int(layer_done_flags) + 4 * n) if layer_done_flags else (int(sel_done_flag) if n == L - 1 else 0), b["err"].data_ptr(), st),
                     "bliss_shard_select_kept")
-                if hook is not None and part == "select":
-                    hook(n)
             # (measured and not kept: the block forked to a side stream INSIDE one graph -- correct, but the forked graph replayed at
             # 4.4 ms instead of 1.4: this runtime serialises branches of one graph badly; see PipelinedShardedTrainStep for the form
-            # that works: a graph of its own on a third stream, ordered by device flags)
-            if build and n not in defer and (layers is None or n in layers):
-                if hook is not None and part == "build":
+            # that works: the blocks in the backward stream's graph, ordered by device flags)
+            if n not in defer and (layers is None or n in layers):
+                if hook is not None:
                     hook(n)
                 keep_flag, c_ws.block_ready_flag = c_ws.block_ready_flag, ((ready_flag if n == L - 1 else 0) or c_ws.block_ready_flag)
                 chk(lib.bliss_build_block(C.byref(eng.c_graph), C.byref(eng._set(n)["c_maps"]), w_pos.data_ptr(), seeds_l.data_ptr(), cs, ops.mode,
                                           eta_f, ome_f, eng.Eg, C.byref(c_ws), C.byref(c_out), st), "bliss_build_block")
                 c_ws.block_ready_flag = keep_flag
             b_indptr, b_src, b_dst, b_pos, b_eid, b_w, b_q, kept, node_prob, cdev, t_indptr, t_edge = lay
-            if not select:                                         # (the block objects exist: made by the "select" part)
+            if not select:                                         # (the block objects exist: made by the call that deferred them)
                 cur, n_seeds, n_seeds_dev = kept, -1, cnt_ptr + 12
                 continue
             # (the destinations' ids = this rank's seeds: bliss_shard_local_seeds wrote them, padded with the list's first entry, into
@@ -313,7 +312,7 @@ class DenseShardedSampler:
             rows = (_lib.Exp3Block * L)()
             for idx in range(L):
                 rows[idx] = _lib.Exp3Block(ops.w_pos[idx].data_ptr(), ops.row_sum[idx].data_ptr(), ops.scratch[idx].data_ptr(),
-                                           ops.norms[idx:].data_ptr(), 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0)
+                                           ops.norms[idx:].data_ptr(), 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0)
             _lib.check(_lib.lib.bliss_exp3_normalize_global_rows(rows, L, self.g.num_edges(), limbs.data_ptr(), limbs.stride(0), st),
                        "bliss_exp3_normalize_global_rows")
             return
@@ -892,17 +891,19 @@ class PipelinedShardedTrainStep(StaticShardedTrainStep):
         if shard.world > 1 and group_b is None:
             group_b = dist.new_group(backend=dist.get_backend(group))
         self.group_b = group_b
-        self.side, self.third = torch.cuda.Stream(), torch.cuda.Stream()
-        # (flag mode builds the next batch's blocks on the third stream, beside the later layers' candidate work: one scratch set
+        self.side = torch.cuda.Stream()
+        # (flag mode builds the next batch's blocks on the backward stream, beside the later layers' candidate work: one scratch set
         # per layer -- a layer's dense maps live until its block is built)
         sampler.ops.eng.scratch_sets = max(sampler.ops.eng.scratch_sets, len(sampler.nodes_per_layer))
         self.slot, self.primed = 0, False
         self.blocks2 = [None, None]
         self.ev_f, self.ev_b = torch.cuda.Event(), torch.cuda.Event()
-        self.g_main, self.g_fx, self.g_s, self.g_b, self.g_blk = [None, None], [None, None], [None, None], [None, None], [None, None]
+        self.g_main, self.g_fx, self.g_s, self.g_b = [None, None], [None, None], [None, None], [None, None]
         self._held = [None, None]
-        self._flags_primed, self.use_flags, self.use_third, self.late_block, self.split_output = False, False, False, False, False
+        self._flags_primed, self.use_flags, self.late_block, self.split_output = False, False, False, False
         self.late_all = False
+
+    use_third = False      # (read by bench.py: the next batch's blocks on a third stream were measured slower and removed)
 
     # ---- the three parts ---------------------------------------------------------------------------------------------------
     def _sample(self, slot):
@@ -938,16 +939,11 @@ class PipelinedShardedTrainStep(StaticShardedTrainStep):
             torch.cuda.synchronize()
             return ok
 
-        for name in ("side", "third"):
-            for _ in range(tries):
-                st = getattr(self, name)
-                # (the third stream's waits must not sit on the backward stream's queue either: a spinning wait there holds B back)
-                if probe(st, main) and probe(main, st) and (name == "side" or (probe(st, self.side) and probe(self.side, st))):
-                    break
-                setattr(self, name, torch.cuda.Stream())
-            else:
-                return False
-        return True
+        for _ in range(tries):
+            if probe(self.side, main) and probe(main, self.side):
+                return True
+            self.side = torch.cuda.Stream()
+        return False
 
     def _flag(self, which, raise_):
         eng = self.sampler.ops.eng
@@ -988,15 +984,12 @@ class PipelinedShardedTrainStep(StaticShardedTrainStep):
             # each graph cost 40-90 us per boundary (profiles/r03_u: 1.10 ms/step with three event-ordered graphs)
             if not self._flags_primed:                           # nothing precedes the first step; its blocks were built by prime()
                 self._flag(self.FLAG_B_DONE, True)
-                if self.use_third or self.late_block:
+                if self.late_block:
                     self._flag(self.FLAG_BLK_DONE, True)
                 self._flags_primed = True
             self.g_main[s].replay()
             with torch.cuda.stream(self.side):
                 self.g_b[s].replay()
-            if self.use_third:
-                with torch.cuda.stream(self.third):
-                    self.g_blk[1 - s].replay()
         elif self.graph is not None:                             # three graphs per step, ordered by stream events
             main.wait_event(self.ev_b)
             self.g_fx[s].replay()
@@ -1021,7 +1014,6 @@ class PipelinedShardedTrainStep(StaticShardedTrainStep):
     def finish(self):
         """Wait for both streams; the trained batch's loss, the sizes of the batch just sampled, the error check."""
         self.side.synchronize()
-        self.third.synchronize()
         torch.cuda.current_stream().synchronize()
         sizes = self.sampler.finish(self.slot)
         self.sampler.check_errors()
@@ -1053,9 +1045,9 @@ class PipelinedShardedTrainStep(StaticShardedTrainStep):
         self.last = {}
         gc.collect()
         torch.cuda.synchronize()
-        pool, pool_b, pool_k = torch.cuda.graph_pool_handle(), torch.cuda.graph_pool_handle(), torch.cuda.graph_pool_handle()
+        pool, pool_b = torch.cuda.graph_pool_handle(), torch.cuda.graph_pool_handle()
         cap = torch.cuda.Stream()                                # (one capture stream for F and B: autograd replays a node on its forward's stream)
-        g_main, g_s, g_b, g_blk = [None, None], [None, None], [None, None], [None, None]
+        g_main, g_s, g_b = [None, None], [None, None], [None, None]
         for s in (0, 1):                                         # (S alone: what prime() replays)
             g_s[s] = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g_s[s], stream=cap, **_cap_kw()):
@@ -1066,10 +1058,6 @@ class PipelinedShardedTrainStep(StaticShardedTrainStep):
             # the waits of this loop sit in front of work that contains collectives: a peer's hiccup of a second must not read as
             # "the flag never came" (the bound is a kernel argument: it is captured with the graphs below)
             _lib.check(_lib.lib.bliss_flag_set_spin_bound(1 << 27), "bliss_flag_set_spin_bound")
-        # BLISS_SHARD_THIRD=1: the next batch's blocks as a graph of their own on a third stream, layer by layer behind "layer n's kept
-        # list is final" flags (the single-GPU loop's arrangement).  Correct (same bits) but 2.6 ms/step instead of 1.02 here: the
-        # spinning waits of that graph sit on a hardware queue the backward pass needs -- measured, off by default
-        self.use_third = self.use_flags and os.environ.get("BLISS_SHARD_THIRD", "0") == "1"
         # BLISS_SHARD_LATE_BLOCK (default on): the input-most block of batch t+1 -- the last and largest of the sampler -- is built on
         # the BACKWARD stream, behind B(t) and a "kept lists final" flag, while the main stream already runs the part of F(t+1) that
         # needs only the kept list (feature rows, halo sum, the input layer's two Linears); F's first aggregation waits for the
@@ -1077,12 +1065,13 @@ class PipelinedShardedTrainStep(StaticShardedTrainStep):
         # (multi-label runs keep the loss on torch ops: their backward stream is the longer chain already -- Yelp-like 1549 steps/s
         # with all blocks there against 1613 with the input-most block only -- so they default to 1)
         late_mode = os.environ.get("BLISS_SHARD_LATE_BLOCK", "1" if self.multilabel else "2")
-        self.late_block = self.use_flags and not self.use_third and late_mode != "0"
+        if late_mode not in ("0", "1", "2"):
+            raise ValueError(f"BLISS_SHARD_LATE_BLOCK must be 0, 1 or 2, not {late_mode!r}")
+        self.late_block = self.use_flags and late_mode != "0"
         # BLISS_SHARD_LATE_BLOCK=2 (default): ALL blocks of batch t+1 go to the backward stream, block n behind "layer n's kept list is
         # final" (raised by that layer's select launch itself): the backward stream had the room since the loss kernel, and the
         # critical stream keeps only the candidate chain.  =1: the input-most block only
-        self.late_all = self.late_block and late_mode in ("2", "3")
-        late_from = 1 if late_mode == "3" else 0                 # (=3: the output block stays on the critical stream)
+        self.late_all = self.late_block and late_mode == "2"
         L_s = len(self.sampler.nodes_per_layer)
         eng = self.sampler.ops.eng
         # BLISS_SHARD_SPLIT_OUTPUT (default on): the forward split of the single-GPU loop (section 6 item 16) -- the EXP3 update reads the
@@ -1096,8 +1085,6 @@ class PipelinedShardedTrainStep(StaticShardedTrainStep):
                 g_main[s] = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g_main[s], pool=pool, stream=cap, **_cap_kw()):
                     self._flag(self.FLAG_B_DONE, False)          # batch t-1: parameters updated, its block slot free again
-                    if self.use_third:
-                        self._flag(self.FLAG_BLK_DONE, False)    # batch t's blocks are built (third stream, during step t-1)
                     blocks = self.blocks2[s]
                     if self.late_block:                          # (consumed by the first aggregation of F: a wait for BLK_DONE)
                         blocks[0]._ready = (eng.flags.data_ptr() + 4 * self.FLAG_BLK_DONE, eng.flag_err.data_ptr())
@@ -1108,22 +1095,14 @@ class PipelinedShardedTrainStep(StaticShardedTrainStep):
                     self.sampler.exp3(blocks)                    # X(t)
                     if self.late_block and self.late_all:        # S(t+1) without its blocks: flag n = "layer n's kept list is final"
                         self._gather_seeds()
-                        self.blocks2[1 - s] = self.sampler.enqueue(self.seeds_g, slot=1 - s, defer=tuple(range(late_from, L_s)),
+                        self.blocks2[1 - s] = self.sampler.enqueue(self.seeds_g, slot=1 - s, defer=tuple(range(L_s)),
                                                                    layer_done_flags=eng.flags.data_ptr())
                     elif self.late_block:                        # S(t+1) but for its last block
                         self._gather_seeds()
                         self.blocks2[1 - s] = self.sampler.enqueue(self.seeds_g, slot=1 - s, defer=(L_s - 1,),
                                                                    sel_done_flag=eng.flags.data_ptr() + 4 * self.FLAG_SEL_DONE)
-                    elif self.use_third:                           # S(t+1) without its blocks; "layer n's kept list is final": flag n
-                        self._gather_seeds()
-                        self.blocks2[1 - s] = self.sampler.enqueue(self.seeds_g, slot=1 - s, part="select", hook=lambda n: self._flag(n, True))
                     else:
                         self._sample(1 - s)                      # S(t+1)
-                if self.use_third:
-                    g_blk[1 - s] = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g_blk[1 - s], pool=pool_k, stream=cap, **_cap_kw()):     # the blocks of batch t+1, third stream
-                        self.sampler.enqueue(self.seeds_g, slot=1 - s, part="build", hook=lambda n: self._flag(n, False))
-                        self._flag(self.FLAG_BLK_DONE, True)
                 # (a pool of its own: B(t) runs BESIDE the S(t+1) part of the main graph, and two graphs that share a pool share the
                 # memory of their temporaries -- the sampler's were overwritten by the backward pass's until the pools were split.
                 # The forward's saved tensors live in the main graph's pool and stay alive through _held.)
@@ -1133,7 +1112,7 @@ class PipelinedShardedTrainStep(StaticShardedTrainStep):
                     self._flag(self.FLAG_B_DONE, True)
                     if self.late_block and self.late_all:        # all blocks of batch t+1, each behind its layer's flag
                         self.sampler.enqueue(self.seeds_g, slot=1 - s, part="build", hook=lambda n: self._flag(n, False),
-                                             layers=tuple(range(late_from, L_s)), ready_flag=eng.flags.data_ptr() + 4 * self.FLAG_BLK_DONE)
+                                             ready_flag=eng.flags.data_ptr() + 4 * self.FLAG_BLK_DONE)
                     elif self.late_block:                        # the input-most block of batch t+1
                         self._flag(self.FLAG_SEL_DONE, False)
                         # (BLK_DONE is raised by bliss_build_block itself, in front of the by-source lists only B(t+1) reads -- this stream)
@@ -1145,7 +1124,7 @@ class PipelinedShardedTrainStep(StaticShardedTrainStep):
                     self._held[s] = self._fwd_x(s)
                 with torch.cuda.graph(g_b[s], pool=pool, stream=cap, **_cap_kw()):
                     self._bwd(self._held[s], s)
-        self.g_main, self.g_fx, self.g_s, self.g_b, self.g_blk = g_main, g_fx, g_s, g_b, g_blk
+        self.g_main, self.g_fx, self.g_s, self.g_b = g_main, g_fx, g_s, g_b
         self.graph = True
         # the captures executed nothing, and the slot the loop trains next now consists of recorded tensors: sample its batch again
         # (my_seeds still holds it) under the SAME step number of the keyed draw -- the loop continues as if nothing had happened
@@ -1156,7 +1135,7 @@ class PipelinedShardedTrainStep(StaticShardedTrainStep):
     def close(self):
         import gc
         torch.cuda.synchronize()
-        self.g_main, self.g_fx, self.g_s, self.g_b, self.g_blk, self._held = ([None, None] for _ in range(6))
+        self.g_main, self.g_fx, self.g_s, self.g_b, self._held = ([None, None] for _ in range(5))
         self.graph, self.last, self.blocks2 = None, {}, [None, None]
         gc.collect()
         torch.cuda.synchronize()

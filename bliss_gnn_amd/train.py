@@ -322,6 +322,8 @@ class PipelinedTrainStep(GraphedTrainStep):
     branches would share a hardware queue on ROCm 7.2, hence three graphs on three real streams.  ``capture`` checks that
     the flags arrive (streams that happen to share a hardware queue would make a waiting kernel block its producer) and
     otherwise falls back to event ordering: F+X, S and B as separate graphs (BLISS_PIPELINE_FLAGS=0 forces that).
+    F.normalize's pass over the bandit rows stays inside X, in place (taken off the critical stream
+    it was no faster).
 
     One call = two optimiser steps on two batches; the batch sampled last is trained by the next call (``drain``
     trains the final one)."""
@@ -340,16 +342,6 @@ class PipelinedTrainStep(GraphedTrainStep):
         self.use_flags = os.environ.get("BLISS_PIPELINE_FLAGS", "1") != "0"
         self.losses = None
         self.last_counts2 = None
-        # BLISS_NORM_DEFER=1: F.normalize's pass over the bandit rows beside the next forward pass instead of in front of the
-        # next sampler (bandit_sampler.normalize_pending; flag mode only, switched on by capture()).  Off by default: same bits,
-        # but measured no faster on the Reddit-like loop once the pass itself took 85 us instead of 129 (0.820 / 0.824 against
-        # 0.823 / 0.836 ms per step, run-to-run noise +-0.008) -- beside the forward pass it still competes for HBM, and the
-        # hand-off adds two small kernels to every step.  Replicas always keep the immediate pass: their update lists are applied
-        # after an exchange, outside the fused exp3 step.
-        self._defer_wanted = (not distributed and hasattr(sampler, "normalize_pending")
-                              and os.environ.get("BLISS_NORM_DEFER", "0") != "0")
-        self._defer = False
-        self.g_norm = None
         self._flag_boundary = os.environ.get("BLISS_FLAG_BOUNDARY", "1") != "0"
         # The input layer's block (the LAST one the sampler builds: ~90 us at the end of its chain) built on the third stream
         # beside the next step's first transform, which needs the kept-node list only; the first aggregation waits for a
@@ -367,28 +359,18 @@ class PipelinedTrainStep(GraphedTrainStep):
         return (hasattr(self.model, "forward_hidden") and len(getattr(self.model, "layers", ())) > 1 and hasattr(self.sampler, "exp3")
                 and os.environ.get("BLISS_SPLIT_FORWARD", "1") != "0")
 
-    FLAG_BLOCK0, FLAG_B_DONE, FLAG_X_DONE = 10, 11, 12    # engine.flags slots (0..L: the sampler's layers; 14: the probe)
+    FLAG_BLOCK0, FLAG_B_DONE = 10, 11                     # engine.flags slots (0..L: the sampler's layers; 14: the probe)
 
-    def _forward(self, mfgs, flagged=False):
+    def _forward(self, mfgs):
         """The part of the step the NEXT batch's sampler waits for: the forward pass up to the output layer's input (every
         block's row norms exist from there on, train_lightning.py:232-238 reads nothing else) and the bandit update.  Returns
         what _backward needs to finish the step."""
-        if self._defer and not flagged:                            # eager: the rows the previous update left pending, inline
-            self.sampler.normalize_pending()
         pending = self._forward_model(mfgs)
-        done_flag = None
-        if self._defer and flagged:
-            # the pass of the PREVIOUS update ran on the third stream (g_norm) and is complete: this graph only starts after
-            # that stream's event.  This update tells g_norm when the rows are ready for the next pass.
-            self.sampler._pend_maybe = False
-            done_flag = self.sampler._engine.flags.data_ptr() + 4 * self.FLAG_X_DONE
         if not hasattr(self.sampler, "exp3"):                      # LADIES samplers keep no bandit state
             return pending
         if self.distributed:
             from . import dist as bdist
             bdist.exp3_all_ranks_static(self.sampler, mfgs, self.g)
-        elif done_flag is not None:
-            self.sampler.exp3(mfgs, self.g, done_flag=done_flag)
         else:
             self.sampler.exp3(mfgs, self.g)
         return pending
@@ -450,10 +432,6 @@ class PipelinedTrainStep(GraphedTrainStep):
 
     def _finish_pair(self, check_flags=True):
         torch.cuda.current_stream().synchronize()
-        if self._defer:                                  # whoever looks at the rows between two calls finds them in _w_pos
-            self.sampler._pend_maybe = True
-            self.sampler._settle()
-            torch.cuda.current_stream().synchronize()
         c1 = self.sampler.finish_static(1, commit=False)
         c0 = self.sampler.finish_static(0, commit=True)
         self.last_counts2 = [c1, c0]                     # the two batches sampled by this replay, in sampling order
@@ -481,9 +459,6 @@ class PipelinedTrainStep(GraphedTrainStep):
             self.use_flags = False
         if self.use_flags:
             eng.scratch_sets = max(eng.scratch_sets, L)      # block n then shares no scratch with any later layer
-        self._defer = self._defer_wanted and self.use_flags
-        if self._defer:
-            self.sampler.enable_deferred_normalize(True)
         self._defer_block0 = (self.use_flags and self._flag_boundary and L > 1 and L < self.FLAG_BLOCK0 and type(self.model).__name__ == "SAGE"
                               and self._split_forward() and os.environ.get("BLISS_DEFER_BLOCK0", "1") != "0")
         tune_gemm = tune_gemm and _enable_gemm_tuning()
@@ -556,17 +531,8 @@ class PipelinedTrainStep(GraphedTrainStep):
         pool = torch.cuda.graph_pool_handle()
         self.graph = None
         self.g_main, self.g_fwd, self.g_bwd, self.g_smp, self.g_blk, self.g_blk0 = ([None, None] for _ in range(6))
-        self.g_norm = None
         held, out = [None, None], [None, None]
         st_ = lambda: torch.cuda.current_stream().cuda_stream
-        if self._defer:
-            # F.normalize's pass, for the third stream: as soon as the bandit update has decided which rows need it, write them
-            # renormalised into their other buffers -- beside the sampler, which keeps reading the old ones (dividing on the fly)
-            # until the pass has switched a row over
-            self.g_norm = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.g_norm, pool=pool, **_cap_kw()):
-                _lib.check(_lib.lib.bliss_flag_wait(eng.flags.data_ptr() + 4 * self.FLAG_X_DONE, eng.flag_err.data_ptr(), st_()), "bliss_flag_wait")
-                self.sampler.normalize_pending()
         for cur, nxt, chain in ((0, 1, False), (1, 0, True)):
             # (the sampler is recorded without its generator: that one is launched ahead of time, see _replay / run)
             self.g_bwd[cur] = torch.cuda.CUDAGraph()
@@ -581,7 +547,7 @@ class PipelinedTrainStep(GraphedTrainStep):
                                    "bliss_flag_wait")
                     if self._defer_block0:              # (the wait itself is recorded by the first aggregation over that block)
                         self.mfgs[cur][0]._ready = (eng.flags.data_ptr() + 4 * self.FLAG_BLOCK0, eng.flag_err.data_ptr())
-                    held[cur] = self._forward(self.mfgs[cur], flagged=True)                     # F + X
+                    held[cur] = self._forward(self.mfgs[cur])                                   # F + X
                     self.mfgs[cur][0]._ready = None
                     self.mfgs[nxt] = self._sample(nxt, chain, external_rng=True, part="main",   # S without the early blocks
                                                   last_block=not self._defer_block0)
@@ -593,11 +559,7 @@ class PipelinedTrainStep(GraphedTrainStep):
                     self.g_blk0[nxt] = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(self.g_blk0[nxt], **_cap_kw()):
                         # (raises FLAG_BLOCK0 itself, before it sorts the by-source index the backward pass will read)
-                        early = os.environ.get("BLISS_BLOCK0_EARLY_FLAG", "1") != "0"
-                        self._sample(nxt, chain, external_rng=True, part="last_block",
-                                     ready_flag=eng.flags.data_ptr() + 4 * self.FLAG_BLOCK0 if early else 0)
-                        if not early:
-                            _lib.check(_lib.lib.bliss_flag_raise(eng.flags.data_ptr() + 4 * self.FLAG_BLOCK0, st_()), "bliss_flag_raise")
+                        self._sample(nxt, chain, external_rng=True, part="last_block", ready_flag=eng.flags.data_ptr() + 4 * self.FLAG_BLOCK0)
                 with torch.cuda.graph(self.g_bwd[cur], pool=pool, stream=side, **_cap_kw()):
                     # B may start once S has (flag 0 is raised by the sampler's first kernel: F and X have completed)
                     _lib.check(_lib.lib.bliss_flag_wait(eng.flags.data_ptr(), eng.flag_err.data_ptr(),
@@ -628,12 +590,9 @@ class PipelinedTrainStep(GraphedTrainStep):
                 # half's g_blk0 (this wait must precede the record further down, which is this half's)
                 side.wait_event(self._blk0_done)
             self.g_main[cur].replay()                    # F + X + S: one graph on the critical stream
-            if self.g_norm is not None or self.g_blk[nxt] is not None:
+            if self.g_blk[nxt] is not None:
                 with torch.cuda.stream(self.third):
-                    if self.g_norm is not None:
-                        self.g_norm.replay()             # F.normalize's pass: waits for X, runs beside S
-                    if self.g_blk[nxt] is not None:
-                        self.g_blk[nxt].replay()         # early blocks of S: each waits for the flag of the next layer
+                    self.g_blk[nxt].replay()             # early blocks of S: each waits for the flag of the next layer
                     self._blk_done.record(self.third)
                     if self.g_blk0[nxt] is not None:
                         self.g_blk0[nxt].replay()        # the input layer's block: waits for the end of S, raises FLAG_BLOCK0
@@ -642,9 +601,8 @@ class PipelinedTrainStep(GraphedTrainStep):
                 self.g_bwd[cur].replay()                 # B: waits for the flag S raises when it starts
                 if on_side is not None:
                     on_side()
-                # one wait on the critical stream instead of two: "B done" below also means "all blocks of S built" (and the
-                # pass complete: the next update may write the rows)
-                if self.g_norm is not None or self.g_blk[nxt] is not None:
+                # one wait on the critical stream instead of two: "B done" below also means "all blocks of S built"
+                if self.g_blk[nxt] is not None:
                     side.wait_event(self._blk_done)
                 if self._flag_boundary:
                     _lib.check(_lib.lib.bliss_flag_raise(self.sampler._engine.flags.data_ptr() + 4 * self.FLAG_B_DONE, side.cuda_stream),
@@ -888,14 +846,12 @@ class PipelinedTrainStep(GraphedTrainStep):
         with torch.cuda.stream(side):
             loss = self._backward(self._forward(self.mfgs[0]))
         main.wait_stream(side)
-        if self._defer:
-            self.sampler._settle()
         main.synchronize()
         self.num_steps += 1
         return loss
 
     def _graph_attrs(self):
-        return ("graph", "g_main", "g_fwd", "g_bwd", "g_smp", "g_blk", "g_blk0", "g_norm")
+        return ("graph", "g_main", "g_fwd", "g_bwd", "g_smp", "g_blk", "g_blk0")
 
     def close(self):
         """Train the batch still in flight (``drain``), wait for every stream of the loop, then destroy the graphs."""
@@ -905,9 +861,6 @@ class PipelinedTrainStep(GraphedTrainStep):
             st.synchronize()
         super().close()
         self.mfgs = [None, None]
-        if self._defer:
-            self.sampler.enable_deferred_normalize(False)
-            self._defer = False
 
     def sizes2(self):
         """sizes() for each of the two batches sampled by the last call."""
