@@ -367,9 +367,13 @@ __global__ void __launch_bounds__(GF_TPB, 4) k_gat_fwd(GatFused p) {
     const int n_mine = wave_edges_in_chunk(n_edges, k, wave);
     ld_wave_rows<VEC4, NG>(raw, p.feat, p.feat_stride, my_s, k * GF_EW, n_mine, coff);
     if (!staged) {                                    // (block-uniform; behind the first chunk's gathers, which stay in flight)
+      // sh_er / sh_at hold NG * 64 * W floats: with HG = 1 or 2 that is fewer than 256 threads' W columns each, and the
+      // threads beyond it must not store (their zeros landed past the array, on the other half's attn / er_i)
       float* dstp = (tid >> 8) ? sh_at : sh_er;
+      if ((tid & 255) < NG * 64) {
 #pragma unroll
-      for (int jj = 0; jj < W; ++jj) dstp[(tid & 255) * W + jj] = er_at.v[jj];
+        for (int jj = 0; jj < W; ++jj) dstp[(tid & 255) * W + jj] = er_at.v[jj];
+      }
       __syncthreads();
       staged = true;
     }

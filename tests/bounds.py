@@ -1,0 +1,409 @@
+"""Per-element error bounds for the bf16 message-passing kernels, their fp64 references, and designed blocks.
+
+A plain helper module, imported by the tests like shard_cpu_ops.py.  Every check has the form
+
+    |got - ref| <= k_ulp * ulp_bf16(ref) + k_mag * 2^-8 * mag            (element by element)
+
+``ref`` is the fp64 value of the operation on the same bf16 operands, ``mag`` the same formula evaluated on the absolute
+values of its terms (so an element 100x smaller than the tensor's largest is held to its own scale), ``k_ulp`` covers the
+final rounding to bf16 and ``k_mag`` the roundings of intermediate values, in units of one bf16 half-spacing pair (2^-8).
+The constants of each tensor are written in the docstring of the test that uses them.
+
+The references work on any device (the GPU tests run them on the GPU in float64, the CPU tests in tests/test_bounds.py on
+small blocks).  ``gat_terms`` restates model.py:82-99 and its backward formula by formula, so that a test can round the
+intermediates the kernels store in bf16 (``sim=True``) or plant a fault in one sum; ``gat_autograd`` is the same forward
+differentiated by torch autograd, the reference the GPU tests compare against.
+"""
+import torch
+
+NEG_SLOPE = 0.2
+
+
+# ------------------------------------------------------------------------------------------------ the bound
+def ulp_bf16(x):
+    """Spacing of bf16 at |x| (float64, same shape): 2^(e - 8) for |x| in [2^(e-1), 2^e); 2^-133 (the subnormal spacing) for
+    zero and every |x| below the smallest normal."""
+    x = x.detach().double().abs()
+    _, e = torch.frexp(x)
+    u = torch.ldexp(torch.ones_like(x), (e - 8).to(torch.int32))
+    return torch.where(x < 2.0 ** -126, torch.full_like(x, 2.0 ** -133), u)
+
+
+def rbf(x):
+    """Round to bf16 (nearest even) and back, keeping the dtype."""
+    return x.to(torch.bfloat16).to(x.dtype)
+
+
+def assert_within(got, ref, mag, k_ulp, k_mag, what):
+    """Every element: |got - ref| <= k_ulp * ulp_bf16(ref) + k_mag * 2^-8 * mag.  Returns the largest |got - ref| / bound (0 where
+    got == ref exactly).  On failure the message names the worst element (index, got, ref, bound, ratio) and how many elements are
+    over the bound.  A non-finite ``got`` counts as over."""
+    got, ref, mag = got.detach().double(), ref.detach().double().to(got.device), mag.detach().double().to(got.device)
+    assert got.shape == ref.shape == mag.shape, (what, tuple(got.shape), tuple(ref.shape), tuple(mag.shape))
+    if got.numel() == 0:
+        return 0.0
+    err = (got - ref).abs()
+    bound = k_ulp * ulp_bf16(ref) + k_mag * 2.0 ** -8 * mag
+    ratio = torch.where(err == 0, torch.zeros_like(err), err / bound)
+    ratio = torch.nan_to_num(ratio, nan=float("inf"))
+    over = int((ratio > 1).sum())
+    worst = int(ratio.reshape(-1).argmax())
+    if over:
+        idx = tuple(int(i) for i in torch.unravel_index(torch.tensor(worst), tuple(got.shape)))
+        raise AssertionError("%s: %d of %d elements over the bound; worst at %s: got %.9g ref %.9g bound %.3g ratio %.3g"
+                             % (what, over, got.numel(), idx, float(got.reshape(-1)[worst]), float(ref.reshape(-1)[worst]),
+                                float(bound.reshape(-1)[worst]), float(ratio.reshape(-1)[worst])))
+    return float(ratio.reshape(-1)[worst])
+
+
+# ------------------------------------------------------------------------------------------------ SpMM (weighted_aggregate)
+def spmm_terms(src, dst, n_rows, h, w=None, mean=True, by_src=False, n_out=None, deg=None, scale=None):
+    """fp64 reference and magnitude of weighted_aggregate and of its transposed backward.
+
+    Forward (by_src=False): out[i] = (1/deg_i if mean) sum_{e -> i} w_e h[src_e]          (h: [K, dim], rows = destinations)
+    Backward (by_src=True): gh[j] = sum_{e : src_e = j} (w_e / deg_{dst_e} if mean) h[dst_e]  (h = d out: [S, dim])
+    ``deg``: in-degrees of the destinations (default: counted from dst).  ``scale``: a per-edge factor that replaces 1/deg
+    (planted faults only).  Returns (ref, mag), both float64 [n_out, dim]."""
+    h = h.double()
+    src, dst = src.long(), dst.long()
+    if deg is None:
+        deg = torch.bincount(dst, minlength=n_rows).double()
+    c = torch.ones(src.numel(), dtype=torch.float64, device=h.device) if w is None else w.double().reshape(-1)
+    if mean:
+        c = c * (scale if scale is not None else 1.0 / deg.clamp(min=1)[dst])
+    rows, nbrs = (src, dst) if by_src else (dst, src)
+    n = n_out if n_out is not None else (int(h.shape[0]) if by_src else n_rows)
+    ref = torch.zeros(n, h.shape[1], dtype=torch.float64, device=h.device).index_add_(0, rows, c[:, None] * h[nbrs])
+    mag = torch.zeros(n, h.shape[1], dtype=torch.float64, device=h.device).index_add_(0, rows, (c.abs()[:, None] * h[nbrs].abs()))
+    return ref, mag
+
+
+# ------------------------------------------------------------------------------------------------ GATv2 message passing
+def _seg_max(v, dst, S):
+    H = v.shape[1]
+    return torch.full((S, H), -float("inf"), dtype=v.dtype, device=v.device).scatter_reduce(
+        0, dst[:, None].expand(-1, H), v, "amax", include_self=True)
+
+
+def _seg_sum(v, dst, S):
+    return torch.zeros((S,) + tuple(v.shape[1:]), dtype=v.dtype, device=v.device).index_add_(0, dst, v)
+
+
+def gat_terms(src, dst, S, feat, attn, H, D, g=None, slope=NEG_SLOPE, mask=None, p=0.0, sim=False, fault=None):
+    """model.py:82-99 and its backward, formula by formula, in float64, with magnitudes.
+
+    feat [K, H*D] (= fc_src(h)), attn [H*D], g = d rst [S, H*D] or None; ``mask`` [B, H] bool (attention dropout kept, with
+    p > 0).  Per edge k = (j = src, i = dst) and head:  x = el_j + er_i, e = attn . lrelu(x), a = softmax_i(e),
+    ad = a mask / (1 - p), rst_i = sum ad el_j;  da = mask / (1 - p) (g_i . el_j), t_i = sum a da, de = a (da - t_i),
+    d er_i = attn sum de lrelu'(x), d el_j = sum_out (de attn lrelu'(x) + ad g_i), d attn = sum de lrelu(x),
+    d feat = d el with d er added on the first S rows.
+
+    sim=True rounds to bf16 what the kernels store in bf16 (e, a, a_drop, da, de, d_er, rst, d el, d feat, d attn) and goes on
+    from the rounded values.  ``fault`` (planted faults of tests/test_bounds.py), a dict of
+      drop_fwd:   edge ids left out of the destination side (never seen: their e stays 0, no softmax, aggregation or d er term)
+      drop_agg:   edge ids left out of the aggregation sum only
+      drop_t:     edge ids left out of t (the softmax backward's row sum)
+      drop_der:   edge ids left out of d er
+      drop_src:   edge ids left out of the by-source sum d el
+      no_drop_scale: the dropout backward multiplies by the mask without 1 / (1 - p)
+    Returns a dict of float64 tensors: e, a, ad, rst, mag_e, mag_rst and, with g, da, t, de, d_er, d_el, d_feat, d_attn,
+    mag_de, mag_der, mag_del, mag_dfeat, mag_dattn.  The magnitudes never see the fault or the rounding."""
+    fault = fault or {}
+    dev = feat.device
+    src, dst = src.long(), dst.long()
+    B, K = src.numel(), feat.shape[0]
+    f = feat.double().view(K, H, D)
+    at = attn.double().reshape(1, H, D)
+    R = rbf if sim else (lambda x: x)
+
+    def keep(name):
+        m = torch.ones(B, dtype=torch.float64, device=dev)
+        if name in fault:
+            m[torch.as_tensor(fault[name], dtype=torch.long, device=dev)] = 0.0
+        return m[:, None]
+
+    k_fwd, k_agg, k_t, k_der, k_src = keep("drop_fwd"), keep("drop_agg"), keep("drop_t"), keep("drop_der"), keep("drop_src")
+    el, er = f[src], f[dst]
+    x = el + er
+    lr = torch.where(x > 0, x, slope * x)
+    lp = torch.where(x > 0, torch.ones_like(x), torch.full_like(x, slope))
+    e_exact = (at * lr).sum(-1)
+    out = dict(mag_e=(at.abs() * lr.abs()).sum(-1))
+    e = R(e_exact) * k_fwd
+    # softmax over the in-edges that are seen (an unseen edge gets no coefficient)
+    m = _seg_max(torch.where(k_fwd > 0, e, torch.full_like(e, -float("inf"))), dst, S)
+    ex = torch.exp(e - m[dst]) * k_fwd
+    a = R(ex / _seg_sum(ex, dst, S)[dst])
+    a = torch.nan_to_num(a)
+    if mask is not None:
+        ms = mask.double() / (1.0 - p)
+    else:
+        ms = torch.ones_like(a)
+    ad = R(a * ms)
+    rst = R(_seg_sum((ad * k_agg)[:, :, None] * el, dst, S))
+    out.update(e=e, a=a, ad=ad, rst=rst.view(S, H * D))
+    out["mag_rst"] = _seg_sum(ad.abs()[:, :, None] * el.abs(), dst, S).view(S, H * D)
+    if g is None:
+        return out
+    gd = g.double().view(S, H, D)[dst]
+    dot = (gd * el).sum(-1)
+    dscale = (mask.double() if fault.get("no_drop_scale") else ms) if mask is not None else ms
+    da = R(R(dot) * dscale) * k_fwd
+    t = _seg_sum(a * da * k_t, dst, S)
+    de = R(a * (da - t[dst])) * k_fwd
+    d_er = R(at[0] * _seg_sum((de * k_der)[:, :, None] * lp, dst, S))
+    d_el = R(torch.zeros(K, H, D, dtype=torch.float64, device=dev).index_add_(
+        0, src, k_src[:, :, None] * (de[:, :, None] * at * lp + ad[:, :, None] * gd)))
+    d_feat = d_el.clone()
+    d_feat[:S] = R(d_feat[:S] + d_er)
+    d_attn = R((de[:, :, None] * lr).sum(0).reshape(-1))
+    # magnitudes: the softmax backward's d e = a (da - t) enters as a (|da| + sum a |da|) (the cancellation in da - t)
+    a_abs, da_abs = a.abs(), da.abs()
+    mag_de = a_abs * (da_abs + _seg_sum(a_abs * da_abs, dst, S)[dst])
+    mag_der = at[0].abs() * _seg_sum(mag_de[:, :, None] * lp, dst, S)
+    mag_del = torch.zeros(K, H, D, dtype=torch.float64, device=dev).index_add_(
+        0, src, mag_de[:, :, None] * at.abs() * lp + ad.abs()[:, :, None] * gd.abs())
+    mag_dfeat = mag_del.clone()
+    mag_dfeat[:S] += mag_der
+    out.update(da=da, t=t, de=de, d_er=d_er.view(S, H * D), d_el=d_el.view(K, H * D), d_feat=d_feat.view(K, H * D), d_attn=d_attn,
+               mag_de=mag_de, mag_der=mag_der.view(S, H * D), mag_del=mag_del.view(K, H * D), mag_dfeat=mag_dfeat.view(K, H * D),
+               mag_dattn=(mag_de[:, :, None] * lr.abs()).sum(0).reshape(-1))
+    return out
+
+
+def gat_autograd(src, dst, S, feat, attn, H, D, g, slope=NEG_SLOPE, mask=None, p=0.0):
+    """fp64 autograd of model.py:82-99 (share_weights: feat_dst = feat_src[:S]) on the bf16 operands: (e, rst, d feat, d attn)."""
+    src, dst = src.long(), dst.long()
+    K = feat.shape[0]
+    f = feat.detach().double().requires_grad_(True)
+    at = attn.detach().double().reshape(1, H, D).requires_grad_(True)
+    fs = f.view(K, H, D)
+    x = torch.nn.functional.leaky_relu(fs[src] + fs[dst], slope)
+    e = (x * at).sum(-1)
+    m = _seg_max(e.detach(), dst, S)
+    ex = torch.exp(e - m[dst])
+    a = ex / _seg_sum(ex, dst, S)[dst]
+    if mask is not None:
+        a = a * mask.double() / (1.0 - p)
+    rst = _seg_sum(a[:, :, None] * fs[src], dst, S).view(S, H * D)
+    (rst * g.double()).sum().backward()
+    return e.detach(), rst.detach(), f.grad, at.grad.reshape(-1)
+
+
+# ------------------------------------------------------------------------------------------------ designed blocks
+class Spec:
+    """A block as plain CPU tensors: n_src K, n_dst S, CSR by destination (indptr int64 [S+1], src, dst int64 [B])."""
+
+    def __init__(self, K, S, indptr, src, dst):
+        self.K, self.S, self.indptr, self.src, self.dst = int(K), int(S), indptr, src, dst
+
+    @property
+    def B(self):
+        return int(self.src.numel())
+
+    def in_degrees(self):
+        return self.indptr[1:] - self.indptr[:-1]
+
+    def out_degrees(self):
+        return torch.bincount(self.src, minlength=self.K)
+
+
+def from_degrees(degs, K, seed, hub_src=None, hub_every=0, n_unused=0):
+    """Destination i gets degs[i] in-edges; sources drawn uniformly from [0, K - n_unused) (the last n_unused sources never
+    send), every ``hub_every``-th edge from source ``hub_src``.  Deterministic in ``seed``."""
+    gen = torch.Generator().manual_seed(seed)
+    degs = torch.as_tensor(degs, dtype=torch.int64)
+    S, B = degs.numel(), int(degs.sum())
+    indptr = torch.zeros(S + 1, dtype=torch.int64)
+    indptr[1:] = torch.cumsum(degs, 0)
+    dst = torch.repeat_interleave(torch.arange(S), degs)
+    src = torch.randint(0, K - n_unused, (B,), generator=gen)
+    if hub_src is not None and hub_every:
+        src[::hub_every] = hub_src
+    return Spec(K, S, indptr, src, dst)
+
+
+EDGE_DEGREES = [0, 1, 2, 15, 16, 17, 63, 64, 65, 255, 256, 257, 512, 513, 1500]
+HUB_DEGREE = 12000                     # ~47 segments of 256 edges
+
+
+def edge_shape_spec(seed=11):
+    """In-degrees 0, 1, 2, 15..17, 63..65, 255..257, 512, 513, 1500, one hub of 12 000 (47 segments) and 240 ordinary rows
+    (3..94); source S + 5 sends every 6th edge (> 3000 out-edges), the last 16 sources send none, the first S sources are the
+    destinations.  ~27 K edges."""
+    degs = EDGE_DEGREES + [HUB_DEGREE] + [3 + (7 * i) % 92 for i in range(240)]
+    S = len(degs)
+    return from_degrees(degs, S + 1400, seed, hub_src=S + 5, hub_every=6, n_unused=16)
+
+
+def many_hubs_spec(seed=12, n_hubs=1536):
+    """1536 destinations of 257..1100 in-edges (4 953 virtual workgroups, far more than the chip holds at
+    once) beside 64 short rows; ~1.05 M edges."""
+    degs = [257 + (613 * i) % 844 for i in range(n_hubs)] + [1 + i % 9 for i in range(64)]
+    S = len(degs)
+    return from_degrees(degs, S + 20000, seed, n_unused=8)
+
+
+def row_count_spec(S, seed=13):
+    """S destinations (16 384: the one-sweep branch of k_gat_segments; 16 385: the two-pass branch), rows of 0..7 in-edges and
+    six hubs of 300..1400."""
+    degs = [i % 8 for i in range(S)]
+    for q, d in enumerate((300, 513, 800, 1024, 1100, 1400)):
+        degs[(q * 2731 + 17) % S] = d
+    return from_degrees(degs, S + 3000, seed, n_unused=8)
+
+
+def spmm_band_spec(B, seed):
+    """~B edges over 4 000 destinations (row lengths 1..2B/4000, none above 16 384), one source with >= 3000 out-edges."""
+    S = 4000
+    mean = B // S
+    degs = [1 + (i * 37) % (2 * mean - 1) for i in range(S)]
+    degs[0] += B - sum(degs)
+    assert 0 < degs[0] <= 16384
+    return from_degrees(degs, S + 6000, seed, hub_src=S + 1, hub_every=max(1, B // 3500), n_unused=8)
+
+
+def to_block(spec, device):
+    """A bliss Block of ``spec`` on ``device``."""
+    from bliss_gnn_amd.graph import Block
+    i32 = lambda t: t.to(torch.int32).to(device)
+    z = torch.zeros(spec.B, dtype=torch.int32, device=device)
+    return Block(None, spec.K, spec.S, i32(spec.indptr), i32(spec.src), i32(spec.dst), z, z.clone(),
+                 torch.arange(spec.K, dtype=torch.int32, device=device))
+
+
+def padded_block(spec, device, extra_s=37, extra_k=101, extra_b=777):
+    """The capacity-padded copy of ``spec`` as the static-shape sampler leaves it: src / dst longer than the true edge count,
+    their padding holding valid but wrong ids (the hub rows' and the hub source's); indptr rows past the true S repeating the
+    edge count (csrc/sampler.hip); n_src / n_dst the capacities; _counts_dev an int32[10] laid out as bliss_layer_counts_t
+    (S at word 0, B at word 4) and _nnz_ptr at its word 4 (_engine.py)."""
+    from bliss_gnn_amd.graph import Block
+    S, K, B = spec.S, spec.K, spec.B
+    Sc, Kc, Bc = S + extra_s, K + extra_k, B + extra_b
+    deg = spec.in_degrees()
+    hub_row = int(deg.argmax())
+    hub_src = int(spec.out_degrees().argmax())
+    indptr = torch.cat([spec.indptr, torch.full((extra_s,), B, dtype=torch.int64)])
+    src = torch.cat([spec.src, torch.full((extra_b,), hub_src, dtype=torch.int64)])
+    dst = torch.cat([spec.dst, torch.full((extra_b,), hub_row, dtype=torch.int64)])
+    counts = torch.zeros(10, dtype=torch.int32)
+    counts[0], counts[4] = S, B
+    counts = counts.to(device)
+    i32 = lambda t: t.to(torch.int32).to(device)
+    z = torch.zeros(Bc, dtype=torch.int32, device=device)
+    blk = Block(None, Kc, Sc, i32(indptr), i32(src), i32(dst), z, z.clone(), torch.arange(Kc, dtype=torch.int32, device=device))
+    blk._counts, blk._counts_dev = None, counts
+    blk._nnz_ptr = counts.data_ptr() + 16
+    return blk
+
+
+def gat_inputs(spec, H, D, seed, device, positive=False, loud=None, loud_scale=64.0):
+    """bf16 operands of the message passing on ``spec``: feat [K, H*D] (= fc_src(h)), attn [1, H, D] scaled so that every logit's
+    magnitude sum_d |attn| |lrelu(x)| is at most 1 (the GATv2 constants below assume it), g = d rst [S, H*D].  ``positive``:
+    feat and g > 0 (no cancellation: what some planted faults need to be seen).  ``loud``: source ids whose feature rows are
+    multiplied by ``loud_scale`` (the dedicated sources of loud_segments)."""
+    gen = torch.Generator().manual_seed(seed)
+    K, S = spec.K, spec.S
+    feat = torch.randn(K, H * D, generator=gen) * 0.5
+    g = torch.randn(S, H * D, generator=gen)
+    if positive:
+        feat, g = feat.abs() + 0.05, g.abs() + 0.05
+    if loud is not None and len(loud):
+        feat[torch.as_tensor(loud, dtype=torch.long)] *= loud_scale
+    attn = torch.randn(H * D, generator=gen)
+    feat, g = feat.bfloat16().to(device), g.bfloat16().to(device)
+    attn = attn.double().to(device)
+    f = feat.double().view(K, H, D)
+    src, dst = spec.src.to(device), spec.dst.to(device)
+    mag = torch.zeros(H, dtype=torch.float64, device=device)
+    for b0 in range(0, spec.B, 1 << 16):                   # (in slices: [B, H, D] at once is large on the many-hubs block)
+        x = f[src[b0:b0 + (1 << 16)]] + f[dst[b0:b0 + (1 << 16)]]
+        lr = torch.where(x > 0, x, NEG_SLOPE * x)
+        mag = torch.maximum(mag, (attn.view(1, H, D).abs() * lr.abs()).sum(-1).amax(0))
+    attn = (attn.view(1, H, D) * (0.9 / mag.clamp(min=1e-30)).view(1, H, 1)).bfloat16()
+    return feat, attn, g
+
+
+SEG = 256                                # edges per workgroup of the fused GATv2 kernels (GF_SEG): longer rows are shared
+
+
+def loud_segments(spec, which="cycle"):
+    """A copy of ``spec`` in which one 256-edge segment of every shared row (in-degree > 256) takes all its edges from a source of
+    its own, appended after the last source: with gat_inputs(positive=True, loud=ids) that segment carries 64x the features of
+    the others, so losing it from t, from d er or from the aggregation moves the row by far more than the bound (shown on the
+    CPU by tests/test_bounds.py for every block the GPU runs with this pattern).  ``which``: the segment of a row with G
+    segments -- "first" (0), "middle" (G // 2), "last" (G - 1) or "cycle" (row mod G: every position on a block with many
+    shared rows).  Returns (spec, loud source ids, [(row, first edge, end)] of the loud segments)."""
+    deg = spec.in_degrees()
+    rows = (deg > SEG).nonzero().reshape(-1).tolist()
+    src = spec.src.clone()
+    ids, segs = [], []
+    for n, r in enumerate(rows):
+        G = (int(deg[r]) + SEG - 1) // SEG
+        q = {"first": 0, "middle": G // 2, "last": G - 1, "cycle": r % G}[which]
+        b0 = int(spec.indptr[r]) + q * SEG
+        b1 = min(b0 + SEG, int(spec.indptr[r + 1]))
+        src[b0:b1] = spec.K + n
+        ids.append(spec.K + n)
+        segs.append((r, b0, b1))
+    return Spec(spec.K + len(rows), spec.S, spec.indptr, src, spec.dst), ids, segs
+
+
+def gat_k(me):
+    """(k_ulp, k_mag) per GATv2 tensor for logits of magnitude sum_d |attn| |lrelu(x)| <= me (derivation: the docstring of
+    tests/test_gpu_grad_edges.py).  The softmax's relative error E_A = 8 for me <= 1 (logit error <= 2 * 2^-8) and 7 me + 2
+    above (logit error <= 2.5 me 2^-8, twice, plus the rounding of e - max, 2 me 2^-8, and the exp / sum / division
+    roundings, 2): rst E_A + 1, d e 2 E_A + 1.5, d feat and d attn 2 E_A + 2, d feat's destination rows one more."""
+    ea = 8.0 if me <= 1 else 7.0 * me + 2.0
+    return {"e": (1, 2), "rst": (1, ea + 1), "d_feat_src": (1, 2 * ea + 2), "d_feat_dst": (1, 2 * ea + 3), "d_attn": (1, 2 * ea + 2)}
+
+
+# Constants of the bound per tensor: (k_ulp, k_mag).  Derivations are in the docstrings of the tests that use them
+# (tests/test_gpu_grad_edges.py); tests/test_bounds.py shows on designed blocks that the planted faults fail them.
+GAT_K = gat_k(1.0)
+SPMM_K = {"bf16": (1, 0.25), "fp32": (0, 0.25)}
+GCN_K = (1, 4)
+SPMM_MAX_ROW = 16384                     # the SpMM constant holds for rows (by destination or by source) up to this length
+
+
+def check_gat_layer(layer, blk, h, out, e, gout, feat, d_feat, what, mask=None, p=0.0):
+    """Per-element checks of a GATv2Conv layer (no fc_src bias): the message passing on the layer's own feat = fc_src(h) against
+    fp64 autograd with gat_k(largest logit magnitude of this data), then the layer's output and the gradients of h and of
+    fc_src's weight through the GEMMs, on magnitudes.  The GEMMs take d feat with |error| <= (k + 2) 2^-8 mag (its ulp term
+    is at most 2^-7 |ref| <= 2^-7 mag) to |W| or |h|, and add their own rounding and the residual's: k_mag = k(d feat, rows
+    < S) + 3 for d h and d W.  The output adds the residual's GEMM rounding and the final add: k(rst) + 1.  Returns the
+    largest ratio of each tensor."""
+    import torch.nn as nn
+    H, D = layer._num_heads, layer._out_feats
+    S, HD = blk.num_dst_nodes(), layer._num_heads * layer._out_feats
+    src, dst = blk.src, blk.dst
+    g64 = gout.reshape(S, HD).double()
+    attn = layer.attn.detach()
+    ref_e, ref_rst, ref_df, ref_da = gat_autograd(src, dst, S, feat, attn, H, D, g64, mask=mask, p=p)
+    T = gat_terms(src, dst, S, feat, attn, H, D, g64, mask=mask, p=p)
+    k = gat_k(float(T["mag_e"].max()))
+    hd = h.detach().double()
+    ref_out, mag_out, dres = ref_rst.clone(), T["mag_rst"].clone(), None
+    if isinstance(layer.res_fc, nn.Linear):
+        rW = layer.res_fc.weight.detach().double()
+        ref_out += hd[:S] @ rW.t()
+        mag_out += hd[:S].abs() @ rW.abs().t()
+        dres = (g64 @ rW, g64.abs() @ rW.abs())
+    elif layer.res_fc is not None:
+        ref_out += hd[:S]
+        mag_out += hd[:S].abs()
+        dres = (g64, g64.abs())
+    W = layer.fc_src.weight.detach().double()
+    ref_dh, mag_dh = ref_df @ W, T["mag_dfeat"] @ W.abs()
+    if dres is not None:
+        ref_dh[:S] += dres[0]
+        mag_dh[:S] += dres[1]
+    kg = k["d_feat_dst"][1] + 3
+    r = {"e": assert_within(e.reshape(-1, H), ref_e, T["mag_e"], *k["e"], what + " e"),
+         "out": assert_within(out.reshape(S, HD), ref_out, mag_out, 1, k["rst"][1] + 1, what + " out"),
+         "d_feat_dst": assert_within(d_feat[:S], ref_df[:S], T["mag_dfeat"][:S], *k["d_feat_dst"], what + " d feat (rows < S)"),
+         "d_feat_src": assert_within(d_feat[S:], ref_df[S:], T["mag_dfeat"][S:], *k["d_feat_src"], what + " d feat (rows >= S)"),
+         "d_attn": assert_within(layer.attn.grad.reshape(-1), ref_da, T["mag_dattn"], *k["d_attn"], what + " d attn"),
+         "d_h": assert_within(h.grad, ref_dh, mag_dh, 1, kg, what + " d h"),
+         "d_W": assert_within(layer.fc_src.weight.grad, ref_df.t() @ hd, T["mag_dfeat"].t() @ hd.abs(), 1, kg, what + " d W")}
+    return r

@@ -4,6 +4,8 @@ import numpy as np
 import pytest
 import torch
 
+from bounds import check_gat_layer
+
 pytestmark = pytest.mark.gpu
 
 
@@ -12,6 +14,12 @@ def _ulp(a, b):
         x = t.detach().cpu().contiguous().view(torch.int16).to(torch.int32).numpy() & 0xFFFF
         return np.where(x & 0x8000, -(x & 0x7FFF), x & 0x7FFF)
     return np.abs(key(a) - key(b))
+
+
+def _keep_feat(cap, o):
+    """Forward hook of fc_src: keep the layer's feat and its gradient (returns None: the output is not replaced)."""
+    cap["feat"] = o
+    o.retain_grad()
 
 
 def _block(cuda, V=3000, E=50000, fan=300, n_seeds=60, seed=41):
@@ -40,10 +48,15 @@ def test_fused_forward_has_the_bits_of_the_separate_kernels(cuda, monkeypatch, f
     for mode in ("1", "0"):
         monkeypatch.setenv("BLISS_GAT_FUSED", mode)
         hd = h.clone().requires_grad_(True)
+        cap = {}                                         # the layer's own feat = fc_src(h), and later its gradient
+        hook = layer.fc_src.register_forward_hook(lambda m, i, o: _keep_feat(cap, o))
         out, e = layer(blk, hd, get_attention=True)
+        hook.remove()
         layer.zero_grad(set_to_none=True)
         gout = torch.randn(out.shape, generator=torch.Generator().manual_seed(7)).bfloat16().to(cuda)
         (out * gout).float().sum().backward()
+        # per element, each path against fp64 (tests/bounds.py, constants of bounds.gat_k for this data's logits)
+        check_gat_layer(layer, blk, hd, out, e, gout, cap["feat"].detach(), cap["feat"].grad, "mode %s %dx%d" % (mode, H, D))
         outs[mode] = (out.detach().clone(), e.detach().clone(), hd.grad.clone(), layer.fc_src.weight.grad.clone(), layer.attn.grad.clone())
     f, u = outs["1"], outs["0"]
     assert torch.equal(f[1].view(torch.int16), u[1].view(torch.int16)), "logits"
@@ -82,6 +95,7 @@ def test_fused_backward_vs_fp32_autograd_with_dropout(cuda):
     h = (torch.randn(K, fin, generator=torch.Generator().manual_seed(6)) * 0.5).bfloat16()
     hd = h.to(cuda).requires_grad_(True)
     feat = layer.fc_src(hd)
+    feat.retain_grad()
     st = layer._fused_state(cuda)
     rst, e = _GatFusedMP.apply(feat, layer.attn, blk, H, D, 0.2, p, st)
     node = rst.grad_fn
@@ -106,6 +120,8 @@ def test_fused_backward_vs_fp32_autograd_with_dropout(cuda):
     assert (hd.grad.float().cpu().double() - hr.grad).abs().max() <= 3 * tol(hr.grad)
     assert (layer.fc_src.weight.grad.float().cpu().double() - W.grad).abs().max() <= 3 * tol(W.grad)
     assert (layer.attn.grad.float().cpu().double().view(-1) - at.grad.view(-1)).abs().max() <= 3 * tol(at.grad)
+    # per element (tests/bounds.py): under the kernel's mask, against fp64 on the layer's feat, constants of bounds.gat_k
+    check_gat_layer(layer, blk, hd, rst, e, gout.to(cuda), feat.detach(), feat.grad, "dropout", mask=keep.to(cuda), p=p)
     # the launch counter advanced: the next launch draws another mask
     with torch.no_grad():
         rst2, _ = _GatFusedMP.apply(feat.detach(), layer.attn.detach(), blk, H, D, 0.2, p, st)

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from conftest import bf16_bits, bits_to_bf16, golden_cases, load_golden
+from bounds import GAT_K, GCN_K, SPMM_K, assert_within, check_gat_layer, gat_terms, spmm_terms
 
 pytestmark = pytest.mark.gpu
 
@@ -211,10 +212,17 @@ def test_spmm_forward_backward_vs_fp32(cuda):
         coef = w.float() / deg[dst]
         gref = torch.zeros(K, D).index_add_(0, src, gout.float()[dst] * coef[:, None])
         assert (hd.grad.float().cpu() - gref).abs().max() <= (gref.abs().max() * 2 ** -8 + 1e-6)
+        # per element (tests/bounds.py): fp64 reference, magnitude = the same sums on absolute values
+        r64, m64 = spmm_terms(src, dst, S, h, w, True)
+        assert_within(out32.cpu(), r64, m64, *SPMM_K["fp32"], "spmm fp32 out")
+        assert_within(out16.cpu(), r64, m64, *SPMM_K["bf16"], "spmm bf16 out")
+        g64, gm64 = spmm_terms(src, dst, S, gout, w, True, by_src=True, n_out=K)
+        assert_within(hd.grad.cpu(), g64, gm64, *SPMM_K["bf16"], "spmm d h")
         # unweighted sum (edge_weight=None, mean=False)
         out_sum = weighted_aggregate(blk, hd, None, mean=False, out_fp32=True)
         ref_sum = torch.zeros(S, D).index_add_(0, dst, h.float()[src])
         assert torch.allclose(out_sum.cpu(), ref_sum, rtol=1e-4, atol=1e-5)
+        assert_within(out_sum.cpu(), *spmm_terms(src, dst, S, h, None, False), *SPMM_K["fp32"], "spmm sum")
 
 
 def test_embed_norm_vs_fp32(cuda):
@@ -511,6 +519,21 @@ def test_gcn_layer_vs_fp32(cuda):
         agg = lambda z: torch.zeros(S, z.shape[1]).index_add_(0, dst, z[src] * w[:, None])
         ref = (agg(x @ W) if fin > fout else agg(x) @ W) * idg[:, None] + layer.bias.float().cpu()
         assert (out - ref).abs().max() <= 4 * ref.abs().max() * 2 ** -8
+        # per element (tests/bounds.py, GCN_K as in test_gpu_grad_edges.py): fp64, magnitude = the formula on absolute values
+        od64 = torch.bincount(src, minlength=K).clamp(min=1).double().pow(-0.5)
+        idg64 = torch.bincount(dst, minlength=S).clamp(min=1).double().pow(-0.5)
+        x64, W64, w64 = h.double().cpu() * od64[:, None], layer.weight.detach().double().cpu(), blk.edata["edge_weights"].double().cpu()
+        agg64 = lambda z, ww: torch.zeros(S, z.shape[1], dtype=torch.float64).index_add_(0, dst, z[src] * ww[:, None])
+        b64 = layer.bias.detach().double().cpu()
+        ref64 = (agg64(x64 @ W64, w64) if fin > fout else agg64(x64, w64) @ W64) * idg64[:, None] + b64
+        mag64 = agg64(x64.abs(), w64.abs()) @ W64.abs() * idg64[:, None] + b64.abs()
+        assert_within(out, ref64, mag64, *GCN_K, "graphconv out")
+
+
+def _keep_feat(cap, o):
+    """Forward hook of fc_src: keep the layer's feat and its gradient (returns None: the output is not replaced)."""
+    cap["feat"] = o
+    o.retain_grad()
 
 
 def _gat_ref(blk_src, blk_dst, S, h, W, attn, H, D, slope, res_W=None):
@@ -546,7 +569,10 @@ def test_gatv2_layer_forward_backward_vs_fp32(cuda):
         layer = layer.to(cuda).bfloat16()
         h = (torch.randn(K, fin, generator=torch.Generator().manual_seed(6)) * 0.5).bfloat16()
         hd = h.to(cuda).requires_grad_(True)
+        cap = {}                                         # the layer's own feat = fc_src(h), and later its gradient
+        hook = layer.fc_src.register_forward_hook(lambda m, i, o: _keep_feat(cap, o))
         out, e = layer(blk, hd, get_attention=True)
+        hook.remove()
         W = layer.fc_src.weight.detach().float().cpu().requires_grad_(True)
         at = layer.attn.detach().float().cpu().requires_grad_(True)
         hr = h.float().requires_grad_(True)
@@ -558,6 +584,9 @@ def test_gatv2_layer_forward_backward_vs_fp32(cuda):
             ref_out = ref_out + hr[:S].view(S, H, D)
         tol = lambda t: 6 * t.abs().max() * 2 ** -8
         assert (e.float().cpu().view(-1, H) - ref_e).abs().max() <= tol(ref_e)
+        # per element (tests/bounds.py): the logits against fp64 on feat = fc_src(h), GAT_K["e"]
+        T = gat_terms(blk.src, blk.dst, S, layer.fc_src(hd.detach()).detach(), layer.attn.detach(), H, D)
+        assert_within(e.view(-1, H), T["e"], T["mag_e"], *GAT_K["e"], "gatv2 logits")
         assert (out.float().cpu() - ref_out).abs().max() <= tol(ref_out)
         gout = torch.randn(S, H, D, generator=torch.Generator().manual_seed(7)).bfloat16()
         (out * gout.to(cuda)).float().sum().backward()
@@ -565,6 +594,9 @@ def test_gatv2_layer_forward_backward_vs_fp32(cuda):
         assert (hd.grad.float().cpu() - hr.grad).abs().max() <= 3 * tol(hr.grad)
         assert (layer.fc_src.weight.grad.float().cpu() - W.grad).abs().max() <= 3 * tol(W.grad)
         assert (layer.attn.grad.float().cpu().view(-1) - at.grad.view(-1)).abs().max() <= 3 * tol(at.grad)
+        # per element (tests/bounds.py): out, d h, d W, d attn and the layer's d feat against fp64 on its own feat, with the
+        # constants of bounds.gat_k for this data's logits; d h and d W through the GEMMs on magnitudes
+        check_gat_layer(layer, blk, hd, out, e, gout.to(cuda), cap["feat"].detach(), cap["feat"].grad, "gatv2 layer %d" % fin)
 
 
 def test_gat_alpha_and_exp3_match_oracle(cuda):
