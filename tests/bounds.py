@@ -1,4 +1,5 @@
-"""Per-element error bounds for the bf16 message-passing kernels, their fp64 references, and designed blocks.
+"""Per-element error bounds for the bf16 message-passing kernels and the dense SAGE kernels, their fp64 references, and
+designed blocks and inputs.
 
 A plain helper module, imported by the tests like shard_cpu_ops.py.  Every check has the form
 
@@ -407,3 +408,219 @@ def check_gat_layer(layer, blk, h, out, e, gout, feat, d_feat, what, mask=None, 
          "d_h": assert_within(h.grad, ref_dh, mag_dh, 1, kg, what + " d h"),
          "d_W": assert_within(layer.fc_src.weight.grad, ref_df.t() @ hd, T["mag_dfeat"].t() @ hd.abs(), 1, kg, what + " d W")}
     return r
+
+
+# ------------------------------------------------------------------------------------------------ dense SAGE kernels
+# csrc/sage.hip (k_tile_gemm), csrc/sage_bwd.hip (k_dgrad, k_wgrad + k_wgrad_reduce).  They accumulate in fp32 and round to
+# bf16 once: k_ulp = 1 (half a spacing of the fp32 sum, which may lie one binade above ref) and k_mag = n_terms * 2^-16
+# (n_terms fp32 roundings of relative size 2^-24, in units of 2^-8).  A bf16 value stored between two launches adds 1 to k_mag
+# (half a spacing <= 2^-8 of its magnitude); a stored SpMM result adds SPMM_K's 0.25 as well.
+TILE, KSTEP, SLAB = 32, 16, 64           # output tile of a wave, k of one MFMA, k of one W slab in LDS
+WGRAD_TARGET, WGRAD_COLS, WGRAD_MIN_ROWS, WGRAD_STEP = 80, 128, 64, 32
+
+
+def dense_k(n_terms, stored=0.0):
+    """(k_ulp, k_mag) of an fp32-accumulated sum of ``n_terms`` terms rounded to bf16 once, whose operands carry ``stored``
+    bf16 roundings (in units of 2^-8 of the magnitude) from earlier launches."""
+    return 1, stored + n_terms * 2.0 ** -16
+
+
+def _dual(a1, b1, a2, b2, bias, m2, fault, acc):
+    """a1 @ b1 (+ a2 @ b2 on rows < m2) + bias with b = [k, n], accumulated in ``acc``; (value with the planted fault, fp64
+    magnitude without it)."""
+    fault = fault or {}
+    M = a1.shape[0]
+    A1, B1 = a1.to(acc), b1.to(acc)
+    if fault.get("drop_w_tail"):                                               # the k beyond the last full 64-slab never loaded
+        kk = A1.shape[1] // SLAB * SLAB
+        A1, B1 = A1[:, :kk], B1[:kk]
+    ref = A1 @ B1
+    mag = a1.double().abs() @ b1.double().abs()
+    if "drop_kstep" in fault:                                                  # (row0, col0, k0): one MFMA of one tile skipped
+        r0, c0, k0 = fault["drop_kstep"]
+        ref[r0:r0 + TILE, c0:c0 + TILE] -= A1[r0:r0 + TILE, k0:k0 + KSTEP] @ B1[k0:k0 + KSTEP, c0:c0 + TILE]
+    if a2 is not None:
+        m = min(M if m2 is None else int(m2), M, a2.shape[0])
+        mf = max(0, min(m + int(fault.get("m2_shift", 0)), M, a2.shape[0]))
+        ref[:mf] += a2[:mf].to(acc) @ b2.to(acc)
+        mag[:m] += a2[:m].double().abs() @ b2.double().abs()
+    if bias is not None:
+        ref += float(fault.get("bias_times", 1)) * bias.to(acc)
+        mag += bias.double().abs()
+    if "swap_tile" in fault:                                                   # (row0, col0): a full tile stored transposed
+        r0, c0 = fault["swap_tile"]
+        ref[r0:r0 + TILE, c0:c0 + TILE] = ref[r0:r0 + TILE, c0:c0 + TILE].t().clone()
+    return ref, mag
+
+
+def gemm_terms(a1, w1, a2=None, w2=None, bias=None, m2=None, fault=None, acc=torch.float64):
+    """The forward product of k_tile_gemm, W = [out, in]: a1 @ w1^T (+ a2 @ w2^T on rows < m2) + bias -> (ref, mag) [M, out].
+    ``acc=torch.float32`` is the kernel's restatement (fp32 accumulation; round the result with rbf).  ``fault``: drop_kstep
+    (row0, col0, k0), drop_w_tail, m2_shift +-1, bias_times 0 | 2, swap_tile (row0, col0); the magnitude never sees it."""
+    return _dual(a1, w1.t(), a2, None if w2 is None else w2.t(), bias, m2, fault, acc)
+
+
+def dgrad_terms(a1, w1, a2=None, w2=None, m2=None, fault=None, acc=torch.float64):
+    """The input gradient of k_dgrad: a1 @ w1 (+ a2 @ w2 on rows < m2) -> (ref, mag) [M, in].  Faults as gemm_terms."""
+    return _dual(a1, w1, a2, w2, None, m2, fault, acc)
+
+
+def wgrad_terms(d, x, rows, fault=None, acc=torch.float64):
+    """The weight and bias gradients of k_wgrad: d[:rows]^T @ x[:rows] and the column sums of d[:rows] ->
+    (dw, mag_dw, db, mag_db).  ``fault``: drop_rows_dw / drop_rows_db (row ids left out of the sum), extra_rows (that many rows
+    at and beyond the count included)."""
+    fault = fault or {}
+    rows = int(rows)
+    D, X = d[:rows].double(), x[:rows].double()
+    mag_dw, mag_db = D.abs().t() @ X.abs(), D.abs().sum(0)
+    n = rows + int(fault.get("extra_rows", 0))
+    kw, kb = torch.ones(n, dtype=torch.bool, device=d.device), torch.ones(n, dtype=torch.bool, device=d.device)
+    if "drop_rows_dw" in fault:
+        kw[torch.as_tensor(fault["drop_rows_dw"], dtype=torch.long, device=d.device)] = False
+    if "drop_rows_db" in fault:
+        kb[torch.as_tensor(fault["drop_rows_db"], dtype=torch.long, device=d.device)] = False
+    dw = d[:n][kw].to(acc).t() @ x[:n][kw].to(acc)
+    db = d[:n][kb].to(acc).sum(0)
+    return dw, mag_dw, db, mag_db
+
+
+def wgrad_plan(problems, target=WGRAD_TARGET):
+    """The chunk plan of one k_wgrad launch as csrc/sage_bwd.hip documents it, for [(rows_bound, k_in)] (one or two problems):
+    chunks = target / (column tiles of all problems together, 128 columns each), at most ceil(rows_bound / 64), at least 1;
+    rows_per_chunk = ceil(rows_bound / chunks) rounded up to 32; chunks = ceil(rows_bound / rows_per_chunk).  Returns
+    [(chunks, rows_per_chunk)] and the fp32 workspace (floats) the launch needs: chunks * 256 * (128 * column tiles + 4) each."""
+    tiles_all = sum(-(-k // WGRAD_COLS) for _, k in problems)
+    plan, floats = [], 0
+    for rows, k in problems:
+        chunks = max(1, min(target // tiles_all, -(-rows // WGRAD_MIN_ROWS)))
+        rpc = -(-(-(-rows // chunks)) // WGRAD_STEP) * WGRAD_STEP
+        chunks = -(-rows // rpc)
+        plan.append((chunks, rpc))
+        floats += chunks * 256 * (-(-k // WGRAD_COLS) * WGRAD_COLS + 4)
+    return plan, floats
+
+
+def wgrad_loud_rows(rows, chunks, rpc):
+    """The rows a chunked sum loses first: the last row of every chunk that holds rows, the first row of the next, and the last
+    valid row."""
+    ids = set()
+    for c in range(1, chunks):
+        if c * rpc < rows:
+            ids.update((c * rpc - 1, c * rpc))
+    ids.add(rows - 1)
+    return sorted(ids)
+
+
+def wgrad_inputs(rows_bound, n_out, k_in, seed, rows=None, loud=None, loud_scale=64.0, pad=float("nan")):
+    """bf16 operands of a weight gradient (CPU): d [rows_bound, n_out] ~ 0.05 N(0, 1), x [rows_bound, k_in] ~ N(0, 1); the rows
+    ``loud`` of d multiplied by ``loud_scale`` (one row then weighs as much in dW and db as 64 ordinary ones, and 4096 in their
+    variance: losing it moves most elements by more than the bound, shown by tests/test_bounds.py); rows at and beyond ``rows``
+    (the device-side count) filled with ``pad``."""
+    gen = torch.Generator().manual_seed(seed)
+    d = torch.randn(rows_bound, n_out, generator=gen) * 0.05
+    x = torch.randn(rows_bound, k_in, generator=gen)
+    if loud is not None and len(loud):
+        d[torch.as_tensor(loud, dtype=torch.long)] *= loud_scale
+    if rows is not None:
+        d[rows:], x[rows:] = pad, pad
+    return d.bfloat16(), x.bfloat16()
+
+
+# the loud-row weight gradients the GPU suite runs and tests/test_bounds.py shows to be sensitive: (rows_bound, rows, n_out, k_in)
+WGRAD_LOUD_CASES = [(11000, 10877, 256, 602), (5000, 4877, 256, 602)]
+
+
+def sage_layer_terms(src, dst, S, h, w_neigh, w_self, bias, ew=None, h_dst=None, g=None, mask=None, p=0.0, relu=True, sim=False,
+                     fault=None):
+    """A SAGEConv('mean') layer with its tail, as model.py:321-333 / nn.SAGEConv state it, in float64 with magnitudes:
+
+        rst = fc_self(h_dst) + fc_neigh(mean_w(h))   (in <= out: aggregate first)
+        rst = fc_self(h_dst) + mean_w(fc_neigh(h))   (in > out: Linear first),        out = mask / (1 - p) * rst
+
+    h [K, in], h_dst = h[:S] unless given, w_* [out, in], bias [out] or None, edge weights ew or None.  ``mask`` [S, out] is the
+    product of the ReLU's mask and the dropout's keep mask (the tests take it from the kernel's output, out > 0, after the forward
+    check has held every element of rst that is further than its bound from zero to the right side); None: rst > 0 when
+    ``relu``, else ones.  The forward is plain torch on its inputs: with float64 leaves that require grad, autograd through
+    ``out`` gives the reference gradients (tests/test_bounds.py checks the formulas below against it).  With ``g`` = d out the
+    backward is written out: d = mask / (1 - p) g, dW_self = d^T h_dst, db = sum d, and
+        aggregate first:  dW_neigh = d^T agg,  T = A^T d (the transposed aggregation),  dh = T W_neigh + [d W_self on rows < S]
+        Linear first:     dZ = A^T d,  dW_neigh = dZ^T h,  dh = dZ W_neigh + [d W_self on rows < S]
+    ``sim=True`` rounds to bf16 what the kernels store in bf16 between launches (Z, Y, agg, rst, out, d, dZ / T and every
+    result).  ``fault``: relu_mask_wrong (the backward takes the mask of fc_self's part alone), no_drop_scale (the backward
+    multiplies by the mask without 1 / (1 - p)), self_rows (fc_self's input gradient lands that many rows further down).
+    Returns a dict: rst, mag_rst, out, mag_out (= mag_rst under the mask), z / agg (the stored intermediate) and with g: d, d_mid (dZ or T), d_wn, d_ws, d_b, d_h, d_hdst
+    (only with h_dst given) and mag_<name> for each.  The magnitudes never see the fault or the rounding."""
+    fault = fault or {}
+    R = rbf if sim else (lambda t: t)
+    lin_first = w_neigh.shape[1] > w_neigh.shape[0]
+    K = h.shape[0]
+    hd = h[:S] if h_dst is None else h_dst
+    H, HD, Wn, Ws = h.double(), hd.double(), w_neigh.double(), w_self.double()
+    b = None if bias is None else bias.double()
+    agg_of = lambda t: spmm_terms(src, dst, S, t, ew, True)
+    y, mag_y = HD @ Ws.t(), HD.abs() @ Ws.abs().t()
+    if b is not None:
+        y, mag_y = y + b, mag_y + b.abs()
+    out = {}
+    if lin_first:
+        z = R(H @ Wn.t())
+        agg = R(agg_of(z)[0])
+        rst = R(R(y) + agg)
+        mag_rst = mag_y + agg_of(H.abs() @ Wn.abs().t())[1]
+        out["z"] = z
+    else:
+        agg = R(agg_of(H)[0])
+        mag_agg = agg_of(H.abs())[1]
+        rst = R(agg @ Wn.t() + y)
+        mag_rst = mag_agg @ Wn.abs().t() + mag_y
+    out["agg"] = agg
+    if mask is None:
+        mask = (rst > 0) if relu else torch.ones_like(rst, dtype=torch.bool)
+    ms = mask.double() / (1.0 - p)
+    out.update(rst=rst, mag_rst=mag_rst, out=R(rst * ms), mag_out=mag_rst * ms)
+    if g is None:
+        return out
+    G = g.double()
+    bmask = mask
+    if fault.get("relu_mask_wrong"):
+        bmask = mask & (y > 0)
+    d = R(G * (bmask.double() if fault.get("no_drop_scale") else bmask.double() / (1.0 - p)))
+    mag_d = G.abs() * ms
+    t_of = lambda t: spmm_terms(src, dst, S, t, ew, True, by_src=True, n_out=K)
+    d_mid, mag_mid = R(t_of(d)[0]), t_of(mag_d)[1]
+    if lin_first:
+        d_wn, mag_wn = R(d_mid.t() @ H), mag_mid.t() @ H.abs()
+    else:
+        d_wn, mag_wn = R(d.t() @ agg), mag_d.t() @ mag_agg
+    d_ws, mag_ws = R(d.t() @ HD), mag_d.t() @ HD.abs()
+    d_self, mag_self = d @ Ws, mag_d @ Ws.abs()
+    d_h, mag_h = d_mid @ Wn, mag_mid @ Wn.abs()
+    if h_dst is None:
+        s0 = int(fault.get("self_rows", 0))
+        d_h[s0:s0 + S] += d_self
+        mag_h[:S] += mag_self
+    else:
+        out.update(d_hdst=R(d_self), mag_d_hdst=mag_self)
+    out.update(d=d, mag_d=mag_d, d_mid=d_mid, mag_d_mid=mag_mid, d_wn=d_wn, mag_d_wn=mag_wn, d_ws=d_ws, mag_d_ws=mag_ws,
+               d_b=R(d.sum(0)), mag_d_b=mag_d.sum(0), d_h=R(d_h), mag_d_h=mag_h)
+    return out
+
+
+def sage_layer_k(fin, fout, rows, dropout, lin_first, two_nodes=False):
+    """(k_ulp, k_mag) per tensor of a SAGE layer on ``rows`` = max(K, S) block rows, from where the kernels round: a value stored
+    in bf16 between launches costs 1 (an SpMM result 1.25, SPMM_K's fp32 sum included), the dropout multiply of the forward
+    and of the backward 1 each, every fp32-accumulated GEMM its n_terms * 2^-16 (dense_k; wgrad: rows + at most 80 chunks).
+    Parallel paths into one sum take the longer one; the last rounding of each tensor is k_ulp.
+      Linear first:    out: Z, agg (2.25);  dZ (1.25) in front of dW_neigh and dh;  dW_self, db, d h_dst: nothing stored.
+      aggregate first: out: agg (1.25);  dW_neigh: agg (1.25);  dh: T (1.25);  dW_self, db, d h_dst: nothing stored.
+    ``two_nodes``: the input gradient passes one more stored value -- dZ W_neigh in front of the index_add_ of fc_self's part
+    (_SageLinearSplit with gathered destinations) or of addmm_ (BLISS_SAGE_MFMA_BWD=0), d W_neigh in front of the transposed
+    SpMM whose stored result addmm_ then adds to (_SageAggDual with BLISS_SAGE_MFMA_BWD=0): dh 2.25.  (_SageDualLinear stores
+    d agg = d W_neigh, 1, and the transposed SpMM of ops.spmm's backward rounds last: 1.25 as well.)"""
+    dr = 1.0 if dropout else 0.0
+    wg = (rows + WGRAD_TARGET) * 2.0 ** -16
+    fwd = (fin + 1) * 2.0 ** -16 if lin_first else (2 * fin + 1) * 2.0 ** -16
+    return {"out": (1, (2.25 if lin_first else 1.25) + dr + fwd),
+            "d_wn": (1, 1.25 + dr + wg), "d_ws": (1, dr + wg), "d_b": (1, dr + wg),
+            "d_h": (1, (2.25 if two_nodes else 1.25) + dr + 2 * fout * 2.0 ** -16),
+            "d_hdst": (1, dr + fout * 2.0 ** -16)}

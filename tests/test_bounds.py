@@ -5,8 +5,9 @@ dropout scale -- fails the same bound with the same constants (bounds.GAT_K, bou
 import pytest
 import torch
 
-from bounds import (GAT_K, SPMM_K, assert_within, from_degrees, gat_autograd, gat_inputs, gat_terms, rbf, spmm_terms,
-                    ulp_bf16)
+from bounds import (GAT_K, SPMM_K, WGRAD_LOUD_CASES, assert_within, dense_k, dgrad_terms, from_degrees, gat_autograd, gat_inputs,
+                    gat_terms, gemm_terms, rbf, sage_layer_k, sage_layer_terms, spmm_terms, ulp_bf16, wgrad_inputs, wgrad_loud_rows,
+                    wgrad_plan, wgrad_terms)
 
 CPU = torch.device("cpu")
 
@@ -307,3 +308,197 @@ def test_loud_segment_inputs_of_the_gpu_suite_expose_a_lost_segment(block, which
     for name in ("drop_agg", "drop_t", "drop_der"):
         with pytest.raises(AssertionError, match="over the bound"):
             _gat_check(spec, gat_terms(*args, sim=True, fault={name: list(range(b0, b1))}), ref)
+
+
+# ------------------------------------------------------------------------------------------------ dense SAGE kernels
+# The "kernel" here is the restatement the derivation rests on: fp32 accumulation (acc=torch.float32), one rounding to bf16.
+# Constants: bounds.dense_k(n_terms) = (1, n_terms * 2^-16) -- k_ulp 1: half a spacing of the fp32 sum, which may lie one
+# binade above ref; k_mag: n_terms fp32 roundings of relative size 2^-24 in units of 2^-8.  n_terms = K1 + K2 (+ 1 with a
+# bias) for the forward and dgrad, rows + chunks for wgrad.
+F32 = torch.float32
+
+
+def _dense_ops(M=130, K1=150, K2=70, N=100, m2=77, seed=5):
+    gen = torch.Generator().manual_seed(seed)
+    rb = lambda *s: torch.randn(*s, generator=gen).bfloat16()
+    return dict(a1=rb(M, K1), w1=rb(N, K1) / K1 ** 0.5, a2=rb(M, K2), w2=rb(N, K2) / K2 ** 0.5, bias=rb(N), m2=m2)
+
+
+def _fwd_check(o, fault=None, what="gemm"):
+    ref, mag = gemm_terms(**o)
+    got = rbf(gemm_terms(**o, fault=fault, acc=F32)[0])
+    return assert_within(got, ref, mag, *dense_k(o["a1"].shape[1] + o["a2"].shape[1] + 1), what)
+
+
+def _dgrad_ops(M=130, K1=100, K2=41, N=150, m2=77, seed=6):
+    gen = torch.Generator().manual_seed(seed)
+    rb = lambda *s: torch.randn(*s, generator=gen).bfloat16()
+    return dict(a1=rb(M, K1) * 0.1, w1=rb(K1, N) * 0.2, a2=rb(M, K2) * 0.1, w2=rb(K2, N) * 0.2, m2=m2)
+
+
+def _dgrad_check(o, fault=None):
+    ref, mag = dgrad_terms(**o)
+    got = rbf(dgrad_terms(**o, fault=fault, acc=F32)[0])
+    return assert_within(got, ref, mag, *dense_k(o["a1"].shape[1] + o["a2"].shape[1]), "dgrad")
+
+
+def _wgrad_check(d, x, rows, chunks, fault=None, which=("dw", "db")):
+    dw, mag_dw, db, mag_db = wgrad_terms(d, x, rows)
+    gw, _, gb, _ = wgrad_terms(d, x, rows, fault=fault, acc=F32)
+    k = dense_k(rows + chunks)
+    r = 0.0
+    if "dw" in which:
+        r = max(r, assert_within(rbf(gw), dw, mag_dw, *k, "wgrad dW"))
+    if "db" in which:
+        r = max(r, assert_within(rbf(gb), db, mag_db, *k, "wgrad db"))
+    return r
+
+
+def test_dense_rounded_reference_passes():
+    assert _fwd_check(_dense_ops()) <= 1
+    assert _fwd_check(_dense_ops(M=65, K1=602, K2=256, N=41, m2=33)) <= 1
+    assert _dgrad_check(_dgrad_ops()) <= 1
+    assert _dgrad_check(_dgrad_ops(M=70, K1=256, K2=256, N=601, m2=70)) <= 1
+    d, x = wgrad_inputs(700, 41, 130, 7)
+    assert _wgrad_check(d, x, 650, 11) <= 1
+
+
+def test_dense_bound_needs_its_magnitude_term():
+    """Where the sum cancels the fp32 roundings exceed an ulp of the result: with k_mag = 0 the restatement fails."""
+    o = _dense_ops(M=777, K1=602, K2=0, N=256)
+    o.update(a2=None, w2=None, m2=None)
+    ref, mag = gemm_terms(**o)
+    got = rbf(gemm_terms(**o, acc=F32)[0])
+    assert assert_within(got, ref, mag, *dense_k(603), "gemm") <= 1
+    with pytest.raises(AssertionError, match="over the bound"):
+        assert_within(got, ref, mag, 0.5, 0, "gemm without the magnitude term")
+
+
+@pytest.mark.parametrize("fault", [{"drop_kstep": (32, 64, 48)}, {"drop_kstep": (96, 0, 144)}, {"drop_w_tail": True}, {"m2_shift": 1},
+                                   {"m2_shift": -1}, {"bias_times": 0}, {"bias_times": 2}, {"swap_tile": (64, 32)}],
+                         ids=lambda f: "-".join("%s=%s" % kv for kv in f.items()).replace(" ", ""))
+def test_dense_forward_faults_fail(fault):
+    """One k-step of 16 missing from one 32 x 32 tile (a full tile and the ragged last one), the W tail beyond the last full
+    64-slab, the second product on m2 + 1 or m2 - 1 rows, the bias twice or not at all, a tile stored transposed."""
+    with pytest.raises(AssertionError, match="over the bound"):
+        _fwd_check(_dense_ops(), fault)
+
+
+@pytest.mark.parametrize("fault", [{"drop_kstep": (32, 64, 48)}, {"drop_kstep": (128, 128, 96)}, {"drop_w_tail": True}, {"m2_shift": 1},
+                                   {"m2_shift": -1}, {"swap_tile": (64, 32)}],
+                         ids=lambda f: "-".join("%s=%s" % kv for kv in f.items()).replace(" ", ""))
+def test_dense_dgrad_faults_fail(fault):
+    with pytest.raises(AssertionError, match="over the bound"):
+        _dgrad_check(_dgrad_ops(), fault)
+
+
+def test_dense_wgrad_faults_fail():
+    """One 64-row chunk missing from dW; the last valid row missing from dW and from db; the first row beyond the count
+    included (finite garbage: the NaN padding of the GPU suite would be louder still)."""
+    d, x = wgrad_inputs(700, 41, 130, 7)
+    rows = 650
+    for fault, which in (({"drop_rows_dw": list(range(128, 192))}, ("dw",)), ({"drop_rows_dw": [rows - 1]}, ("dw",)),
+                         ({"drop_rows_db": [rows - 1]}, ("db",)), ({"extra_rows": 1}, ("dw",)), ({"extra_rows": 1}, ("db",))):
+        with pytest.raises(AssertionError, match="over the bound"):
+            _wgrad_check(d, x, rows, 11, fault, which)
+
+
+def test_dense_chunk_of_64_rows_out_of_11000_fails_but_one_ordinary_row_is_below_bf16_visibility():
+    """At the input layer's size (11 000 rows, 16 chunks) a lost 64-row chunk fails the bound, but one ordinary row -- every
+    entry one standard deviation of its operand, random signs -- is 1 / 11 000 of the magnitude and 1 / 100 of the sum's standard
+    deviation: inside the bound of every element.  (A random row is over it only where two tail values meet: 2 of 6 144 elements
+    at 5 sigma^2 when this was written.)  That is why the GPU inputs at this size carry loud rows."""
+    R, n_out, k_in = 11000, 64, 96
+    d, x = wgrad_inputs(R, n_out, k_in, 8)
+    d[5000], x[5000] = torch.sign(d[5000].float()) * 0.05, torch.sign(x[5000].float())
+    with pytest.raises(AssertionError, match="over the bound"):
+        _wgrad_check(d, x, R, 16, {"drop_rows_dw": list(range(704, 768))}, ("dw",))
+    assert _wgrad_check(d, x, R, 16, {"drop_rows_dw": [5000]}, ("dw",)) <= 1
+    assert _wgrad_check(d, x, R, 16, {"drop_rows_db": [5000]}, ("db",)) <= 1
+
+
+@pytest.mark.parametrize("rows_bound,rows,n_out,k_in", WGRAD_LOUD_CASES)
+def test_loud_row_inputs_of_the_gpu_suite_expose_a_lost_row(rows_bound, rows, n_out, k_in):
+    """The inputs tests/test_gpu_sage_dense_edges.py::test_wgrad_loud_rows gives k_wgrad (same builder, same seed, same plan):
+    the rounded restatement passes, and losing any single loud row -- the last row of a chunk, the first of the next, the last
+    valid row -- from dW or from db fails the bound."""
+    (chunks, rpc), = wgrad_plan([(rows_bound, k_in)])[0]
+    loud = wgrad_loud_rows(rows, chunks, rpc)
+    assert rows - 1 in loud and rpc - 1 in loud and rpc in loud
+    d, x = wgrad_inputs(rows_bound, n_out, k_in, 91, rows=rows, loud=loud, pad=0.0)
+    assert _wgrad_check(d, x, rows, chunks) <= 1
+    for r in (loud[0], loud[1], loud[len(loud) // 2], loud[-2], loud[-1]):
+        for name, which in (("drop_rows_dw", ("dw",)), ("drop_rows_db", ("db",))):
+            with pytest.raises(AssertionError, match="over the bound"):
+                _wgrad_check(d, x, rows, chunks, {name: [r]}, which)
+
+
+def test_wgrad_plan_restates_the_documented_rule():
+    assert wgrad_plan([(64, 128)])[0] == [(1, 64)] and wgrad_plan([(1, 5)])[0] == [(1, 32)] and wgrad_plan([(33, 7)])[0] == [(1, 64)]
+    assert wgrad_plan([(65, 128)])[0] == [(2, 64)] and wgrad_plan([(130, 128)])[0] == [(3, 64)] and wgrad_plan([(640, 128)])[0] == [(10, 64)]
+    assert wgrad_plan([(5120, 128)])[0] == [(80, 64)] and wgrad_plan([(11000, 602)])[0] == [(16, 704)]
+    assert wgrad_plan([(5000, 602), (5000, 602)])[0] == [(8, 640)] * 2
+    assert wgrad_plan([(5000, 602), (3000, 256)])[0] == [(11, 480), (11, 288)]
+    assert wgrad_plan([(5000, 602)], target=37)[0] == [(7, 736)] and wgrad_plan([(5000, 602)], target=1)[0] == [(1, 5024)]
+
+
+# ------------------------------------------------------------------------------------------------ SAGE layers
+def _sage_case(fin, fout, seed=3, bias=True, split=False):
+    spec = from_degrees([0, 1, 2, 40, 300] + [1 + i % 9 for i in range(40)], 260, seed=seed, n_unused=4)
+    gen = torch.Generator().manual_seed(seed)
+    rb = lambda *s: torch.randn(*s, generator=gen).bfloat16()
+    o = dict(src=spec.src, dst=spec.dst, S=spec.S, h=rb(spec.K, fin), w_neigh=rb(fout, fin) / fin ** 0.5, w_self=rb(fout, fin) / fin ** 0.5,
+             bias=rb(fout) if bias else None, ew=(torch.rand(spec.B, generator=gen) + 0.05).bfloat16())
+    if split:
+        o["h_dst"] = rb(spec.S, fin)
+    return spec, o, rb(spec.S, fout)
+
+
+def _sage_check(spec, o, got, ref, p, two_nodes=False):
+    fout, fin = o["w_neigh"].shape
+    k = sage_layer_k(fin, fout, max(spec.K, spec.S), p > 0, fin > fout, two_nodes=two_nodes)
+    names = ["out", "d_wn", "d_ws", "d_h"] + (["d_b"] if o["bias"] is not None else []) + (["d_hdst"] if "h_dst" in o else [])
+    return max(assert_within(got[n], ref[n], ref["mag_" + n], *k[n], "sage " + n) for n in names)
+
+
+@pytest.mark.parametrize("fin,fout", [(48, 16), (16, 48)])
+@pytest.mark.parametrize("split", [False, True])
+def test_sage_formulas_are_the_autograd_of_the_forward(fin, fout, split):
+    spec, o, g = _sage_case(fin, fout, split=split)
+    p = 0.25
+    mask = sage_layer_terms(**o)["rst"] > 0
+    mask &= torch.rand(mask.shape, generator=torch.Generator().manual_seed(1)) >= p
+    names = ["h", "w_neigh", "w_self", "bias"] + (["h_dst"] if split else [])
+    leaves = {n: o[n].double().requires_grad_(True) for n in names}
+    out = sage_layer_terms(**{**o, **leaves}, mask=mask, p=p)["out"]
+    (out * g.double()).sum().backward()
+    t = sage_layer_terms(**o, g=g, mask=mask, p=p)
+    for n, m in (("h", "d_h"), ("w_neigh", "d_wn"), ("w_self", "d_ws"), ("bias", "d_b")) + ((("h_dst", "d_hdst"),) if split else ()):
+        assert torch.allclose(leaves[n].grad, t[m], rtol=1e-12, atol=1e-12), m
+
+
+@pytest.mark.parametrize("fin,fout", [(48, 16), (16, 48)])
+@pytest.mark.parametrize("p", [0.0, 0.25])
+@pytest.mark.parametrize("split", [False, True])
+def test_sage_rounded_reference_passes(fin, fout, p, split):
+    spec, o, g = _sage_case(fin, fout, split=split)
+    sim = sage_layer_terms(**o, g=g, sim=True)
+    mask = sim["out"] > 0
+    if p > 0:
+        mask &= torch.rand(mask.shape, generator=torch.Generator().manual_seed(1)) >= p
+    ref = sage_layer_terms(**o, g=g, mask=mask, p=p)
+    assert _sage_check(spec, o, sage_layer_terms(**o, g=g, mask=mask, p=p, sim=True), ref, p) <= 1
+
+
+@pytest.mark.parametrize("fin,fout", [(48, 16), (16, 48)])
+@pytest.mark.parametrize("fault,p", [({"relu_mask_wrong": True}, 0.0), ({"no_drop_scale": True}, 0.25), ({"self_rows": 1}, 0.0)])
+def test_sage_layer_faults_fail(fin, fout, fault, p):
+    """The ReLU mask of the epilogue backward taken from fc_self's part instead of the layer's output; the dropout scale missing
+    in the backward; fc_self's input gradient applied one row further down."""
+    spec, o, g = _sage_case(fin, fout)
+    mask = sage_layer_terms(**o, sim=True)["out"] > 0
+    if p > 0:
+        mask &= torch.rand(mask.shape, generator=torch.Generator().manual_seed(1)) >= p
+    ref = sage_layer_terms(**o, g=g, mask=mask, p=p)
+    with pytest.raises(AssertionError, match="over the bound"):
+        _sage_check(spec, o, sage_layer_terms(**o, g=g, mask=mask, p=p, sim=True, fault=fault), ref, p)

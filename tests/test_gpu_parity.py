@@ -10,7 +10,8 @@ import pytest
 import torch
 
 from conftest import bf16_bits, bits_to_bf16, golden_cases, load_golden
-from bounds import GAT_K, GCN_K, SPMM_K, assert_within, check_gat_layer, gat_terms, spmm_terms
+from bounds import (GAT_K, GCN_K, SPMM_K, assert_within, check_gat_layer, dense_k, dgrad_terms, gat_terms, spmm_terms, wgrad_plan,
+                    wgrad_terms)
 
 pytestmark = pytest.mark.gpu
 
@@ -1806,10 +1807,18 @@ def test_mfma_dual_product_and_pair_launch(cuda):
     assert torch.equal(norm.view(torch.int16), bnn.embed_norm(out.detach()).view(torch.int16))
     g = torch.randn(S, N, generator=gen).bfloat16().to(cuda)
     out.backward(g)
-    d = torch.where(out > 0, g.float(), torch.zeros_like(g.float()))
-    for got, want in ((wn.grad, d.t() @ agg.detach().float()), (ws.grad, d.t() @ h.detach().float()[:S]), (b.grad, d.sum(0)),
-                      (agg.grad, d @ wn.detach().float()), (h.grad[:S], d @ ws.detach().float())):
-        assert torch.allclose(got.float(), want, rtol=2e-2, atol=2e-2 * float(want.abs().max()))
+    # every gradient element against fp64 on its own scale: bounds.dense_k(n) = (1, n 2^-16), an fp32 sum of n terms rounded once
+    # (weight and bias gradients: the S rows + the chunks of the plan; input gradients: the N columns of d)
+    d = torch.where(out > 0, g, torch.zeros_like(g))
+    (chunks, _), _ = wgrad_plan([(S, D), (S, D)])[0]
+    dwn, mwn, db_, mb_ = wgrad_terms(d, agg.detach(), S)
+    dws, mws, _, _ = wgrad_terms(d, h.detach(), S)
+    assert_within(wn.grad, dwn, mwn, *dense_k(S + chunks), "d W_neigh")
+    assert_within(ws.grad, dws, mws, *dense_k(S + chunks), "d W_self")
+    assert_within(b.grad, db_, mb_, *dense_k(S + chunks), "d b")
+    assert_within(agg.grad, *dgrad_terms(d, wn.detach()), *dense_k(N), "d agg")
+    assert_within(h.grad[:S], *dgrad_terms(d, ws.detach()), *dense_k(N), "d h_dst")
+    assert not bool(h.grad[S:].any())
     # (ii)
     F, Kb, Sb = 602, 500, 120
     x = torch.randn(Kb, F, generator=gen).bfloat16().to(cuda).requires_grad_()
@@ -1823,11 +1832,13 @@ def test_mfma_dual_product_and_pair_launch(cuda):
     assert rows is x or torch.equal(rows, x.detach())
     gz, gy = torch.randn(Kb, N, generator=gen).bfloat16().to(cuda), torch.randn(Sb, N, generator=gen).bfloat16().to(cuda)
     torch.autograd.backward([z, y], [gz, gy])
-    want_dx = gz.float() @ wn2.detach().float()
-    want_dx[:Sb] += gy.float() @ ws2.detach().float()
-    for got, want in ((wn2.grad, gz.float().t() @ x.detach().float()), (ws2.grad, gy.float().t() @ x.detach().float()[:Sb]),
-                      (b2.grad, gy.float().sum(0)), (x.grad, want_dx)):
-        assert torch.allclose(got.float(), want, rtol=2e-2, atol=2e-2 * float(want.abs().max()))
+    (cz, _), (cy, _) = wgrad_plan([(Kb, F), (Sb, F)])[0]
+    dwn, mwn, _, _ = wgrad_terms(gz, x.detach(), Kb)
+    dws, mws, db_, mb_ = wgrad_terms(gy, x.detach(), Sb)
+    assert_within(wn2.grad, dwn, mwn, *dense_k(Kb + cz), "pair d W_neigh")
+    assert_within(ws2.grad, dws, mws, *dense_k(Sb + cy), "pair d W_self")
+    assert_within(b2.grad, db_, mb_, *dense_k(Sb + cy), "pair d b")
+    assert_within(x.grad, *dgrad_terms(gz, wn2.detach(), gy, ws2.detach(), m2=Sb), *dense_k(2 * N), "pair d x")
 
 
 def test_sage_mfma_path_matches_unfused_path(cuda, monkeypatch):

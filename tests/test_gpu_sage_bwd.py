@@ -5,6 +5,8 @@ import numpy as np
 import pytest
 import torch
 
+from bounds import assert_within, dense_k, dgrad_terms, wgrad_plan, wgrad_terms
+
 pytestmark = pytest.mark.gpu
 
 
@@ -53,13 +55,15 @@ def test_wgrad_exact_integers(cuda, R, n_out, k_in):
     assert torch.equal(dw2.float().cpu(), d2[:R2].float().t() @ x2[:R2].float())
 
 
-@pytest.mark.parametrize("R,n_out,k_in,split", [(11000, 256, 602, None), (5000, 256, 602, "37"), (2100, 256, 256, None), (2000, 41, 256, None)])
-def test_wgrad_vs_fp32_full_size(cuda, R, n_out, k_in, split, monkeypatch):
+@pytest.mark.parametrize("R,n_out,k_in", [(11000, 256, 602), (2100, 256, 256), (2000, 41, 256)])
+def test_wgrad_vs_fp32_full_size(cuda, R, n_out, k_in):
     """The weight-gradient shapes of the Reddit-like step (11 K x 256 x 602, ...) on random bf16 data against fp64 sums:
-    within one bf16 rounding of the exact value (fp32 partial tiles summed in chunk order), and bitwise reproducible."""
+    within one bf16 rounding of the exact value (fp32 partial tiles summed in chunk order), and bitwise reproducible.  Every
+    element is also held to its own scale, bounds.dense_k(rows + chunks) = (1, (rows + chunks) 2^-16): one rounding to bf16 of
+    an fp32 sum over the rows of a chunk and then over the chunks.  (The chunk plan under another BLISS_WGRAD_WGS, which is read
+    once per process, runs in child processes: test_gpu_sage_dense_edges.py::
+    test_wgrad_target_from_the_environment_in_child_processes.)"""
     from bliss_gnn_amd.nn import sage_wgrad
-    if split:
-        monkeypatch.setenv("BLISS_WGRAD_WGS", split)       # (read once per process: only effective if this test runs first)
     g = torch.Generator().manual_seed(R)
     d = (torch.randn(R, n_out, generator=g) * 0.05).bfloat16()
     x = torch.randn(R, k_in, generator=g).bfloat16()
@@ -75,9 +79,15 @@ def test_wgrad_vs_fp32_full_size(cuda, R, n_out, k_in, split, monkeypatch):
     err = (dw.double().cpu() - ref).abs()
     assert (err <= ref.abs() * 2.0 ** -8 + 1e-3 * ref.abs().max() * 2.0 ** -8).all(), float((err / ref.abs().clamp_min(1e-9)).max())
     assert ((db.double().cpu() - refb).abs() <= refb.abs() * 2.0 ** -8 + 1e-6).all()
+    (chunks, _), = wgrad_plan([(R, k_in)])[0]
+    rw, mw, rb, mb = wgrad_terms(dd, xd, Rt)
+    assert_within(dw, rw, mw, *dense_k(Rt + chunks), "dW")
+    assert_within(db, rb, mb, *dense_k(Rt + chunks), "db")
 
 
 def test_dgrad_vs_fp32_full_size(cuda):
+    """Both products of the hidden layer's input gradient at full size: within one bf16 rounding of the fp64 value, and every
+    element within bounds.dense_k(K1 + K2) of its own magnitude (fp32 accumulation of 512 terms, one rounding)."""
     from bliss_gnn_amd.nn import sage_dgrad
     g = torch.Generator().manual_seed(3)
     M, M2 = 3300, 1300
@@ -88,6 +98,7 @@ def test_dgrad_vs_fp32_full_size(cuda):
     ref[:M2] += a2.double() @ w2.double()
     err = (out.double().cpu() - ref).abs()
     assert (err <= ref.abs() * 2.0 ** -8 + 1e-3 * ref.abs().max() * 2.0 ** -8).all()
+    assert_within(out, *dgrad_terms(a1.to(cuda), w1.to(cuda), a2.to(cuda), w2.to(cuda), m2=M2), *dense_k(512), "dgrad")
 
 
 def test_sage_training_gradients_match_the_library_path(cuda, monkeypatch):
