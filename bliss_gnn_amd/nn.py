@@ -178,6 +178,86 @@ class CrossEntropyLoss(nn.Module):
         return loss
 
 
+class _BCEWithLogits(torch.autograd.Function):
+    """nn.BCEWithLogitsLoss() (mean) on bf16 logits and fp32 targets, forward and gradient in one launch (train_lightning.py:77-79)."""
+
+    @staticmethod
+    def forward(ctx, logits, target, state):
+        loss, dx = _bce_launch(logits, target, state)
+        ctx.save_for_backward(dx)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (dx,) = ctx.saved_tensors
+        return dx * g.to(dx.dtype), None, None
+
+
+def _bce_launch(x, targets, state, x2=None, label_ids=None):
+    n, c = x.shape
+    dx = torch.empty(n, c, dtype=torch.bfloat16, device=x.device)
+    rows = torch.empty(n, dtype=torch.float32, device=x.device)
+    loss = torch.empty((), dtype=torch.float32, device=x.device)
+    if x2 is None and label_ids is None:
+        _lib.check(_lib.lib.bliss_bce_logits(x.data_ptr(), x.stride(0), targets.data_ptr(), n, c, rows.data_ptr(), dx.data_ptr(),
+                                             dx.stride(0), loss.data_ptr(), state.data_ptr(), state.data_ptr() + 4, _stream()),
+                   "bliss_bce_logits")
+    else:
+        _lib.check(_lib.lib.bliss_bce_logits_sum(x.data_ptr(), x.stride(0), 0 if x2 is None else x2.data_ptr(),
+                                                 0 if x2 is None else x2.stride(0), targets.data_ptr(),
+                                                 0 if label_ids is None else label_ids.data_ptr(), n, c, rows.data_ptr(), dx.data_ptr(),
+                                                 dx.stride(0), loss.data_ptr(), state.data_ptr(), state.data_ptr() + 4, _stream()),
+                   "bliss_bce_logits_sum")
+    return loss, dx
+
+
+class BCEWithLogitsLoss(nn.Module):
+    """``nn.BCEWithLogitsLoss()`` as the reference builds it for the multi-label dataset (train_lightning.py:77-79): mean over
+    all (row, class) pairs, no ``weight``, no ``pos_weight``.  bf16 logits on the GPU with fp32 targets take the one-launch
+    kernel (csrc/loss.hip: k_bce_logits; the loss is an fp32 scalar, as torch's is for these dtypes); anything else goes to
+    torch's functional form."""
+
+    def _eligible(self, logits, target):
+        return (logits.is_cuda and logits.dtype == torch.bfloat16 and logits.dim() == 2 and logits.stride(1) == 1 and logits.numel() > 0
+                and target.dtype == torch.float32 and target.shape == logits.shape and target.is_contiguous()
+                and target.device == logits.device and not target.requires_grad)
+
+    def _state_on(self, device):
+        if getattr(self, "_state", None) is None or self._state.device != device:
+            self._state = torch.zeros(2, dtype=torch.int32, device=device)                 # [0] ticket, [1] error word
+        return self._state
+
+    def forward(self, logits, target):
+        if self._eligible(logits, target):
+            return _BCEWithLogits.apply(logits, target, self._state_on(logits.device))
+        return torch.nn.functional.binary_cross_entropy_with_logits(logits, target)
+
+    def backward_from(self, logits, target):
+        """loss.backward() without the loss node (see CrossEntropyLoss.backward_from).  Returns the loss (fp32 scalar, detached)."""
+        if not self._eligible(logits, target):
+            loss = self.forward(logits, target)
+            loss.backward()
+            return loss.detach()
+        loss, dx = _bce_launch(logits.detach(), target, self._state_on(logits.device))
+        logits.backward(dx)
+        return loss
+
+    def backward_from_parts(self, a, b, label_table, label_ids):
+        """backward_from for logits = a + b that are never formed (the output layer's fc_self + h_neigh) and targets
+        = label_table[label_ids] ([V, n_cls] fp32) that are never gathered: one launch, then the same gradient into both addends."""
+        ok = (a.is_cuda and a.dtype == torch.bfloat16 and b.dtype == torch.bfloat16 and a.shape == b.shape and a.dim() == 2
+              and a.numel() > 0 and a.stride(1) == 1 and b.stride(1) == 1 and b.device == a.device
+              and label_table.dtype == torch.float32 and label_table.dim() == 2 and label_table.shape[1] == a.shape[1]
+              and label_table.is_contiguous() and label_table.device == a.device and not label_table.requires_grad
+              and label_ids.dtype == torch.int32 and label_ids.is_contiguous() and label_ids.numel() == a.shape[0]
+              and label_ids.device == a.device)
+        if not ok:
+            return self.backward_from(a + b, torch.index_select(label_table, 0, label_ids.long()))
+        loss, dx = _bce_launch(a.detach(), label_table, self._state_on(a.device), x2=b.detach(), label_ids=label_ids)
+        torch.autograd.backward([a, b], [dx, dx])
+        return loss
+
+
 # ------------------------------------------------------------------------------------------------ MFMA tile GEMM (csrc/sage.hip)
 TILE_GEMM_MAX_K, TILE_GEMM_MAX_N = 1024, 256
 

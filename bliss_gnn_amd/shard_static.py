@@ -686,7 +686,7 @@ class StaticShardedTrainStep:
                 blk.srcdata["embed_norm"] = in_norm
             agg = weighted_aggregate(blk, z, blk.edata["edge_weights"], mean=True)
             if last and self._fused_loss_ok(y):
-                h = (y, agg)                                   # (the loss launch adds them: bliss_cross_entropy_masked)
+                h = (y, agg)                                   # (the loss launch adds them: bliss_cross_entropy_masked / bliss_bce_logits_masked)
             else:
                 h = (y + agg) if last else sage_epilogue(y, agg, p, ctr, seed)[0]
         else:
@@ -696,16 +696,19 @@ class StaticShardedTrainStep:
         return h
 
     def _fused_loss_ok(self, logits):
-        """nn.CrossEntropyLoss on the in-tree kernel (csrc/loss.hip, masked form): bf16 logits on the GPU, class-index labels."""
+        """The loss on the in-tree kernels (csrc/loss.hip, masked forms): bf16 logits on the GPU and class-index labels
+        (nn.CrossEntropyLoss) or, for a multi-label run, an fp32 [nodes, classes] target table (nn.BCEWithLogitsLoss)."""
         import os
         lab = self.g.ndata_owned.get("labels") if hasattr(self.g.ndata_owned, "get") else None
-        return (os.environ.get("BLISS_SHARD_FUSED_LOSS", "1") != "0" and not self.multilabel and logits.is_cuda
-                and logits.dtype == torch.bfloat16 and logits.dim() == 2 and logits.stride(1) == 1 and lab is not None
-                and lab.dtype == torch.int64 and lab.dim() == 1 and lab.is_contiguous())
+        if lab is None or not lab.is_contiguous():
+            return False
+        lab_ok = (lab.dtype == torch.float32 and lab.dim() == 2) if self.multilabel else (lab.dtype == torch.int64 and lab.dim() == 1)
+        return (os.environ.get("BLISS_SHARD_FUSED_LOSS", "1") != "0" and lab_ok and logits.is_cuda and logits.dtype == torch.bfloat16
+                and logits.dim() == 2 and logits.stride(1) == 1 and (not self.multilabel or lab.shape[1] == logits.shape[1]))
 
     def _fused_loss_backward_step(self, blocks, pred, slot, grp):
-        """The loss and its gradient in ONE launch (masked mean cross-entropy over this rank's output seeds, divided by the GLOBAL
-        batch, the output layer's two addends summed inside), ``backward`` from that gradient, gradient all-reduce, Adam."""
+        """The loss and its gradient in ONE launch (masked mean cross-entropy -- multi-label: binary cross-entropy with logits -- over
+        this rank's output seeds, divided by the GLOBAL batch, the output layer's two addends summed inside), ``backward`` from that gradient, gradient all-reduce, Adam."""
         g = self.g
         a, b = pred if isinstance(pred, tuple) else (pred, None)
         last = blocks[-1]
@@ -718,12 +721,14 @@ class StaticShardedTrainStep:
         rows = torch.empty(n_rows, dtype=torch.float32, device=a.device)
         loss = torch.empty(1, dtype=torch.float32, device=a.device)
         ad, bd = a.detach(), (None if b is None else b.detach())
-        _lib.check(_lib.lib.bliss_cross_entropy_masked(ad.data_ptr(), ad.stride(0), 0 if bd is None else bd.data_ptr(),
-                                                       0 if bd is None else bd.stride(0), lab.data_ptr(), lab.numel(), nid.data_ptr(), g.lo,
-                                                       n_rows, n_mine.data_ptr(), float(self.batch * g.world), n_cls, rows.data_ptr(),
-                                                       dx.data_ptr(), dx.stride(0), loss.data_ptr(), self._ce_state.data_ptr(),
-                                                       self._ce_state.data_ptr() + 4, torch.cuda.current_stream().cuda_stream),
-                   "bliss_cross_entropy_masked")
+        # (multi-label: the mean runs over (row, class) pairs, so the divisor carries the classes too -- as _loss_backward_step's scale)
+        name, denom = (("bliss_bce_logits_masked", float(self.batch * g.world * n_cls)) if self.multilabel
+                       else ("bliss_cross_entropy_masked", float(self.batch * g.world)))
+        _lib.check(getattr(_lib.lib, name)(ad.data_ptr(), ad.stride(0), 0 if bd is None else bd.data_ptr(),
+                                           0 if bd is None else bd.stride(0), lab.data_ptr(), lab.shape[0], nid.data_ptr(), g.lo,
+                                           n_rows, n_mine.data_ptr(), denom, n_cls, rows.data_ptr(),
+                                           dx.data_ptr(), dx.stride(0), loss.data_ptr(), self._ce_state.data_ptr(),
+                                           self._ce_state.data_ptr() + 4, torch.cuda.current_stream().cuda_stream), name)
         self.opt.zero_grad(set_to_none=True)
         if b is None:
             a.backward(dx)
@@ -1062,9 +1067,10 @@ class PipelinedShardedTrainStep(StaticShardedTrainStep):
         # the BACKWARD stream, behind B(t) and a "kept lists final" flag, while the main stream already runs the part of F(t+1) that
         # needs only the kept list (feature rows, halo sum, the input layer's two Linears); F's first aggregation waits for the
         # block (nn._wait_block), as in the single-GPU loop.  Two streams, two graphs per step as before
-        # (multi-label runs keep the loss on torch ops: their backward stream is the longer chain already -- Yelp-like 1549 steps/s
-        # with all blocks there against 1613 with the input-most block only -- so they default to 1)
-        late_mode = os.environ.get("BLISS_SHARD_LATE_BLOCK", "1" if self.multilabel else "2")
+        # (multi-label runs defaulted to 1 while their loss was on torch ops and their backward stream the longer chain; with the
+        # one-launch loss, bliss_bce_logits_masked, mode 2 is the faster one for them too: Yelp-like, world of one rank, medians of
+        # three alternating 400-step runs, 1777 steps/s with all blocks there against 1739 with the input-most block only)
+        late_mode = os.environ.get("BLISS_SHARD_LATE_BLOCK", "2")
         if late_mode not in ("0", "1", "2"):
             raise ValueError(f"BLISS_SHARD_LATE_BLOCK must be 0, 1 or 2, not {late_mode!r}")
         self.late_block = self.use_flags and late_mode != "0"

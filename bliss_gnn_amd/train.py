@@ -72,9 +72,16 @@ def _ce_loss():
     return CrossEntropyLoss()
 
 
+def _bce_loss():
+    if os.environ.get("BLISS_FUSED_BCE", "1") == "0":
+        return nn.BCEWithLogitsLoss()
+    from .nn import BCEWithLogitsLoss
+    return BCEWithLogitsLoss()
+
+
 def _loss_backward(loss_fn, pred, labels, opt):
     """loss = loss_fn(pred, labels); opt.zero_grad(); loss.backward() (train_lightning.py:142 + Lightning).  The one-launch
-    cross-entropy hands d loss / d pred over with the loss, so its route skips the loss node.  Returns the detached loss."""
+    losses of csrc/loss.hip hand d loss / d pred over with the loss, so their route skips the loss node.  Returns the detached loss."""
     opt.zero_grad(set_to_none=True)
     if hasattr(loss_fn, "backward_from"):
         return loss_fn.backward_from(pred, labels)
@@ -100,7 +107,7 @@ class TrainStep:
 
     def __init__(self, g, sampler, model, lr=0.002, multilabel=False, bandit=True, grad_sync=None, exp3_sync=None):
         self.g, self.sampler, self.model = g, sampler, model
-        self.loss_fn = nn.BCEWithLogitsLoss() if multilabel else _ce_loss()             # :77-79
+        self.loss_fn = _bce_loss() if multilabel else _ce_loss()                        # :77-79
         self.opt = make_adam(model, lr)                                                  # :206
         self.bandit = bandit and hasattr(sampler, "exp3")          # train_lightning.py:469: only for the bandit samplers
         self.grad_sync, self.exp3_sync = grad_sync, exp3_sync
@@ -173,7 +180,7 @@ class GraphedTrainStep:
     def __init__(self, g, sampler, model, batch_size, lr=0.002, multilabel=False, distributed=False):
         self.g, self.sampler, self.model, self.bs = g, sampler, model, int(batch_size)
         self.distributed = distributed          # replicas: gradient all-reduce + EXP3 exchange recorded in the graph too
-        self.loss_fn = nn.BCEWithLogitsLoss() if multilabel else _ce_loss()
+        self.loss_fn = _bce_loss() if multilabel else _ce_loss()
         # ONE launch for all parameter tensors (csrc/optim.hip; torch's foreach path is ~40 launches of >= 5 us inside a graph,
         # its fused multi-tensor kernel ~50 us)
         self.opt = make_adam(model, lr, capturable=True)

@@ -363,6 +363,29 @@ int bliss_cross_entropy_masked(const void* logits, int64_t stride, const void* l
                                float denom, int32_t n_cls, float* row_loss, void* dlogits, int64_t d_stride, float* loss_out,
                                uint32_t* ticket, int32_t* err, void* stream);
 
+/* nn.BCEWithLogitsLoss() (mean; no weight, no pos_weight: train_lightning.py:77-79 for the multi-label dataset, load_graph.py:69-71)
+ * on bf16 logits [n_rows, n_cls] and fp32 targets [n_rows, n_cls] (rows contiguous), forward and gradient in one launch, in fp32 from
+ * e = exp(-|x|): *loss_out = mean (max(x, 0) - x y + log1p(e)), dlogits = bf16((sigmoid(x) - y) / (n_rows n_cls)), one rounding.
+ * Logits of any magnitude give a finite gradient; an infinite logit gives the limit values (loss 0 where the target agrees with it
+ * entirely, infinite elsewhere); NaN propagates.  row_loss: float[n_rows] scratch; ticket: zero-initialised uint32 (left zero). */
+int bliss_bce_logits(const void* logits, int64_t stride, const float* targets, int32_t n_rows, int32_t n_cls, float* row_loss,
+                     void* dlogits, int64_t d_stride, float* loss_out, uint32_t* ticket, int32_t* err, void* stream);
+/* The same with the two launches in front of it taken in, as bliss_cross_entropy_sum: logits2 != NULL: the logits are
+ * bf16(logits + logits2), dlogits the gradient of both addends; label_ids != NULL: row r's targets are row label_ids[r] of
+ * target_table ([V, n_cls] floats, rows contiguous).  At least one of the two must be given. */
+int bliss_bce_logits_sum(const void* logits, int64_t stride, const void* logits2, int64_t stride2, const float* target_table,
+                         const int32_t* label_ids, int32_t n_rows, int32_t n_cls, float* row_loss, void* dlogits, int64_t d_stride,
+                         float* loss_out, uint32_t* ticket, int32_t* err, void* stream);
+/* The same for a rank of a sharded step, as bliss_cross_entropy_masked: only the first *n_rows_dev of the n_rows (capacity) rows
+ * count -- the others get a zero gradient row and no loss, whatever their logits hold --, row r's targets are row
+ * label_ids[r] - id_off of the owner's target_table (n_table rows; an id outside it sets bit 2 in *err and the row counts for
+ * nothing), and the divisor is `denom`, the GLOBAL number of (row, class) pairs (batch x world x n_cls): the ranks' losses and
+ * gradients ADD to the global mean.  logits2 may be NULL. */
+int bliss_bce_logits_masked(const void* logits, int64_t stride, const void* logits2, int64_t stride2, const float* target_table,
+                            int32_t n_table, const int32_t* label_ids, int32_t id_off, int32_t n_rows, const int32_t* n_rows_dev,
+                            float denom, int32_t n_cls, float* row_loss, void* dlogits, int64_t d_stride, float* loss_out,
+                            uint32_t* ticket, int32_t* err, void* stream);
+
 /* th.optim.Adam(self.parameters(), lr) (train_lightning.py:205-206) for a bf16 module: parameters, gradients and both moment
  * buffers bf16, one launch over all tensors, math in fp32, one rounding per stored value.  state: float[4] on the device --
  * [0] step count (incremented by the launch), [1] learning rate (the caller rewrites it when its scheduler does,
