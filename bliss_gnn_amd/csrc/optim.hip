@@ -70,7 +70,9 @@ extern "C" int bliss_adam_step(const bliss_adam_t* t, float* state, float beta1,
   AdamTensors a;
   int total = 0;
   for (int i = 0; i < t->count; ++i) {
-    if (!t->param[i] || !t->grad[i] || !t->exp_avg[i] || !t->exp_avg_sq[i] || t->numel[i] < 0) return BLISS_EINVAL;
+    if (t->numel[i] < 0) return BLISS_EINVAL;
+    // (a tensor of no elements has no storage: torch hands out a null data pointer for it; it gets no workgroup)
+    if (t->numel[i] > 0 && (!t->param[i] || !t->grad[i] || !t->exp_avg[i] || !t->exp_avg_sq[i])) return BLISS_EINVAL;
     a.p[i] = (bf16_t*)t->param[i]; a.g[i] = (const bf16_t*)t->grad[i]; a.m[i] = (bf16_t*)t->exp_avg[i]; a.v[i] = (bf16_t*)t->exp_avg_sq[i];
     a.n[i] = t->numel[i];
     a.wg_begin[i] = total;

@@ -210,6 +210,8 @@ def evaluate(g, sampler, model, ids, batch_size, multilabel=False, loss_fn=None)
         if loss_fn is not None:
             losses.append(float(loss_fn(pred, y)) * seeds.numel())
     model.train(was)
+    if hasattr(loss_fn, "check_errors"):
+        loss_fn.check_errors()                                                   # (every batch's loss was read back above)
     pred, y = torch.cat(preds), torch.cat(labels)
     return micro_f1(pred, y, multilabel), (sum(losses) / max(ids.numel(), 1) if losses else None)
 

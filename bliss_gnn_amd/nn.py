@@ -133,6 +133,20 @@ def _ce_launch(x, labels, state, x2=None, label_ids=None):
     return loss, dx
 
 
+def _check_loss_errors(module, name):
+    """Read the loss kernel's error word, clear it, and raise if it was set (one tiny read-back: call it where the loop
+    synchronises anyway)."""
+    st = getattr(module, "_state", None)
+    if st is None:
+        return
+    word = int(st[1].item())
+    if word:
+        st[1] = 0
+        raise RuntimeError("%s: the loss kernel met labels out of range -- a class index outside [0, n_classes) or a label id "
+                           "outside the label table (error 0x%x, %s); the rows concerned counted for nothing"
+                           % (name, word, _lib.err_string(word)))
+
+
 class CrossEntropyLoss(nn.Module):
     """``nn.CrossEntropyLoss()`` as the reference builds it (train_lightning.py:77-79): mean over the batch, class-index
     targets.  bf16 logits on the GPU take the one-launch kernel; anything else goes to torch's functional form."""
@@ -146,6 +160,11 @@ class CrossEntropyLoss(nn.Module):
 
     def _eligible(self, logits, target):
         return logits.is_cuda and logits.dtype == torch.bfloat16 and logits.dim() == 2 and target.dtype == torch.int64 and target.dim() == 1
+
+    def check_errors(self):
+        """torch raises a device assert on a class index outside [0, n_classes); the kernel sets a word instead (the row gets no
+        loss and no one-hot).  This reads the word, clears it and raises."""
+        _check_loss_errors(self, "CrossEntropyLoss")
 
     def backward_from(self, logits, target):
         """loss.backward() without the loss node: the kernel produces d loss / d logits with the loss, so the train loops call
@@ -226,6 +245,10 @@ class BCEWithLogitsLoss(nn.Module):
         if getattr(self, "_state", None) is None or self._state.device != device:
             self._state = torch.zeros(2, dtype=torch.int32, device=device)                 # [0] ticket, [1] error word
         return self._state
+
+    def check_errors(self):
+        """A label id outside the target table (backward_from_parts) sets a word; this reads it, clears it and raises."""
+        _check_loss_errors(self, "BCEWithLogitsLoss")
 
     def forward(self, logits, target):
         if self._eligible(logits, target):

@@ -837,6 +837,8 @@ class PipelinedTrainStep(GraphedTrainStep):
             # the exchange truncates an update list that outgrew its capacity and only flags it on the sampler: surface
             # it with the call that produced it, not at the end of training (one tiny read-back per run(), not per step)
             self.sampler.check_errors()
+        if hasattr(self.loss_fn, "check_errors"):
+            self.loss_fn.check_errors()                  # a label out of range trains silently otherwise (same read-back point)
         return sizes
 
     def eager_pair(self, loader):

@@ -624,3 +624,226 @@ def sage_layer_k(fin, fout, rows, dropout, lin_first, two_nodes=False):
             "d_wn": (1, 1.25 + dr + wg), "d_ws": (1, dr + wg), "d_b": (1, dr + wg),
             "d_h": (1, (2.25 if two_nodes else 1.25) + dr + 2 * fout * 2.0 ** -16),
             "d_hdst": (1, dr + fout * 2.0 ** -16)}
+
+
+# ------------------------------------------------------------------------------------------------ cross-entropy (csrc/loss.hip)
+# k_cross_entropy: one wave per row of bf16 logits; max, sum of exponentials, one reciprocal, (p - onehot) * inv_n in fp32, one
+# rounding to bf16; the row losses m + log s - x_y summed in row order by the last workgroup.  Derivations of ce_k / ce_k_loss:
+# the docstring of tests/test_gpu_cross_entropy.py.
+CE_GRID_ROWS = 4096                      # rows of one trip of the grid-stride loop (1024 workgroups of 4 waves)
+_NEG_LIMIT = -1.0e4                      # a -inf logit at its limit: exp(-1e4 - m) == 0 in float64 for every finite bf16 m in use
+
+
+def f32(v):
+    """The fp32 value a C ``float`` argument receives, as a Python float."""
+    return float(torch.tensor(float(v), dtype=torch.float32))
+
+
+def ce_terms(x, labels, denom, x2=None, n_valid=None, fault=None, acc=torch.float64):
+    """Mean-reduced cross-entropy on bf16 logits x [n, c] (``bf16(x + x2)``, the sum taken in fp32 as the kernel takes it, when
+    ``x2`` is given) with class indices ``labels`` [n]: returns (loss, mag_loss, grad, mag_grad).
+
+        loss = (1/denom) sum_{r < n_valid} (m_r + log s_r - x_{r,y}),   grad = (softmax(x) - onehot) / denom  (0 on rows >= n_valid)
+        mag_loss = (1/denom) sum_r (|m_r| + |log s_r| + |x_{r,y}|),     mag_grad = 1 / denom  (every element)
+
+    A row whose label is outside [0, c) is the kernel's refused row: no loss term, no one-hot (the softmax alone).  A -inf logit
+    is evaluated at its limit (replaced by -1e4: its exponential is exactly 0); a -inf logit ON the label makes the loss +inf.
+    ``acc=torch.float32`` is the kernel's restatement: max, exp2(fl((x - m) * log2 e)) with fp32-subnormal results flushed, sum,
+    one reciprocal, (p - onehot) * inv_n, then rbf; the row losses m + log s - x_y summed in fp32 and scaled by inv_n.
+    ``fault`` (tests/test_bounds.py), a dict of
+      no_onehot: True;  onehot_shift: +-1 (the one-hot lands on class y + shift);  inv_n_rows: True (1 / n instead of 1 / denom);
+      no_max: True (exponentials of x itself);  drop_tail: True (classes >= 64 * (c // 64) left out of the sum and the gradient);
+      drop_rows_loss: True (rows >= 4096 left out of the loss sum);  no_round_sum: True (x + x2 not rounded to bf16).
+    The magnitudes never see the fault."""
+    fault = fault or {}
+    n, c = x.shape
+    dev = x.device
+    if x2 is not None:
+        xs = x.float() + x2.float()
+        xq = xs.bfloat16()
+        X = (x.double() + x2.double()).to(acc) if fault.get("no_round_sum") else xq.to(acc)
+        Xm = xq.double()
+    else:
+        X, Xm = x.to(acc), x.double()
+    n_valid = n if n_valid is None else max(0, min(int(n_valid), n))
+    labels = labels.long().to(dev)
+    ok = (labels >= 0) & (labels < c)
+    ok[n_valid:] = False
+    ys = torch.where(ok, labels, torch.zeros_like(labels))
+    label_inf = bool((torch.isinf(Xm.gather(1, ys[:, None])[:, 0]) & ok).any())
+    X = torch.where(torch.isinf(X) & (X < 0), torch.full_like(X, _NEG_LIMIT), X)
+    Xm = torch.where(torch.isinf(Xm) & (Xm < 0), torch.full_like(Xm, _NEG_LIMIT), Xm)
+    inv_n = torch.tensor(1.0 / (n if fault.get("inv_n_rows") else denom), dtype=acc, device=dev)
+    m = torch.zeros(n, 1, dtype=acc, device=dev) if fault.get("no_max") else X.amax(1, keepdim=True)
+    if acc == torch.float32:
+        e = torch.exp2((X - m) * torch.tensor(1.4426950408889634, dtype=acc, device=dev))
+        e = torch.where(e < 2.0 ** -126, torch.zeros_like(e), e)
+    else:
+        e = torch.exp(X - m)
+    cols = torch.arange(c, device=dev)
+    if fault.get("drop_tail"):
+        e = e * (cols < 64 * (c // 64)).to(acc)
+    s = e.sum(1, keepdim=True)
+    p = e * (1.0 / s)
+    shift = int(fault.get("onehot_shift", 0))
+    hot = (cols[None, :] == (ys[:, None] + shift)) & ok[:, None]
+    if fault.get("no_onehot"):
+        hot = torch.zeros_like(hot)
+    grad = (p - hot.to(acc)) * inv_n
+    if fault.get("drop_tail"):
+        grad = grad * (cols < 64 * (c // 64)).to(acc)
+    grad[n_valid:] = 0
+    xy = X.gather(1, ys[:, None])[:, 0]
+    rows = torch.where(ok, m[:, 0] + torch.log(s[:, 0]) - xy, torch.zeros_like(xy))
+    if fault.get("drop_rows_loss"):
+        rows = rows[:CE_GRID_ROWS]
+    loss = rows.sum() * inv_n
+    if label_inf:
+        loss = torch.full_like(loss, float("inf"))
+    # magnitudes, float64 on the unfaulted operands
+    mm = Xm.amax(1, keepdim=True)
+    sm = torch.exp(Xm - mm).sum(1)
+    mag_rows = torch.where(ok, mm[:, 0].abs() + torch.log(sm).abs() + Xm.gather(1, ys[:, None])[:, 0].abs(), torch.zeros_like(sm))
+    mag_loss = mag_rows.sum() / denom
+    if acc == torch.float32:
+        grad = rbf(grad)
+    return loss, mag_loss, grad, torch.full((n, c), 1.0 / denom, dtype=torch.float64, device=dev)
+
+
+def ce_k(n_cls):
+    """k of the gradient bound |got - ref| <= 1 ulp_bf16(ref) + k 2^-24 / denom (tests/test_gpu_cross_entropy.py):
+    17 + 3 ln(n_cls) + ceil(n_cls / 64)."""
+    import math
+    return 17.0 + 3.0 * math.log(n_cls) + -(-n_cls // 64)
+
+
+def ce_k_loss(n_rows, n_cls):
+    """k_loss of the loss bound |got - ref| <= k_loss 2^-24 mag_loss: the row's chain 3 ln(n_cls) + ceil(n_cls / 64) + 13 plus
+    the row-ordered sum's ceil(n_rows / 256) + 12."""
+    import math
+    return 3.0 * math.log(n_cls) + -(-n_cls // 64) + 13.0 + -(-n_rows // 256) + 12.0
+
+
+def ce_check(got_loss, got_grad, x, labels, denom, what, x2=None, n_valid=None, loss_bf16=False, skip_rows=None):
+    """Both bounds on one launch's results against ce_terms in float64; prints the two ratios before it asserts and returns them.
+    ``loss_bf16``: the loss went through bf16 (CrossEntropyLoss.forward): one bf16 ulp on top.  ``skip_rows``: rows that hold a
+    planted non-finite logit whose gradient the caller checks itself (the loss is then not held to the bound either)."""
+    n, c = x.shape
+    loss, mag_loss, grad, mag = ce_terms(x, labels, denom, x2=x2, n_valid=n_valid)
+    got_grad = got_grad.double()
+    if skip_rows is not None and len(skip_rows):
+        keep = torch.ones(n, dtype=torch.bool, device=x.device)
+        keep[torch.as_tensor(skip_rows, dtype=torch.long, device=x.device)] = False
+        got_grad, grad, mag = got_grad[keep], grad[keep], mag[keep]
+    ratio = assert_within(got_grad, grad, mag, 1, ce_k(c) * 2.0 ** -16, what + " gradient")
+    got_loss = got_loss.double().reshape(())
+    if skip_rows is not None and len(skip_rows):
+        loss_ratio = 0.0
+    elif bool(torch.isinf(loss)):
+        loss_ratio = 0.0 if float(got_loss) == float("inf") else float("inf")
+    else:
+        bound = ce_k_loss(n, c) * 2.0 ** -24 * float(mag_loss) + (float(ulp_bf16(loss)) if loss_bf16 else 0.0)
+        err = abs(float(got_loss) - float(loss))
+        loss_ratio = 0.0 if err == 0 else (err / bound if bound > 0 else float("inf"))
+    print("%s: gradient worst ratio %.3f, loss %.9g ref %.9g ratio %.3f" % (what, ratio, float(got_loss), float(loss), loss_ratio))
+    assert loss_ratio <= 1.0, (what, float(got_loss), float(loss), loss_ratio)
+    return ratio, loss_ratio
+
+
+CE_SHAPES = [(256, 41), (1000, 100), (7, 1000), (32, 3), (1, 1), (5, 2), (300, 63), (300, 64), (300, 65), (33, 128), (33, 129),
+             (4096, 7), (4097, 7), (9001, 3)]
+CE_PLANTS = [0.0, -0.0, 88.0, -88.0, 200.0, -200.0]
+
+
+def ce_case(shape, scale, confident, seed):
+    """bf16 logits N(0, 1) * scale with the plants 0, -0, +-88, +-200 in the first entries, labels uniform over the classes;
+    ``confident``: every row's label logit raised by 30 (p_y within 1e-13 of 1 at scale 1: the cancellation in p - 1).  CPU."""
+    gen = torch.Generator().manual_seed(seed)
+    n, c = shape
+    x = torch.randn(n, c, generator=gen) * scale
+    y = torch.randint(0, c, (n,), generator=gen)
+    if confident:
+        x[torch.arange(n), y] += 30.0
+    x = x.bfloat16()
+    k = min(len(CE_PLANTS), n * c)
+    x.view(-1)[:k] = torch.tensor(CE_PLANTS[:k]).bfloat16()
+    return x, y
+
+
+# ------------------------------------------------------------------------------------------------ Adam (csrc/optim.hip)
+ADAM_PER_WG = 2048                       # elements of one workgroup of k_adam
+ADAM_SIZES = [(2047,), (2048,), (2049,), (1,), (4096,), (4097,), (0,), (256, 602)]
+
+
+def adam_terms(p, g, m, v, step, lr, beta1, beta2, eps, weight_decay, fault=None, acc=torch.float64):
+    """One step of torch.optim.Adam (no amsgrad, L2 weight decay) on bf16 p, g, m, v: returns (p', mag_p, m', mag_m, v', mag_v).
+    ``step`` is the count BEFORE the step (what state[0] holds); lr, betas, eps, weight_decay enter as the fp32 values the C ABI
+    receives (rounded here).
+
+        gw = g + wd p;  m' = m + (gw - m)(1 - b1);  v' = b2 v + (1 - b2) gw^2;  t = step + 1
+        denom = sqrt(v') / sqrt(1 - b2^t) + eps;  update = lr / (1 - b1^t) * m' / denom;  p' = p - update
+
+    Magnitudes (the same formulas on the absolute values of their terms):
+        mag_m = |m| + (1 - b1)(|g| + wd |p| + |m|)
+        mag_v = b2 v + (1 - b2)(|g| + wd |p|)^2                      (= v' unless g and wd p cancel)
+        mag_p = |p| + lr / (1 - b1^t) * mag_m / denom * (mag_v / v')   (= |p| + |update| unless m' or g + wd p cancels: an error
+                of m' reaches p' at the scale of mag_m, not of |m'|, and one of v' at the scale of mag_v)
+    ``acc=torch.float32`` is the kernel's restatement (every operation in fp32, results rounded with rbf).  ``fault``:
+      no_wd, bias_at_step (corrections at ``step`` instead of step + 1), eps_inside (sqrt(v' / bc2 + eps)), beta1_swapped (beta1
+      where 1 - beta1 belongs), skip_block_last (the last element of every 2048-block keeps p, m, v), g_other (a tensor read as
+      the gradient instead of g).  The magnitudes never see the fault."""
+    fault = fault or {}
+    lr, b1, b2, eps, wd = f32(lr), f32(beta1), f32(beta2), f32(eps), f32(weight_decay)
+    shape = p.shape
+    P, M, V = p.reshape(-1).to(acc), m.reshape(-1).to(acc), v.reshape(-1).to(acc)
+    G = (fault["g_other"] if "g_other" in fault else g).reshape(-1).to(acc)
+    c = lambda val: torch.tensor(val, dtype=acc, device=p.device)
+    one = c(1.0)
+    gw = G if (wd == 0.0 or fault.get("no_wd")) else G + c(wd) * P
+    w1 = c(b1) if fault.get("beta1_swapped") else one - c(b1)
+    m2 = M + (gw - M) * w1
+    v2 = c(b2) * V + (one - c(b2)) * gw * gw
+    t = float(step) + (0.0 if fault.get("bias_at_step") else 1.0)
+    bc1, bc2 = one - torch.pow(c(b1), c(t)), one - torch.pow(c(b2), c(t))
+    if fault.get("eps_inside"):
+        denom = torch.sqrt(v2 / bc2 + c(eps))
+    else:
+        denom = torch.sqrt(v2) / torch.sqrt(bc2) + c(eps)
+    p2 = P - (c(lr) / bc1) * (m2 / denom)
+    if fault.get("skip_block_last"):
+        last = torch.arange(ADAM_PER_WG - 1, P.numel(), ADAM_PER_WG, device=p.device)
+        p2[last], m2[last], v2[last] = P[last], M[last], V[last]
+    # magnitudes: float64, exact step, no fault
+    Pd, Gd, Md, Vd = p.reshape(-1).double().abs(), g.reshape(-1).double().abs(), m.reshape(-1).double().abs(), v.reshape(-1).double()
+    gm = Gd + wd * Pd
+    mag_m = Md + (1.0 - b1) * (gm + Md)
+    mag_v = b2 * Vd + (1.0 - b2) * gm * gm
+    gx = g.reshape(-1).double() + wd * p.reshape(-1).double()
+    vx = b2 * Vd + (1.0 - b2) * gx * gx
+    dx = vx.sqrt() / (1.0 - b2 ** (step + 1.0)) ** 0.5 + eps
+    rho = torch.where(vx > 0, mag_v / vx.clamp(min=1e-300), torch.ones_like(vx))
+    mag_p = Pd + lr / (1.0 - b1 ** (step + 1.0)) * mag_m / dx * rho
+    if acc == torch.float32:
+        p2, m2, v2 = rbf(p2), rbf(m2), rbf(v2)
+    r = lambda t_: t_.reshape(shape)
+    return r(p2), r(mag_p), r(m2), r(mag_m), r(v2), r(mag_v)
+
+
+def adam_k(step, beta1, beta2):
+    """(k_ulp, k_mag) of p', m', v' for the step count ``step`` before the update (tests/test_gpu_adam.py derives them): k_mag in
+    units of 2^-8 as assert_within takes it.  C(b, t) = 1 + 4 b^t / (1 - b^t) is the conditioning of 1 - b^t in fp32."""
+    b1, b2, t = f32(beta1), f32(beta2), step + 1.0
+    cond = lambda b: 1.0 + 4.0 * b ** t / (1.0 - b ** t)
+    return {"p": (1, (25.0 + cond(b1) + 0.5 * cond(b2)) * 2.0 ** -16), "m": (1, 5.0 * 2.0 ** -16), "v": (1, 8.0 * 2.0 ** -16)}
+
+
+def adam_case(shape, g_scale, m_sign, v0, seed):
+    """bf16 (p, g, m, v) of one tensor: p ~ 0.1 N(0, 1), g ~ g_scale N(0, 1) (exactly 0 with g_scale 0), m = m_sign * sign(g) *
+    |0.5 g_scale N(0, 1)| (0.01 N(0, 1) where g is 0), v = v0 * (0.5 + U(0, 1)) (0 with v0 0).  CPU."""
+    gen = torch.Generator().manual_seed(seed)
+    p = torch.randn(shape, generator=gen) * 0.1
+    g = torch.randn(shape, generator=gen) * g_scale
+    a = torch.randn(shape, generator=gen).abs()
+    m = m_sign * torch.sign(g) * a * 0.5 * g_scale if g_scale else torch.randn(shape, generator=gen) * 0.01
+    v = (torch.rand(shape, generator=gen) + 0.5) * v0
+    return p.bfloat16(), g.bfloat16(), m.bfloat16(), v.bfloat16()

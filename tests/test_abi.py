@@ -70,3 +70,36 @@ def test_new_entry_points_refuse_bad_arguments_before_any_launch():
     rows = (_lib.Exp3Block * 1)()
     assert lib.bliss_exp3_normalize_global_rows(rows, 1, 100, p, 96, 0) == E             # a row without buffers
     assert lib.bliss_exp3_normalize_global_rows(rows, 0, 100, p, 96, 0) == E
+
+
+def test_adam_step_refuses_bad_arguments_before_any_launch():
+    """bliss_adam_step validates on the host: a tensor count of 0 or above BLISS_ADAM_MAX_TENSORS, a null pointer for a tensor that
+    has elements, a negative element count, no state.  (A tensor of NO elements may come with null pointers -- torch gives an
+    empty tensor none -- and a list of only such tensors launches nothing: 0.)"""
+    import ctypes as C
+    from bliss_gnn_amd import _lib
+    lib, E = _lib.lib, _lib.EINVAL
+    buf = (C.c_int64 * 64)()
+    p = C.addressof(buf)
+
+    def tensors(count, numel=8):
+        t = _lib.AdamTensors()
+        for i in range(min(count, _lib.ADAM_MAX_TENSORS)):
+            t.param[i], t.grad[i], t.exp_avg[i], t.exp_avg_sq[i], t.numel[i] = p, p, p, p, numel
+        t.count = count
+        return t
+    step = lambda t, state=p: lib.bliss_adam_step(C.byref(t), state, 0.9, 0.999, 1e-8, 0.0, 0)
+    assert step(tensors(0)) == E                                                          # no tensors
+    assert step(tensors(_lib.ADAM_MAX_TENSORS + 1)) == E                                  # one more than the struct holds
+    for field in ("param", "grad", "exp_avg", "exp_avg_sq"):
+        t = tensors(3)
+        getattr(t, field)[1] = None
+        assert step(t) == E, field                                                        # a null pointer
+    t = tensors(3)
+    t.numel[2] = -1
+    assert step(t) == E                                                                   # a negative element count
+    assert step(tensors(3), state=0) == E                                                 # no state
+    assert lib.bliss_adam_step(None, p, 0.9, 0.999, 1e-8, 0.0, 0) == E                    # no tensor list
+    t = tensors(2, numel=0)
+    t.param[0] = t.grad[1] = None
+    assert step(t) == 0                                                                   # only empty tensors: nothing to launch

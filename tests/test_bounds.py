@@ -5,9 +5,9 @@ dropout scale -- fails the same bound with the same constants (bounds.GAT_K, bou
 import pytest
 import torch
 
-from bounds import (GAT_K, SPMM_K, WGRAD_LOUD_CASES, assert_within, dense_k, dgrad_terms, from_degrees, gat_autograd, gat_inputs,
-                    gat_terms, gemm_terms, rbf, sage_layer_k, sage_layer_terms, spmm_terms, ulp_bf16, wgrad_inputs, wgrad_loud_rows,
-                    wgrad_plan, wgrad_terms)
+from bounds import (ADAM_SIZES, CE_SHAPES, GAT_K, SPMM_K, WGRAD_LOUD_CASES, adam_case, adam_k, adam_terms, assert_within, ce_case,
+                    ce_k, ce_k_loss, ce_terms, dense_k, dgrad_terms, from_degrees, gat_autograd, gat_inputs, gat_terms, gemm_terms, rbf,
+                    sage_layer_k, sage_layer_terms, spmm_terms, ulp_bf16, wgrad_inputs, wgrad_loud_rows, wgrad_plan, wgrad_terms)
 
 CPU = torch.device("cpu")
 
@@ -502,3 +502,167 @@ def test_sage_layer_faults_fail(fin, fout, fault, p):
     ref = sage_layer_terms(**o, g=g, mask=mask, p=p)
     with pytest.raises(AssertionError, match="over the bound"):
         _sage_check(spec, o, sage_layer_terms(**o, g=g, mask=mask, p=p, sim=True, fault=fault), ref, p)
+
+
+# ------------------------------------------------------------------------------------------------ cross-entropy
+def _ce_ratios(x, y, denom, x2=None, n_valid=None, fault=None, acc=torch.float32):
+    """(gradient ratio, loss ratio) of ce_terms in ``acc`` (with ``fault``) against the float64 reference, raising like the GPU
+    tests' ce_check when either bound is missed."""
+    n, c = x.shape
+    loss, mag_loss, grad, mag = ce_terms(x, y, denom, x2=x2, n_valid=n_valid)
+    got_loss, _, got, _ = ce_terms(x, y, denom, x2=x2, n_valid=n_valid, fault=fault, acc=acc)
+    r = assert_within(got, grad, mag, 1, ce_k(c) * 2.0 ** -16, "ce gradient")
+    err, bound = abs(float(got_loss) - float(loss)), ce_k_loss(n, c) * 2.0 ** -24 * float(mag_loss)
+    rl = 0.0 if err == 0 else (err / bound if bound > 0 else float("inf"))
+    assert rl <= 1.0, ("ce loss", float(got_loss), float(loss), rl)
+    return r, rl
+
+
+@pytest.mark.parametrize("confident", [False, True])
+@pytest.mark.parametrize("scale", [1, 3, 20])
+@pytest.mark.parametrize("shape", CE_SHAPES)
+def test_ce_fp32_restatement_passes_on_the_gpu_cases(shape, scale, confident):
+    """The kernel's fp32 restatement on the inputs of tests/test_gpu_cross_entropy.py stays within both bounds; the worst
+    gradient element is well inside (the orientation figure of the derivation: under 1 ulp + 2^-22 / denom, a k of 4)."""
+    x, y = ce_case(shape, scale, confident, 11 + 7 * scale + confident)
+    r, rl = _ce_ratios(x, y, float(shape[0]))
+    assert r <= 1.0 and rl <= 1.0
+
+
+def test_ce_fp32_restatement_passes_with_two_addends_and_a_row_count():
+    gen = torch.Generator().manual_seed(5)
+    a = (torch.randn(300, 65, generator=gen) * 3).bfloat16()
+    b = (torch.randn(300, 65, generator=gen) * 3).bfloat16()
+    y = torch.randint(0, 65, (300,), generator=gen)
+    for n_valid in (300, 299, 1, 0):
+        _ce_ratios(a, y, 512.0, x2=b, n_valid=n_valid)
+    loss, _, grad, _ = ce_terms(a, y, 512.0, x2=b, n_valid=7)
+    assert not grad[7:].any() and float(loss) > 0
+
+
+def test_ce_minus_inf_takes_its_limit():
+    x, y = ce_case((32, 3), 3, False, 3)
+    x[4, (int(y[4]) + 1) % 3] = -float("inf")
+    loss, _, grad, _ = ce_terms(x, y, 32.0)
+    assert float(grad[4, (int(y[4]) + 1) % 3]) == 0.0 and bool(torch.isfinite(loss)) and bool(torch.isfinite(grad).all())
+    x[9, int(y[9])] = -float("inf")
+    loss, _, grad, _ = ce_terms(x, y, 32.0)
+    assert float(loss) == float("inf") and float(grad[9, int(y[9])]) == -1.0 / 32 and bool(torch.isfinite(grad).all())
+
+
+CE_FAULTS = [{"no_onehot": True}, {"onehot_shift": 1}, {"onehot_shift": -1}, {"inv_n_rows": True}, {"drop_tail": True}]
+
+
+@pytest.mark.parametrize("fault", CE_FAULTS, ids=lambda f: next(iter(f)) + str(next(iter(f.values()))))
+@pytest.mark.parametrize("shape", [(300, 65), (33, 129), (256, 41)])
+def test_ce_planted_faults_fail(shape, fault):
+    """Each one-line fault of the gradient fails the gradient bound (inv_n from the row count: with the divisor of the masked
+    form, 512).  drop_tail on (256, 41) drops every class: the sum is 0 and the row NaN."""
+    x, y = ce_case(shape, 3, False, 21)
+    with pytest.raises(AssertionError, match="ce gradient"):
+        _ce_ratios(x, y, 512.0, fault=fault, acc=torch.float64)
+
+
+def test_ce_fault_max_left_out():
+    """Without the max the exponential of a logit above 88.7 is +inf in fp32 (the planted 200 and, at scale 20, the confident
+    rows): NaN in those rows.  In float64 the same fault is invisible -- exp(200) is finite there and the softmax is
+    shift-invariant -- so this fault is planted in the fp32 restatement, where the kernel would meet it."""
+    x, y = ce_case((300, 65), 3, False, 21)
+    with pytest.raises(AssertionError, match="ce gradient"):
+        _ce_ratios(x, y, 300.0, fault={"no_max": True}, acc=torch.float32)
+    _ce_ratios(x, y, 300.0, fault={"no_max": True}, acc=torch.float64)          # invisible in float64: shift invariance
+
+
+def test_ce_fault_rows_beyond_the_first_grid_trip_dropped_from_the_loss():
+    """Rows >= 4096 left out of the row-ordered sum: invisible at 4096 rows (nothing dropped), over the loss bound at 4097 rows
+    (one row of ~1.6 in 4097: 2.4e-4 of the loss against a bound of ~3e-6) and at 9001."""
+    for n, visible in ((4096, False), (4097, True), (9001, True)):
+        x, y = ce_case((n, 7), 3, False, 23)
+        if visible:
+            with pytest.raises(AssertionError, match="ce loss"):
+                _ce_ratios(x, y, float(n), fault={"drop_rows_loss": True}, acc=torch.float64)
+        else:
+            _ce_ratios(x, y, float(n), fault={"drop_rows_loss": True}, acc=torch.float64)
+
+
+def test_ce_fault_sum_of_addends_not_rounded():
+    gen = torch.Generator().manual_seed(5)
+    a = (torch.randn(300, 65, generator=gen) * 3).bfloat16()
+    b = (torch.randn(300, 65, generator=gen) * 3).bfloat16()
+    y = torch.randint(0, 65, (300,), generator=gen)
+    with pytest.raises(AssertionError, match="ce gradient"):
+        _ce_ratios(a, y, 300.0, x2=b, fault={"no_round_sum": True}, acc=torch.float64)
+
+
+# ------------------------------------------------------------------------------------------------ Adam
+ADAM_HYPER = dict(lr=2e-3, beta1=0.9, beta2=0.999, eps=1e-8)
+
+
+def _adam_check(args, step, wd, fault=None, acc=torch.float32, lr=2e-3):
+    hp = dict(ADAM_HYPER, lr=lr)
+    ref = adam_terms(*args, step, weight_decay=wd, **hp)
+    got = adam_terms(*args, step, weight_decay=wd, fault=fault, acc=acc, **hp)
+    k = adam_k(step, 0.9, 0.999)
+    return [assert_within(got[2 * i], ref[2 * i], ref[2 * i + 1], *k[name], "adam " + name) for i, name in enumerate("pmv")]
+
+
+@pytest.mark.parametrize("v0", [0.0, 1e-12, 1e-4])
+@pytest.mark.parametrize("g_scale", [1.0, 1e-2, 1e-6, 0.0])
+@pytest.mark.parametrize("step", [0, 1, 6, 999, 99999])
+def test_adam_fp32_restatement_passes_on_the_gpu_cases(step, g_scale, v0):
+    """The kernel's fp32 restatement on the inputs of tests/test_gpu_adam.py: every tensor size, both signs of m, both learning
+    rates, the three weight decays."""
+    for si, shape in enumerate(ADAM_SIZES):
+        for m_sign in (1.0, -1.0):
+            args = adam_case(shape, g_scale, m_sign, v0, 100 + si)
+            for lr in (2e-3, 2e-5):
+                for wd in (0.0, 0.01, 0.1):
+                    _adam_check(args, step, wd, lr=lr)
+
+
+def _adam_fault_fails(fault, step=6, wd=0.1, g_scale=1e-2, m_sign=-1.0, v0=1e-4, shape=(4097,), what="adam"):
+    args = adam_case(shape, g_scale, m_sign, v0, 7)
+    with pytest.raises(AssertionError, match=what):
+        _adam_check(args, step, wd, fault=fault, acc=torch.float64)
+
+
+def test_adam_fault_weight_decay_dropped():
+    _adam_fault_fails({"no_wd": True}, wd=0.1)
+    _adam_fault_fails({"no_wd": True}, wd=0.01, g_scale=1e-6)
+    _adam_check(adam_case((4097,), 1e-2, 1.0, 1e-4, 7), 6, 0.0, fault={"no_wd": True}, acc=torch.float64)   # wd 0: nothing to drop
+
+
+def test_adam_fault_bias_corrections_one_step_behind():
+    """At step 0 the corrections are 1 - beta^0 = 0 (a division by zero); at 1 and 6 the update is off by 90 % and 13 %, over
+    the bound on every parameter small enough for its bf16 spacing to show 13 % of lr; at 999 sqrt(1 - 0.999^t) still differs
+    from its neighbour by 3e-4 relative, which the parameters below 1e-3 show (about 1 % of these 4097).  At 99 999 both
+    corrections are 1 at either step: invisible, and asserted so."""
+    for step in (0, 1, 6, 999):
+        _adam_fault_fails({"bias_at_step": True}, step=step, wd=0.0, g_scale=1.0, what="adam p")
+    _adam_check(adam_case((4097,), 1.0, 1.0, 1e-4, 7), 99999, 0.0, fault={"bias_at_step": True}, acc=torch.float64)
+
+
+def test_adam_fault_eps_inside_the_square_root():
+    """sqrt(v / bc2 + eps): with v = 0 and g = 0 the denominator is 1e-4 where 1e-8 belongs, with v ~ 1e-12 likewise; at
+    v ~ 1e-4 it moves the denominator by 5e-5 relative, invisible and asserted so."""
+    _adam_fault_fails({"eps_inside": True}, g_scale=0.0, v0=0.0, wd=0.0, what="adam p")
+    _adam_fault_fails({"eps_inside": True}, g_scale=1e-6, v0=1e-12, wd=0.0, what="adam p")
+    _adam_check(adam_case((4097,), 1e-2, 1.0, 1e-4, 7), 6, 0.0, fault={"eps_inside": True}, acc=torch.float64)
+
+
+def test_adam_fault_beta1_where_one_minus_beta1_belongs():
+    _adam_fault_fails({"beta1_swapped": True}, what="adam p")
+    _adam_fault_fails({"beta1_swapped": True}, wd=0.0, g_scale=1.0, m_sign=1.0, what="adam p")
+
+
+@pytest.mark.parametrize("shape", [(2048,), (2049,), (4096,), (4097,), (256, 602)])
+def test_adam_fault_last_element_of_a_block_left_unchanged(shape):
+    _adam_fault_fails({"skip_block_last": True}, shape=shape, g_scale=1.0, wd=0.0)
+    if shape == (2048,):                                    # 2047 elements: no block is complete, nothing is skipped
+        _adam_check(adam_case((2047,), 1.0, -1.0, 1e-4, 7), 6, 0.0, fault={"skip_block_last": True}, acc=torch.float64)
+
+
+def test_adam_fault_neighbouring_tensors_gradient():
+    """Tensor i updated with tensor i - 1's gradient (a slip in the workgroup-to-tensor search)."""
+    other = adam_case((4097,), 1e-2, -1.0, 1e-4, 8)[1]
+    _adam_fault_fails({"g_other": other})

@@ -22,6 +22,7 @@ Measured on the MI355X (kernel on the accurate expf / log1pf; the fast __expf / 
 bound over logit scales 1, 3, 20, both kinds of target, with and without the infinite plants -- gradient / loss:
     (256, 100) 0.500 / 0.020    (1000, 100) 0.500 / 0.022    (7, 1000) 0.500 / 0.023
     (32, 3)    0.499 / 0.016    (1, 1)      0.346 / 0.001    (300, 65) 0.500 / 0.027
+    (4097, 5)  0.500 / 0.016    (9001, 3)   0.500 / 0.025    (the second trip of the grid-stride row loop; the full 1024-workgroup grid)
 i.e. the gradient is the correctly rounded bf16 of the fp64 value up to the rounding's own half ulp, as the fp32 restatement with
 an exact exponential is on the CPU, and the loss is within 1e-7 relative.
 """
@@ -37,7 +38,7 @@ pytestmark = pytest.mark.gpu
 
 from bounds import assert_within, ulp_bf16   # noqa: E402
 
-SHAPES = [(256, 100), (1000, 100), (7, 1000), (32, 3), (1, 1), (300, 65)]
+SHAPES = [(256, 100), (1000, 100), (7, 1000), (32, 3), (1, 1), (300, 65), (4097, 5), (9001, 3)]
 PLANTS = [0.0, -0.0, 88.0, -88.0, 200.0, -200.0, float("inf"), -float("inf")]
 LOSS_REL = 2.0 ** -18
 
