@@ -120,6 +120,8 @@ class DenseShardedSampler:
         if self._bufs is not None and self._bufs["key"] == key:
             return self._bufs
         nb = V // 1024 + 4
+        # (the two ordered compactions index ceil(V / 1024) status words each -- cap_c is V here -- and one ticket word behind them)
+        assert 2 * nb >= 2 * ((V + 1023) // 1024) + 1, "status-word scratch smaller than bliss_shard_candidates / _select_kept index"
         b = dict(key=key, counts=torch.zeros(L * 10, dtype=torch.int32, device=dev), rec=torch.zeros(L, 10, dtype=torch.int32, device=dev),
                  dense=torch.zeros(2 * V, dtype=torch.int64, device=dev),
                  cand=torch.zeros(V, dtype=torch.int32, device=dev), p=torch.zeros(V, dtype=torch.bfloat16, device=dev),

@@ -26,8 +26,10 @@ def _free_port():
     s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close(); return p
 
 
-def _problem():
+def _problem(size=None):
+    """``size``: (nodes, edges) of the Chung-Lu graph; None = the module's V, E."""
     from bliss_gnn_amd.synth import chung_lu_csc
+    V, E = size or (globals()["V"], globals()["E"])
     ip, ix, ei = chung_lu_csc(V, E, seed=8)
     gen = torch.Generator().manual_seed(4)
     batches = [torch.randperm(V, generator=gen)[:BATCH].to(torch.int32) for _ in range(STEPS)]

@@ -37,14 +37,18 @@ def _block_content(b, S=None, K=None, B=None):
     return dict(rec=rec, kept=nid[:K].tolist(), prob=_bits(b.srcdata["node_prob"].cpu()[:K]).tolist(), dst=dst_nid.tolist())
 
 
-def _sampler_worker(rank, world, port, outdir):
+BIG = (140000, 1400000)                                     # 137 look-back blocks: the walks of the two ordered compactions leave their first round
+
+
+def _sampler_worker(rank, world, port, outdir, size=None):
+    V = size[0] if size else globals()["V"]
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     dist.init_process_group("gloo", rank=rank, world_size=world)
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     from bliss_gnn_amd import shard as sh
     from bliss_gnn_amd import shard_static as ss
-    ip, ix, ei, batches, embed, _, _ = _problem()
+    ip, ix, ei, batches, embed, _, _ = _problem(size)
     bounds = sh.partition_by_in_edges(ip, world)
     g = sh.GraphShard.from_global(ip, ix, ei, bounds, rank, device=dev)
     eager = sh.ShardedPoissonBanditSampler(g, FAN, eta=ETA, seed=SEED)
@@ -76,10 +80,10 @@ def _sampler_worker(rank, world, port, outdir):
     dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("world", [1, 2])
-def test_static_sharded_sampler_equals_the_routed_one(cuda, world):
+@pytest.mark.parametrize("world,size", [(1, None), (2, None), (1, BIG)], ids=["1", "2", "1-big"])
+def test_static_sharded_sampler_equals_the_routed_one(cuda, world, size):
     with tempfile.TemporaryDirectory() as outdir:
-        res = _spawn(_sampler_worker, world, outdir)
+        res = _spawn(_sampler_worker, world, outdir, size)
     for r in res:
         assert r["problems"] == [], r["problems"][:6]
 
@@ -275,7 +279,7 @@ def test_row_kernels_place_and_take(cuda):
     from bliss_gnn_amd import shard_static as ss
     dev = torch.device("cuda:0")
     gen = torch.Generator().manual_seed(5)
-    for cap_s, n, n_rows, D in ((64, 37, 500, 256), (300, 300, 301, 602), (128, 0, 77, 2), (50, 1, 9, 130)):
+    for cap_s, n, n_rows, D in ((64, 37, 500, 256), (300, 300, 301, 602), (128, 0, 77, 2), (50, 1, 9, 130), (40, 17, 90, 1030)):
         pos_true = torch.sort(torch.randperm(n_rows, generator=gen)[:n]).values.to(torch.int32)
         pos = torch.zeros(cap_s, dtype=torch.int32)
         pos[:n] = pos_true                                        # (the padding entries point at row 0, as the sampler leaves them)
