@@ -48,7 +48,22 @@ class _LayerWs:
         self.p = torch.empty(cap_c, dtype=torch.bfloat16, device=dev)
         self.P = torch.empty(cap_c, dtype=torch.bfloat16, device=dev)
         self.uniforms = torch.empty(cap_c, dtype=torch.float32, device=dev)     # explicit-uniforms path only
+        # device-side multinomial draw (csrc/mn_draw.hip): race keys + bins / ticket / tie counts (zero once, left zero by every call)
+        self.keys = torch.empty(cap_c, dtype=torch.float32, device=dev)
+        self.draw_scr = torch.zeros(int(_lib.lib.bliss_multinomial_draw_scratch_bytes(cap_c)) // 4, dtype=torch.int32, device=dev)
         self.src_cnt = None
+
+
+class DrawState:
+    """Seed and step counter of the keyed multinomial draw (``draw="device"``).  The counter lives on the device: the last
+    layer of every sampler call bumps it, also when the call is a replayed HIP graph."""
+
+    def __init__(self, seed, step, device):
+        self.seed = int(seed) & ((1 << 64) - 1)
+        self.step_dev = torch.tensor([int(step)], dtype=torch.int64, device=device)
+
+    def step(self):
+        return int(self.step_dev.item())
 
 
 class LayerEngine:
@@ -92,6 +107,8 @@ class LayerEngine:
         self.mt_host = torch.empty(626, dtype=torch.int32).pin_memory()        # state handed to the device
         self.mt_back = torch.empty(626, dtype=torch.int32).pin_memory()        # state handed back
         self._static = {}
+        self._static_draw = {}
+        self.exact_k = False                # device-drawn multinomial layers keep at most fanout + S nodes: K capacities are that bound
         self._slot_bufs, self._slot_counts, self._slot_counts_host = {}, {}, {}
         self.caps = None
         self.ws = None
@@ -233,12 +250,23 @@ class LayerEngine:
         return self._finish(out, cnts)
 
     # ------------------------------------------------------------------ non-Poisson samplers (multinomial draw)
-    def sample_blocks_multinomial(self, w_rows, seeds, fanouts, mode, eta, replace=False, fp32_importance=False):
+    def sample_blocks_multinomial(self, w_rows, seeds, fanouts, mode, eta, replace=False, fp32_importance=False, draw="host",
+                                  draw_state=None):
         """BanditLadiesSampler / LadiesSampler (bandit_sampler.py:84-99, ladies_sampler.py:54-69): the node importances
         are computed on the device; the draw is ``torch.multinomial`` itself, on the host, on those bits (ATen's CPU
         kernel takes its exponentials from an MKL stream seeded by the global generator -- there is nothing to restate),
         so this path syncs once per layer like the reference does.  ``fp32_importance``: hand the draw fp32 importances
-        (LadiesSampler's non-importance branch builds fp32 ones, ladies_sampler.py:50; ATen draws in the input's dtype)."""
+        (LadiesSampler's non-importance branch builds fp32 ones, ladies_sampler.py:50; ATen draws in the input's dtype).
+
+        ``draw="device"`` (with ``draw_state``, a DrawState): the keyed draw of csrc/mn_draw.hip instead -- frontier_prob,
+        multinomial_draw, multinomial_select_marked and build_block of all L layers are only enqueued and the call synchronises
+        once, at the end, like sample_blocks; torch's CPU generator is not touched."""
+        if draw == "device":
+            if replace:
+                raise NotImplementedError("the device draw is without replacement only (replace=True needs draw='host')")
+            return self._sample_blocks_mn_device(w_rows, seeds, fanouts, mode, eta, draw_state)
+        if draw != "host":
+            raise ValueError("draw must be 'host' or 'device', not %r" % (draw,))
         seeds = seeds.to(torch.int32).contiguous()
         L = len(fanouts)
         self._ensure(int(seeds.numel()), fanouts)
@@ -290,6 +318,43 @@ class LayerEngine:
             if bad == 0:
                 return self._finish((counts, layers), cnts)
             self._grow([c.err for c in cnts])
+            self._ensure(int(seeds.numel()), fanouts)
+
+    def _mn_exact_caps(self, fanouts):
+        """A device-drawn layer keeps union(drawn, seeds): at most fanout + S nodes, so that is its K capacity."""
+        for n in range(len(fanouts)):
+            need = min(self.V, int(fanouts[n]) + self.caps[n]["S"])
+            if self.caps[n]["K"] < need:
+                self.caps[n]["K"] = need
+            if n + 1 < len(fanouts) and self.caps[n + 1]["S"] < self.caps[n]["K"]:
+                self.caps[n + 1]["S"] = self.caps[n]["K"]
+                self.ws = None
+
+    def _sample_blocks_mn_device(self, w_rows, seeds, fanouts, mode, eta, draw_state):
+        if draw_state is None:
+            raise ValueError("draw='device' needs a draw_state")
+        seeds = seeds.to(torch.int32).contiguous()
+        L = len(fanouts)
+        self._ensure(int(seeds.numel()), fanouts)
+        self._mn_exact_caps(fanouts)
+        self._ensure(int(seeds.numel()), fanouts)
+        while True:
+            out = self._enqueue(w_rows, seeds, fanouts, mode, eta, 0.0, None, None, draw_state=draw_state)
+            self.counts_host.copy_(out[0], non_blocking=True)
+            torch.cuda.current_stream().synchronize()                 # the one sync of the call
+            raw = self.counts_host.numpy().tobytes()
+            cnts = [_lib.LayerCounts.from_buffer_copy(raw[40 * n: 40 * n + 40]) for n in range(L)]
+            bad = 0
+            for c in cnts:
+                bad |= c.err
+            if bad & ~_CAP_ERRS or bad & 1 or (bad & 2 and not self.n_bins):
+                raise RuntimeError(f"sampler kernel error 0x{bad:x}: {_lib.err_string(bad)}")
+            if bad == 0:
+                return self._finish(out, cnts, keys=True)
+            draw_state.step_dev.sub_(1)                                # the repeated call is the same draw step
+            self._grow([c.err for c in cnts])
+            self._ensure(int(seeds.numel()), fanouts)
+            self._mn_exact_caps(fanouts)
             self._ensure(int(seeds.numel()), fanouts)
 
     def _layer_buffers(self, n, counts, slot=None):
@@ -360,6 +425,8 @@ class LayerEngine:
         caps, s = [], int(S0)
         for n, f in enumerate(fanouts):
             k = min(self.V, int(k_margin * max_sizes[n]["K"]) + 256)
+            if self.exact_k:                # (device-drawn multinomial layer: the exact bound, such a step cannot overflow K)
+                k = min(self.V, int(f) + s)
             b = int(min(self.Eg, int(b_margin * max_sizes[n]["B"]) + 4096))
             # E only sizes launch grids (every kernel strides over the true count): a tight bound lets the hardware balance
             # the workgroups instead of a capped grid looping unevenly
@@ -419,7 +486,7 @@ class LayerEngine:
         _lib.check(_lib.lib.bliss_rng_stream_ready(_stream()), "bliss_rng_stream_ready")
 
     def enqueue_static(self, w_rows, seeds, fanouts, mode, eta, eps=0.9999, slot=0, chain_rng=False, external_rng=False, part=None,
-                       last_block=True, ready_flag=0):
+                       last_block=True, ready_flag=0, draw_state=None):
         """Enqueue one sample_blocks on the current stream with capacity-padded outputs and NO sync.  Returns the
         blocks (sampling order); sizes, errors and the generator state are read back by finish().
 
@@ -431,18 +498,25 @@ class LayerEngine:
         no scratch with any later layer) and external_rng.  The caller orders the next "main" after both parts.
         ``last_block=False`` with "main": the last-sampled layer's block is left out as well and ``flags[L]`` is raised at the end
         (its draw is done); part "last_block" = only that block, behind a bliss_flag_wait on ``flags[L]``; ``ready_flag``
-        (address of a device flag) is raised as soon as the block's forward arrays are final, before its by-source index."""
+        (address of a device flag) is raised as soon as the block's forward arrays are final, before its by-source index.
+        ``draw_state`` (a DrawState): the layers draw with the device-side multinomial draw instead of the Poisson chain
+        (whole calls only; no generator is involved)."""
+        if draw_state is not None and (part is not None or external_rng or chain_rng):
+            raise NotImplementedError("the device-side multinomial draw has no split / external-generator enqueue "
+                                      "(the pipelined two-stream loop is out of scope)")
         if part is not None and (self.scratch_sets < len(fanouts) or not external_rng):
             raise ValueError("split enqueue needs one scratch set per layer and an external generator")
         L = len(fanouts)
         out = self._enqueue(w_rows, seeds, fanouts, mode, eta, eps, None, True, slot=slot, chain_rng=chain_rng,
-                            external_rng=external_rng, part=part, last_block=last_block, ready_flag=ready_flag)
+                            external_rng=external_rng, part=part, last_block=last_block, ready_flag=ready_flag, draw_state=draw_state)
+        self._static_draw[slot] = draw_state is not None
         counts_dev, layers = out
         if slot not in self._slot_counts_host:
             self._slot_counts_host[slot] = torch.empty(L * 10, dtype=torch.int32).pin_memory()
         if not external_rng:                     # (external: static_rng_end copies both, off the consumer's critical path)
             self._slot_counts_host[slot].copy_(counts_dev, non_blocking=True)
-            self.mt_back.copy_(self.mt_dev, non_blocking=True)
+            if draw_state is None:
+                self.mt_back.copy_(self.mt_dev, non_blocking=True)
         blocks = []
         for n, lay in enumerate(layers):
             b_indptr, b_src, b_dst, b_pos, b_eid, b_w, b_q, kept_nid, node_prob, cdev, t_indptr, t_edge = lay
@@ -469,7 +543,7 @@ class LayerEngine:
             bad |= c.err
         for b, c in zip(blocks, cnts):
             b._counts = c
-        if commit:
+        if commit and not self._static_draw.get(slot):       # (the device draw consumed nothing from torch's generator)
             self._commit_rng(self._static_snapshot)
         if bad:
             raise RuntimeError(f"static-shape step exceeded its capacities or hit a kernel error 0x{bad:x} "
@@ -477,10 +551,10 @@ class LayerEngine:
         return cnts
 
     def _enqueue(self, w_rows, seeds, fanouts, mode, eta, eps, uniforms, snapshot, slot=None, chain_rng=False, external_rng=False,
-                 part=None, last_block=True, ready_flag=0):
+                 part=None, last_block=True, ready_flag=0, draw_state=None):
         dev, st = self.g.device, _stream()
         L = len(fanouts)
-        if snapshot is not None and not chain_rng and not external_rng:
+        if draw_state is None and snapshot is not None and not chain_rng and not external_rng:
             if snapshot is not True:
                 self._stage_rng(snapshot)
             self.mt_dev.copy_(self.mt_host, non_blocking=True)
@@ -490,7 +564,7 @@ class LayerEngine:
             if slot not in self._slot_counts or self._slot_counts[slot].numel() != L * 10:
                 self._slot_counts[slot] = torch.empty(L * 10, dtype=torch.int32, device=dev)
             counts = self._slot_counts[slot]
-        use_rng = uniforms is None
+        use_rng = uniforms is None and draw_state is None
         if use_rng and not external_rng:      # fork the generator: it runs beside everything below
             _lib.check(_lib.lib.bliss_rng_stream_begin(self.mt_dev.data_ptr(), self.rng_ctl.data_ptr(), self.rng_out.data_ptr(),
                                                        self.rng_raw.data_ptr(), self.rng_cap, st), "bliss_rng_stream_begin")
@@ -506,7 +580,16 @@ class LayerEngine:
             last = n == L - 1
             if part == "main":                  # layer n raises flag n when it starts (= everything before it has completed)
                 c_ws.entry_flag = self.flags.data_ptr() + 4 * n
-            if part in (None, "main"):          # candidates, probabilities, draw: all the next layer needs (its seeds = kept_nid)
+            if draw_state is not None:          # multinomial samplers, keyed draw: 1 + 5 + 4 launches, then the block
+                _lib.check(_lib.lib.bliss_frontier_prob(C.byref(self.c_graph), C.byref(self._set(n)["c_maps"]), w_pos.data_ptr(),
+                                                        cur_seeds.data_ptr(), n_seeds, n_seeds_dev, cs, mode, eta_f, ome_f,
+                                                        cap.get("E", self.Eg), C.byref(c_ws), st), "bliss_frontier_prob")
+                _lib.check(_lib.lib.bliss_multinomial_draw(ws.cand_nid.data_ptr(), ws.p.data_ptr(), cnt_ptr, cap["C"], int(fanouts[n]), 0,
+                                                           draw_state.seed, draw_state.step_dev.data_ptr(), n, int(last),
+                                                           ws.draw_scr.data_ptr(), ws.keys.data_ptr(), ws.new_id.data_ptr(), st),
+                           "bliss_multinomial_draw")
+                _lib.check(_lib.lib.bliss_multinomial_select_marked(C.byref(c_ws), st), "bliss_multinomial_select_marked")
+            elif part in (None, "main"):        # candidates, probabilities, draw: all the next layer needs (its seeds = kept_nid)
                 if self.n_bins and self.fuse_scale:
                     # the Poisson scale rides in the last workgroup of the candidate numbering (one launch less per layer)
                     c_ws.fs_ticket = self.fs_ticket.data_ptr()
@@ -548,7 +631,7 @@ class LayerEngine:
                                                      self.rng_cap, counts.data_ptr() + 20, _stream()), "bliss_rng_stream_end")
         return counts, layers
 
-    def _finish(self, out, cnts):
+    def _finish(self, out, cnts, keys=False):
         _, layers = out
         blocks = []
         for n, (lay, c) in enumerate(zip(layers, cnts)):
@@ -561,5 +644,7 @@ class LayerEngine:
                 blk._transposed = (t_indptr[:K + 1], t_edge[:max(B, 1)])
             ws = self.ws[n]
             blk._trace = dict(p=ws.p[:c.C], P=ws.P[:c.C], cand_nid=ws.cand_nid[:c.C], new_id=ws.new_id[:c.C])
+            if keys:
+                blk._trace["keys"] = ws.keys[:c.C]
             blocks.append(blk)
         return blocks

@@ -148,6 +148,8 @@ SIGNATURES = {
     "bliss_mt19937_uniform": [_P, _P, _I32, _P, _I32, _P],
     "bliss_poisson_select": [C.POINTER(LayerWs), _I32, _D, _P, _P, _P, C.c_int, _I32, _I64, _P],
     "bliss_multinomial_select": [C.POINTER(LayerWs), _P, _I32, _P],
+    "bliss_multinomial_draw": [_P, _P, _P, _I32, _I32, _P, C.c_uint64, _P, _I32, C.c_int, _P, _P, _P, _P],
+    "bliss_multinomial_select_marked": [C.POINTER(LayerWs), _P],
     "bliss_tile_gemm": [C.POINTER(TileGemm), C.POINTER(TileGemm), _P],
     "bliss_cross_entropy": [_P, _I64, _P, _I32, _I32, _P, _P, _I64, _P, _P, _P, _P],
     "bliss_cross_entropy_sum": [_P, _I64, _P, _I64, _P, _P, _I32, _I32, _P, _P, _I64, _P, _P, _P, _P],
@@ -209,7 +211,8 @@ SIGNATURES = {
 
 
 SPECIAL_SIGNATURES = ("bliss_prof_kernel_name", "bliss_block_transpose_temp_bytes", "bliss_graph_prepare_capacity",
-                      "bliss_graph_prepare_temp_bytes", "bliss_rng_stream_handle", "bliss_sage_wgrad_workspace")   # non-int return types, set in _load()
+                      "bliss_graph_prepare_temp_bytes", "bliss_rng_stream_handle", "bliss_sage_wgrad_workspace",
+                      "bliss_multinomial_draw_scratch_bytes")   # non-int return types, set in _load()
 
 
 def _load():
@@ -229,6 +232,8 @@ def _load():
     for name in ("bliss_graph_prepare_capacity", "bliss_graph_prepare_temp_bytes"):
         getattr(lib, name).argtypes = [_I64, _I32, C.c_int]
         getattr(lib, name).restype = C.c_int64
+    lib.bliss_multinomial_draw_scratch_bytes.argtypes = [_I32]
+    lib.bliss_multinomial_draw_scratch_bytes.restype = C.c_int64
     lib.bliss_rng_stream_handle.argtypes = []
     lib.bliss_rng_stream_handle.restype = C.c_int64
     lib.bliss_prof_kernel_name.argtypes = [C.c_int]

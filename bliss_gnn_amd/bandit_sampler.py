@@ -14,7 +14,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._engine import LayerEngine, _stream
+from ._engine import DrawState, LayerEngine, _stream
 from .graph import EID, NID, Graph, as_graph
 
 
@@ -52,16 +52,53 @@ class BlockSampler:
         return self.sample_blocks(g, seed_nodes, exclude_eids=exclude_eids)
 
 
-class BanditLadiesSampler(BlockSampler):
+class DeviceDraw:
+    """The ``draw=`` keyword of the two multinomial samplers.  ``"host"`` (default): ``torch.multinomial`` on the host, the
+    reference's draw, one sync per layer.  ``"device"``: the keyed exponential race of csrc/mn_draw.hip
+    -- no host round trip, so ``sample_blocks_static`` exists and the sampler can run inside a captured train step; the
+    draw is a function of (seed, draw step, layer, node id) and consumes nothing from torch's generator."""
+
+    _NO_STATIC = "the multinomial draw is torch.multinomial on the host: no static-shape variant (use draw='device')"
+
+    def _init_draw(self, draw, replace):
+        if draw not in ("host", "device"):
+            raise ValueError("draw must be 'host' or 'device', not %r" % (draw,))
+        if draw == "device" and self._poisson:
+            raise ValueError("draw='device' is the multinomial samplers' draw; the Poisson samplers always draw on the device")
+        if draw == "device" and replace:
+            raise NotImplementedError("the device draw is without replacement only (replace=True needs draw='host')")
+        self.draw = draw
+        self._draw_init, self._draw_state = (None, 0), None
+
+    def reset_draw(self, seed=None, step=0):
+        """Set the draw state: ``seed`` (None = ``torch.initial_seed()``, taken at first use) and the step counter."""
+        self._draw_init, self._draw_state = (seed, int(step)), None
+
+    def draw_step(self):
+        """The step counter (one sync): how many sampler calls have drawn since the state was set, plus its start."""
+        return self._draw_init[1] if self._draw_state is None else self._draw_state.step()
+
+    def _draw_state_on(self, device):
+        if self.draw != "device":
+            return None
+        if self._draw_state is None:
+            seed, step = self._draw_init
+            self._draw_state = DrawState(torch.initial_seed() if seed is None else seed, step, device)
+        return self._draw_state
+
+
+class BanditLadiesSampler(DeviceDraw, BlockSampler):
     """bandit_sampler.py:29-367.  ``select_neighbors`` (:84-99) is ``torch.multinomial`` on the device-computed
-    importances, drawn on the host (one sync per layer, like the reference)."""
+    importances, drawn on the host (one sync per layer, like the reference), or with ``draw="device"`` the keyed draw on
+    the device (DeviceDraw)."""
 
     _poisson = False
 
     def __init__(self, nodes_per_layer, importance_sampling=True, weight="w", out_weight="edge_weights",
                  node_embedding="nfeat", node_prob="node_prob", replace=False, eta=0.4, num_steps=5000,
-                 model="sage"):
+                 model="sage", *, draw="host"):
         super().__init__()
+        self._init_draw(draw, replace)
         self.nodes_per_layer = nodes_per_layer
         self.importance_sampling = importance_sampling
         self.edge_weight = weight
@@ -93,6 +130,7 @@ class BanditLadiesSampler(BlockSampler):
         g = self._graph(g)
         if self._engine is None or self._engine.g is not g:
             self._engine = LayerEngine(g)
+            self._engine.exact_k = self.draw == "device"
         return self._engine
 
     def _ensure_weights(self, g):
@@ -142,7 +180,8 @@ class BanditLadiesSampler(BlockSampler):
         if self._poisson:
             blks = eng.sample_blocks(rows, seed_nodes, fan, self._mode(), self.eta, self.eps, uniforms)
         else:                                                             # select_neighbors :84-99 (torch.multinomial)
-            blks = eng.sample_blocks_multinomial(rows, seed_nodes, fan, self._mode(), self.eta, self.replace)
+            blks = eng.sample_blocks_multinomial(rows, seed_nodes, fan, self._mode(), self.eta, self.replace, draw=self.draw,
+                                                 draw_state=self._draw_state_on(g.device))
         blocks = []
         for blk in blks:
             blk.edata[self.output_weight] = blk._edge_weights           # :324
@@ -157,13 +196,15 @@ class BanditLadiesSampler(BlockSampler):
         before and ``finish_static()`` after the stream has been synchronised.  Padded rows / edges are inert:
         ids past the true K point at node 0 and no edge references them; edges past the true B are ignored by
         every kernel (the true counts live on the device)."""
+        if not self._poisson and self.draw != "device":
+            raise NotImplementedError(self._NO_STATIC)
         g = self._graph(g)
         eng = self._bind(g)
         self._ensure_weights(g)
         order = list(reversed(range(len(self.nodes_per_layer))))
         blks = eng.enqueue_static([self._w_pos[b] for b in order], seed_nodes, [self.nodes_per_layer[b] for b in order],
                                   self._mode(), self.eta, self.eps, slot=slot, chain_rng=chain_rng, external_rng=external_rng, part=part,
-                                  last_block=last_block, ready_flag=ready_flag)
+                                  last_block=last_block, ready_flag=ready_flag, draw_state=self._draw_state_on(g.device))
         blocks = []
         for blk in blks:
             blk.edata[self.output_weight] = blk._edge_weights

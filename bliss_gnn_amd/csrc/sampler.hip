@@ -1059,6 +1059,10 @@ __global__ void __launch_bounds__(TPB) k_mn_mark(LayerCounts* cnt, const int* __
     if (j >= 0 && j < C) new_id[j] = 1; else atomicOr(&cnt->err, BLISS_ERR_CAP_CAND);
   }
 }
+__global__ void __launch_bounds__(TPB) k_mn_copy_p(const LayerCounts* cnt, const bf16_t* __restrict__ p, bf16_t* __restrict__ P, int cap_c) {
+  const int C = min(cnt->C, cap_c);
+  for (int j = blockIdx.x * TPB + threadIdx.x; j < C; j += gridDim.x * TPB) P[j] = p[j];
+}
 template <bool EMIT>
 __global__ void __launch_bounds__(TPB) k_mn_select(LayerCounts* cnt, const bf16_t* __restrict__ P, int* __restrict__ chunk_io,
                                                    const int* __restrict__ cand_nid, int* __restrict__ new_id,
@@ -1541,6 +1545,20 @@ int bliss_multinomial_select(const bliss_layer_ws_t* ws, const int32_t* chosen, 
   const int gc = grid_for(ws->cap_c, CHUNK), ge = grid_for(ws->cap_c, TPB);
   k_mn_prepare<<<ge, TPB, 0, st>>>(cnt, (const bf16_t*)ws->p, (bf16_t*)ws->P, ws->new_id, ws->cap_c);
   if (n_chosen > 0) k_mn_mark<<<grid_for(n_chosen, TPB), TPB, 0, st>>>(cnt, chosen, n_chosen, ws->new_id, ws->cap_c);
+  k_mn_select<false><<<gc, TPB, 0, st>>>(cnt, (const bf16_t*)ws->P, ws->chunk_cnt, ws->cand_nid, ws->new_id, ws->kept_nid, (bf16_t*)ws->node_prob, ws->cap_c, ws->cap_k, ws->kept_map);
+  k_chunk_scan<<<1, 1024, 0, st>>>(ws->chunk_cnt, cnt, 1, ws->cap_k);
+  k_mn_select<true><<<gc, TPB, 0, st>>>(cnt, (const bf16_t*)ws->P, ws->chunk_cnt, ws->cand_nid, ws->new_id, ws->kept_nid, (bf16_t*)ws->node_prob, ws->cap_c, ws->cap_k, ws->kept_map);
+  return (int)hipGetLastError();
+}
+
+int bliss_multinomial_select_marked(const bliss_layer_ws_t* ws, void* stream_) {
+  if (!ws || !ws->counts || !ws->p || !ws->P || !ws->new_id || !ws->cand_nid || !ws->chunk_cnt || !ws->kept_nid || !ws->node_prob ||
+      ws->cap_c <= 0 || ws->cap_k <= 0)
+    return BLISS_EINVAL;
+  hipStream_t st = (hipStream_t)stream_;
+  LayerCounts* cnt = (LayerCounts*)ws->counts;
+  const int gc = grid_for(ws->cap_c, CHUNK), ge = grid_for(ws->cap_c, TPB);
+  k_mn_copy_p<<<ge, TPB, 0, st>>>(cnt, (const bf16_t*)ws->p, (bf16_t*)ws->P, ws->cap_c);
   k_mn_select<false><<<gc, TPB, 0, st>>>(cnt, (const bf16_t*)ws->P, ws->chunk_cnt, ws->cand_nid, ws->new_id, ws->kept_nid, (bf16_t*)ws->node_prob, ws->cap_c, ws->cap_k, ws->kept_map);
   k_chunk_scan<<<1, 1024, 0, st>>>(ws->chunk_cnt, cnt, 1, ws->cap_k);
   k_mn_select<true><<<gc, TPB, 0, st>>>(cnt, (const bf16_t*)ws->P, ws->chunk_cnt, ws->cand_nid, ws->new_id, ws->kept_nid, (bf16_t*)ws->node_prob, ws->cap_c, ws->cap_k, ws->kept_map);

@@ -96,18 +96,19 @@ class NeighborSampler(BlockSampler):
         return blocks[0].srcdata[NID], seed_nodes, blocks
 
 
-def make_sampler(name, fanouts, importance_sampling=1, num_steps=5000, eta=0.1, model="sage"):
-    """The sampler-name dispatch of DataModule.__init__ (train_lightning.py:348-370)."""
+def make_sampler(name, fanouts, importance_sampling=1, num_steps=5000, eta=0.1, model="sage", draw="host"):
+    """The sampler-name dispatch of DataModule.__init__ (train_lightning.py:348-370).  ``draw``: where the two multinomial
+    samplers ("ladies", "bandit") draw -- "host" (torch.multinomial) or "device" (the keyed draw, graph-capturable)."""
     from . import BanditLadiesSampler, LadiesSampler, PoissonBanditLadiesSampler, PoissonLadiesSampler as PLS
     if name == "full":
         return MultiLayerFullNeighborSampler(len(fanouts))
     if name == "neighbor":
         return NeighborSampler(fanouts)
     if "ladies" in name and "bandit" not in name:
-        return (PLS if "poisson" in name else LadiesSampler)(fanouts)
+        return PLS(fanouts) if "poisson" in name else LadiesSampler(fanouts, draw=draw)
     if "bandit" in name:
-        return (PoissonBanditLadiesSampler if "poisson" in name else BanditLadiesSampler)(
-            fanouts, importance_sampling=importance_sampling, node_embedding="features", num_steps=num_steps, eta=eta, model=model)
+        kw = dict(importance_sampling=importance_sampling, node_embedding="features", num_steps=num_steps, eta=eta, model=model)
+        return PoissonBanditLadiesSampler(fanouts, **kw) if "poisson" in name else BanditLadiesSampler(fanouts, draw=draw, **kw)
     raise ValueError("unknown sampler %r" % (name,))
 
 

@@ -6,18 +6,20 @@ import torch
 
 from . import _lib
 from ._engine import LayerEngine
-from .bandit_sampler import BlockSampler, find_indices_in, normalized_edata, union  # noqa: F401  (same helpers, ladies_sampler.py:6-22)
+from .bandit_sampler import BlockSampler, DeviceDraw, find_indices_in, normalized_edata, union  # noqa: F401  (same helpers, ladies_sampler.py:6-22)
 from .graph import NID
 
 
-class LadiesSampler(BlockSampler):
-    """ladies_sampler.py:24-123.  ``select_neighbors`` (:54-69) = ``torch.multinomial`` on the device-computed importances."""
+class LadiesSampler(DeviceDraw, BlockSampler):
+    """ladies_sampler.py:24-123.  ``select_neighbors`` (:54-69) = ``torch.multinomial`` on the device-computed importances,
+    or with ``draw="device"`` the keyed draw on the device (bandit_sampler.DeviceDraw)."""
 
     _poisson = False
 
     def __init__(self, nodes_per_layer, importance_sampling=True, weight="w", out_weight="edge_weights",
-                 replace=False, allow_zero_in_degree=False):
+                 replace=False, allow_zero_in_degree=False, *, draw="host"):
         super().__init__()
+        self._init_draw(draw, replace)
         self.nodes_per_layer = nodes_per_layer
         self.importance_sampling = importance_sampling
         self.edge_weight = weight
@@ -44,7 +46,8 @@ class LadiesSampler(BlockSampler):
             blks = self._engine.sample_blocks([w_pos] * len(order), seed_nodes, fan, self._mode(), 0.0, self.eps, uniforms)
         else:                                                            # select_neighbors :54-69 (torch.multinomial)
             blks = self._engine.sample_blocks_multinomial([w_pos] * len(order), seed_nodes, fan, self._mode(), 0.0, self.replace,
-                                                          fp32_importance=not self.importance_sampling)
+                                                          fp32_importance=not self.importance_sampling, draw=self.draw,
+                                                          draw_state=self._draw_state_on(g.device))
         blocks = []
         for blk in blks:
             blk.edata[self.output_weight] = blk._edge_weights            # :100
@@ -52,7 +55,8 @@ class LadiesSampler(BlockSampler):
         return blocks[0].srcdata[NID], output_nodes, blocks              # :121,:123
 
 
-    # -- static-shape variant (graph-capturable; Poisson only): same contract as PoissonBanditLadiesSampler's ------------
+    # -- static-shape variant (graph-capturable; Poisson, or the multinomial samplers' device draw): same contract as
+    # PoissonBanditLadiesSampler's --------------------------------------------------------------------------------------
     def _graph(self, g):
         from .graph import as_graph
         if not hasattr(self, "_graphs"):
@@ -63,17 +67,19 @@ class LadiesSampler(BlockSampler):
         g = self._graph(g)
         if self._engine is None or self._engine.g is not g:
             self._engine = LayerEngine(g)
+            self._engine.exact_k = self.draw == "device"
         return self._engine
 
     def sample_blocks_static(self, g, seed_nodes, slot=0, chain_rng=False, external_rng=False, part=None, last_block=True, ready_flag=0):
-        if not self._poisson:
-            raise NotImplementedError("the multinomial draw is torch.multinomial on the host: no static-shape variant")
+        if not self._poisson and self.draw != "device":
+            raise NotImplementedError(self._NO_STATIC)
         g = self._graph(g)
         eng = self._bind(g)
         w_pos = g.edata_by_position(self.edge_weight)
         order = list(reversed(range(len(self.nodes_per_layer))))
         blks = eng.enqueue_static([w_pos] * len(order), seed_nodes, [self.nodes_per_layer[b] for b in order], self._mode(), 0.0,
-                                  self.eps, slot=slot, chain_rng=chain_rng, external_rng=external_rng, part=part, last_block=last_block, ready_flag=ready_flag)
+                                  self.eps, slot=slot, chain_rng=chain_rng, external_rng=external_rng, part=part, last_block=last_block, ready_flag=ready_flag,
+                                  draw_state=self._draw_state_on(g.device))
         blocks = []
         for blk in blks:
             blk.edata[self.output_weight] = blk._edge_weights

@@ -172,6 +172,26 @@ int bliss_poisson_select(const bliss_layer_ws_t* ws, int32_t fanout, double eps,
  * union(chosen, seeds) as block sources, only drawn nodes as edge sources (bandit_sampler.py:287-298), P = p (:309). */
 int bliss_multinomial_select(const bliss_layer_ws_t* ws, const int32_t* chosen, int32_t n_chosen, void* stream);
 
+/* The same samplers' draw ON THE DEVICE (draw="device"; no reference counterpart: a defined-mode keyed draw like
+ * bliss_keyed_select, restated on the CPU by tests/mn_draw_ref.py).  The exponential race torch.multinomial runs on the CPU,
+ * with counter-based uniforms:
+ *   u_j   = keyed_uniform(seed, *step_dev, layer, cand_nid[j]) + 2^-24   (in (0, 1]; or uniforms[j] when uniforms != NULL)
+ *   key_j = (float)(-log((double)u_j) / (double)p_j), +inf unless p_j > 0
+ *   drawn = the k = min(fanout, C) smallest (bits of key_j, j), ties to the lower position; C = counts->C, read on the device.
+ * Out: keys fp32 [cap_c] and drawn int32 [cap_c] (1 = drawn, 0 = not; entries [0, C) are written) -- the mark format
+ * bliss_multinomial_select_marked reads from ws->new_id.  bump_step: the last workgroup of the first kernel increments
+ * *step_dev once.  scratch: bliss_multinomial_draw_scratch_bytes(cap_c) bytes, 16-byte aligned, zero-initialised ONCE; every
+ * call leaves it ready for the next (also when replayed from a captured graph).  Five launches, no host round trip.
+ * BLISS_EINVAL: a null pointer (uniforms may be NULL; step_dev only with uniforms and without bump_step), fanout < 0,
+ * cap_c <= 0, misaligned scratch. */
+int64_t bliss_multinomial_draw_scratch_bytes(int32_t cap_c);
+int bliss_multinomial_draw(const int32_t* cand_nid, const void* p_bf16, const void* counts, int32_t cap_c, int32_t fanout,
+                           const float* uniforms, uint64_t seed, int64_t* step_dev, int32_t layer, int bump_step, void* scratch,
+                           float* keys, int32_t* drawn, void* stream);
+/* The tail of bliss_multinomial_select for marks that are already in ws->new_id (1 = drawn, 0 = not, for the C candidates):
+ * P = p (:309), union(drawn, seeds) numbered as block sources, kept_nid / node_prob / K.  No host-side count. */
+int bliss_multinomial_select_marked(const bliss_layer_ws_t* ws, void* stream);
+
 /* generate_block      bandit_sampler.py:269-339 (BANDIT: Hajek weights) / ladies_sampler.py:71-107.
  * Same g, maps, w_pos, seeds, eta as the matching bliss_frontier_prob call.  Out: counts{B}, the block;
  * leaves the node maps clean. */
