@@ -52,6 +52,7 @@ class _LayerWs:
         self.keys = torch.empty(cap_c, dtype=torch.float32, device=dev)
         self.draw_scr = torch.zeros(int(_lib.lib.bliss_multinomial_draw_scratch_bytes(cap_c)) // 4, dtype=torch.int32, device=dev)
         self.src_cnt = None
+        self.tr_temp = None                 # neighbor layers: bliss_block_transpose's temporary, (capacities, bytes, tensor)
 
 
 class DrawState:
@@ -109,6 +110,8 @@ class LayerEngine:
         self._static = {}
         self._static_draw = {}
         self.exact_k = False                # device-drawn multinomial layers keep at most fanout + S nodes: K capacities are that bound
+        self.exact_b = False                # neighbor layers keep at most fanout edges per seed: B capacities are that bound
+        self._nb_scr = None                 # csrc/neighbor.hip: tickets + node bitmap (zero once, left zero by every call)
         self._slot_bufs, self._slot_counts, self._slot_counts_host = {}, {}, {}
         self.caps = None
         self.ws = None
@@ -357,6 +360,74 @@ class LayerEngine:
             self._mn_exact_caps(fanouts)
             self._ensure(int(seeds.numel()), fanouts)
 
+    # ------------------------------------------------------------------ neighbor sampler (keyed per-column draw)
+    def _nb_caps(self, S0, fanouts):
+        """Capacities of neighbor layers from their bounds: a layer keeps at most ``fanout`` edges per seed (B exactly bounded
+        when fanout >= 0) and, besides its seeds, at most one new source per kept edge."""
+        caps, s = [], int(S0)
+        for f in fanouts:
+            f = int(f)
+            b = int(min(self.Eg, s * f)) if f >= 0 else int(min(self.Eg, max(1 << 16, 48 * s)))
+            k = int(min(self.V, s + b)) if f >= 0 else self.V
+            caps.append(dict(S=s, C=self.V, K=k, B=b))
+            s = k
+        return caps
+
+    def _ensure_neighbor(self, S0, fan):
+        if self.caps is None or len(self.caps) != len(fan) or self.caps[0]["S"] < S0:
+            fresh = self._nb_caps(S0, fan)
+            if self.caps is not None and len(self.caps) == len(fan):
+                fresh = [{k: max(a.get(k, 0), b[k]) for k in b} for a, b in zip(self.caps, fresh)]
+            self.caps, self.ws = fresh, None
+        self._ensure(S0, fan)
+
+    def sample_blocks_neighbor(self, seeds, fanouts, draw_state):
+        """fit.NeighborSampler with ``draw="device"`` (csrc/neighbor.hip): the L layers (``fanouts`` in
+        SAMPLING order) are only enqueued and the call synchronises once, at the end; torch's generators are not touched."""
+        if draw_state is None:
+            raise ValueError("draw='device' needs a draw_state")
+        seeds = seeds.to(torch.int32).contiguous()
+        L = len(fanouts)
+        self._ensure_neighbor(int(seeds.numel()), fanouts)
+        while True:
+            out = self._enqueue(None, seeds, fanouts, 0, 0.0, 0.0, None, None, draw_state=draw_state, neighbor=True)
+            self.counts_host.copy_(out[0], non_blocking=True)
+            torch.cuda.current_stream().synchronize()                 # the one sync of the call
+            raw = self.counts_host.numpy().tobytes()
+            cnts = [_lib.LayerCounts.from_buffer_copy(raw[40 * n: 40 * n + 40]) for n in range(L)]
+            bad = 0
+            for c in cnts:
+                bad |= c.err
+            if bad & ~_CAP_ERRS or bad & 3:
+                raise RuntimeError(f"sampler kernel error 0x{bad:x}: {_lib.err_string(bad)}")
+            if bad == 0:
+                return self._finish(out, cnts)
+            draw_state.step_dev.sub_(1)                                # the repeated call is the same draw step
+            self._grow([c.err for c in cnts])
+            self._ensure_neighbor(int(seeds.numel()), fanouts)
+
+    def _enqueue_neighbor_layer(self, n, fanout, cur_seeds, n_seeds, n_seeds_dev, draw_state, last, c_ws, c_out, lay, cnt_ptr, st):
+        """One bliss_neighbor_layer + the by-source index of its block (bliss_block_transpose on the device-resident B)."""
+        cap, ws = self.caps[n], self.ws[n]
+        if self._nb_scr is None:
+            nbytes = int(_lib.lib.bliss_neighbor_scratch_bytes(self.V, 1))
+            self._nb_scr = torch.zeros(nbytes // 4, dtype=torch.int32, device=self.g.device)
+        _lib.check(_lib.lib.bliss_neighbor_layer(C.byref(self.c_graph), cur_seeds.data_ptr(), n_seeds, n_seeds_dev, cap["S"], int(fanout),
+                                                 0, draw_state.seed, draw_state.step_dev.data_ptr(), n, int(last), C.byref(c_ws),
+                                                 C.byref(c_out), self._nb_scr.data_ptr(), st), "bliss_neighbor_layer")
+        b_src, t_indptr, t_edge = lay[1], lay[10], lay[11]
+        if t_indptr is None:
+            return                                                     # (Block.transposed builds it on demand)
+        ck, cb = cap["K"], cap["B"]
+        if ws.tr_temp is None or ws.tr_temp[0] != (cb, ck):
+            nbytes = int(_lib.lib.bliss_block_transpose_temp_bytes(cb, ck)) if cb else 0
+            if nbytes < 0:
+                raise RuntimeError("bliss_block_transpose_temp_bytes failed")
+            ws.tr_temp = ((cb, ck), nbytes, torch.empty(max(nbytes, 1), dtype=torch.uint8, device=self.g.device))
+        _, nbytes, temp = ws.tr_temp
+        _lib.check(_lib.lib.bliss_block_transpose(b_src.data_ptr(), cnt_ptr + 16, cb, cb, ck, t_indptr.data_ptr(), t_edge.data_ptr(),
+                                                  temp.data_ptr(), nbytes, st), "bliss_block_transpose")
+
     def _layer_buffers(self, n, counts, slot=None):
         """Caller-owned outputs of layer n (one int32 and one bf16 allocation, sliced) + the C descriptors.
         ``slot``: static-shape callers keep one persistent set of outputs per slot (a pipelined train loop holds two
@@ -428,6 +499,8 @@ class LayerEngine:
             if self.exact_k:                # (device-drawn multinomial layer: the exact bound, such a step cannot overflow K)
                 k = min(self.V, int(f) + s)
             b = int(min(self.Eg, int(b_margin * max_sizes[n]["B"]) + 4096))
+            if self.exact_b and int(f) >= 0:    # (neighbor layer: the exact bound, such a step cannot overflow B)
+                b = int(min(self.Eg, s * int(f)))
             # E only sizes launch grids (every kernel strides over the true count): a tight bound lets the hardware balance
             # the workgroups instead of a capped grid looping unevenly
             e = int(min(self.Eg, int(1.5 * max_sizes[n].get("E", self.Eg)) + 65536))
@@ -486,7 +559,7 @@ class LayerEngine:
         _lib.check(_lib.lib.bliss_rng_stream_ready(_stream()), "bliss_rng_stream_ready")
 
     def enqueue_static(self, w_rows, seeds, fanouts, mode, eta, eps=0.9999, slot=0, chain_rng=False, external_rng=False, part=None,
-                       last_block=True, ready_flag=0, draw_state=None):
+                       last_block=True, ready_flag=0, draw_state=None, neighbor=False):
         """Enqueue one sample_blocks on the current stream with capacity-padded outputs and NO sync.  Returns the
         blocks (sampling order); sizes, errors and the generator state are read back by finish().
 
@@ -500,7 +573,11 @@ class LayerEngine:
         (its draw is done); part "last_block" = only that block, behind a bliss_flag_wait on ``flags[L]``; ``ready_flag``
         (address of a device flag) is raised as soon as the block's forward arrays are final, before its by-source index.
         ``draw_state`` (a DrawState): the layers draw with the device-side multinomial draw instead of the Poisson chain
-        (whole calls only; no generator is involved)."""
+        (whole calls only; no generator is involved).  ``neighbor``: the layers are neighbor layers (csrc/neighbor.hip; needs
+        ``draw_state``, whole calls only; ``w_rows`` / ``mode`` / ``eta`` / ``eps`` are ignored)."""
+        if neighbor and (draw_state is None or part is not None or external_rng or chain_rng):
+            raise NotImplementedError("the device-side neighbor sampler needs a draw_state and has no split / external-generator "
+                                      "enqueue (the pipelined two-stream loop is out of scope)")
         if draw_state is not None and (part is not None or external_rng or chain_rng):
             raise NotImplementedError("the device-side multinomial draw has no split / external-generator enqueue "
                                       "(the pipelined two-stream loop is out of scope)")
@@ -508,7 +585,8 @@ class LayerEngine:
             raise ValueError("split enqueue needs one scratch set per layer and an external generator")
         L = len(fanouts)
         out = self._enqueue(w_rows, seeds, fanouts, mode, eta, eps, None, True, slot=slot, chain_rng=chain_rng,
-                            external_rng=external_rng, part=part, last_block=last_block, ready_flag=ready_flag, draw_state=draw_state)
+                            external_rng=external_rng, part=part, last_block=last_block, ready_flag=ready_flag, draw_state=draw_state,
+                            neighbor=neighbor)
         self._static_draw[slot] = draw_state is not None
         counts_dev, layers = out
         if slot not in self._slot_counts_host:
@@ -551,7 +629,7 @@ class LayerEngine:
         return cnts
 
     def _enqueue(self, w_rows, seeds, fanouts, mode, eta, eps, uniforms, snapshot, slot=None, chain_rng=False, external_rng=False,
-                 part=None, last_block=True, ready_flag=0, draw_state=None):
+                 part=None, last_block=True, ready_flag=0, draw_state=None, neighbor=False):
         dev, st = self.g.device, _stream()
         L = len(fanouts)
         if draw_state is None and snapshot is not None and not chain_rng and not external_rng:
@@ -576,8 +654,14 @@ class LayerEngine:
             cap = self.caps[n]
             cs, ws = cap["S"], self.ws[n]
             c_ws, c_out, lay, cnt_ptr, kept_nid = self._layer_buffers(n, counts, slot)
-            w_pos = w_rows[n]
             last = n == L - 1
+            if neighbor:                        # neighbor layer: 6 launches and the by-source index, nothing else
+                self._enqueue_neighbor_layer(n, fanouts[n], cur_seeds, n_seeds, n_seeds_dev, draw_state, last, c_ws, c_out, lay,
+                                             cnt_ptr, st)
+                layers.append(lay)
+                cur_seeds, n_seeds, n_seeds_dev = kept_nid, -1, cnt_ptr + 12
+                continue
+            w_pos = w_rows[n]
             if part == "main":                  # layer n raises flag n when it starts (= everything before it has completed)
                 c_ws.entry_flag = self.flags.data_ptr() + 4 * n
             if draw_state is not None:          # multinomial samplers, keyed draw: 1 + 5 + 4 launches, then the block

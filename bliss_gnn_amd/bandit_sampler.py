@@ -56,7 +56,8 @@ class DeviceDraw:
     """The ``draw=`` keyword of the two multinomial samplers.  ``"host"`` (default): ``torch.multinomial`` on the host, the
     reference's draw, one sync per layer.  ``"device"``: the keyed exponential race of csrc/mn_draw.hip
     -- no host round trip, so ``sample_blocks_static`` exists and the sampler can run inside a captured train step; the
-    draw is a function of (seed, draw step, layer, node id) and consumes nothing from torch's generator."""
+    draw is a function of (seed, draw step, layer, node id) and consumes nothing from torch's generator.
+    (fit.NeighborSampler shares the keyword and the draw state: its device draw is csrc/neighbor.hip, keyed by the edge.)"""
 
     _NO_STATIC = "the multinomial draw is torch.multinomial on the host: no static-shape variant (use draw='device')"
 

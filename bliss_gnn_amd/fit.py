@@ -4,6 +4,7 @@ pytorch_lightning, reduced to plain loops -- Lightning / torchmetrics / tensorbo
   * ``MultiLayerFullNeighborSampler`` / ``NeighborSampler``: the two non-LADIES ``--sampler`` choices
     (train_lightning.py:349-357).  (With them the reference's models fail at ``block.edata["edge_weights"]``,
     model.py:321-329 -- DGL's own samplers attach no such field -- so they are baselines here, with unit weights.)
+    ``NeighborSampler(..., draw="device")``: the keyed per-column draw of csrc/neighbor.hip, graph-capturable.
   * ``fit``: epochs of TrainStep, ``StepLR(gamma=0.01, step_size=5)`` stepped per epoch (:205-216), validation with the same
     sampler (:179-203, :410-422), best-``val_acc`` checkpoint (:620-625), early stop on ``val_acc_target`` / patience
     (:627-634), then the best checkpoint reloaded for the layer-wise full-neighbour inference and the Final Accuracy of the
@@ -16,7 +17,8 @@ import os
 
 import torch
 
-from .bandit_sampler import BlockSampler
+from ._engine import LayerEngine
+from .bandit_sampler import BlockSampler, DeviceDraw
 from .graph import NID, Block, as_graph
 from .ladies_sampler import PoissonLadiesSampler
 from .train import BatchLoader, TrainStep, _inputs
@@ -49,18 +51,62 @@ class MultiLayerFullNeighborSampler(BlockSampler):
         return inp, outp, blocks
 
 
-class NeighborSampler(BlockSampler):
+class NeighborSampler(DeviceDraw, BlockSampler):
     """``dgl.dataloading.NeighborSampler(fanouts)`` (train_lightning.py:351-357): up to ``fanout`` in-neighbours per
-    destination, uniformly without replacement, per layer.  A baseline outside the hot path: device tensor ops (random key
-    per frontier edge, rank inside its column), its own torch generator, no parity claim (DGL draws with its own RNG)."""
+    destination, uniformly without replacement, per layer.  No parity claim (DGL draws with its own RNG).
 
-    def __init__(self, fanouts, seed=0, **_ignored):
+    ``draw="host"`` (default): a baseline outside the hot path -- device tensor ops (random key per frontier edge, rank inside
+    its column), its own torch generator, one host read per layer.  ``draw="device"``: the keyed per-column draw of
+    csrc/neighbor.hip -- a function of (seed, draw step, layer, CSC position), no host round trip, so
+    ``sample_blocks_static`` exists and the sampler runs inside a captured train step; ``seed`` starts its draw state
+    (``reset_draw`` / ``draw_step`` as for the multinomial samplers) and no torch generator is touched."""
+
+    _poisson = False                                       # (DeviceDraw's Poisson / replace checks have no subject here)
+
+    def __init__(self, fanouts, seed=0, *, draw="host", **_ignored):
         super().__init__()
+        self._init_draw(draw, False)
+        self._draw_init = (seed, 0)
         self.fanouts, self.nodes_per_layer = list(fanouts), list(fanouts)
         self._seed, self._gen = seed, None
+        self._engine = None
+
+    # -- draw="device" ----------------------------------------------------------------------------------------------
+    def _bind(self, g):
+        g = as_graph(g, self.__dict__.setdefault("_graphs", {}))
+        if self._engine is None or self._engine.g is not g:
+            self._engine = LayerEngine(g)
+            self._engine.exact_b = True
+        return self._engine
+
+    def _blocks(self, blks, seed_nodes):
+        blocks = []
+        for blk in blks:                                   # sampling order -> input-most first
+            blk.edata["edge_weights"] = blk._edge_weights
+            blocks.insert(0, blk)
+        return blocks[0].srcdata[NID], seed_nodes, blocks
+
+    def sample_blocks_static(self, g, seed_nodes, slot=0, **split):
+        """sample_blocks with capacity-padded blocks, only ENQUEUED (the contract of the LADIES samplers' method of this name);
+        whole calls only: any split / external-generator keyword raises."""
+        if self.draw != "device":
+            raise NotImplementedError("the host draw reads sizes back per layer: no static-shape variant (use draw='device')")
+        eng = self._bind(g)
+        fan = list(reversed(self.fanouts))
+        return self._blocks(eng.enqueue_static(None, seed_nodes, fan, 0, 0.0, slot=slot, draw_state=self._draw_state_on(eng.g.device),
+                                               neighbor=True, **split), seed_nodes)
+
+    def finish_static(self, slot=0, commit=True):
+        return self._engine.finish(slot, commit)
+
+    def check_errors(self):
+        pass                                               # no bandit state; sampler errors surface through finish()
 
     def sample_blocks(self, g, seed_nodes, exclude_eids=None):
         g = as_graph(g, self.__dict__.setdefault("_graphs", {}))
+        if self.draw == "device":
+            blks = self._bind(g).sample_blocks_neighbor(seed_nodes, list(reversed(self.fanouts)), self._draw_state_on(g.device))
+            return self._blocks(blks, seed_nodes)
         dev = g.device
         if self._gen is None:
             self._gen = torch.Generator(device=dev)
@@ -98,12 +144,13 @@ class NeighborSampler(BlockSampler):
 
 def make_sampler(name, fanouts, importance_sampling=1, num_steps=5000, eta=0.1, model="sage", draw="host"):
     """The sampler-name dispatch of DataModule.__init__ (train_lightning.py:348-370).  ``draw``: where the two multinomial
-    samplers ("ladies", "bandit") draw -- "host" (torch.multinomial) or "device" (the keyed draw, graph-capturable)."""
+    samplers ("ladies", "bandit") and "neighbor" draw -- "host" (torch.multinomial / torch tensor ops) or "device" (the keyed
+    draws, graph-capturable)."""
     from . import BanditLadiesSampler, LadiesSampler, PoissonBanditLadiesSampler, PoissonLadiesSampler as PLS
     if name == "full":
         return MultiLayerFullNeighborSampler(len(fanouts))
     if name == "neighbor":
-        return NeighborSampler(fanouts)
+        return NeighborSampler(fanouts, draw=draw)
     if "ladies" in name and "bandit" not in name:
         return PLS(fanouts) if "poisson" in name else LadiesSampler(fanouts, draw=draw)
     if "bandit" in name:

@@ -338,7 +338,7 @@ class PipelinedTrainStep(GraphedTrainStep):
     def __init__(self, g, sampler, model, batch_size, lr=0.002, multilabel=False, distributed=False):
         if getattr(sampler, "draw", "host") == "device":
             raise NotImplementedError("PipelinedTrainStep splits the sampler over streams and runs its generator beside it; the "
-                                      "device-side multinomial draw has neither: use GraphedTrainStep with draw='device'")
+                                      "device-side draws (multinomial, neighbor) have neither: use GraphedTrainStep with draw='device'")
         super().__init__(g, sampler, model, batch_size, lr, multilabel, distributed)
         self.seeds2 = [torch.zeros(self.bs, dtype=torch.int32, device=g.device) for _ in range(2)]
         self.mfgs = [None, None]

@@ -192,6 +192,33 @@ int bliss_multinomial_draw(const int32_t* cand_nid, const void* p_bf16, const vo
  * P = p (:309), union(drawn, seeds) numbered as block sources, kept_nid / node_prob / K.  No host-side count. */
 int bliss_multinomial_select_marked(const bliss_layer_ws_t* ws, void* stream);
 
+/* dgl.dataloading.NeighborSampler(fanouts) ON THE DEVICE, one layer (fit.NeighborSampler with draw="device"; a defined-mode keyed
+ * draw like bliss_multinomial_draw with the key on the EDGE, restated on the CPU by tests/neighbor_ref.py):
+ *   key(pos) = (uint32)(z >> 32), z = SplitMix64 finaliser of mix(seed, *step_dev, layer) ^ (uint64)pos  -- bliss_multinomial_draw's
+ *              (seed, step, layer) mixing with the CSC position in the node id's place; keys_override[pos] when keys_override != NULL
+ *              (uint32 [num_edges], by CSC position: lets a test plant ties)
+ *   seed column s, CSC positions [a, b), d = b - a:  k = d if fanout < 0 or d <= fanout, else fanout; kept = the k smallest pairs
+ *              (key(pos), pos), ties to the lower position
+ *   block:     edges column by column in seed order, ascending position inside a column; indptr[s + 1] - indptr[s] = k;
+ *              sources = the seeds (local ids 0 .. S-1 in the order given), then the other sources of kept edges, each once, in
+ *              ascending node id; edge_weights = q_ij = 1; eid = g->eid[pos], or pos when g->eid == NULL
+ * Seeds (unique) and their count as in bliss_frontier_prob: n_seeds if >= 0, else *n_seeds_dev; cap_s >= count sizes seg_ptr / indptr.
+ * Read from ws: counts, seg_ptr, kept_nid, kept_map, cap_k, node_prob (optional).  Read from out: indptr, src, dst, pos, eid, edge_weights, q_ij, cap_b
+ * (the by-source index is not built here: bliss_block_transpose on out->src with the record's B).  Every other field is ignored.
+ * Out: counts{S, E = sum d, C = K, K, B, err}, seg_ptr, kept_nid, the block arrays; capacity padding as bliss_build_block leaves it
+ * (indptr rows S .. cap_s empty, kept_nid[K .. cap_k) = 0); ws->node_prob, when not NULL, = 1 for all cap_k entries.  A count beyond cap_s / cap_k / cap_b raises
+ * the matching BLISS_ERR_CAP_* bit and is clamped; nothing is written beyond a capacity.  ws->kept_map: [num_nodes], -1 everywhere
+ * on entry and on exit.  bump_step: the last workgroup of the select kernel increments *step_dev once, after every workgroup has
+ * read it.  scratch: bliss_neighbor_scratch_bytes(num_nodes, cap_s) bytes (cap_s > 0 is checked; nothing is sized by it), 16-byte aligned, zero-initialised ONCE; its words are
+ * [0, 16) tickets, then the node bitmap (ceil(num_nodes / 32) words rounded up to a multiple of 1024) -- both left zero by every
+ * call, also a replayed one -- then one offset per 1024 bitmap words, rewritten by every call.  Six launches, no host round trip.
+ * BLISS_EINVAL before any launch: a null pointer (keys_override may be NULL; n_seeds_dev with n_seeds >= 0; step_dev only with
+ * keys_override and without bump_step), cap_s <= 0, fanout == 0, ws->cap_k <= 0, num_edges > INT32_MAX, misaligned scratch. */
+int64_t bliss_neighbor_scratch_bytes(int32_t num_nodes, int32_t cap_s);
+int bliss_neighbor_layer(const bliss_graph_t* g, const int32_t* seeds, int32_t n_seeds, const int32_t* n_seeds_dev, int32_t cap_s,
+                         int32_t fanout, const uint32_t* keys_override, uint64_t seed, int64_t* step_dev, int32_t layer,
+                         int bump_step, const bliss_layer_ws_t* ws, const bliss_block_out_t* out, void* scratch, void* stream);
+
 /* generate_block      bandit_sampler.py:269-339 (BANDIT: Hajek weights) / ladies_sampler.py:71-107.
  * Same g, maps, w_pos, seeds, eta as the matching bliss_frontier_prob call.  Out: counts{B}, the block;
  * leaves the node maps clean. */
