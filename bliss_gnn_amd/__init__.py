@@ -9,3 +9,4 @@ from . import _lib  # noqa: F401  (fail loudly when the HIP library is absent)
 from .graph import Block, Graph, NID, EID  # noqa: F401
 from .bandit_sampler import BanditLadiesSampler, PoissonBanditLadiesSampler, normalized_edata  # noqa: F401
 from .ladies_sampler import LadiesSampler, PoissonLadiesSampler  # noqa: F401
+from .metrics import MicroF1  # noqa: F401

@@ -112,6 +112,7 @@ class GatFused(C.Structure):                           # bliss_gat_fused_t
 
 
 ADAM_MAX_TENSORS = 32
+F1_MAX_WORKGROUPS, F1_ROWS_PER_WORKGROUP, F1_PAIRS_PER_WORKGROUP = 1024, 4, 256    # BLISS_F1_MAX_WORKGROUPS; csrc/metrics.hip
 
 
 class AdamTensors(C.Structure):                        # bliss_adam_t
@@ -159,6 +160,8 @@ SIGNATURES = {
     "bliss_bce_logits": [_P, _I64, _P, _I32, _I32, _P, _P, _I64, _P, _P, _P, _P],
     "bliss_bce_logits_sum": [_P, _I64, _P, _I64, _P, _P, _I32, _I32, _P, _P, _I64, _P, _P, _P, _P],
     "bliss_bce_logits_masked": [_P, _I64, _P, _I64, _P, _I32, _P, _I32, _I32, _P, _F, _I32, _P, _P, _I64, _P, _P, _P, _P],
+    "bliss_f1_multiclass": [_P, _I64, _I32, _P, _P, _P, _I32, _P, _I32, _P, _I32, _P, _P, _P],
+    "bliss_f1_multilabel": [_P, _I64, _I32, _P, _P, _P, _I32, _P, _I32, _P, _I32, _P, _P, _P],
     "bliss_adam_step": [C.POINTER(AdamTensors), _P, _F, _F, _F, _F, _P],
     "bliss_cand_importance": [_P, _I32, C.c_int, _P, _P, _P],
     "bliss_poisson_scale": [_P, _P, _I32, _D, _P, _P],

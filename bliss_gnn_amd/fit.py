@@ -21,7 +21,7 @@ from ._engine import LayerEngine
 from .bandit_sampler import BlockSampler, DeviceDraw
 from .graph import NID, Block, as_graph
 from .ladies_sampler import PoissonLadiesSampler
-from .train import BatchLoader, TrainStep, _inputs
+from .train import BatchLoader, GraphedEvalStep, TrainStep, _inputs
 
 
 # ----------------------------------------------------------------------------------------------- baseline samplers
@@ -171,6 +171,20 @@ def micro_f1(pred, labels, multilabel=False):
     return 2 * tp / max(2 * tp + fp + fn, 1.0)
 
 
+def _split_f1(pred, labels, nid, multilabel):
+    """micro_f1(pred[nid], labels[nid]) of a full-graph prediction.  bf16 on the GPU: counted by metrics.MicroF1 straight from
+    ``pred`` and the label table through ``row_ids`` / ``label_ids`` -- neither slice is materialised --, and the counts give
+    micro_f1's own float (metrics.micro_f1_from_counts)."""
+    if pred.is_cuda and pred.dtype == torch.bfloat16 and pred.dim() == 2:
+        from .metrics import MicroF1, micro_f1_from_counts
+        ids = nid.to(device=pred.device, dtype=torch.int32).contiguous()
+        m = MicroF1(multilabel)
+        m.update(pred, label_table=labels, label_ids=ids, row_ids=ids)
+        m.check_errors()
+        return micro_f1_from_counts(m.counts(), multilabel, pred.device)
+    return micro_f1(pred[nid.long()].float(), labels[nid.long()], multilabel)
+
+
 class StepLR:
     """``th.optim.lr_scheduler.StepLR(optimizer, gamma=0.01, step_size=5)`` stepped once per EPOCH (train_lightning.py:205-216,
     Lightning's default interval): lr x 0.01 every 5 epochs.  Works with any optimiser exposing ``param_groups``."""
@@ -245,8 +259,12 @@ class ModelCheckpoint:
 
 
 @torch.no_grad()
-def evaluate(g, sampler, model, ids, batch_size, multilabel=False, loss_fn=None):
-    """validation_step over a split (train_lightning.py:179-203): the same sampler object, no bandit update, no optimiser."""
+def evaluate(g, sampler, model, ids, batch_size, multilabel=False, loss_fn=None, step=None):
+    """validation_step over a split (train_lightning.py:179-203): the same sampler object, no bandit update, no optimiser.
+    ``step``: a train.GraphedEvalStep built on the same (g, sampler, model, batch_size) -- the pass is then its ``run(ids)``:
+    full batches replayed from one graph, metric and loss kept on the device and read back once."""
+    if step is not None:
+        return step.run(ids)
     was = model.training
     model.eval()
     preds, labels, losses = [], [], []
@@ -265,10 +283,17 @@ def evaluate(g, sampler, model, ids, batch_size, multilabel=False, loss_fn=None)
 
 
 def fit(g, sampler, model, train_nid, val_nid, test_nid=None, batch_size=1024, lr=0.002, max_epochs=10, max_steps=None,
-        multilabel=False, val_acc_target=1.0, early_stopping_patience=1000, checkpoint_path=None, seed=0, log=None):
-    """One run of ``trainer.fit`` + the final evaluation (train_lightning.py:640-705).  Returns a dict of metrics."""
+        multilabel=False, val_acc_target=1.0, early_stopping_patience=1000, checkpoint_path=None, seed=0, log=None,
+        eval_step="eager", train_metric=False):
+    """One run of ``trainer.fit`` + the final evaluation (train_lightning.py:640-705).  Returns a dict of metrics.
+    ``eval_step``: "eager" (``evaluate`` as it stands) or "graphed" (one train.GraphedEvalStep serves every epoch's validation;
+    the sampler needs a static-shape path).  ``train_metric``: keep train_acc (:143) on the device beside every step and add it,
+    reset per epoch, to the history entries."""
+    if eval_step not in ("eager", "graphed"):
+        raise ValueError("eval_step must be 'eager' or 'graphed', not %r" % (eval_step,))
     g = as_graph(g)
-    step = TrainStep(g, sampler, model, lr=lr, multilabel=multilabel)
+    step = TrainStep(g, sampler, model, lr=lr, multilabel=multilabel, train_metric=train_metric)
+    ev = GraphedEvalStep(g, sampler, model, batch_size, multilabel, loss_fn=step.loss_fn) if eval_step == "graphed" else None
     sched, stopper, ckpt = StepLR(step.opt, 5, 0.01), EarlyStopping(val_acc_target, early_stopping_patience), ModelCheckpoint(checkpoint_path)
     loader = BatchLoader(train_nid, batch_size, shuffle=True, drop_last=True, seed=seed)
     history, n_steps = [], 0
@@ -279,21 +304,27 @@ def fit(g, sampler, model, train_nid, val_nid, test_nid=None, batch_size=1024, l
             tot += float(step(seeds)); cnt += 1; n_steps += 1
             if max_steps is not None and n_steps >= max_steps:
                 break
-        val_acc, val_loss = evaluate(g, sampler, model, val_nid, batch_size, multilabel, step.loss_fn)
+        val_acc, val_loss = evaluate(g, sampler, model, val_nid, batch_size, multilabel, step.loss_fn, step=ev)
         ckpt.update(val_acc, model, epoch)
         history.append(dict(epoch=epoch, train_loss=tot / max(cnt, 1), val_acc=val_acc, val_loss=val_loss, lr=step.opt.param_groups[0]["lr"]))
+        if train_metric:
+            history[-1]["train_acc"] = step.train_acc.compute()                 # (one read-back per epoch)
+            step.train_acc.reset()
+            step.train_acc.check_errors()
         if log:
             log(history[-1])
         sched.step()                                                             # per epoch (:205-216)
         if stopper.should_stop(val_acc) or (max_steps is not None and n_steps >= max_steps):
             break
+    if ev is not None:
+        ev.close()
     ckpt.restore(model)                                                          # the best val_acc checkpoint (:662-685)
     final = {}
     if hasattr(model, "inference") and "features" in g.ndata:
         pred = model.inference(g)                                                # :686-693 layer-wise full-neighbour inference
         for name, nid in (("Train", train_nid), ("Validation", val_nid), ("Test", test_nid)):
             if nid is not None and nid.numel():
-                final[name] = micro_f1(pred[nid.long()].float(), g.ndata["labels"][nid.long()], multilabel)    # :694-705
+                final[name] = _split_f1(pred, g.ndata["labels"], nid, multilabel)                            # :694-705
     return dict(history=history, best_val_acc=ckpt.best, steps=n_steps, final=final)
 
 

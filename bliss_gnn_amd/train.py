@@ -90,6 +90,25 @@ def _loss_backward(loss_fn, pred, labels, opt):
     return loss.detach()
 
 
+def _update_metric(metric, pred, mfgs):
+    """``metric.update`` for a batch: the output block's labels as (label table, destination ids) -- the pair the one-launch
+    losses take, so nothing is gathered for the metric -- or, for a block without a parent table, its own labels."""
+    lab = mfgs[-1].dstdata
+    parent = getattr(lab, "_parent", None)
+    if parent is not None and "labels" in parent:
+        from .graph import NID
+        metric.update(pred, label_table=parent["labels"], label_ids=lab[NID])
+    else:
+        metric.update(pred, lab["labels"])
+
+
+def _train_metric(train_metric, multilabel):
+    if not train_metric:
+        return None
+    from .metrics import MicroF1
+    return MicroF1(multilabel)
+
+
 def make_adam(model, lr, capturable=False):
     """th.optim.Adam(self.parameters(), lr) (train_lightning.py:206).  For the reference's precision (bf16 module on the GPU,
     :596-618) this is the one-launch gfx950 Adam of csrc/optim.hip; anything else gets torch's own."""
@@ -105,9 +124,12 @@ def make_adam(model, lr, capturable=False):
 class TrainStep:
     """One optimiser step of ModelLightning (train_lightning.py:50-216) with the bandit callback."""
 
-    def __init__(self, g, sampler, model, lr=0.002, multilabel=False, bandit=True, grad_sync=None, exp3_sync=None):
+    def __init__(self, g, sampler, model, lr=0.002, multilabel=False, bandit=True, grad_sync=None, exp3_sync=None, train_metric=False):
         self.g, self.sampler, self.model = g, sampler, model
         self.loss_fn = _bce_loss() if multilabel else _ce_loss()                        # :77-79
+        # train_acc (:68-70, updated per step at :143): counts on the device, one launch per step and no read-back until
+        # ``train_acc.compute()`` (metrics.MicroF1); None unless asked for
+        self.train_acc = _train_metric(train_metric, multilabel)
         self.opt = make_adam(model, lr)                                                  # :206
         self.bandit = bandit and hasattr(sampler, "exp3")          # train_lightning.py:469: only for the bandit samplers
         self.grad_sync, self.exp3_sync = grad_sync, exp3_sync
@@ -138,6 +160,8 @@ class TrainStep:
         batch_inputs = _inputs(self.model, mfgs)                                         # :138
         batch_labels = mfgs[-1].dstdata["labels"]                                        # :139
         batch_pred = self.model(mfgs, batch_inputs)                                      # :141
+        if self.train_acc is not None:
+            _update_metric(self.train_acc, batch_pred, mfgs)                             # :143
         loss = _loss_backward(self.loss_fn, batch_pred, batch_labels, self.opt)          # :142
         if self.grad_sync is not None:
             self.grad_sync(self.model)
@@ -149,6 +173,11 @@ class TrainStep:
                 self.sampler.exp3(mfgs, self.g)                                          # :469-471
         self.last = dict(loss=loss, mfgs=mfgs, pred=batch_pred, labels=batch_labels)
         return loss
+
+    def last_batch_counts(self):
+        """(tp, fp, fn, n) added to ``train_acc`` since the previous call (one read-back): the last batch's, when called after
+        every step."""
+        return self.train_acc.delta()
 
 
 def _enable_gemm_tuning():
@@ -177,10 +206,13 @@ class GraphedTrainStep:
     blocks are padded to capacities learned from a few eager steps (``calibrate``); true sizes stay on the device
     and come back with the step's single end-of-step sync.  Results are bit-identical to the eager path."""
 
-    def __init__(self, g, sampler, model, batch_size, lr=0.002, multilabel=False, distributed=False):
+    def __init__(self, g, sampler, model, batch_size, lr=0.002, multilabel=False, distributed=False, train_metric=False):
         self.g, self.sampler, self.model, self.bs = g, sampler, model, int(batch_size)
         self.distributed = distributed          # replicas: gradient all-reduce + EXP3 exchange recorded in the graph too
         self.loss_fn = _bce_loss() if multilabel else _ce_loss()
+        # train_acc: one more launch inside the captured graph (metrics.MicroF1: counts stay on the device); None unless asked
+        # for, and the graph is then exactly the one without it
+        self.train_acc = _train_metric(train_metric, multilabel)
         # ONE launch for all parameter tensors (csrc/optim.hip; torch's foreach path is ~40 launches of >= 5 us inside a graph,
         # its fused multi-tensor kernel ~50 us)
         self.opt = make_adam(model, lr, capturable=True)
@@ -214,6 +246,8 @@ class GraphedTrainStep:
         x = _inputs(self.model, mfgs)
         y = mfgs[-1].dstdata["labels"]
         pred = self.model(mfgs, x)
+        if self.train_acc is not None:
+            _update_metric(self.train_acc, pred, mfgs)             # train_lightning.py:143
         loss = _loss_backward(self.loss_fn, pred, y, self.opt)
         bandit = hasattr(self.sampler, "exp3")                     # train_lightning.py:469: only for the bandit samplers
         if self.distributed:
@@ -281,6 +315,11 @@ class GraphedTrainStep:
         self._finish()
         return loss
 
+    def last_batch_counts(self):
+        """(tp, fp, fn, n) added to ``train_acc`` since the previous call (one read-back): the last batch's, when called after
+        every step."""
+        return self.train_acc.delta()
+
     def sizes(self):
         """Per block (input-most first): the true S, E, C, K, B of the last step."""
         return [dict(S=c.S, E=c.E, C=c.C, K=c.K, B=c.B) for c in reversed(self.last_counts)]
@@ -335,7 +374,10 @@ class PipelinedTrainStep(GraphedTrainStep):
     One call = two optimiser steps on two batches; the batch sampled last is trained by the next call (``drain``
     trains the final one)."""
 
-    def __init__(self, g, sampler, model, batch_size, lr=0.002, multilabel=False, distributed=False):
+    def __init__(self, g, sampler, model, batch_size, lr=0.002, multilabel=False, distributed=False, train_metric=False):
+        if train_metric:
+            raise NotImplementedError("PipelinedTrainStep keeps no train_acc (its forward pass is split over two graphs and two "
+                                      "streams): use TrainStep or GraphedTrainStep with train_metric=True")
         if getattr(sampler, "draw", "host") == "device":
             raise NotImplementedError("PipelinedTrainStep splits the sampler over streams and runs its generator beside it; the "
                                       "device-side draws (multinomial, neighbor) have neither: use GraphedTrainStep with draw='device'")
@@ -877,3 +919,229 @@ class PipelinedTrainStep(GraphedTrainStep):
     def sizes2(self):
         """sizes() for each of the two batches sampled by the last call."""
         return [[dict(S=c.S, E=c.E, C=c.C, K=c.K, B=c.B) for c in reversed(cs)] for cs in self.last_counts2]
+
+
+@contextlib.contextmanager
+def _keep_static_caps(eng):
+    """Eager sampling beside captured graphs: the engine's retry loop answers a capacity overflow by growing the capacities and
+    re-allocating its workspaces -- which captured graphs still point at.  Whatever the block changed of the engine's static
+    capacities is put back on leaving it (the buffers were kept alive meanwhile); the blocks it sampled stay valid."""
+    names = ("ws", "counts_host", "rng_cap", "rng_plan", "rng_out", "rng_raw", "rng_ctl", "n_bins")
+    static = eng.caps is not None and all("E" in c for c in eng.caps)
+    saved = {k: getattr(eng, k, None) for k in names}
+    caps = [dict(c) for c in eng.caps] if static else None
+    try:
+        yield
+    finally:
+        if static and (eng.ws is not saved["ws"] or eng.caps != caps):
+            eng.caps = caps
+            for k, v in saved.items():
+                setattr(eng, k, v)
+
+
+class GraphedEvalStep:
+    """validation_step over a split (train_lightning.py:179-203, :410-422) with every full batch REPLAYED from one HIP graph:
+    ``sample_blocks_static`` on an output slot of its own, ``model.eval()`` forward under ``no_grad``, the loss, the micro-F1
+    update (metrics.MicroF1: counts on the device) and loss * n, all into a per-batch buffer the graph zeroes itself.  The host
+    adds that buffer to the split's accumulators (a device add, enqueued) only once ``finish_static`` has passed for the batch;
+    metric and loss are read back once, at the end of ``run``.  What ``fit.evaluate`` does eagerly -- ~150 launches and L + 1
+    syncs per batch, a ``float()`` per batch, every prediction of the split concatenated -- with the same sampler calls in the
+    same order: torch's generator, the draw step and the EXP3 rows end up where the eager pass leaves them (no bandit update).
+
+    Capacities: the sampler engine's static ones when a train step has fixed them already (they are never re-fixed here: a
+    captured train graph depends on them); otherwise ``calibrate`` fixes them, from the split's own batches, the first time
+    ``run`` needs them.  The ragged last batch runs eagerly through ``sampler.sample`` into the same accumulators, and so does a
+    batch whose replay exceeded a capacity (``finish_static`` raised): its per-batch buffer is dropped, torch's generator and the
+    draw step are put back, and the batch is sampled again by the engine's regrowing eager loop (``fallbacks`` counts these)."""
+
+    SLOT = 2                                   # (0 and 1 are the training loops')
+
+    def __init__(self, g, sampler, model, batch_size, multilabel=False, loss_fn=None):
+        static = hasattr(sampler, "sample_blocks_static") and (getattr(sampler, "_poisson", False)
+                                                               or getattr(sampler, "draw", "host") == "device")
+        if not static:
+            raise NotImplementedError("GraphedEvalStep needs a sampler with a static-shape path; %s%s has none (the Poisson samplers "
+                                      "have one, the multinomial samplers and NeighborSampler with draw='device')"
+                                      % (type(sampler).__name__, " with draw='host'" if hasattr(sampler, "draw") else ""))
+        from .metrics import MicroF1
+        self.g, self.sampler, self.model, self.bs, self.multilabel = g, sampler, model, int(batch_size), bool(multilabel)
+        self.loss_fn = loss_fn if loss_fn is not None else (_bce_loss() if multilabel else _ce_loss())
+        dev = g.device
+        self.seeds = torch.zeros(self.bs, dtype=torch.int32, device=dev)
+        self.metric, self._batch_metric = MicroF1(multilabel), MicroF1(multilabel)
+        self.metric._state_on(dev)
+        self._batch_metric._state_on(dev)
+        self._loss_sum = torch.zeros((), dtype=torch.float32, device=dev)          # sum over batches of loss * n, fp32
+        self._batch_loss = torch.zeros((), dtype=torch.float32, device=dev)
+        self.graph, self._captured_for = None, None
+        self.fallbacks, self.captures = 0, 0
+
+    # -- capacities -------------------------------------------------------------------------------------------------------
+    def _engine(self):
+        return self.sampler._bind(self.g)
+
+    def has_static_caps(self):
+        caps = self._engine().caps
+        L = len(self.sampler.nodes_per_layer)
+        if caps is None or len(caps) != L or not all("E" in c for c in caps):
+            return False
+        if caps[0]["S"] != self.bs:
+            raise ValueError("the sampler's static capacities were fixed for batches of %d, not %d: a GraphedEvalStep shares them "
+                             "with the train step that fixed them and needs its batch size" % (caps[0]["S"], self.bs))
+        return True
+
+    @contextlib.contextmanager
+    def _rng_kept(self):
+        """Sampler calls that must leave no trace: torch's CPU generator and the device draw step are put back."""
+        state = torch.get_rng_state()
+        ds = self.sampler._draw_state_on(self.g.device) if hasattr(self.sampler, "_draw_state_on") else None
+        step = ds.step_dev.clone() if ds is not None else None
+        try:
+            yield
+        finally:
+            torch.set_rng_state(state)
+            if ds is not None:
+                ds.step_dev.copy_(step)
+
+    def calibrate(self, loader, steps=8, k_margin=1.5, b_margin=3.0):
+        """GraphedTrainStep.calibrate for a sampler no train step has fixed capacities for: eager sampling to learn per-layer
+        sizes (leaving generator and draw step as they were), then the static capacities."""
+        if self.has_static_caps():
+            raise RuntimeError("the sampler's static capacities are fixed already (a captured graph may depend on them)")
+        L = len(self.sampler.nodes_per_layer)
+        mx = [dict(K=0, B=0, E=0) for _ in range(L)]
+        with self._rng_kept():
+            for _ in range(steps):
+                seeds = next(loader)
+                if seeds.numel() != self.bs:
+                    continue
+                _, _, blocks = self.sampler.sample_blocks(self.g, seeds)
+                for n, b in enumerate(reversed(blocks)):                  # sampling order
+                    mx[n]["K"] = max(mx[n]["K"], b.num_src_nodes())
+                    mx[n]["B"] = max(mx[n]["B"], b.num_edges())
+                    mx[n]["E"] = max(mx[n]["E"], b._counts.E)
+        fan = [self.sampler.nodes_per_layer[b] for b in reversed(range(L))]
+        self._engine().set_static_caps(self.bs, fan, mx, k_margin, b_margin)
+
+    # -- the batch --------------------------------------------------------------------------------------------------------
+    def _body(self):
+        self._batch_metric._counts.zero_()
+        _, _, mfgs = self.sampler.sample_blocks_static(self.g, self.seeds, slot=self.SLOT)
+        with torch.no_grad():
+            pred = self.model(mfgs, _inputs(self.model, mfgs))
+            loss = self.loss_fn(pred, mfgs[-1].dstdata["labels"])
+            _update_metric(self._batch_metric, pred, mfgs)
+            self._batch_loss.copy_(loss.float() * float(self.bs))
+
+    def _signature(self):
+        eng = self._engine()
+        return (eng.ws, eng.n_bins, [dict(c) for c in eng.caps])
+
+    def _stale(self):
+        """The engine's workspaces are no longer the ones the graph was captured on (an eager sampler call elsewhere grew a
+        capacity).  The graph keeps the old ones alive through ``_captured_for``; it is simply recorded again."""
+        ws, n_bins, caps = self._captured_for
+        eng = self._engine()
+        return eng.ws is not ws or eng.n_bins != n_bins or eng.caps != caps
+
+    def capture(self, seeds, warmup=2):
+        """Static-shape warm-up batches on a side stream (allocator and the engine's per-slot buffers), then the capture.
+        Leaves torch's generator, the draw step and the accumulators untouched; the model must be in eval mode."""
+        import gc
+        eng = self._engine()
+        self.graph = None
+        with self._rng_kept():
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                for _ in range(warmup):
+                    with self._rng_kept():
+                        self.seeds.copy_(seeds)
+                        eng.stage_rng_from_torch()
+                        self._body()
+                        side.synchronize()
+                        try:
+                            self.sampler.finish_static(self.SLOT)
+                        except RuntimeError:
+                            pass                                          # (a warm-up batch over a capacity: nothing is kept of it)
+            torch.cuda.current_stream().wait_stream(side)
+            gc.collect()
+            torch.cuda.synchronize()
+            self.seeds.copy_(seeds)
+            eng.stage_rng_from_torch()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, **_cap_kw()):
+                self._body()
+        self.graph, self._captured_for = graph, self._signature()
+        self.captures += 1
+
+    def _replayed(self, seeds):
+        eng = self._engine()
+        if self.graph is None or self._stale():
+            self.capture(seeds)
+        state = torch.get_rng_state()
+        ds = self.sampler._draw_state_on(self.g.device) if hasattr(self.sampler, "_draw_state_on") else None
+        self.seeds.copy_(seeds)
+        eng.stage_rng_from_torch()
+        self.graph.replay()
+        torch.cuda.current_stream().synchronize()
+        try:
+            self.sampler.finish_static(self.SLOT)
+        except RuntimeError:
+            # over a capacity: the per-batch buffer is not added; the same draw again, eagerly (the engine regrows there)
+            torch.set_rng_state(state)
+            if ds is not None:
+                ds.step_dev.sub_(1)                                      # as the engine's capacity-regrow loop rewinds it
+            self.fallbacks += 1
+            self._eager(seeds)
+            return
+        self.metric._counts.add_(self._batch_metric._counts)
+        self._loss_sum.add_(self._batch_loss)
+
+    def _eager(self, seeds):
+        with _keep_static_caps(self._engine()):
+            _, _, mfgs = self.sampler.sample(self.g, seeds)
+        with torch.no_grad():
+            pred = self.model(mfgs, _inputs(self.model, mfgs))
+            loss = self.loss_fn(pred, mfgs[-1].dstdata["labels"])
+            _update_metric(self.metric, pred, mfgs)
+            self._loss_sum.add_(loss.float() * float(seeds.numel()))
+
+    def run(self, ids):
+        """One pass over ``ids`` in order: ``(micro_f1, mean_loss)``, the pair ``fit.evaluate`` returns."""
+        from .metrics import micro_f1_from_counts
+        was = self.model.training
+        self.model.eval()
+        try:
+            self.metric.reset()
+            self._loss_sum.zero_()
+            if ids.numel() >= self.bs and not self.has_static_caps():
+                self.calibrate(BatchLoader(ids, self.bs, shuffle=False, drop_last=True).forever())
+            for seeds in BatchLoader(ids, self.bs, shuffle=False, drop_last=False):
+                if seeds.numel() == self.bs:
+                    self._replayed(seeds)
+                else:
+                    self._eager(seeds)
+            words = [self.metric._err, self._batch_metric._err]
+            st = getattr(self.loss_fn, "_state", None)
+            if st is not None:
+                words.append(st[1:2])
+            out = torch.cat([self.metric._counts.double(), self._loss_sum.double().reshape(1)]
+                            + [w.double() for w in words]).tolist()                                         # THE read-back
+        finally:
+            self.model.train(was)
+        if any(out[5:]):                                                  # (the error words came with it: read again only to raise)
+            for m in (self.metric, self._batch_metric):
+                m.check_errors()
+            if hasattr(self.loss_fn, "check_errors"):
+                self.loss_fn.check_errors()
+        self.last_counts = tuple(int(v) for v in out[:4])
+        return micro_f1_from_counts(self.last_counts, self.multilabel, self.g.device), out[4] / max(ids.numel(), 1)
+
+    def close(self):
+        """Quiesce the device and destroy the captured graph now."""
+        import gc
+        torch.cuda.synchronize()
+        self.graph, self._captured_for = None, None
+        gc.collect()
+        torch.cuda.synchronize()

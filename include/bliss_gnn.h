@@ -433,6 +433,43 @@ int bliss_bce_logits_masked(const void* logits, int64_t stride, const void* logi
                             float denom, int32_t n_cls, float* row_loss, void* dlogits, int64_t d_stride, float* loss_out,
                             uint32_t* ticket, int32_t* err, void* stream);
 
+/* Micro-F1 (torchmetrics Multiclass / MultilabelF1Score(average='micro'), train_lightning.py:68-70, :143, :179-203) as counts on
+ * the device: one launch ADDS this batch's {tp, fp, fn, n} to counts[0..3] (int64; never overwritten) with 64-bit integer atomics,
+ * at most one per workgroup and counter -- integer adds commute, so the result does not depend on the schedule.  Nothing allocates,
+ * syncs or reads back; the kernels keep no state besides counts and err, so a captured launch replays as it is.
+ *
+ *   logits       bf16 [*, n_cls], row stride `stride` (>= n_cls) elements; n_pred_rows: how many rows it holds (0 = not checked)
+ *   row_ids      NULL: row r reads logits row r.  int32 [n_rows]: row r reads logits row row_ids[r] (pred[nid] never materialised)
+ *   labels       direct: row r's label is labels[r]  (int64 [n_rows] / fp32 [n_rows, n_cls], rows contiguous)
+ *   label_table, label_ids   or: row r's label is label_table[label_ids[r]] (int32 ids; n_table rows, 0 = not checked) -- the form
+ *                bliss_cross_entropy_sum / bliss_bce_logits_sum take.  Exactly one of the two forms must be given.
+ *   n_rows       host bound (and launch size); n_rows_dev != NULL: only the first min(max(*n_rows_dev, 0), n_rows) rows count
+ *                (the convention of the masked losses); nothing of the other rows is read.
+ *
+ * The rule (normative):
+ *   single-label  The prediction of a row is the FIRST index of its largest logit.  A NaN logit counts as larger than everything
+ *                 and the first NaN wins (torch.argmax).  +0 and -0 are equal.  A row of -inf predicts 0.  A correct row adds
+ *                 tp += 1, a wrong row fp += 1 and fn += 1, every counted row n += 1.  A label outside [0, n_cls) sets bit 2 of
+ *                 *err and the row is left out of all four counts (the loss's "no loss term"); so does a label id outside a
+ *                 checked table or a row id outside a checked prediction.
+ *   multi-label   Per (row, class) pair: hit = x > 0, y = target > 0.5; tp = hit & y, fp = hit & !y, fn = !hit & y; n += n_cls per
+ *                 counted row.  x > 0 is the exact statement of sigmoid(x) > 0.5 (a sigmoid evaluated in fp32 rounds to 0.5 for
+ *                 0 < x < 2^-23: the one difference to such an implementation).  NaN is no hit and no positive target; x = +-0 is
+ *                 no hit.  Ids outside a checked table / prediction: as above.
+ *   micro-F1 = 2 tp / max(2 tp + fp + fn, 1).
+ *
+ * Launch shape: single-label one wave per row (256 threads = 4 rows per workgroup), multi-label one thread per pair; both loop
+ * with the grid as stride under a cap of BLISS_F1_MAX_WORKGROUPS workgroups (4096 rows / 262144 pairs per trip).
+ * BLISS_EINVAL before any launch: logits, counts or err NULL, n_cls <= 0, n_rows < 0, stride < n_cls, n_pred_rows or n_table < 0,
+ * neither or both label forms.  n_rows == 0 launches nothing and returns 0. */
+#define BLISS_F1_MAX_WORKGROUPS 1024
+int bliss_f1_multiclass(const void* logits, int64_t stride, int32_t n_pred_rows, const int32_t* row_ids, const int64_t* labels,
+                        const int64_t* label_table, int32_t n_table, const int32_t* label_ids, int32_t n_rows,
+                        const int32_t* n_rows_dev, int32_t n_cls, int64_t* counts, int32_t* err, void* stream);
+int bliss_f1_multilabel(const void* logits, int64_t stride, int32_t n_pred_rows, const int32_t* row_ids, const float* labels,
+                        const float* label_table, int32_t n_table, const int32_t* label_ids, int32_t n_rows,
+                        const int32_t* n_rows_dev, int32_t n_cls, int64_t* counts, int32_t* err, void* stream);
+
 /* th.optim.Adam(self.parameters(), lr) (train_lightning.py:205-206) for a bf16 module: parameters, gradients and both moment
  * buffers bf16, one launch over all tensors, math in fp32, one rounding per stored value.  state: float[4] on the device --
  * [0] step count (incremented by the launch), [1] learning rate (the caller rewrites it when its scheduler does,
