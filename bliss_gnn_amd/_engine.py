@@ -112,6 +112,7 @@ class LayerEngine:
         self.exact_k = False                # device-drawn multinomial layers keep at most fanout + S nodes: K capacities are that bound
         self.exact_b = False                # neighbor layers keep at most fanout edges per seed: B capacities are that bound
         self._nb_scr = None                 # csrc/neighbor.hip: tickets + node bitmap (zero once, left zero by every call)
+        self._lb_scr = None                 # csrc/labor.hip: the same words + one kept count per seed column; (cap_s, tensor)
         self._slot_bufs, self._slot_counts, self._slot_counts_host = {}, {}, {}
         self.caps = None
         self.ws = None
@@ -406,15 +407,78 @@ class LayerEngine:
             self._grow([c.err for c in cnts])
             self._ensure_neighbor(int(seeds.numel()), fanouts)
 
-    def _enqueue_neighbor_layer(self, n, fanout, cur_seeds, n_seeds, n_seeds_dev, draw_state, last, c_ws, c_out, lay, cnt_ptr, st):
-        """One bliss_neighbor_layer + the by-source index of its block (bliss_block_transpose on the device-resident B)."""
+    # ------------------------------------------------------------------ LABOR-0 sampler (keyed per-source draw)
+    def _lb_caps(self, S0, fanouts):
+        """Starting capacities of LABOR layers.  A column keeps ``fanout`` edges in expectation, not at most: B is NOT exactly
+        bounded, so it starts at twice the expectation (the neighbor rule for fanout < 0) and the regrow loop covers the rest."""
+        caps, s = [], int(S0)
+        for f in fanouts:
+            f = int(f)
+            b = int(min(self.Eg, 2 * s * f + 4096)) if f >= 0 else int(min(self.Eg, max(1 << 16, 48 * s)))
+            k = int(min(self.V, s + b)) if f >= 0 else self.V
+            caps.append(dict(S=s, C=self.V, K=k, B=b))
+            s = k
+        return caps
+
+    def _ensure_labor(self, S0, fan):
+        if self.caps is None or len(self.caps) != len(fan) or self.caps[0]["S"] < S0:
+            fresh = self._lb_caps(S0, fan)
+            if self.caps is not None and len(self.caps) == len(fan):
+                fresh = [{k: max(a.get(k, 0), b[k]) for k in b} for a, b in zip(self.caps, fresh)]
+            self.caps, self.ws = fresh, None
+        self._ensure(S0, fan)
+
+    def sample_blocks_labor(self, seeds, fanouts, draw_state, layer_dependency=False):
+        """fit.LaborSampler (csrc/labor.hip): the L layers (``fanouts`` in SAMPLING order) are only enqueued
+        and the call synchronises once, at the end; torch's generators are not touched.  ``layer_dependency``: one variate per
+        vertex for all layers of a step."""
+        if draw_state is None:
+            raise ValueError("the LABOR sampler needs a draw_state")
+        seeds = seeds.to(torch.int32).contiguous()
+        L = len(fanouts)
+        self._ensure_labor(int(seeds.numel()), fanouts)
+        while True:
+            out = self._enqueue(None, seeds, fanouts, 0, 0.0, 0.0, None, None, draw_state=draw_state, labor=True,
+                                layer_dependency=layer_dependency)
+            self.counts_host.copy_(out[0], non_blocking=True)
+            torch.cuda.current_stream().synchronize()                 # the one sync of the call
+            raw = self.counts_host.numpy().tobytes()
+            cnts = [_lib.LayerCounts.from_buffer_copy(raw[40 * n: 40 * n + 40]) for n in range(L)]
+            bad = 0
+            for c in cnts:
+                bad |= c.err
+            if bad & ~_CAP_ERRS or bad & 3:
+                raise RuntimeError(f"sampler kernel error 0x{bad:x}: {_lib.err_string(bad)}")
+            if bad == 0:
+                return self._finish(out, cnts)
+            draw_state.step_dev.sub_(1)                                # the repeated call is the same draw step
+            self._grow([c.err for c in cnts])
+            self._ensure_labor(int(seeds.numel()), fanouts)
+
+    def _labor_scratch(self, cap_s):
+        if self._lb_scr is None or self._lb_scr[0] < cap_s:           # (sized once for any seed capacity up to |V|)
+            rows = max(self.V, int(cap_s))
+            nbytes = int(_lib.lib.bliss_labor_scratch_bytes(self.V, rows))
+            self._lb_scr = (rows, torch.zeros(nbytes // 4, dtype=torch.int32, device=self.g.device))
+        return self._lb_scr[1]
+
+    def _enqueue_neighbor_layer(self, n, fanout, cur_seeds, n_seeds, n_seeds_dev, draw_state, last, c_ws, c_out, lay, cnt_ptr, st,
+                                labor=False, layer_dependency=False):
+        """One bliss_neighbor_layer (``labor``: one bliss_labor_layer) + the by-source index of its block (bliss_block_transpose
+        on the device-resident B)."""
         cap, ws = self.caps[n], self.ws[n]
-        if self._nb_scr is None:
-            nbytes = int(_lib.lib.bliss_neighbor_scratch_bytes(self.V, 1))
-            self._nb_scr = torch.zeros(nbytes // 4, dtype=torch.int32, device=self.g.device)
-        _lib.check(_lib.lib.bliss_neighbor_layer(C.byref(self.c_graph), cur_seeds.data_ptr(), n_seeds, n_seeds_dev, cap["S"], int(fanout),
-                                                 0, draw_state.seed, draw_state.step_dev.data_ptr(), n, int(last), C.byref(c_ws),
-                                                 C.byref(c_out), self._nb_scr.data_ptr(), st), "bliss_neighbor_layer")
+        if labor:
+            _lib.check(_lib.lib.bliss_labor_layer(C.byref(self.c_graph), cur_seeds.data_ptr(), n_seeds, n_seeds_dev, cap["S"], int(fanout),
+                                                  0, draw_state.seed, draw_state.step_dev.data_ptr(), n, int(last),
+                                                  int(bool(layer_dependency)), C.byref(c_ws), C.byref(c_out),
+                                                  self._labor_scratch(cap["S"]).data_ptr(), st), "bliss_labor_layer")
+        else:
+            if self._nb_scr is None:
+                nbytes = int(_lib.lib.bliss_neighbor_scratch_bytes(self.V, 1))
+                self._nb_scr = torch.zeros(nbytes // 4, dtype=torch.int32, device=self.g.device)
+            _lib.check(_lib.lib.bliss_neighbor_layer(C.byref(self.c_graph), cur_seeds.data_ptr(), n_seeds, n_seeds_dev, cap["S"], int(fanout),
+                                                     0, draw_state.seed, draw_state.step_dev.data_ptr(), n, int(last), C.byref(c_ws),
+                                                     C.byref(c_out), self._nb_scr.data_ptr(), st), "bliss_neighbor_layer")
         b_src, t_indptr, t_edge = lay[1], lay[10], lay[11]
         if t_indptr is None:
             return                                                     # (Block.transposed builds it on demand)
@@ -559,7 +623,7 @@ class LayerEngine:
         _lib.check(_lib.lib.bliss_rng_stream_ready(_stream()), "bliss_rng_stream_ready")
 
     def enqueue_static(self, w_rows, seeds, fanouts, mode, eta, eps=0.9999, slot=0, chain_rng=False, external_rng=False, part=None,
-                       last_block=True, ready_flag=0, draw_state=None, neighbor=False):
+                       last_block=True, ready_flag=0, draw_state=None, neighbor=False, labor=False, layer_dependency=False):
         """Enqueue one sample_blocks on the current stream with capacity-padded outputs and NO sync.  Returns the
         blocks (sampling order); sizes, errors and the generator state are read back by finish().
 
@@ -574,7 +638,11 @@ class LayerEngine:
         (address of a device flag) is raised as soon as the block's forward arrays are final, before its by-source index.
         ``draw_state`` (a DrawState): the layers draw with the device-side multinomial draw instead of the Poisson chain
         (whole calls only; no generator is involved).  ``neighbor``: the layers are neighbor layers (csrc/neighbor.hip; needs
-        ``draw_state``, whole calls only; ``w_rows`` / ``mode`` / ``eta`` / ``eps`` are ignored)."""
+        ``draw_state``, whole calls only; ``w_rows`` / ``mode`` / ``eta`` / ``eps`` are ignored).  ``labor``: the layers are LABOR-0
+        layers (csrc/labor.hip; the same conditions), with one variate per vertex for all layers when ``layer_dependency``."""
+        if labor and (neighbor or draw_state is None or part is not None or external_rng or chain_rng):
+            raise NotImplementedError("the LABOR sampler needs a draw_state and has no split / external-generator enqueue "
+                                      "(the pipelined two-stream loop is out of scope)")
         if neighbor and (draw_state is None or part is not None or external_rng or chain_rng):
             raise NotImplementedError("the device-side neighbor sampler needs a draw_state and has no split / external-generator "
                                       "enqueue (the pipelined two-stream loop is out of scope)")
@@ -586,7 +654,7 @@ class LayerEngine:
         L = len(fanouts)
         out = self._enqueue(w_rows, seeds, fanouts, mode, eta, eps, None, True, slot=slot, chain_rng=chain_rng,
                             external_rng=external_rng, part=part, last_block=last_block, ready_flag=ready_flag, draw_state=draw_state,
-                            neighbor=neighbor)
+                            neighbor=neighbor, labor=labor, layer_dependency=layer_dependency)
         self._static_draw[slot] = draw_state is not None
         counts_dev, layers = out
         if slot not in self._slot_counts_host:
@@ -629,7 +697,7 @@ class LayerEngine:
         return cnts
 
     def _enqueue(self, w_rows, seeds, fanouts, mode, eta, eps, uniforms, snapshot, slot=None, chain_rng=False, external_rng=False,
-                 part=None, last_block=True, ready_flag=0, draw_state=None, neighbor=False):
+                 part=None, last_block=True, ready_flag=0, draw_state=None, neighbor=False, labor=False, layer_dependency=False):
         dev, st = self.g.device, _stream()
         L = len(fanouts)
         if draw_state is None and snapshot is not None and not chain_rng and not external_rng:
@@ -655,9 +723,9 @@ class LayerEngine:
             cs, ws = cap["S"], self.ws[n]
             c_ws, c_out, lay, cnt_ptr, kept_nid = self._layer_buffers(n, counts, slot)
             last = n == L - 1
-            if neighbor:                        # neighbor layer: 6 launches and the by-source index, nothing else
+            if neighbor or labor:               # neighbor / LABOR layer: 6 / 7 launches and the by-source index, nothing else
                 self._enqueue_neighbor_layer(n, fanouts[n], cur_seeds, n_seeds, n_seeds_dev, draw_state, last, c_ws, c_out, lay,
-                                             cnt_ptr, st)
+                                             cnt_ptr, st, labor=labor, layer_dependency=layer_dependency)
                 layers.append(lay)
                 cur_seeds, n_seeds, n_seeds_dev = kept_nid, -1, cnt_ptr + 12
                 continue

@@ -5,6 +5,8 @@ pytorch_lightning, reduced to plain loops -- Lightning / torchmetrics / tensorbo
     (train_lightning.py:349-357).  (With them the reference's models fail at ``block.edata["edge_weights"]``,
     model.py:321-329 -- DGL's own samplers attach no such field -- so they are baselines here, with unit weights.)
     ``NeighborSampler(..., draw="device")``: the keyed per-column draw of csrc/neighbor.hip, graph-capturable.
+  * ``LaborSampler``: LABOR-0, the node-wise baseline with one random variate per SOURCE vertex shared by all seeds of a layer
+    (csrc/labor.hip) -- the sampler the reference's training script was derived from and dropped.
   * ``fit``: epochs of TrainStep, ``StepLR(gamma=0.01, step_size=5)`` stepped per epoch (:205-216), validation with the same
     sampler (:179-203, :410-422), best-``val_acc`` checkpoint (:620-625), early stop on ``val_acc_target`` / patience
     (:627-634), then the best checkpoint reloaded for the layer-wise full-neighbour inference and the Final Accuracy of the
@@ -142,6 +144,55 @@ class NeighborSampler(DeviceDraw, BlockSampler):
         return blocks[0].srcdata[NID], seed_nodes, blocks
 
 
+class LaborSampler(NeighborSampler):
+    """``dgl.dataloading.LaborSampler(fanouts, importance_sampling=0)`` -- LABOR-0 (Balin & Catalyurek, "Layer-Neighbor Sampling"):
+    per layer, one uniform variate r_u per SOURCE vertex shared by all seeds; the edge u -> s is kept iff r_u < fanout / deg(s).
+    Per destination that is the neighbor sampler's expected edge count and estimator variance, out of far fewer distinct
+    sources.  No parity claim (DGL draws with its own RNG): a defined mode, the keyed draw of csrc/labor.hip restated by
+    tests/labor_ref.py.  Every kept edge of a column has the same inclusion probability, so the Hajek
+    weight under the mean aggregation is exactly 1: unit ``edge_weights``.  A destination may keep no edge at all.
+
+    There is no host path: ``draw`` is always ``"device"`` -- a function of (seed, draw step, layer, source node id), no host
+    round trip, so ``sample_blocks_static`` exists and the sampler runs inside a captured train step (``reset_draw`` /
+    ``draw_step`` / ``finish_static`` / ``check_errors`` as ``NeighborSampler(draw="device")`` has them); no torch generator is
+    touched.  ``layer_dependency=True``: the same variate per vertex in all layers of a step.  Out of scope (raise):
+    ``importance_sampling != 0`` (LABOR-i's fixed-point iterations), ``prob``, ``batch_dependency != 1``, ``edge_dir != "in"``."""
+
+    def __init__(self, fanouts, edge_dir="in", prob=None, importance_sampling=0, layer_dependency=False, batch_dependency=1, seed=0,
+                 **_ignored):
+        if importance_sampling != 0:
+            raise NotImplementedError("LaborSampler is LABOR-0: importance_sampling must be 0 (LABOR-i's importance iterations "
+                                      "are out of scope)")
+        if prob is not None:
+            raise NotImplementedError("LaborSampler: edge probabilities (prob=) are out of scope")
+        if batch_dependency != 1:
+            raise NotImplementedError("LaborSampler: batch_dependency must be 1 (variates shared across batches are out of scope)")
+        if edge_dir != "in":
+            raise NotImplementedError("LaborSampler samples in-edges only (edge_dir='in')")
+        super().__init__(fanouts, seed=seed, draw="device")
+        self.layer_dependency = bool(layer_dependency)
+
+    def _bind(self, g):
+        g = as_graph(g, self.__dict__.setdefault("_graphs", {}))
+        if self._engine is None or self._engine.g is not g:
+            self._engine = LayerEngine(g)                   # (exact_b stays False: a column's kept count is data dependent)
+        return self._engine
+
+    def sample_blocks_static(self, g, seed_nodes, slot=0, **split):
+        """sample_blocks with capacity-padded blocks, only ENQUEUED; whole calls only: any split / external-generator keyword
+        raises.  A step over its calibrated capacities is reported by ``finish_static``."""
+        eng = self._bind(g)
+        fan = list(reversed(self.fanouts))
+        return self._blocks(eng.enqueue_static(None, seed_nodes, fan, 0, 0.0, slot=slot, draw_state=self._draw_state_on(eng.g.device),
+                                               labor=True, layer_dependency=self.layer_dependency, **split), seed_nodes)
+
+    def sample_blocks(self, g, seed_nodes, exclude_eids=None):
+        g = as_graph(g, self.__dict__.setdefault("_graphs", {}))
+        blks = self._bind(g).sample_blocks_labor(seed_nodes, list(reversed(self.fanouts)), self._draw_state_on(g.device),
+                                                 self.layer_dependency)
+        return self._blocks(blks, seed_nodes)
+
+
 def make_sampler(name, fanouts, importance_sampling=1, num_steps=5000, eta=0.1, model="sage", draw="host"):
     """The sampler-name dispatch of DataModule.__init__ (train_lightning.py:348-370).  ``draw``: where the two multinomial
     samplers ("ladies", "bandit") and "neighbor" draw -- "host" (torch.multinomial / torch tensor ops) or "device" (the keyed
@@ -151,6 +202,8 @@ def make_sampler(name, fanouts, importance_sampling=1, num_steps=5000, eta=0.1, 
         return MultiLayerFullNeighborSampler(len(fanouts))
     if name == "neighbor":
         return NeighborSampler(fanouts, draw=draw)
+    if name == "labor":
+        return LaborSampler(fanouts)                        # (LABOR-0; always the device draw)
     if "ladies" in name and "bandit" not in name:
         return PLS(fanouts) if "poisson" in name else LadiesSampler(fanouts, draw=draw)
     if "bandit" in name:

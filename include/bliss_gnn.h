@@ -219,7 +219,35 @@ int bliss_neighbor_layer(const bliss_graph_t* g, const int32_t* seeds, int32_t n
                          int32_t fanout, const uint32_t* keys_override, uint64_t seed, int64_t* step_dev, int32_t layer,
                          int bump_step, const bliss_layer_ws_t* ws, const bliss_block_out_t* out, void* scratch, void* stream);
 
-/* generate_block      bandit_sampler.py:269-339 (BANDIT: Hajek weights) / ladies_sampler.py:71-107.
+/* dgl.dataloading.LaborSampler(fanouts, importance_sampling=0) ON THE DEVICE, one layer (fit.LaborSampler; LABOR-0: a defined-mode
+ * keyed draw like bliss_neighbor_layer with the key on the edge's SOURCE NODE and a per-column threshold instead of a per-column
+ * select, restated on the CPU by tests/labor_ref.py).  Integers only:
+ *   key(u)  = (uint32)(z >> 32), z = SplitMix64 finaliser of mix(seed, *step_dev, layer') ^ (uint64)u, u = g->indices[pos] --
+ *             bliss_neighbor_layer's mixing; layer' = layer, or 0 for every layer when layer_dependency != 0 (the same variate per
+ *             vertex in all layers of a step); keys_override[u] when keys_override != NULL (uint32 [num_nodes], by NODE ID)
+ *   seed column s, CSC positions [a, b), d = b - a:  if fanout < 0 or d <= fanout every edge is kept and no key is computed;
+ *             otherwise thr = ((uint64)fanout << 32) / d (integer division, 1 <= thr < 2^32) and the edge at pos is kept iff
+ *             (uint64)key(indices[pos]) < thr.  The edges of a multi-edge are kept or dropped together; a column may keep NO edge.
+ *   block:    edges column by column in seed order, ascending position inside a column; indptr[s + 1] - indptr[s] = c_s, the kept
+ *             count of column s, B = sum c_s (data dependent: neither is known before the draw); sources = the seeds (local ids
+ *             0 .. S-1 in the order given), then the other sources of kept edges, each once, in ascending node id;
+ *             edge_weights = q_ij = 1 (every kept edge of a column has the same inclusion probability: the Hajek weight under the
+ *             mean aggregation is exactly 1); eid = g->eid[pos], or pos when g->eid == NULL
+ * Seeds, ws, out, the counts record {S, E = sum d, C = K, K, B, err}, the capacity padding, the clamps and BLISS_ERR_CAP_* bits,
+ * ws->kept_map (-1 on entry and on exit) and bump_step (the last workgroup of the writing kernel increments *step_dev once, after
+ * every workgroup has read it) are bliss_neighbor_layer's; no source is marked for an edge that was not written.  scratch:
+ * bliss_labor_scratch_bytes(num_nodes, cap_s) bytes, 16-byte aligned, zero-initialised ONCE: bliss_neighbor_layer's words (tickets
+ * and bitmap left zero by every call, also a replayed one and one that flagged an overflow; one offset per 1024 bitmap words) and
+ * then cap_s words for c_s, rewritten by every call.  Seven launches, no host round trip.
+ * BLISS_EINVAL before any launch: the set bliss_neighbor_layer refuses -- a null pointer (keys_override may be NULL; n_seeds_dev
+ * with n_seeds >= 0; step_dev only with keys_override and without bump_step), cap_s <= 0, fanout == 0, ws->cap_k <= 0,
+ * num_edges > INT32_MAX, misaligned scratch. */
+int64_t bliss_labor_scratch_bytes(int32_t num_nodes, int32_t cap_s);
+int bliss_labor_layer(const bliss_graph_t* g, const int32_t* seeds, int32_t n_seeds, const int32_t* n_seeds_dev, int32_t cap_s,
+                      int32_t fanout, const uint32_t* keys_override, uint64_t seed, int64_t* step_dev, int32_t layer, int bump_step,
+                      int layer_dependency, const bliss_layer_ws_t* ws, const bliss_block_out_t* out, void* scratch, void* stream);
+
+/* generate_block     bandit_sampler.py:269-339 (BANDIT: Hajek weights) / ladies_sampler.py:71-107.
  * Same g, maps, w_pos, seeds, eta as the matching bliss_frontier_prob call.  Out: counts{B}, the block;
  * leaves the node maps clean. */
 int bliss_build_block(const bliss_graph_t* g, const bliss_node_maps_t* maps, const void* w_pos,
