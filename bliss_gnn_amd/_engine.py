@@ -113,6 +113,8 @@ class LayerEngine:
         self.exact_b = False                # neighbor layers keep at most fanout edges per seed: B capacities are that bound
         self._nb_scr = None                 # csrc/neighbor.hip: tickets + node bitmap (zero once, left zero by every call)
         self._lb_scr = None                 # csrc/labor.hip: the same words + one kept count per seed column; (cap_s, tensor)
+        self.labor_is = False               # LABOR layers run csrc/labor_is.hip also with 0 iterations (fit.ImportanceLaborSampler)
+        self._li_scr = None                 # csrc/labor_is.hip: + two |V|-word importance buffers, scales, p_e; (cap_s, cap_b, tensor)
         self._slot_bufs, self._slot_counts, self._slot_counts_host = {}, {}, {}
         self.caps = None
         self.ws = None
@@ -428,10 +430,11 @@ class LayerEngine:
             self.caps, self.ws = fresh, None
         self._ensure(S0, fan)
 
-    def sample_blocks_labor(self, seeds, fanouts, draw_state, layer_dependency=False):
+    def sample_blocks_labor(self, seeds, fanouts, draw_state, layer_dependency=False, iterations=0):
         """fit.LaborSampler (csrc/labor.hip): the L layers (``fanouts`` in SAMPLING order) are only enqueued
         and the call synchronises once, at the end; torch's generators are not touched.  ``layer_dependency``: one variate per
-        vertex for all layers of a step."""
+        vertex for all layers of a step.  ``iterations`` > 0: LABOR-i layers (fit.ImportanceLaborSampler, csrc/labor_is.hip,
+        DESIGN.md section 16)."""
         if draw_state is None:
             raise ValueError("the LABOR sampler needs a draw_state")
         seeds = seeds.to(torch.int32).contiguous()
@@ -439,7 +442,7 @@ class LayerEngine:
         self._ensure_labor(int(seeds.numel()), fanouts)
         while True:
             out = self._enqueue(None, seeds, fanouts, 0, 0.0, 0.0, None, None, draw_state=draw_state, labor=True,
-                                layer_dependency=layer_dependency)
+                                layer_dependency=layer_dependency, labor_iterations=iterations)
             self.counts_host.copy_(out[0], non_blocking=True)
             torch.cuda.current_stream().synchronize()                 # the one sync of the call
             raw = self.counts_host.numpy().tobytes()
@@ -462,12 +465,28 @@ class LayerEngine:
             self._lb_scr = (rows, torch.zeros(nbytes // 4, dtype=torch.int32, device=self.g.device))
         return self._lb_scr[1]
 
+    def _labor_is_scratch(self, cap_s, cap_b):
+        """Sized once for any seed capacity up to |V| and the largest edge capacity of the layers; regrows with B."""
+        if self._li_scr is None or self._li_scr[0] < cap_s or self._li_scr[1] < cap_b:
+            rows, edges = max(self.V, int(cap_s)), max(int(cap_b), max(c["B"] for c in self.caps))
+            nbytes = int(_lib.lib.bliss_labor_is_scratch_bytes(self.V, rows, edges))
+            if nbytes < 0:
+                raise RuntimeError("bliss_labor_is_scratch_bytes failed")
+            self._li_scr = (rows, edges, torch.zeros(nbytes // 4, dtype=torch.int32, device=self.g.device))
+        return self._li_scr[2]
+
     def _enqueue_neighbor_layer(self, n, fanout, cur_seeds, n_seeds, n_seeds_dev, draw_state, last, c_ws, c_out, lay, cnt_ptr, st,
-                                labor=False, layer_dependency=False):
-        """One bliss_neighbor_layer (``labor``: one bliss_labor_layer) + the by-source index of its block (bliss_block_transpose
-        on the device-resident B)."""
+                                labor=False, layer_dependency=False, labor_iterations=0):
+        """One bliss_neighbor_layer (``labor``: one bliss_labor_layer, or one bliss_labor_is_layer when ``labor_iterations`` > 0)
+        + the by-source index of its block (bliss_block_transpose on the device-resident B)."""
         cap, ws = self.caps[n], self.ws[n]
-        if labor:
+        if labor and (labor_iterations > 0 or self.labor_is):
+            _lib.check(_lib.lib.bliss_labor_is_layer(C.byref(self.c_graph), cur_seeds.data_ptr(), n_seeds, n_seeds_dev, cap["S"],
+                                                     int(fanout), 0, draw_state.seed, draw_state.step_dev.data_ptr(), n, int(last),
+                                                     int(bool(layer_dependency)), int(labor_iterations), C.byref(c_ws), C.byref(c_out),
+                                                     self._labor_is_scratch(cap["S"], c_out.cap_b).data_ptr(), st),
+                       "bliss_labor_is_layer")
+        elif labor:
             _lib.check(_lib.lib.bliss_labor_layer(C.byref(self.c_graph), cur_seeds.data_ptr(), n_seeds, n_seeds_dev, cap["S"], int(fanout),
                                                   0, draw_state.seed, draw_state.step_dev.data_ptr(), n, int(last),
                                                   int(bool(layer_dependency)), C.byref(c_ws), C.byref(c_out),
@@ -623,7 +642,8 @@ class LayerEngine:
         _lib.check(_lib.lib.bliss_rng_stream_ready(_stream()), "bliss_rng_stream_ready")
 
     def enqueue_static(self, w_rows, seeds, fanouts, mode, eta, eps=0.9999, slot=0, chain_rng=False, external_rng=False, part=None,
-                       last_block=True, ready_flag=0, draw_state=None, neighbor=False, labor=False, layer_dependency=False):
+                       last_block=True, ready_flag=0, draw_state=None, neighbor=False, labor=False, layer_dependency=False,
+                       labor_iterations=0):
         """Enqueue one sample_blocks on the current stream with capacity-padded outputs and NO sync.  Returns the
         blocks (sampling order); sizes, errors and the generator state are read back by finish().
 
@@ -639,7 +659,8 @@ class LayerEngine:
         ``draw_state`` (a DrawState): the layers draw with the device-side multinomial draw instead of the Poisson chain
         (whole calls only; no generator is involved).  ``neighbor``: the layers are neighbor layers (csrc/neighbor.hip; needs
         ``draw_state``, whole calls only; ``w_rows`` / ``mode`` / ``eta`` / ``eps`` are ignored).  ``labor``: the layers are LABOR-0
-        layers (csrc/labor.hip; the same conditions), with one variate per vertex for all layers when ``layer_dependency``."""
+        layers (csrc/labor.hip; the same conditions), with one variate per vertex for all layers when ``layer_dependency``; ``labor_iterations`` > 0:
+        LABOR-i layers (csrc/labor_is.hip)."""
         if labor and (neighbor or draw_state is None or part is not None or external_rng or chain_rng):
             raise NotImplementedError("the LABOR sampler needs a draw_state and has no split / external-generator enqueue "
                                       "(the pipelined two-stream loop is out of scope)")
@@ -654,7 +675,7 @@ class LayerEngine:
         L = len(fanouts)
         out = self._enqueue(w_rows, seeds, fanouts, mode, eta, eps, None, True, slot=slot, chain_rng=chain_rng,
                             external_rng=external_rng, part=part, last_block=last_block, ready_flag=ready_flag, draw_state=draw_state,
-                            neighbor=neighbor, labor=labor, layer_dependency=layer_dependency)
+                            neighbor=neighbor, labor=labor, layer_dependency=layer_dependency, labor_iterations=labor_iterations)
         self._static_draw[slot] = draw_state is not None
         counts_dev, layers = out
         if slot not in self._slot_counts_host:
@@ -697,7 +718,8 @@ class LayerEngine:
         return cnts
 
     def _enqueue(self, w_rows, seeds, fanouts, mode, eta, eps, uniforms, snapshot, slot=None, chain_rng=False, external_rng=False,
-                 part=None, last_block=True, ready_flag=0, draw_state=None, neighbor=False, labor=False, layer_dependency=False):
+                 part=None, last_block=True, ready_flag=0, draw_state=None, neighbor=False, labor=False, layer_dependency=False,
+                 labor_iterations=0):
         dev, st = self.g.device, _stream()
         L = len(fanouts)
         if draw_state is None and snapshot is not None and not chain_rng and not external_rng:
@@ -725,7 +747,8 @@ class LayerEngine:
             last = n == L - 1
             if neighbor or labor:               # neighbor / LABOR layer: 6 / 7 launches and the by-source index, nothing else
                 self._enqueue_neighbor_layer(n, fanouts[n], cur_seeds, n_seeds, n_seeds_dev, draw_state, last, c_ws, c_out, lay,
-                                             cnt_ptr, st, labor=labor, layer_dependency=layer_dependency)
+                                             cnt_ptr, st, labor=labor, layer_dependency=layer_dependency,
+                                             labor_iterations=labor_iterations)
                 layers.append(lay)
                 cur_seeds, n_seeds, n_seeds_dev = kept_nid, -1, cnt_ptr + 12
                 continue

@@ -7,6 +7,8 @@ pytorch_lightning, reduced to plain loops -- Lightning / torchmetrics / tensorbo
     ``NeighborSampler(..., draw="device")``: the keyed per-column draw of csrc/neighbor.hip, graph-capturable.
   * ``LaborSampler``: LABOR-0, the node-wise baseline with one random variate per SOURCE vertex shared by all seeds of a layer
     (csrc/labor.hip) -- the sampler the reference's training script was derived from and dropped.
+    ``ImportanceLaborSampler``: LABOR-i, the same draw after i fixed-point iterations over per-vertex importances
+    (csrc/labor_is.hip).
   * ``fit``: epochs of TrainStep, ``StepLR(gamma=0.01, step_size=5)`` stepped per epoch (:205-216), validation with the same
     sampler (:179-203, :410-422), best-``val_acc`` checkpoint (:620-625), early stop on ``val_acc_target`` / patience
     (:627-634), then the best checkpoint reloaded for the layer-wise full-neighbour inference and the Final Accuracy of the
@@ -156,7 +158,10 @@ class LaborSampler(NeighborSampler):
     round trip, so ``sample_blocks_static`` exists and the sampler runs inside a captured train step (``reset_draw`` /
     ``draw_step`` / ``finish_static`` / ``check_errors`` as ``NeighborSampler(draw="device")`` has them); no torch generator is
     touched.  ``layer_dependency=True``: the same variate per vertex in all layers of a step.  Out of scope (raise):
-    ``importance_sampling != 0`` (LABOR-i's fixed-point iterations), ``prob``, ``batch_dependency != 1``, ``edge_dir != "in"``."""
+    ``importance_sampling != 0`` (LABOR-i's fixed-point iterations), ``prob``, ``batch_dependency != 1``, ``edge_dir != "in"``.
+    (LABOR-i is a class of its own: ``ImportanceLaborSampler``.)"""
+
+    _iterations = 0                                         # (ImportanceLaborSampler: LABOR-i layers, csrc/labor_is.hip)
 
     def __init__(self, fanouts, edge_dir="in", prob=None, importance_sampling=0, layer_dependency=False, batch_dependency=1, seed=0,
                  **_ignored):
@@ -184,19 +189,49 @@ class LaborSampler(NeighborSampler):
         eng = self._bind(g)
         fan = list(reversed(self.fanouts))
         return self._blocks(eng.enqueue_static(None, seed_nodes, fan, 0, 0.0, slot=slot, draw_state=self._draw_state_on(eng.g.device),
-                                               labor=True, layer_dependency=self.layer_dependency, **split), seed_nodes)
+                                               labor=True, layer_dependency=self.layer_dependency,
+                                               labor_iterations=self._iterations, **split), seed_nodes)
 
     def sample_blocks(self, g, seed_nodes, exclude_eids=None):
         g = as_graph(g, self.__dict__.setdefault("_graphs", {}))
         blks = self._bind(g).sample_blocks_labor(seed_nodes, list(reversed(self.fanouts)), self._draw_state_on(g.device),
-                                                 self.layer_dependency)
+                                                 self.layer_dependency, iterations=self._iterations)
         return self._blocks(blks, seed_nodes)
+
+
+class ImportanceLaborSampler(LaborSampler):
+    """LABOR-i (Balin & Catalyurek, "Layer-Neighbor Sampling"; ``dgl.dataloading.LaborSampler(fanouts, importance_sampling=i)``):
+    LABOR-0's one variate r_u per source vertex, with the edge u -> s kept iff r_u < c_s * pi_u, where the per-vertex importances
+    pi come from ``iterations`` fixed-point iterations (pi_u <- the largest c_s * pi_u over the layer's edges out of u) and c_s
+    is the scale at which column s keeps ``fanout`` edges in expectation.  Every destination's expected edge count stays
+    ``fanout``; the set of distinct sources shrinks with every iteration.  No parity claim (DGL is not installable here and draws
+    with its own RNG; its form also seems to clamp the per-edge probability at 1 inside the maximum -- from memory, unchecked): a
+    defined mode in unsigned integers, csrc/labor_is.hip restated by tests/labor_is_ref.py.
+    ``edge_weights`` are the Hajek weights under the mean aggregation, (1 / p_e) * k_s / sum over the column's kept edges of
+    1 / p_e', exactly 1 in a column that is kept whole.
+
+    Everything else is ``LaborSampler``'s: always the device draw, ``layer_dependency``, ``reset_draw`` / ``draw_step`` /
+    ``sample_blocks_static`` / ``finish_static`` / ``check_errors``; it runs inside a captured train step.  ``iterations`` is a
+    launch-time constant in 0 .. 8 (0 = LABOR-0 through these kernels); DGL's ``-1`` (iterate until convergence) is out of scope:
+    a data-dependent launch count cannot be captured."""
+
+    def __init__(self, fanouts, iterations=1, layer_dependency=False, seed=0, **_ignored):
+        if isinstance(iterations, bool) or int(iterations) != iterations or not 0 <= int(iterations) <= 8:
+            raise ValueError("ImportanceLaborSampler: iterations must be an integer in 0 .. 8, got %r" % (iterations,))
+        super().__init__(fanouts, layer_dependency=layer_dependency, seed=seed)
+        self.iterations = self._iterations = int(iterations)
+
+    def _bind(self, g):
+        eng = super()._bind(g)
+        eng.labor_is = True                                 # (also iterations = 0 runs csrc/labor_is.hip, not csrc/labor.hip)
+        return eng
 
 
 def make_sampler(name, fanouts, importance_sampling=1, num_steps=5000, eta=0.1, model="sage", draw="host"):
     """The sampler-name dispatch of DataModule.__init__ (train_lightning.py:348-370).  ``draw``: where the two multinomial
     samplers ("ladies", "bandit") and "neighbor" draw -- "host" (torch.multinomial / torch tensor ops) or "device" (the keyed
-    draws, graph-capturable)."""
+    draws, graph-capturable).  "labor" and "labor-<i>" (i in 1 .. 8: ``ImportanceLaborSampler`` with i iterations) always draw on
+    the device."""
     from . import BanditLadiesSampler, LadiesSampler, PoissonBanditLadiesSampler, PoissonLadiesSampler as PLS
     if name == "full":
         return MultiLayerFullNeighborSampler(len(fanouts))
@@ -204,6 +239,11 @@ def make_sampler(name, fanouts, importance_sampling=1, num_steps=5000, eta=0.1, 
         return NeighborSampler(fanouts, draw=draw)
     if name == "labor":
         return LaborSampler(fanouts)                        # (LABOR-0; always the device draw)
+    if name.startswith("labor-"):                           # "labor-1" .. "labor-8": LABOR-i
+        i = name[len("labor-"):]
+        if i not in ("1", "2", "3", "4", "5", "6", "7", "8"):
+            raise ValueError("unknown sampler %r (LABOR-i: 'labor-1' .. 'labor-8'; LABOR-0 is 'labor')" % (name,))
+        return ImportanceLaborSampler(fanouts, iterations=int(i))
     if "ladies" in name and "bandit" not in name:
         return PLS(fanouts) if "poisson" in name else LadiesSampler(fanouts, draw=draw)
     if "bandit" in name:

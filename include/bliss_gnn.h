@@ -247,6 +247,31 @@ int bliss_labor_layer(const bliss_graph_t* g, const int32_t* seeds, int32_t n_se
                       int32_t fanout, const uint32_t* keys_override, uint64_t seed, int64_t* step_dev, int32_t layer, int bump_step,
                       int layer_dependency, const bliss_layer_ws_t* ws, const bliss_block_out_t* out, void* scratch, void* stream);
 
+/* LABOR-i ON THE DEVICE, one layer (fit.ImportanceLaborSampler; the LABOR paper's importance iterations on bliss_labor_layer's keyed
+ * per-source draw, restated on the CPU by tests/labor_is_ref.py).  Unsigned integers up to the weights, ONE = 2^32:
+ *   seed column s, CSC positions [a, b), d = b - a, is WHOLE if fanout < 0 or d <= fanout: every edge is kept, no key is computed.
+ *   Every position is its own term below (a multi-edge is m equal terms, kept or dropped as one).
+ *   pi^(0)_u = ONE;  c_s(pi) = the largest c in [0, ONE - 1] with sum_pos (c * pi_{indices[pos]}) >> 32 <= fanout * ONE (non-whole columns)
+ *   `iterations` (0 .. 8) times:  pi^(i+1)_u = max(1, max over the frontier edges u -> s of P),  P = ONE if s is whole, else
+ *             (c_s(pi^(i)) * pi^(i)_u) >> 32 -- the maximum over the new values only; vertices outside the frontier are never read
+ *   draw:     p_pos = (c_s(pi^(I)) * pi^(I)_u) >> 32 (< ONE); the edge at pos is kept iff (uint64)key(u) < p_pos, key = bliss_labor_layer's
+ *             (keys_override by NODE ID, layer_dependency as there).  iterations = 0 is bliss_labor_layer's rule bit for bit.
+ *   block, sources, counts record, capacity padding, clamps, BLISS_ERR_CAP_* bits, ws->kept_map, bump_step: bliss_labor_layer's.
+ *   q_ij = bf16(fp32(p_pos) * 2^-32), both roundings to nearest even; edge_weights = the Hajek weight under the mean aggregation,
+ *             W_e = (ONE / p_e) * k_s / sum_{kept e' of column s} (ONE / p_e'), k_s the column's kept count, evaluated in fp64 (the sum
+ *             in a fixed order, so a replay is bit-equal) and rounded once to bf16; both exactly 1 in whole columns; node_prob = 1.
+ * scratch: bliss_labor_is_scratch_bytes(num_nodes, cap_s, cap_b) bytes for cap_b = out->cap_b, 16-byte aligned, zero-initialised
+ * ONCE: tickets, bitmap, tile offsets, TWO num_nodes-word importance buffers (pi - 1 per vertex) -- tickets, bitmap and both
+ * buffers are left zero by every call, also a replayed one, one that flagged an overflow and one with a seed id out of range --
+ * then cap_s kept counts, cap_s scales and cap_b words of p_e, rewritten by every call.  8 launches for iterations = 0, else
+ * 2 * iterations + 9; no host round trip.  BLISS_EINVAL before any launch: the set bliss_labor_layer refuses, cap_b < 0 and
+ * iterations outside 0 .. 8. */
+int64_t bliss_labor_is_scratch_bytes(int32_t num_nodes, int32_t cap_s, int32_t cap_b);
+int bliss_labor_is_layer(const bliss_graph_t* g, const int32_t* seeds, int32_t n_seeds, const int32_t* n_seeds_dev, int32_t cap_s,
+                         int32_t fanout, const uint32_t* keys_override, uint64_t seed, int64_t* step_dev, int32_t layer,
+                         int bump_step, int layer_dependency, int32_t iterations, const bliss_layer_ws_t* ws,
+                         const bliss_block_out_t* out, void* scratch, void* stream);
+
 /* generate_block     bandit_sampler.py:269-339 (BANDIT: Hajek weights) / ladies_sampler.py:71-107.
  * Same g, maps, w_pos, seeds, eta as the matching bliss_frontier_prob call.  Out: counts{B}, the block;
  * leaves the node maps clean. */
