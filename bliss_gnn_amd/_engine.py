@@ -112,6 +112,7 @@ class LayerEngine:
         self.exact_k = False                # device-drawn multinomial layers keep at most fanout + S nodes: K capacities are that bound
         self.exact_b = False                # neighbor layers keep at most fanout edges per seed: B capacities are that bound
         self._nb_scr = None                 # csrc/neighbor.hip: tickets + node bitmap (zero once, left zero by every call)
+        self._wn_scr = None                 # csrc/neighbor_w.hip: the same words + a record per seed and a staged key per CSC position
         self._lb_scr = None                 # csrc/labor.hip: the same words + one kept count per seed column; (cap_s, tensor)
         self.labor_is = False               # LABOR layers run csrc/labor_is.hip also with 0 iterations (fit.ImportanceLaborSampler)
         self._li_scr = None                 # csrc/labor_is.hip: + two |V|-word importance buffers, scales, p_e; (cap_s, cap_b, tensor)
@@ -384,16 +385,17 @@ class LayerEngine:
             self.caps, self.ws = fresh, None
         self._ensure(S0, fan)
 
-    def sample_blocks_neighbor(self, seeds, fanouts, draw_state):
+    def sample_blocks_neighbor(self, seeds, fanouts, draw_state, nb_prob=None):
         """fit.NeighborSampler with ``draw="device"`` (csrc/neighbor.hip): the L layers (``fanouts`` in
-        SAMPLING order) are only enqueued and the call synchronises once, at the end; torch's generators are not touched."""
+        SAMPLING order) are only enqueued and the call synchronises once, at the end; torch's generators are not touched.
+        ``nb_prob``: the weighted draw of csrc/neighbor_w.hip -- ``neighbor_prob(...)``'s record."""
         if draw_state is None:
             raise ValueError("draw='device' needs a draw_state")
         seeds = seeds.to(torch.int32).contiguous()
         L = len(fanouts)
         self._ensure_neighbor(int(seeds.numel()), fanouts)
         while True:
-            out = self._enqueue(None, seeds, fanouts, 0, 0.0, 0.0, None, None, draw_state=draw_state, neighbor=True)
+            out = self._enqueue(None, seeds, fanouts, 0, 0.0, 0.0, None, None, draw_state=draw_state, neighbor=True, nb_prob=nb_prob)
             self.counts_host.copy_(out[0], non_blocking=True)
             torch.cuda.current_stream().synchronize()                 # the one sync of the call
             raw = self.counts_host.numpy().tobytes()
@@ -475,12 +477,39 @@ class LayerEngine:
             self._li_scr = (rows, edges, torch.zeros(nbytes // 4, dtype=torch.int32, device=self.g.device))
         return self._li_scr[2]
 
+    def neighbor_prob(self, rows, eta=None):
+        """The probability source of weighted neighbor layers (csrc/neighbor_w.hip).  ``rows``: bf16 [|E|] tensors by CSC position,
+        one per layer in SAMPLING order (or one tensor for all layers).  ``eta`` None: raw mode, the rows are the unnormalised
+        edge probabilities; a number: EXP3 mode, the rows are the EXP3 weights."""
+        rows = [rows] if torch.is_tensor(rows) else list(rows)
+        for r in rows:
+            if r.dtype != torch.bfloat16 or r.dim() != 1 or r.numel() != self.Eg or not r.is_contiguous() or not r.is_cuda:
+                raise ValueError("neighbor probabilities: contiguous bf16 [|E|] rows by CSC position on the device")
+        if eta is None:
+            return dict(mode=_lib.WN_RAW, rows=rows, eta_f=0.0, ome_f=0.0)
+        return dict(mode=_lib.WN_EXP3, rows=rows, eta_f=float(np.float32(eta)), ome_f=float(np.float32(1.0 - eta)))
+
+    def _wneighbor_scratch(self):
+        if self._wn_scr is None:                                      # (sized once for any seed capacity up to |V|)
+            nbytes = int(_lib.lib.bliss_wneighbor_scratch_bytes(self.V, self.V, self.Eg))
+            if nbytes < 0:
+                raise RuntimeError("bliss_wneighbor_scratch_bytes failed")
+            self._wn_scr = torch.zeros(nbytes // 4, dtype=torch.int32, device=self.g.device)
+        return self._wn_scr
+
     def _enqueue_neighbor_layer(self, n, fanout, cur_seeds, n_seeds, n_seeds_dev, draw_state, last, c_ws, c_out, lay, cnt_ptr, st,
-                                labor=False, layer_dependency=False, labor_iterations=0):
-        """One bliss_neighbor_layer (``labor``: one bliss_labor_layer, or one bliss_labor_is_layer when ``labor_iterations`` > 0)
-        + the by-source index of its block (bliss_block_transpose on the device-resident B)."""
+                                labor=False, layer_dependency=False, labor_iterations=0, nb_prob=None):
+        """One bliss_neighbor_layer (``labor``: one bliss_labor_layer, or one bliss_labor_is_layer when ``labor_iterations`` > 0;
+        ``nb_prob``: one bliss_wneighbor_layer) + the by-source index of its block (bliss_block_transpose on the device-resident B)."""
         cap, ws = self.caps[n], self.ws[n]
-        if labor and (labor_iterations > 0 or self.labor_is):
+        if nb_prob is not None:
+            row = nb_prob["rows"][n if len(nb_prob["rows"]) > 1 else 0]
+            _lib.check(_lib.lib.bliss_wneighbor_layer(C.byref(self.c_graph), cur_seeds.data_ptr(), n_seeds, n_seeds_dev, cap["S"],
+                                                      int(fanout), 0, draw_state.seed, draw_state.step_dev.data_ptr(), n, int(last),
+                                                      nb_prob["mode"], row.data_ptr(), nb_prob["eta_f"], nb_prob["ome_f"], 0,
+                                                      C.byref(c_ws), C.byref(c_out), self._wneighbor_scratch().data_ptr(), st),
+                       "bliss_wneighbor_layer")
+        elif labor and (labor_iterations > 0 or self.labor_is):
             _lib.check(_lib.lib.bliss_labor_is_layer(C.byref(self.c_graph), cur_seeds.data_ptr(), n_seeds, n_seeds_dev, cap["S"],
                                                      int(fanout), 0, draw_state.seed, draw_state.step_dev.data_ptr(), n, int(last),
                                                      int(bool(layer_dependency)), int(labor_iterations), C.byref(c_ws), C.byref(c_out),
@@ -643,7 +672,7 @@ class LayerEngine:
 
     def enqueue_static(self, w_rows, seeds, fanouts, mode, eta, eps=0.9999, slot=0, chain_rng=False, external_rng=False, part=None,
                        last_block=True, ready_flag=0, draw_state=None, neighbor=False, labor=False, layer_dependency=False,
-                       labor_iterations=0):
+                       labor_iterations=0, nb_prob=None):
         """Enqueue one sample_blocks on the current stream with capacity-padded outputs and NO sync.  Returns the
         blocks (sampling order); sizes, errors and the generator state are read back by finish().
 
@@ -660,7 +689,10 @@ class LayerEngine:
         (whole calls only; no generator is involved).  ``neighbor``: the layers are neighbor layers (csrc/neighbor.hip; needs
         ``draw_state``, whole calls only; ``w_rows`` / ``mode`` / ``eta`` / ``eps`` are ignored).  ``labor``: the layers are LABOR-0
         layers (csrc/labor.hip; the same conditions), with one variate per vertex for all layers when ``layer_dependency``; ``labor_iterations`` > 0:
-        LABOR-i layers (csrc/labor_is.hip)."""
+        LABOR-i layers (csrc/labor_is.hip).  ``nb_prob`` (with ``neighbor``): the weighted draw of csrc/neighbor_w.hip, from
+        ``neighbor_prob(...)``."""
+        if nb_prob is not None and not neighbor:
+            raise ValueError("nb_prob belongs to the neighbor layers")
         if labor and (neighbor or draw_state is None or part is not None or external_rng or chain_rng):
             raise NotImplementedError("the LABOR sampler needs a draw_state and has no split / external-generator enqueue "
                                       "(the pipelined two-stream loop is out of scope)")
@@ -675,7 +707,8 @@ class LayerEngine:
         L = len(fanouts)
         out = self._enqueue(w_rows, seeds, fanouts, mode, eta, eps, None, True, slot=slot, chain_rng=chain_rng,
                             external_rng=external_rng, part=part, last_block=last_block, ready_flag=ready_flag, draw_state=draw_state,
-                            neighbor=neighbor, labor=labor, layer_dependency=layer_dependency, labor_iterations=labor_iterations)
+                            neighbor=neighbor, labor=labor, layer_dependency=layer_dependency, labor_iterations=labor_iterations,
+                            nb_prob=nb_prob)
         self._static_draw[slot] = draw_state is not None
         counts_dev, layers = out
         if slot not in self._slot_counts_host:
@@ -719,7 +752,7 @@ class LayerEngine:
 
     def _enqueue(self, w_rows, seeds, fanouts, mode, eta, eps, uniforms, snapshot, slot=None, chain_rng=False, external_rng=False,
                  part=None, last_block=True, ready_flag=0, draw_state=None, neighbor=False, labor=False, layer_dependency=False,
-                 labor_iterations=0):
+                 labor_iterations=0, nb_prob=None):
         dev, st = self.g.device, _stream()
         L = len(fanouts)
         if draw_state is None and snapshot is not None and not chain_rng and not external_rng:
@@ -748,7 +781,7 @@ class LayerEngine:
             if neighbor or labor:               # neighbor / LABOR layer: 6 / 7 launches and the by-source index, nothing else
                 self._enqueue_neighbor_layer(n, fanouts[n], cur_seeds, n_seeds, n_seeds_dev, draw_state, last, c_ws, c_out, lay,
                                              cnt_ptr, st, labor=labor, layer_dependency=layer_dependency,
-                                             labor_iterations=labor_iterations)
+                                             labor_iterations=labor_iterations, nb_prob=nb_prob if neighbor else None)
                 layers.append(lay)
                 cur_seeds, n_seeds, n_seeds_dev = kept_nid, -1, cnt_ptr + 12
                 continue

@@ -11,6 +11,7 @@ LIB_PATH = os.path.join(_HERE, "libbliss_gnn.so")
 
 EINVAL = -1
 MODE_BANDIT, MODE_LADIES, MODE_UNIFORM_NODES, MODE_PARTIALS = 0, 1, 4, 8
+WN_RAW, WN_EXP3 = 0, 1                 # bliss_wneighbor_layer: probabilities as given / EXP3 weights
 
 ERR_BITS = {
     1: "frontier larger than 2^31-1 edges",
@@ -153,6 +154,8 @@ SIGNATURES = {
     "bliss_multinomial_select_marked": [C.POINTER(LayerWs), _P],
     "bliss_neighbor_layer": [C.POINTER(Graph), _P, _I32, _P, _I32, _I32, _P, C.c_uint64, _P, _I32, C.c_int, C.POINTER(LayerWs),
                              C.POINTER(BlockOut), _P, _P],
+    "bliss_wneighbor_layer": [C.POINTER(Graph), _P, _I32, _P, _I32, _I32, _P, C.c_uint64, _P, _I32, C.c_int, _I32, _P, _F, _F, _P,
+                              C.POINTER(LayerWs), C.POINTER(BlockOut), _P, _P],
     "bliss_labor_layer": [C.POINTER(Graph), _P, _I32, _P, _I32, _I32, _P, C.c_uint64, _P, _I32, C.c_int, C.c_int, C.POINTER(LayerWs),
                           C.POINTER(BlockOut), _P, _P],
     "bliss_labor_is_layer": [C.POINTER(Graph), _P, _I32, _P, _I32, _I32, _P, C.c_uint64, _P, _I32, C.c_int, C.c_int, _I32,
@@ -221,7 +224,7 @@ SIGNATURES = {
 
 SPECIAL_SIGNATURES = ("bliss_prof_kernel_name", "bliss_block_transpose_temp_bytes", "bliss_graph_prepare_capacity",
                       "bliss_graph_prepare_temp_bytes", "bliss_rng_stream_handle", "bliss_sage_wgrad_workspace",
-                      "bliss_multinomial_draw_scratch_bytes", "bliss_neighbor_scratch_bytes",
+                      "bliss_multinomial_draw_scratch_bytes", "bliss_neighbor_scratch_bytes", "bliss_wneighbor_scratch_bytes",
                       "bliss_labor_scratch_bytes", "bliss_labor_is_scratch_bytes")   # non-int return types, set in _load()
 
 
@@ -246,6 +249,8 @@ def _load():
     lib.bliss_multinomial_draw_scratch_bytes.restype = C.c_int64
     lib.bliss_neighbor_scratch_bytes.argtypes = [_I32, _I32]
     lib.bliss_neighbor_scratch_bytes.restype = C.c_int64
+    lib.bliss_wneighbor_scratch_bytes.argtypes = [_I32, _I32, _I64]
+    lib.bliss_wneighbor_scratch_bytes.restype = C.c_int64
     lib.bliss_labor_scratch_bytes.argtypes = [_I32, _I32]
     lib.bliss_labor_scratch_bytes.restype = C.c_int64
     lib.bliss_labor_is_scratch_bytes.argtypes = [_I32, _I32, _I32]

@@ -23,6 +23,7 @@
 #include "common.cuh"
 #include "bliss_gnn.h"
 #include "prof.h"
+#include "edge_q.cuh"                // edge_q / edge_q_pre: q_ij with the reference's bf16 roundings (shared with neighbor_w.hip)
 #include <cstdlib>
 
 #ifndef TPB
@@ -72,23 +73,6 @@ __device__ __forceinline__ int chunk_wave_offset(int wave_total, int* sh4, int* 
   for (int w = 0; w < TPB / 64; ++w) { const int v = sh4[w]; tot += v; if (w < wave) off += v; }
   *chunk_total = tot;
   return off;
-}
-
-// q_ij = eta/n_i + (1-eta) * w_ij / sum_j w_ij        bandit_sampler.py:131-137
-__device__ __forceinline__ bf16_t edge_q(bf16_t w, bf16_t wsum, int n, float eta_f, float ome_f) {
-  float wd = rbf(bf2f(w) / bf2f(wsum));     // :131 e_div_v
-  // :137 (self.eta / n_i).bfloat16(): Python `scalar / tensor` is Tensor.__rtruediv__ = reciprocal() * scalar,
-  // i.e. TWO fp32 roundings on the int32 -> fp32 degree, then one to bf16
-  float a = rbf((1.0f / (float)n) * eta_f);
-  float b = rbf(ome_f * wd);                // :137 (1 - self.eta) * exp_weights_divided
-  return f2bf(a + b);                       // :137 v_add_e
-}
-
-// the same with the per-seed part a = rbf((1/n) * eta) taken from k_col_sums' per-seed record
-__device__ __forceinline__ bf16_t edge_q_pre(bf16_t w, bf16_t wsum, float a, float ome_f) {
-  float wd = rbf(bf2f(w) / bf2f(wsum));
-  float b = rbf(ome_f * wd);
-  return f2bf(a + b);
 }
 
 // ---------------------------------------------------------------- K_a: seed columns -> seg_ptr

@@ -4,7 +4,10 @@ pytorch_lightning, reduced to plain loops -- Lightning / torchmetrics / tensorbo
   * ``MultiLayerFullNeighborSampler`` / ``NeighborSampler``: the two non-LADIES ``--sampler`` choices
     (train_lightning.py:349-357).  (With them the reference's models fail at ``block.edata["edge_weights"]``,
     model.py:321-329 -- DGL's own samplers attach no such field -- so they are baselines here, with unit weights.)
-    ``NeighborSampler(..., draw="device")``: the keyed per-column draw of csrc/neighbor.hip, graph-capturable.
+    ``NeighborSampler(..., draw="device")``: the keyed per-column draw of csrc/neighbor.hip, graph-capturable (DESIGN.md section 13);
+    with ``prob=`` the weighted draw of csrc/neighbor_w.hip.
+  * ``BanditNeighborSampler``: the node-wise bandit sampler (GCN-BS) -- that weighted draw over the EXP3 edge probabilities, with
+    ``BanditLadiesSampler``'s state and reward update.
   * ``LaborSampler``: LABOR-0, the node-wise baseline with one random variate per SOURCE vertex shared by all seeds of a layer
     (csrc/labor.hip) -- the sampler the reference's training script was derived from and dropped.
     ``ImportanceLaborSampler``: LABOR-i, the same draw after i fixed-point iterations over per-vertex importances
@@ -22,7 +25,7 @@ import os
 import torch
 
 from ._engine import LayerEngine
-from .bandit_sampler import BlockSampler, DeviceDraw
+from .bandit_sampler import BanditLadiesSampler, BlockSampler, DeviceDraw
 from .graph import NID, Block, as_graph
 from .ladies_sampler import PoissonLadiesSampler
 from .train import BatchLoader, GraphedEvalStep, TrainStep, _inputs
@@ -63,13 +66,21 @@ class NeighborSampler(DeviceDraw, BlockSampler):
     its column), its own torch generator, one host read per layer.  ``draw="device"``: the keyed per-column draw of
     csrc/neighbor.hip -- a function of (seed, draw step, layer, CSC position), no host round trip, so
     ``sample_blocks_static`` exists and the sampler runs inside a captured train step; ``seed`` starts its draw state
-    (``reset_draw`` / ``draw_step`` as for the multinomial samplers) and no torch generator is touched."""
+    (``reset_draw`` / ``draw_step`` as for the multinomial samplers) and no torch generator is touched.
+
+    ``prob`` (DGL's keyword; ``draw="device"`` only, the host draw raises): unnormalised edge probabilities, a tensor [|E|] by EDGE ID
+    or the name of an entry of ``g.edata``, converted to bf16 by CSC position once per graph.  The draw is then the weighted one of
+    csrc/neighbor_w.hip (a keyed exponential race per column, an edge with probability <= 0 taken only as
+    a filler); ``edge_weights`` carry the Hajek weights under the mean aggregation and ``edata["q_ij"]`` the probabilities."""
 
     _poisson = False                                       # (DeviceDraw's Poisson / replace checks have no subject here)
 
-    def __init__(self, fanouts, seed=0, *, draw="host", **_ignored):
+    def __init__(self, fanouts, seed=0, *, draw="host", prob=None, **_ignored):
         super().__init__()
         self._init_draw(draw, False)
+        if prob is not None and draw != "device":
+            raise NotImplementedError("NeighborSampler: edge probabilities (prob=) need draw='device'; the host draw is uniform")
+        self.prob, self._prob_pos = prob, None
         self._draw_init = (seed, 0)
         self.fanouts, self.nodes_per_layer = list(fanouts), list(fanouts)
         self._seed, self._gen = seed, None
@@ -83,10 +94,24 @@ class NeighborSampler(DeviceDraw, BlockSampler):
             self._engine.exact_b = True
         return self._engine
 
+    def _nb_prob(self, eng):
+        """The engine's probability record of the weighted draw (None without ``prob``); bf16 by position, once per graph."""
+        if self.prob is None:
+            return None
+        g = eng.g
+        if self._prob_pos is None or self._prob_pos[0] is not g:
+            p = g.edata[self.prob] if isinstance(self.prob, str) else torch.as_tensor(self.prob)
+            if p.dim() != 1 or p.numel() != g.num_edges():
+                raise ValueError("NeighborSampler: prob must hold one value per edge, by edge id")
+            self._prob_pos = (g, g.by_position(p.to(g.device).to(torch.bfloat16)).contiguous())
+        return eng.neighbor_prob(self._prob_pos[1])
+
     def _blocks(self, blks, seed_nodes):
         blocks = []
         for blk in blks:                                   # sampling order -> input-most first
             blk.edata["edge_weights"] = blk._edge_weights
+            if self.prob is not None:
+                blk.edata["q_ij"] = blk._q
             blocks.insert(0, blk)
         return blocks[0].srcdata[NID], seed_nodes, blocks
 
@@ -98,7 +123,7 @@ class NeighborSampler(DeviceDraw, BlockSampler):
         eng = self._bind(g)
         fan = list(reversed(self.fanouts))
         return self._blocks(eng.enqueue_static(None, seed_nodes, fan, 0, 0.0, slot=slot, draw_state=self._draw_state_on(eng.g.device),
-                                               neighbor=True, **split), seed_nodes)
+                                               neighbor=True, nb_prob=self._nb_prob(eng), **split), seed_nodes)
 
     def finish_static(self, slot=0, commit=True):
         return self._engine.finish(slot, commit)
@@ -109,7 +134,9 @@ class NeighborSampler(DeviceDraw, BlockSampler):
     def sample_blocks(self, g, seed_nodes, exclude_eids=None):
         g = as_graph(g, self.__dict__.setdefault("_graphs", {}))
         if self.draw == "device":
-            blks = self._bind(g).sample_blocks_neighbor(seed_nodes, list(reversed(self.fanouts)), self._draw_state_on(g.device))
+            eng = self._bind(g)
+            blks = eng.sample_blocks_neighbor(seed_nodes, list(reversed(self.fanouts)), self._draw_state_on(g.device),
+                                              nb_prob=self._nb_prob(eng))
             return self._blocks(blks, seed_nodes)
         dev = g.device
         if self._gen is None:
@@ -144,6 +171,59 @@ class NeighborSampler(DeviceDraw, BlockSampler):
             blocks.insert(0, blk)
             seeds = src_nid
         return blocks[0].srcdata[NID], seed_nodes, blocks
+
+
+class BanditNeighborSampler(BanditLadiesSampler):
+    """The node-wise bandit sampler (Liu et al., "Bandit Samplers for Training GNNs", GCN-BS; BLISS is its layer-wise extension): up
+    to ``fanout`` in-neighbours per destination, drawn without replacement with the EXP3 edge probabilities q_ij = eta / n_i +
+    (1 - eta) * w_ij / sum_j w_ij -- the weighted draw of csrc/neighbor_w.hip in EXP3 mode, layer ``b``'s row
+    of the EXP3 weights for block ``b``.  No parity claim: a defined mode restated by tests/wneighbor_ref.py.
+
+    The EXP3 state (``exp3_weights`` [L, |E|] by edge id, exact row sums), ``exp3(mfgs, g)`` (also ``model="gat"``) and
+    ``check_errors`` are ``BanditLadiesSampler``'s; blocks carry ``edge_weights`` (Hajek weights under the mean aggregation),
+    ``q_ij`` and ``node_prob`` = 1.  Always ``draw="device"``: ``reset_draw`` / ``draw_step`` / ``sample_blocks_static`` /
+    ``finish_static`` as ``NeighborSampler(draw="device")`` has them, it runs inside a captured train step, and the pipelined
+    two-stream loop refuses it."""
+
+    def __init__(self, fanouts, eta=0.4, num_steps=5000, model="sage", seed=0, **_ignored):
+        super().__init__(list(fanouts), eta=eta, num_steps=num_steps, model=model, draw="device")
+        self.fanouts = list(fanouts)
+        self._draw_init = (seed, 0)
+
+    def _bind(self, g):
+        g = self._graph(g)
+        if self._engine is None or self._engine.g is not g:
+            self._engine = LayerEngine(g)
+            self._engine.exact_b = True                     # (a column keeps at most fanout edges, as the uniform draw)
+        return self._engine
+
+    def _sample(self, g, seed_nodes, static, **kw):
+        g = self._graph(g)
+        eng = self._bind(g)
+        self._ensure_weights(g)
+        order = list(reversed(range(len(self.fanouts))))   # sampling order: the last block first
+        fan = [self.fanouts[b] for b in order]
+        prob = eng.neighbor_prob([self._w_pos[b] for b in order], eta=self.eta)
+        ds = self._draw_state_on(g.device)
+        if static:
+            blks = eng.enqueue_static(None, seed_nodes, fan, 0, 0.0, draw_state=ds, neighbor=True, nb_prob=prob, **kw)
+        else:
+            blks = eng.sample_blocks_neighbor(seed_nodes, fan, ds, nb_prob=prob)
+        blocks = []
+        for blk in blks:
+            blk.edata[self.output_weight] = blk._edge_weights
+            blk.edata["q_ij"] = blk._q
+            blk.srcdata[self.node_prob] = blk._node_prob
+            blocks.insert(0, blk)
+        return blocks[0].srcdata[NID], seed_nodes, blocks
+
+    def sample_blocks(self, g, seed_nodes, exclude_eids=None):
+        return self._sample(g, seed_nodes, False)
+
+    def sample_blocks_static(self, g, seed_nodes, slot=0, **split):
+        """sample_blocks with capacity-padded blocks, only ENQUEUED; whole calls only: any split / external-generator keyword
+        raises."""
+        return self._sample(g, seed_nodes, True, slot=slot, **split)
 
 
 class LaborSampler(NeighborSampler):
@@ -231,12 +311,14 @@ def make_sampler(name, fanouts, importance_sampling=1, num_steps=5000, eta=0.1, 
     """The sampler-name dispatch of DataModule.__init__ (train_lightning.py:348-370).  ``draw``: where the two multinomial
     samplers ("ladies", "bandit") and "neighbor" draw -- "host" (torch.multinomial / torch tensor ops) or "device" (the keyed
     draws, graph-capturable).  "labor" and "labor-<i>" (i in 1 .. 8: ``ImportanceLaborSampler`` with i iterations) always draw on
-    the device."""
+    the device.  "neighbor-exp3": ``BanditNeighborSampler`` (EXP3-weighted node-wise draw, always on the device)."""
     from . import BanditLadiesSampler, LadiesSampler, PoissonBanditLadiesSampler, PoissonLadiesSampler as PLS
     if name == "full":
         return MultiLayerFullNeighborSampler(len(fanouts))
     if name == "neighbor":
         return NeighborSampler(fanouts, draw=draw)
+    if name == "neighbor-exp3":                             # the node-wise bandit sampler; always the device draw
+        return BanditNeighborSampler(fanouts, eta=eta, num_steps=num_steps, model=model)
     if name == "labor":
         return LaborSampler(fanouts)                        # (LABOR-0; always the device draw)
     if name.startswith("labor-"):                           # "labor-1" .. "labor-8": LABOR-i

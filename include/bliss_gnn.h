@@ -219,6 +219,40 @@ int bliss_neighbor_layer(const bliss_graph_t* g, const int32_t* seeds, int32_t n
                          int32_t fanout, const uint32_t* keys_override, uint64_t seed, int64_t* step_dev, int32_t layer,
                          int bump_step, const bliss_layer_ws_t* ws, const bliss_block_out_t* out, void* scratch, void* stream);
 
+/* bliss_neighbor_layer with edge probabilities: a WEIGHTED draw without replacement per seed column (fit.NeighborSampler(draw="device",
+ * prob=...) and fit.BanditNeighborSampler; a defined-mode keyed exponential race, restated on the CPU by tests/wneighbor_ref.py;
+ * DESIGN.md section 17).
+ *   q_pos   = prob_pos[pos] (mode BLISS_WN_RAW: bf16 [num_edges] by CSC position, unnormalised, used as given), or
+ *             eta / n_i + (1 - eta) * w_pos / sum_col(w) (mode BLISS_WN_EXP3: prob_pos = the EXP3 row w by CSC position; the
+ *             roundings of bliss_frontier_prob's q_ij -- the column sum exact, rounded once to bf16, (1 / n_i) * eta and the product
+ *             each rounded to bf16 -- with eta and one_minus_eta the fp32 values of eta and 1 - eta)
+ *   u_pos   = ((key(pos) >> 8) + 1) * 2^-24 with bliss_neighbor_layer's key(pos); in (0, 1], exact in fp32
+ *   key_pos = (float)(-log((double)u_pos) / (double)q_pos), the sign of zero dropped; +inf unless q_pos > 0 (a NaN q gives +inf);
+ *             keys_override[pos] when keys_override != NULL (uint32 [num_edges]: fp32 bit patterns by CSC position)
+ *   seed column s, CSC positions [a, b), d = b - a:  k = d if fanout < 0 or d <= fanout (a WHOLE column: no key is computed), else
+ *             k = fanout and kept = the k smallest pairs (bits of key_pos, pos): an edge with q <= 0 is taken only as a filler
+ *   block, sources, counts record {S, E, C = K, K, B, err}, capacity padding, clamps, BLISS_ERR_CAP_* bits, ws->kept_map, bump_step
+ *             (here the last workgroup of the key kernel): bliss_neighbor_layer's.
+ *   q_ij = q_pos for every kept edge, whole columns included; edge_weights = the Hajek weight under the mean aggregation,
+ *             W_e = (1 / q_e) * k_s / sum_{kept e' of column s} (1 / q_e') from the bf16 q in fp64 (the sum in a fixed order, so a
+ *             replay is bit-equal), rounded once to bf16; exactly 1 in a whole column and in a column that keeps an edge whose q is
+ *             not a positive finite number; node_prob = 1.  EXP3 mode: a non-finite weight raises BLISS_ERR_NONFINITE.
+ * keys_out (optional, a test hook: NULL in every product path): uint32 [num_edges]; the key bits of every position of a non-whole
+ * seed column are stored there.  scratch: bliss_wneighbor_scratch_bytes(num_nodes, cap_s, num_edges) bytes, 16-byte aligned,
+ * zero-initialised ONCE: bliss_neighbor_layer's words (tickets and bitmap left zero by every call, also a replayed one, one that
+ * flagged an overflow and one with a seed id out of range; one offset per 1024 bitmap words), then cap_s per-seed records and
+ * num_edges staged keys, rewritten by every call before they are read.  Eight launches, no host round trip.
+ * BLISS_EINVAL before any launch: the set bliss_neighbor_layer refuses, prob_pos NULL or not 2-byte aligned, a mode other than the
+ * two, keys_override / keys_out not 4-byte aligned, eta or one_minus_eta negative or NaN in EXP3 mode; the scratch size also
+ * num_edges < 0 or > INT32_MAX. */
+#define BLISS_WN_RAW 0
+#define BLISS_WN_EXP3 1
+int64_t bliss_wneighbor_scratch_bytes(int32_t num_nodes, int32_t cap_s, int64_t num_edges);
+int bliss_wneighbor_layer(const bliss_graph_t* g, const int32_t* seeds, int32_t n_seeds, const int32_t* n_seeds_dev, int32_t cap_s,
+                          int32_t fanout, const uint32_t* keys_override, uint64_t seed, int64_t* step_dev, int32_t layer,
+                          int bump_step, int32_t mode, const void* prob_pos, float eta, float one_minus_eta, uint32_t* keys_out,
+                          const bliss_layer_ws_t* ws, const bliss_block_out_t* out, void* scratch, void* stream);
+
 /* dgl.dataloading.LaborSampler(fanouts, importance_sampling=0) ON THE DEVICE, one layer (fit.LaborSampler; LABOR-0: a defined-mode
  * keyed draw like bliss_neighbor_layer with the key on the edge's SOURCE NODE and a per-column threshold instead of a per-column
  * select, restated on the CPU by tests/labor_ref.py).  Integers only:
