@@ -122,6 +122,49 @@ class AdamTensors(C.Structure):                        # bliss_adam_t
                 ("numel", C.c_int64 * ADAM_MAX_TENSORS), ("count", C.c_int32)]
 
 
+LEDGER_MAX_LAYERS = 8                                  # BLISS_LEDGER_MAX_LAYERS
+LEDGER_STEP, LEDGER_RESET_EPOCH, LEDGER_REARM = 0, 1, 2
+LEDGER_LOSS_BF16, LEDGER_LOSS_F32 = 0, 1
+_LEDGER_STRUCTS = {}
+
+
+def ledger_struct(n_layers):
+    """The step ledger's record for ``n_layers`` layers (include/bliss_gnn.h, csrc/ledger.hip) as a ctypes.Structure class."""
+    L = int(n_layers)
+    if not 1 <= L <= LEDGER_MAX_LAYERS:
+        raise ValueError("the step ledger holds 1 .. %d layers, not %r" % (LEDGER_MAX_LAYERS, n_layers))
+    if L not in _LEDGER_STRUCTS:
+        pad = (-12 * L) % 8
+        fields = [("steps_epoch", C.c_uint64), ("steps_total", C.c_uint64), ("loss_last", C.c_double), ("loss_sum", C.c_double),
+                  ("nonfinite", C.c_uint64), ("cum_out", C.c_double), ("first_bad_step", C.c_int64), ("first_near_step", C.c_int64),
+                  ("err", C.c_int32), ("near", C.c_int32), ("n_layers", C.c_int32), ("reserved", C.c_int32),
+                  ("cum_nodes", C.c_double * L), ("cum_edges", C.c_double * L),
+                  ("hw_K", C.c_int32 * L), ("hw_B", C.c_int32 * L), ("hw_E", C.c_int32 * L)]
+        if pad:
+            fields.append(("pad", C.c_int32 * (pad // 4)))
+        _LEDGER_STRUCTS[L] = type("StepLedger%d" % L, (C.Structure,), {"_fields_": fields})
+    return _LEDGER_STRUCTS[L]
+
+
+def ledger_new(n_layers):
+    """A fresh record: all zero except first_bad_step = first_near_step = -1 (and n_layers)."""
+    rec = ledger_struct(n_layers)()
+    rec.first_bad_step = rec.first_near_step = -1
+    rec.n_layers = int(n_layers)
+    return rec
+
+
+def ledger_dict(rec):
+    """A record as a plain dict (arrays as lists, the padding left out)."""
+    out = {}
+    for name, _ in rec._fields_:
+        if name in ("pad", "reserved"):
+            continue
+        v = getattr(rec, name)
+        out[name] = list(v) if hasattr(v, "__len__") else v
+    return out
+
+
 class BlockOut(C.Structure):
     _fields_ = [("indptr", C.c_void_p), ("src", C.c_void_p), ("dst", C.c_void_p), ("pos", C.c_void_p),
                 ("eid", C.c_void_p), ("edge_weights", C.c_void_p), ("q_ij", C.c_void_p), ("t_indptr", C.c_void_p),
@@ -170,6 +213,8 @@ SIGNATURES = {
     "bliss_f1_multiclass": [_P, _I64, _I32, _P, _P, _P, _I32, _P, _I32, _P, _I32, _P, _P, _P],
     "bliss_f1_multilabel": [_P, _I64, _I32, _P, _P, _P, _I32, _P, _I32, _P, _I32, _P, _P, _P],
     "bliss_adam_step": [C.POINTER(AdamTensors), _P, _F, _F, _F, _F, _P],
+    "bliss_step_ledger_bytes": [C.c_int],
+    "bliss_step_ledger": [C.c_int, _P, C.c_int, _P, C.c_int, C.POINTER(C.c_int32), _D, _D, _P, _P],
     "bliss_cand_importance": [_P, _I32, C.c_int, _P, _P, _P],
     "bliss_poisson_scale": [_P, _P, _I32, _D, _P, _P],
     "bliss_keyed_select": [_P, _P, _P, _I32, _P, C.c_uint64, C.c_uint64, _I32, _P, _P, _P],
@@ -260,6 +305,8 @@ def _load():
     lib.bliss_prof_kernel_name.argtypes = [C.c_int]
     lib.bliss_prof_kernel_name.restype = C.c_char_p
     assert lib.bliss_layer_counts_bytes() == C.sizeof(LayerCounts), "LayerCounts layout mismatch"
+    assert all(lib.bliss_step_ledger_bytes(n) == C.sizeof(ledger_struct(n)) for n in range(1, LEDGER_MAX_LAYERS + 1)), \
+        "step ledger layout mismatch"
     return lib
 
 

@@ -24,11 +24,12 @@ import os
 
 import torch
 
+from . import _lib
 from ._engine import LayerEngine
 from .bandit_sampler import BanditLadiesSampler, BlockSampler, DeviceDraw
 from .graph import NID, Block, as_graph
 from .ladies_sampler import PoissonLadiesSampler
-from .train import BatchLoader, GraphedEvalStep, TrainStep, _inputs
+from .train import BatchLoader, GraphedEvalStep, GraphedTrainStep, TrainStep, _inputs, _keep_static_caps, _rng_kept
 
 
 # ----------------------------------------------------------------------------------------------- baseline samplers
@@ -459,14 +460,22 @@ def evaluate(g, sampler, model, ids, batch_size, multilabel=False, loss_fn=None,
 
 def fit(g, sampler, model, train_nid, val_nid, test_nid=None, batch_size=1024, lr=0.002, max_epochs=10, max_steps=None,
         multilabel=False, val_acc_target=1.0, early_stopping_patience=1000, checkpoint_path=None, seed=0, log=None,
-        eval_step="eager", train_metric=False):
+        eval_step="eager", train_metric=False, train_step="eager"):
     """One run of ``trainer.fit`` + the final evaluation (train_lightning.py:640-705).  Returns a dict of metrics.
     ``eval_step``: "eager" (``evaluate`` as it stands) or "graphed" (one train.GraphedEvalStep serves every epoch's validation;
     the sampler needs a static-shape path).  ``train_metric``: keep train_acc (:143) on the device beside every step and add it,
-    reset per epoch, to the history entries."""
+    reset per epoch, to the history entries.  ``train_step``: "eager" (TrainStep, a loss read back per step) or "graphed" (the
+    epoch's steps replayed from one captured train.GraphedTrainStep whose ledger keeps the epoch's statistics on the device,
+    DESIGN.md section 18: the same batches, random streams and bits; the sampler needs a static-shape path and the model the
+    one-launch Adam); its history entries also carry ``sampled_nodes`` / ``sampled_edges``."""
     if eval_step not in ("eager", "graphed"):
         raise ValueError("eval_step must be 'eager' or 'graphed', not %r" % (eval_step,))
+    if train_step not in ("eager", "graphed"):
+        raise ValueError("train_step must be 'eager' or 'graphed', not %r" % (train_step,))
     g = as_graph(g)
+    if train_step == "graphed":
+        return _fit_graphed(g, sampler, model, train_nid, val_nid, test_nid, batch_size, lr, max_epochs, max_steps, multilabel,
+                            val_acc_target, early_stopping_patience, checkpoint_path, seed, log, eval_step, train_metric)
     step = TrainStep(g, sampler, model, lr=lr, multilabel=multilabel, train_metric=train_metric)
     ev = GraphedEvalStep(g, sampler, model, batch_size, multilabel, loss_fn=step.loss_fn) if eval_step == "graphed" else None
     sched, stopper, ckpt = StepLR(step.opt, 5, 0.01), EarlyStopping(val_acc_target, early_stopping_patience), ModelCheckpoint(checkpoint_path)
@@ -493,6 +502,12 @@ def fit(g, sampler, model, train_nid, val_nid, test_nid=None, batch_size=1024, l
             break
     if ev is not None:
         ev.close()
+    return dict(history=history, best_val_acc=ckpt.best, steps=n_steps, final=_final_metrics(g, model, ckpt, train_nid, val_nid, test_nid,
+                                                                                             multilabel))
+
+
+def _final_metrics(g, model, ckpt, train_nid, val_nid, test_nid, multilabel):
+    """The best checkpoint reloaded, then the Final Accuracy of the three splits (train_lightning.py:662-705)."""
     ckpt.restore(model)                                                          # the best val_acc checkpoint (:662-685)
     final = {}
     if hasattr(model, "inference") and "features" in g.ndata:
@@ -500,7 +515,69 @@ def fit(g, sampler, model, train_nid, val_nid, test_nid=None, batch_size=1024, l
         for name, nid in (("Train", train_nid), ("Validation", val_nid), ("Test", test_nid)):
             if nid is not None and nid.numel():
                 final[name] = _split_f1(pred, g.ndata["labels"], nid, multilabel)                            # :694-705
-    return dict(history=history, best_val_acc=ckpt.best, steps=n_steps, final=final)
+    return final
+
+
+def _fit_graphed(g, sampler, model, train_nid, val_nid, test_nid, batch_size, lr, max_epochs, max_steps, multilabel, val_acc_target,
+                 early_stopping_patience, checkpoint_path, seed, log, eval_step, train_metric):
+    """``fit`` with the epoch's steps replayed from one captured train step (train.GraphedTrainStep with its ledger): the same
+    protocol, batches, random streams and bits as the eager loop; the host reads one ledger record per epoch."""
+    static = hasattr(sampler, "sample_blocks_static") and (getattr(sampler, "_poisson", False) or getattr(sampler, "draw", "host") == "device")
+    if not static:
+        raise NotImplementedError("fit(train_step='graphed') needs a sampler with a static-shape path; %s%s has none (the Poisson "
+                                  "samplers have one, and the samplers that draw on the device: draw='device', labor, neighbor-exp3)"
+                                  % (type(sampler).__name__, " with draw='host'" if hasattr(sampler, "draw") else ""))
+    from .optim import Adam
+    step = GraphedTrainStep(g, sampler, model, batch_size, lr=lr, multilabel=multilabel, train_metric=train_metric, ledger=True)
+    if not isinstance(step.opt, Adam):
+        raise TypeError("fit(train_step='graphed') needs the one-launch Adam of bliss_gnn_amd.optim (contiguous bf16 parameters on the "
+                        "GPU, at most %d tensors): a replayed step runs no Python, so the learning rate StepLR rewrites must live on "
+                        "the device; this model's parameters get %s" % (_lib.ADAM_MAX_TENSORS, type(step.opt).__name__))
+    ev = GraphedEvalStep(g, sampler, model, batch_size, multilabel, loss_fn=step.loss_fn) if eval_step == "graphed" else None
+    sched, stopper, ckpt = StepLR(step.opt, 5, 0.01), EarlyStopping(val_acc_target, early_stopping_patience), ModelCheckpoint(checkpoint_path)
+    loader = BatchLoader(train_nid, batch_size, shuffle=True, drop_last=True, seed=seed)
+    L = len(sampler.nodes_per_layer)
+    history, n_steps = [], 0
+    try:
+        model.train()
+        # capacities from a second loader with the same ids and seed, leaving torch's generator and the draw step where they
+        # were: the epoch's batches and the sampler's random stream stay those of the eager loop
+        with _rng_kept(sampler, g):
+            step.calibrate(BatchLoader(train_nid, batch_size, shuffle=True, drop_last=True, seed=seed).forever())
+        eng = sampler._engine
+        for epoch in range(max_epochs):
+            model.train()
+            n = len(loader) if max_steps is None else min(len(loader), max_steps - n_steps)
+            step.run(iter(loader), n)                                            # (the first one captures: its steps are epoch 0's)
+            n_steps += n
+            rec = step.ledger()                                                  # THE read-back of the epoch
+            step.reset_epoch()
+            if ev is not None:
+                val_acc, val_loss = evaluate(g, sampler, model, val_nid, batch_size, multilabel, step.loss_fn, step=ev)
+            else:
+                with _keep_static_caps(eng):                                     # (eager sampling beside the captured train graph)
+                    val_acc, val_loss = evaluate(g, sampler, model, val_nid, batch_size, multilabel, step.loss_fn)
+            ckpt.update(val_acc, model, epoch)
+            history.append(dict(epoch=epoch, train_loss=rec["loss_sum"] / max(rec["steps_epoch"], 1), val_acc=val_acc, val_loss=val_loss,
+                                lr=step.opt.param_groups[0]["lr"]))
+            if train_metric:
+                history[-1]["train_acc"] = step.train_acc.compute()             # (one read-back per epoch)
+                step.train_acc.reset()
+                step.train_acc.check_errors()
+            history[-1]["sampled_nodes"] = [step.num_sampled_nodes(i, rec) for i in range(L + 1)]
+            history[-1]["sampled_edges"] = [step.num_sampled_edges(i, rec) for i in range(L)]
+            if log:
+                log(history[-1])
+            sched.step()                                                         # per epoch (:205-216)
+            step.opt.sync_lr()                                                   # a replay runs no Python: the new rate goes to the device here
+            if stopper.should_stop(val_acc) or (max_steps is not None and n_steps >= max_steps):
+                break
+    finally:
+        if ev is not None:
+            ev.close()
+        step.close()
+    return dict(history=history, best_val_acc=ckpt.best, steps=n_steps, final=_final_metrics(g, model, ckpt, train_nid, val_nid, test_nid,
+                                                                                             multilabel))
 
 
 def k_runs(run_fn, k):

@@ -11,6 +11,7 @@ replays, in order, exactly what they do to the sampler and the model each step
     sampler.exp3(mfgs, g)                                                      BatchSizeCallback :469-471
 """
 import contextlib
+import ctypes as C
 import os
 import time
 
@@ -206,9 +207,16 @@ class GraphedTrainStep:
     blocks are padded to capacities learned from a few eager steps (``calibrate``); true sizes stay on the device
     and come back with the step's single end-of-step sync.  Results are bit-identical to the eager path."""
 
-    def __init__(self, g, sampler, model, batch_size, lr=0.002, multilabel=False, distributed=False, train_metric=False):
+    def __init__(self, g, sampler, model, batch_size, lr=0.002, multilabel=False, distributed=False, train_metric=False, ledger=False):
         self.g, self.sampler, self.model, self.bs = g, sampler, model, int(batch_size)
         self.distributed = distributed          # replicas: gradient all-reduce + EXP3 exchange recorded in the graph too
+        # ledger: one more launch at the end of the step (csrc/ledger.hip) folds it into a device-resident record -- what ``run``
+        # needs to leave the host out of the loop; False: the step and its graph are exactly the ones without it
+        self._ledger_on, self._ledger, self.w = bool(ledger), None, 0.99
+        self.regrows, self._want_regrow, self._ledger_regrow_at = 0, False, None
+        if self._ledger_on:
+            rec = _lib.ledger_new(len(sampler.nodes_per_layer))
+            self._ledger = torch.frombuffer(bytearray(bytes(rec)), dtype=torch.int64).to(g.device)
         self.loss_fn = _bce_loss() if multilabel else _ce_loss()
         # train_acc: one more launch inside the captured graph (metrics.MicroF1: counts stay on the device); None unless asked
         # for, and the graph is then exactly the one without it
@@ -261,7 +269,10 @@ class GraphedTrainStep:
             if bandit:
                 self.sampler.exp3(mfgs, self.g)
         # detach: a live autograd graph would pin the warm-up stream's AccumulateGrad nodes into the capture
-        return loss.detach()
+        loss = loss.detach()
+        if self._ledger_on:
+            self._ledger_step(loss)
+        return loss
 
     def _finish(self):
         torch.cuda.current_stream().synchronize()
@@ -287,12 +298,16 @@ class GraphedTrainStep:
         torch.cuda.current_stream().wait_stream(side)
         if tune_gemm:
             torch.cuda.tunable.tuning_enable(False)        # keep using the tuned solutions, stop measuring
+        self._capture_graph(loader)
+
+    def _capture_graph(self, loader):
+        """Record the step on the next batch of ``loader`` and replay it once: that batch is a real step."""
         self.loss = None
         import gc
         gc.collect()
         torch.cuda.synchronize()
         self.seeds.copy_(next(loader))
-        eng.stage_rng_from_torch()
+        self.sampler._engine.stage_rng_from_torch()
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph, **_cap_kw()):
             self.loss = self._body()
@@ -314,6 +329,212 @@ class GraphedTrainStep:
         loss = self._body()
         self._finish()
         return loss
+
+    # -- the step ledger (ledger=True): epoch statistics on the device, a loop without the host ---------------------------
+    # Capacities come from a few steps taken while a bandit sampler's weights are uniform; the kept sets drift as they move.  A
+    # step over a capacity is clamped and flagged only afterwards (its update is invalid), so the ledger raises ``near`` once a
+    # size passes ``regrow_at`` of its capacity and ``run`` acts BEFORE the overflow: it finishes what is enqueued, re-fixes the
+    # capacities from the high-water marks, re-captures and carries on.
+    regrow_at = 0.85
+    capture_warmup = 3                                   # warm-up steps of the capture ``run`` makes when there is no graph yet
+
+    def _n_layers(self):
+        return len(self.sampler.nodes_per_layer)
+
+    def _ledger_caps(self):
+        """{cap_K, cap_B, cap_E} per layer (sampling order) for the ledger's early warning.  A dimension whose capacity is an
+        exact bound (the engine's ``exact_k`` / ``exact_b``) cannot overflow: it is passed as INT32_MAX and never raises ``near``."""
+        eng, L, big = self.sampler._engine, self._n_layers(), 2 ** 31 - 1
+        fan = [self.sampler.nodes_per_layer[b] for b in reversed(range(L))]
+        arr = (C.c_int32 * (3 * L))()
+        for n, c in enumerate(eng.caps):
+            arr[3 * n] = big if eng.exact_k else c["K"]
+            arr[3 * n + 1] = big if (eng.exact_b and int(fan[n]) >= 0) else c["B"]
+            arr[3 * n + 2] = c["E"]
+        return arr
+
+    def _ledger_step(self, loss):
+        if loss.numel() != 1 or loss.dtype not in (torch.bfloat16, torch.float32):
+            raise TypeError("the step ledger takes a bf16 or fp32 scalar loss, not %s %s" % (loss.dtype, tuple(loss.shape)))
+        code = _lib.LEDGER_LOSS_BF16 if loss.dtype == torch.bfloat16 else _lib.LEDGER_LOSS_F32
+        self._ledger_regrow_at = float(self.regrow_at)             # (a launch argument: fixed in a captured graph)
+        _lib.check(_lib.lib.bliss_step_ledger(_lib.LEDGER_STEP, loss.data_ptr(), code, self.sampler._engine._slot_counts[0].data_ptr(),
+                                              self._n_layers(), self._ledger_caps(), self.w, self._ledger_regrow_at,
+                                              self._ledger.data_ptr(), torch.cuda.current_stream().cuda_stream), "bliss_step_ledger")
+
+    def _ledger_mode(self, mode):
+        _lib.check(_lib.lib.bliss_step_ledger(mode, None, 0, None, self._n_layers(), None, 0.0, 0.0, self._ledger.data_ptr(),
+                                              torch.cuda.current_stream().cuda_stream), "bliss_step_ledger")
+
+    def _parse(self, buf):
+        """A host copy of the record (an int64 tensor) as a dict."""
+        return _lib.ledger_dict(_lib.ledger_struct(self._n_layers()).from_buffer_copy(buf.numpy().tobytes()))
+
+    def ledger(self):
+        """The record as a dict, behind everything enqueued on the current stream (one read-back)."""
+        if not self._ledger_on:
+            raise RuntimeError("this step keeps no ledger (ledger=True)")
+        return self._parse(self._ledger.cpu())
+
+    def reset_epoch(self):
+        """Enqueue the epoch reset: steps_epoch, loss_sum and nonfinite start again, everything else carries on."""
+        self._ledger_mode(_lib.LEDGER_RESET_EPOCH)
+
+    def num_sampled_edges(self, i, rec=None):
+        """TrainStep.num_sampled_edges (train_lightning.py:91-98) from the ledger (``rec``: a record read already)."""
+        rec = rec if rec is not None else self.ledger()
+        return rec["cum_edges"][self._n_layers() - 1 - i] * (1 - self.w) / (1 - self.w ** rec["steps_total"])
+
+    def num_sampled_nodes(self, i, rec=None):
+        """TrainStep.num_sampled_nodes (:82-89) from the ledger; ``i == n_layers``: the output nodes."""
+        rec = rec if rec is not None else self.ledger()
+        L = self._n_layers()
+        cum = rec["cum_out"] if i == L else rec["cum_nodes"][L - 1 - i]
+        return cum * (1 - self.w) / (1 - self.w ** rec["steps_total"])
+
+    def regrow(self):
+        """Have the next ``run`` re-fix the capacities from the ledger's high-water marks and re-capture before it goes on."""
+        self._want_regrow = True
+
+    def _ledger_error(self, rec, where=""):
+        bad = rec["err"]
+        return RuntimeError(f"static-shape step exceeded its capacities or hit a kernel error 0x{bad:x} ({_lib.err_string(bad)}) "
+                            f"at step {rec['first_bad_step']} of the ledger's count{where}; the results are invalid from that step "
+                            f"on -- raise the margins or lower regrow_at")
+
+    def _regrow_now(self, loader, refix=True):
+        """Finish what is enqueued, enlarge the capacities to the high-water marks (x the calibration margins), re-capture.  The
+        capture replays once: one real step on the next batch of ``loader``.  ``refix=False``: only the re-capture (a launch
+        argument of the recorded ledger launch changed, ``regrow_at``)."""
+        import gc
+        eng, L = self.sampler._engine, self._n_layers()
+        torch.cuda.current_stream().synchronize()
+        rec = self.ledger()
+        if rec["err"]:
+            raise self._ledger_error(rec)
+        self.graph, self.loss = None, None                 # quiesced above: drop the graph recorded for the old shapes
+        gc.collect()
+        torch.cuda.synchronize()
+        if refix:
+            mx = [dict(K=max(h.get("K", 0), rec["hw_K"][n]), B=max(h.get("B", 0), rec["hw_B"][n]), E=max(h.get("E", 0), rec["hw_E"][n]))
+                  for n, h in enumerate(self._hw)]
+            fan = [self.sampler.nodes_per_layer[b] for b in reversed(range(L))]
+            eng.set_static_caps(self.bs, fan, mx, *self._margins)
+            self._hw = mx
+            self._ledger_mode(_lib.LEDGER_REARM)
+            self._want_regrow = False
+            self.regrows += 1
+        self._capture_graph(loader)
+
+    def _check_errors_once(self):
+        """The error words nothing reads per step (one small read-back each, once per ``run``)."""
+        if hasattr(self.sampler, "check_errors"):
+            self.sampler.check_errors()
+        if hasattr(self.loss_fn, "check_errors"):
+            self.loss_fn.check_errors()                  # a label out of range trains silently otherwise
+        for m in self.model.modules():
+            if m is not self.model and hasattr(m, "check_errors"):
+                m.check_errors()                         # (GATv2Conv's fused kernels)
+
+    def run(self, loader, n_steps, poll=16, ring=8):
+        """``n_steps`` train steps on the next batches of ``loader`` (an iterator); returns nothing per step: the ledger has the
+        loss sum and the size averages, and ``sizes()`` / ``last_counts`` / the blocks' ``_counts`` describe the last step.
+
+        A sampler that draws on the device (``draw == "device"``) runs FREE: per step the host enqueues the seed copy and the
+        graph replay, nothing else.  Every ``poll`` steps it enqueues a non-blocking copy of the ledger into a ring of ``ring``
+        pinned buffers, each with an event, after looking at the copies that have landed (never the one just enqueued; a buffer
+        about to be reused is waited for, so the host stays at most ``ring`` polls ahead).  The stream is synchronised once, at
+        the end.  The Poisson samplers draw from torch's CPU generator, which the host stages per step and takes back after it:
+        they keep the per-step protocol (stage, replay, one sync, ``finish_static``) and use the ledger for everything else.
+
+        A record with an error word stops the enqueueing: the device finishes and RuntimeError names ``first_bad_step``.  A
+        record with ``near`` set (or ``regrow()``) makes the loop finish what is enqueued, re-fix the capacities, re-capture
+        (that replay is one of the ``n_steps``) and carry on: batches, their order, the draw step, torch's generator and the
+        number of optimiser steps are those of the plain loop.  Without a graph yet, the first ``capture_warmup`` + 1 steps
+        are the capture's (fewer steps than that run kernel by kernel)."""
+        if not self._ledger_on:
+            raise RuntimeError("run() needs the step ledger: GraphedTrainStep(..., ledger=True)")
+        if self.distributed:
+            raise NotImplementedError("run() is the single-process loop (every rank would have to take the same regrow decision)")
+        if getattr(self, "_hw", None) is None:
+            raise RuntimeError("calibrate() first: run() needs the static capacities")
+        # (a generation-2 garbage collection in the middle of the loop can take longer than the host's lead: not during the loop)
+        import gc
+        was_enabled = gc.isenabled()
+        if was_enabled:
+            gc.disable()
+        try:
+            self._run(loader, int(n_steps), max(int(poll), 1), max(int(ring), 1))
+        finally:
+            if was_enabled:
+                gc.enable()
+
+    def _run(self, loader, n_steps, poll, ring):
+        eng = self.sampler._engine
+        free = getattr(self.sampler, "draw", "host") == "device"
+        done = 0
+        if self.graph is None and n_steps > 0:
+            if n_steps < self.capture_warmup + 1:
+                for _ in range(n_steps):
+                    self.loss = self.eager_step(next(loader))
+                done = n_steps
+            else:
+                self.capture(loader, warmup=self.capture_warmup)
+                done = self.capture_warmup + 1
+        if getattr(self, "_ring", None) is None or len(self._ring) != ring:
+            self._ring = [torch.empty(self._ledger.numel(), dtype=torch.int64).pin_memory() for _ in range(ring)]
+            self._ring_ev = [torch.cuda.Event() for _ in range(ring)]
+        pending, polls, bad = [], 0, None                # ring slots in flight, oldest first
+        while done < n_steps:
+            if self._want_regrow or self._ledger_regrow_at != float(self.regrow_at):
+                pending.clear()                          # (copies from before the regrow carry the old warning)
+                self._regrow_now(loader, refix=self._want_regrow)
+                done += 1
+                continue
+            self.seeds.copy_(next(loader))
+            if free:
+                self.graph.replay()
+                self.num_steps += 1
+            else:
+                eng.stage_rng_from_torch()
+                self.graph.replay()
+                self._finish()
+            done += 1
+            if done % poll or done >= n_steps:
+                continue
+            slot, rec = polls % ring, None
+            while pending and (pending[0] == slot or self._ring_ev[pending[0]].query()):
+                i = pending.pop(0)
+                if not self._ring_ev[i].query():
+                    self._ring_ev[i].synchronize()       # the ring is full: the host is `ring` polls ahead of the device
+                rec = self._parse(self._ring[i])         # (err, near and the marks are cumulative: the newest record says it all)
+                if rec["err"]:
+                    break
+            if rec is not None and rec["err"]:
+                bad = rec                                # every later step builds on invalid blocks: stop enqueueing
+                break
+            if rec is not None and rec["near"]:
+                self._want_regrow = True
+                continue
+            self._ring[slot].copy_(self._ledger, non_blocking=True)
+            self._ring_ev[slot].record()
+            pending.append(slot)
+            polls += 1
+        torch.cuda.current_stream().synchronize()        # let the device finish: THE sync of a free-running run
+        rec = self.ledger()
+        if bad is not None and not rec["err"]:
+            rec = bad
+        if free and done:
+            try:
+                self.last_counts = self.sampler.finish_static()
+            except RuntimeError:
+                if not rec["err"]:
+                    raise
+        if rec["err"]:
+            raise self._ledger_error(rec, f" ({done} of this run's {n_steps} steps were enqueued)")
+        if rec["near"]:
+            self._want_regrow = True                     # seen too late for this run: the next one starts with the regrow
+        self._check_errors_once()
 
     def last_batch_counts(self):
         """(tp, fp, fn, n) added to ``train_acc`` since the previous call (one read-back): the last batch's, when called after
@@ -939,6 +1160,21 @@ def _keep_static_caps(eng):
                 setattr(eng, k, v)
 
 
+@contextlib.contextmanager
+def _rng_kept(sampler, g):
+    """Sampler calls that must leave no trace (a calibration beside a run): torch's CPU generator and the device draw step are
+    put back on leaving the block."""
+    state = torch.get_rng_state()
+    ds = sampler._draw_state_on(g.device) if hasattr(sampler, "_draw_state_on") else None
+    step = ds.step_dev.clone() if ds is not None else None
+    try:
+        yield
+    finally:
+        torch.set_rng_state(state)
+        if ds is not None:
+            ds.step_dev.copy_(step)
+
+
 class GraphedEvalStep:
     """validation_step over a split (train_lightning.py:179-203, :410-422) with every full batch REPLAYED from one HIP graph:
     ``sample_blocks_static`` on an output slot of its own, ``model.eval()`` forward under ``no_grad``, the loss, the micro-F1
@@ -990,18 +1226,8 @@ class GraphedEvalStep:
                              "with the train step that fixed them and needs its batch size" % (caps[0]["S"], self.bs))
         return True
 
-    @contextlib.contextmanager
     def _rng_kept(self):
-        """Sampler calls that must leave no trace: torch's CPU generator and the device draw step are put back."""
-        state = torch.get_rng_state()
-        ds = self.sampler._draw_state_on(self.g.device) if hasattr(self.sampler, "_draw_state_on") else None
-        step = ds.step_dev.clone() if ds is not None else None
-        try:
-            yield
-        finally:
-            torch.set_rng_state(state)
-            if ds is not None:
-                ds.step_dev.copy_(step)
+        return _rng_kept(self.sampler, self.g)
 
     def calibrate(self, loader, steps=8, k_margin=1.5, b_margin=3.0):
         """GraphedTrainStep.calibrate for a sampler no train step has fixed capacities for: eager sampling to learn per-layer

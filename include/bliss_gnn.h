@@ -572,6 +572,46 @@ typedef struct {
 } bliss_adam_t;
 int bliss_adam_step(const bliss_adam_t* tensors, float* state, float beta1, float beta2, float eps, float weight_decay, void* stream);
 
+/* Step ledger (csrc/ledger.hip): ONE launch of one 64-thread workgroup at the end of a train step folds the finished step into a
+ * device-resident record -- the epoch's loss sum, the reference's sampled-size averages (train_lightning.py:76-136), high-water
+ * marks, the OR of the sampler's error words and an early warning -- so that a loop of replayed steps needs no host read per step.
+ * Plain fixed-order arithmetic, no atomics, no flags; every pointer is fixed at launch and every value read is on the device, so
+ * the launch sits inside a captured graph.
+ *
+ * The record (8-byte aligned; L = n_layers; bliss_step_ledger_bytes(L) = 80 + 16 L + 8 ceil(12 L / 8) bytes):
+ *   offset  0  uint64 steps_epoch        16  double loss_last         32  uint64 nonfinite        48  int64 first_bad_step
+ *           8  uint64 steps_total        24  double loss_sum          40  double cum_out          56  int64 first_near_step
+ *          64  int32 err     68  int32 near     72  int32 n_layers (the caller's; not read)     76  int32 reserved
+ *          80  double cum_nodes[L], double cum_edges[L], int32 hw_K[L], int32 hw_B[L], int32 hw_E[L], zero padding to 8 bytes
+ * A fresh record is all zero except first_bad_step = first_near_step = -1 (and n_layers).  Layers are in SAMPLING order, the
+ * order of the counts record.
+ *
+ * The rule (normative; restated by tests/ledger_ref.py) -- mode BLISS_LEDGER_STEP, counts = bliss_layer_counts_t[L]:
+ *   loss_last = the loss widened exactly to fp64;  loss_sum += loss_last (one fp64 add);  nonfinite += 1 if it is not finite
+ *   cum_nodes[n] = cum_nodes[n] * w + (double)K_n;  cum_edges[n] = cum_edges[n] * w + (double)B_n;
+ *   cum_out = cum_out * w + (double)S_0            -- an fp64 product, then an fp64 sum, never fused
+ *   hw_K[n], hw_B[n], hw_E[n] = running maxima of K_n, B_n, E_n
+ *   e = OR of every layer's err word;  err |= e;  first_bad_step = steps_total (before its increment) at the first step with e != 0
+ *   near = 1 once any (double)K_n > regrow_at * (double)cap_K_n or (double)B_n > regrow_at * (double)cap_B_n;
+ *                                         first_near_step = steps_total (before its increment) at the first such step
+ *   steps_epoch += 1;  steps_total += 1
+ * mode BLISS_LEDGER_RESET_EPOCH: steps_epoch = 0, loss_sum = 0, nonfinite = 0, nothing else (only `ledger` is read).
+ * mode BLISS_LEDGER_REARM: near = 0, first_near_step = -1, nothing else (after the capacities were re-fixed).
+ *
+ * caps: HOST array int32 [3 L] = {cap_K, cap_B, cap_E} per layer, taken by value at the call (cap_E takes part in no comparison:
+ * E sizes launch grids only).  loss_dtype: BLISS_LEDGER_LOSS_BF16 / _F32, one scalar on the device.
+ * BLISS_EINVAL before any launch: ledger NULL; n_layers outside 1 .. BLISS_LEDGER_MAX_LAYERS; an unknown mode; in mode STEP loss,
+ * counts or caps NULL or an unknown loss_dtype.  bliss_step_ledger_bytes: BLISS_EINVAL for n_layers outside that range. */
+#define BLISS_LEDGER_MAX_LAYERS 8
+#define BLISS_LEDGER_STEP 0
+#define BLISS_LEDGER_RESET_EPOCH 1
+#define BLISS_LEDGER_REARM 2
+#define BLISS_LEDGER_LOSS_BF16 0
+#define BLISS_LEDGER_LOSS_F32 1
+int bliss_step_ledger_bytes(int n_layers);
+int bliss_step_ledger(int mode, const void* loss, int loss_dtype, const int32_t* counts, int n_layers, const int32_t* caps,
+                      double w, double regrow_at, void* ledger, void* stream);
+
 /* normalized_edata    bandit_sampler.py:20-27: w_pos[p] = bf16(1 / bf16(indeg(dst(p)))). */
 int bliss_normalized_edata(const bliss_graph_t* g, void* w_pos, void* stream);
 
