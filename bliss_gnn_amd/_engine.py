@@ -116,6 +116,8 @@ class LayerEngine:
         self._lb_scr = None                 # csrc/labor.hip: the same words + one kept count per seed column; (cap_s, tensor)
         self.labor_is = False               # LABOR layers run csrc/labor_is.hip also with 0 iterations (fit.ImportanceLaborSampler)
         self._li_scr = None                 # csrc/labor_is.hip: + two |V|-word importance buffers, scales, p_e; (cap_s, cap_b, tensor)
+        self._wl_scr = None                 # csrc/labor_w.hip: + three records per seed column and p_e; (cap_s, cap_b, tensor)
+        self._wl_p = {}                     # its p_ij outputs: per static slot (slot, layer, cap_b) -> bf16 [cap_b]
         self._slot_bufs, self._slot_counts, self._slot_counts_host = {}, {}, {}
         self.caps = None
         self.ws = None
@@ -432,11 +434,12 @@ class LayerEngine:
             self.caps, self.ws = fresh, None
         self._ensure(S0, fan)
 
-    def sample_blocks_labor(self, seeds, fanouts, draw_state, layer_dependency=False, iterations=0):
+    def sample_blocks_labor(self, seeds, fanouts, draw_state, layer_dependency=False, iterations=0, lb_prob=None):
         """fit.LaborSampler (csrc/labor.hip): the L layers (``fanouts`` in SAMPLING order) are only enqueued
         and the call synchronises once, at the end; torch's generators are not touched.  ``layer_dependency``: one variate per
         vertex for all layers of a step.  ``iterations`` > 0: LABOR-i layers (fit.ImportanceLaborSampler, csrc/labor_is.hip,
-        DESIGN.md section 16)."""
+        DESIGN.md section 16).  ``lb_prob``: LABOR layers with edge probabilities (csrc/labor_w.hip) --
+        ``neighbor_prob(...)``'s record; the blocks then carry ``_p``, the inclusion probabilities."""
         if draw_state is None:
             raise ValueError("the LABOR sampler needs a draw_state")
         seeds = seeds.to(torch.int32).contiguous()
@@ -444,7 +447,7 @@ class LayerEngine:
         self._ensure_labor(int(seeds.numel()), fanouts)
         while True:
             out = self._enqueue(None, seeds, fanouts, 0, 0.0, 0.0, None, None, draw_state=draw_state, labor=True,
-                                layer_dependency=layer_dependency, labor_iterations=iterations)
+                                layer_dependency=layer_dependency, labor_iterations=iterations, lb_prob=lb_prob)
             self.counts_host.copy_(out[0], non_blocking=True)
             torch.cuda.current_stream().synchronize()                 # the one sync of the call
             raw = self.counts_host.numpy().tobytes()
@@ -455,7 +458,10 @@ class LayerEngine:
             if bad & ~_CAP_ERRS or bad & 3:
                 raise RuntimeError(f"sampler kernel error 0x{bad:x}: {_lib.err_string(bad)}")
             if bad == 0:
-                return self._finish(out, cnts)
+                blocks = self._finish(out, cnts)
+                for blk, c, p in zip(blocks, cnts, self._wl_out if lb_prob is not None else ()):
+                    blk._p = p[:c.B]
+                return blocks
             draw_state.step_dev.sub_(1)                                # the repeated call is the same draw step
             self._grow([c.err for c in cnts])
             self._ensure_labor(int(seeds.numel()), fanouts)
@@ -477,8 +483,27 @@ class LayerEngine:
             self._li_scr = (rows, edges, torch.zeros(nbytes // 4, dtype=torch.int32, device=self.g.device))
         return self._li_scr[2]
 
+    def _wlabor_scratch(self, cap_s, cap_b):
+        """Sized once for any seed capacity up to |V| and the largest edge capacity of the layers; regrows with B."""
+        if self._wl_scr is None or self._wl_scr[0] < cap_s or self._wl_scr[1] < cap_b:
+            rows, edges = max(self.V, int(cap_s)), max(int(cap_b), max(c["B"] for c in self.caps))
+            nbytes = int(_lib.lib.bliss_wlabor_scratch_bytes(self.V, rows, edges))
+            if nbytes < 0:
+                raise RuntimeError("bliss_wlabor_scratch_bytes failed")
+            self._wl_scr = (rows, edges, torch.zeros(nbytes // 4, dtype=torch.int32, device=self.g.device))
+        return self._wl_scr[2]
+
+    def _wlabor_p(self, n, slot, cap_b):
+        """The p_ij output of weighted LABOR layer n: persistent per static slot, fresh memory per call otherwise."""
+        if slot is None:
+            return torch.empty(max(cap_b, 1), dtype=torch.bfloat16, device=self.g.device)
+        key = (slot, n, cap_b)
+        if key not in self._wl_p:
+            self._wl_p[key] = torch.empty(max(cap_b, 1), dtype=torch.bfloat16, device=self.g.device)
+        return self._wl_p[key]
+
     def neighbor_prob(self, rows, eta=None):
-        """The probability source of weighted neighbor layers (csrc/neighbor_w.hip).  ``rows``: bf16 [|E|] tensors by CSC position,
+        """The probability source of weighted neighbor layers (csrc/neighbor_w.hip) and weighted LABOR layers (csrc/labor_w.hip).  ``rows``: bf16 [|E|] tensors by CSC position,
         one per layer in SAMPLING order (or one tensor for all layers).  ``eta`` None: raw mode, the rows are the unnormalised
         edge probabilities; a number: EXP3 mode, the rows are the EXP3 weights."""
         rows = [rows] if torch.is_tensor(rows) else list(rows)
@@ -498,11 +523,19 @@ class LayerEngine:
         return self._wn_scr
 
     def _enqueue_neighbor_layer(self, n, fanout, cur_seeds, n_seeds, n_seeds_dev, draw_state, last, c_ws, c_out, lay, cnt_ptr, st,
-                                labor=False, layer_dependency=False, labor_iterations=0, nb_prob=None):
-        """One bliss_neighbor_layer (``labor``: one bliss_labor_layer, or one bliss_labor_is_layer when ``labor_iterations`` > 0;
-        ``nb_prob``: one bliss_wneighbor_layer) + the by-source index of its block (bliss_block_transpose on the device-resident B)."""
+                                labor=False, layer_dependency=False, labor_iterations=0, nb_prob=None, lb_prob=None, p_out=None):
+        """One bliss_neighbor_layer (``labor``: one bliss_labor_layer, or one bliss_labor_is_layer when ``labor_iterations`` > 0, or
+        one bliss_wlabor_layer with ``lb_prob``, its p_ij into ``p_out``; ``nb_prob``: one bliss_wneighbor_layer) + the by-source
+        index of its block (bliss_block_transpose on the device-resident B)."""
         cap, ws = self.caps[n], self.ws[n]
-        if nb_prob is not None:
+        if labor and lb_prob is not None:
+            row = lb_prob["rows"][n if len(lb_prob["rows"]) > 1 else 0]
+            _lib.check(_lib.lib.bliss_wlabor_layer(C.byref(self.c_graph), cur_seeds.data_ptr(), n_seeds, n_seeds_dev, cap["S"],
+                                                   int(fanout), 0, draw_state.seed, draw_state.step_dev.data_ptr(), n, int(last),
+                                                   int(bool(layer_dependency)), lb_prob["mode"], row.data_ptr(), lb_prob["eta_f"],
+                                                   lb_prob["ome_f"], C.byref(c_ws), C.byref(c_out), p_out.data_ptr(),
+                                                   self._wlabor_scratch(cap["S"], c_out.cap_b).data_ptr(), st), "bliss_wlabor_layer")
+        elif nb_prob is not None:
             row = nb_prob["rows"][n if len(nb_prob["rows"]) > 1 else 0]
             _lib.check(_lib.lib.bliss_wneighbor_layer(C.byref(self.c_graph), cur_seeds.data_ptr(), n_seeds, n_seeds_dev, cap["S"],
                                                       int(fanout), 0, draw_state.seed, draw_state.step_dev.data_ptr(), n, int(last),
@@ -672,7 +705,7 @@ class LayerEngine:
 
     def enqueue_static(self, w_rows, seeds, fanouts, mode, eta, eps=0.9999, slot=0, chain_rng=False, external_rng=False, part=None,
                        last_block=True, ready_flag=0, draw_state=None, neighbor=False, labor=False, layer_dependency=False,
-                       labor_iterations=0, nb_prob=None):
+                       labor_iterations=0, nb_prob=None, lb_prob=None):
         """Enqueue one sample_blocks on the current stream with capacity-padded outputs and NO sync.  Returns the
         blocks (sampling order); sizes, errors and the generator state are read back by finish().
 
@@ -690,9 +723,12 @@ class LayerEngine:
         ``draw_state``, whole calls only; ``w_rows`` / ``mode`` / ``eta`` / ``eps`` are ignored).  ``labor``: the layers are LABOR-0
         layers (csrc/labor.hip; the same conditions), with one variate per vertex for all layers when ``layer_dependency``; ``labor_iterations`` > 0:
         LABOR-i layers (csrc/labor_is.hip).  ``nb_prob`` (with ``neighbor``): the weighted draw of csrc/neighbor_w.hip, from
-        ``neighbor_prob(...)``."""
+        ``neighbor_prob(...)``.  ``lb_prob`` (with ``labor``, ``labor_iterations`` = 0): LABOR layers with edge probabilities
+        (csrc/labor_w.hip), from the same record; the blocks then carry ``_p``, the inclusion probabilities."""
         if nb_prob is not None and not neighbor:
             raise ValueError("nb_prob belongs to the neighbor layers")
+        if lb_prob is not None and not labor:
+            raise ValueError("lb_prob belongs to the LABOR layers")
         if labor and (neighbor or draw_state is None or part is not None or external_rng or chain_rng):
             raise NotImplementedError("the LABOR sampler needs a draw_state and has no split / external-generator enqueue "
                                       "(the pipelined two-stream loop is out of scope)")
@@ -708,7 +744,7 @@ class LayerEngine:
         out = self._enqueue(w_rows, seeds, fanouts, mode, eta, eps, None, True, slot=slot, chain_rng=chain_rng,
                             external_rng=external_rng, part=part, last_block=last_block, ready_flag=ready_flag, draw_state=draw_state,
                             neighbor=neighbor, labor=labor, layer_dependency=layer_dependency, labor_iterations=labor_iterations,
-                            nb_prob=nb_prob)
+                            nb_prob=nb_prob, lb_prob=lb_prob)
         self._static_draw[slot] = draw_state is not None
         counts_dev, layers = out
         if slot not in self._slot_counts_host:
@@ -723,6 +759,8 @@ class LayerEngine:
             cap = self.caps[n]
             blk = Block(self.g, cap["K"], cap["S"], b_indptr, b_src, b_dst, b_pos, b_eid, kept_nid)
             blk._edge_weights, blk._q, blk._node_prob = b_w, b_q, node_prob
+            if lb_prob is not None:
+                blk._p = self._wl_out[n][:cap["B"]]
             blk._counts, blk._counts_dev = None, cdev
             blk._nnz_ptr = counts_dev.data_ptr() + 40 * n + 16
             blk._xcap = int(cap.get("X", cap["B"]))
@@ -752,7 +790,9 @@ class LayerEngine:
 
     def _enqueue(self, w_rows, seeds, fanouts, mode, eta, eps, uniforms, snapshot, slot=None, chain_rng=False, external_rng=False,
                  part=None, last_block=True, ready_flag=0, draw_state=None, neighbor=False, labor=False, layer_dependency=False,
-                 labor_iterations=0, nb_prob=None):
+                 labor_iterations=0, nb_prob=None, lb_prob=None):
+        if lb_prob is not None and (labor_iterations > 0 or self.labor_is):
+            raise NotImplementedError("LABOR-i with edge probabilities is out of scope")
         dev, st = self.g.device, _stream()
         L = len(fanouts)
         if draw_state is None and snapshot is not None and not chain_rng and not external_rng:
@@ -772,6 +812,7 @@ class LayerEngine:
         eta_f = float(np.float32(eta))
         ome_f = float(np.float32(1.0 - eta))
         layers = []
+        self._wl_out = []                       # the p_ij outputs of weighted LABOR layers, in sampling order
         cur_seeds, n_seeds, n_seeds_dev = seeds, int(seeds.numel()), 0
         for n in range(L):
             cap = self.caps[n]
@@ -779,9 +820,14 @@ class LayerEngine:
             c_ws, c_out, lay, cnt_ptr, kept_nid = self._layer_buffers(n, counts, slot)
             last = n == L - 1
             if neighbor or labor:               # neighbor / LABOR layer: 6 / 7 launches and the by-source index, nothing else
+                p_out = None
+                if labor and lb_prob is not None:
+                    p_out = self._wlabor_p(n, slot, cap["B"])
+                    self._wl_out.append(p_out)
                 self._enqueue_neighbor_layer(n, fanouts[n], cur_seeds, n_seeds, n_seeds_dev, draw_state, last, c_ws, c_out, lay,
                                              cnt_ptr, st, labor=labor, layer_dependency=layer_dependency,
-                                             labor_iterations=labor_iterations, nb_prob=nb_prob if neighbor else None)
+                                             labor_iterations=labor_iterations, nb_prob=nb_prob if neighbor else None,
+                                             lb_prob=lb_prob if labor else None, p_out=p_out)
                 layers.append(lay)
                 cur_seeds, n_seeds, n_seeds_dev = kept_nid, -1, cnt_ptr + 12
                 continue

@@ -11,7 +11,7 @@ LIB_PATH = os.path.join(_HERE, "libbliss_gnn.so")
 
 EINVAL = -1
 MODE_BANDIT, MODE_LADIES, MODE_UNIFORM_NODES, MODE_PARTIALS = 0, 1, 4, 8
-WN_RAW, WN_EXP3 = 0, 1                 # bliss_wneighbor_layer: probabilities as given / EXP3 weights
+WN_RAW, WN_EXP3 = 0, 1                 # bliss_wneighbor_layer / bliss_wlabor_layer: probabilities as given / EXP3 weights
 
 ERR_BITS = {
     1: "frontier larger than 2^31-1 edges",
@@ -203,6 +203,8 @@ SIGNATURES = {
                           C.POINTER(BlockOut), _P, _P],
     "bliss_labor_is_layer": [C.POINTER(Graph), _P, _I32, _P, _I32, _I32, _P, C.c_uint64, _P, _I32, C.c_int, C.c_int, _I32,
                              C.POINTER(LayerWs), C.POINTER(BlockOut), _P, _P],
+    "bliss_wlabor_layer": [C.POINTER(Graph), _P, _I32, _P, _I32, _I32, _P, C.c_uint64, _P, _I32, C.c_int, C.c_int, _I32, _P, _F, _F,
+                           C.POINTER(LayerWs), C.POINTER(BlockOut), _P, _P, _P],
     "bliss_tile_gemm": [C.POINTER(TileGemm), C.POINTER(TileGemm), _P],
     "bliss_cross_entropy": [_P, _I64, _P, _I32, _I32, _P, _P, _I64, _P, _P, _P, _P],
     "bliss_cross_entropy_sum": [_P, _I64, _P, _I64, _P, _P, _I32, _I32, _P, _P, _I64, _P, _P, _P, _P],
@@ -270,7 +272,7 @@ SIGNATURES = {
 SPECIAL_SIGNATURES = ("bliss_prof_kernel_name", "bliss_block_transpose_temp_bytes", "bliss_graph_prepare_capacity",
                       "bliss_graph_prepare_temp_bytes", "bliss_rng_stream_handle", "bliss_sage_wgrad_workspace",
                       "bliss_multinomial_draw_scratch_bytes", "bliss_neighbor_scratch_bytes", "bliss_wneighbor_scratch_bytes",
-                      "bliss_labor_scratch_bytes", "bliss_labor_is_scratch_bytes")   # non-int return types, set in _load()
+                      "bliss_labor_scratch_bytes", "bliss_labor_is_scratch_bytes", "bliss_wlabor_scratch_bytes")   # non-int return types, set in _load()
 
 
 def _load():
@@ -300,6 +302,8 @@ def _load():
     lib.bliss_labor_scratch_bytes.restype = C.c_int64
     lib.bliss_labor_is_scratch_bytes.argtypes = [_I32, _I32, _I32]
     lib.bliss_labor_is_scratch_bytes.restype = C.c_int64
+    lib.bliss_wlabor_scratch_bytes.argtypes = [_I32, _I32, _I32]
+    lib.bliss_wlabor_scratch_bytes.restype = C.c_int64
     lib.bliss_rng_stream_handle.argtypes = []
     lib.bliss_rng_stream_handle.restype = C.c_int64
     lib.bliss_prof_kernel_name.argtypes = [C.c_int]

@@ -27,22 +27,6 @@
 
 namespace {
 
-#define LI_ONE (1ull << 32)
-#define LI_WAVE_D 256         // a wave solves a column up to this degree from registers: four positions per lane
-#define LI_STAGE 2048         // the workgroup stages a column's importances in LDS up to this degree
-#define LI_COLS 4             // columns per workgroup and trip in the wave-per-column kernels (= waves per workgroup)
-
-// column s: first CSC position and degree; an empty column for a seed id outside [0, V)
-__device__ __forceinline__ void li_column(const long long* __restrict__ g_indptr, const int* __restrict__ seeds, int V, int s, int* a,
-                                          int* d) {
-  const int nid = seeds[s];
-  *a = 0; *d = 0;
-  if ((unsigned)nid < (unsigned)V) {
-    const long long a64 = g_indptr[nid];
-    *a = (int)a64; *d = (int)(g_indptr[nid + 1] - a64);
-  }
-}
-__device__ __forceinline__ bool li_whole(int fanout, int d) { return fanout < 0 || d <= fanout; }
 __device__ __forceinline__ unsigned long long li_closed(int fanout, int d) {
   return ((unsigned long long)(unsigned)fanout << 32) / (unsigned long long)d;
 }
@@ -253,17 +237,6 @@ __global__ void __launch_bounds__(NB_TPB) k_li_write(const long long* __restrict
     __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     *step_dev += 1;
   }
-}
-
-// fp64 -> bf16, ONE rounding to nearest even (positive normal values in bf16's range: the weights)
-__device__ __forceinline__ bf16_t li_d2bf(double x) {
-  const unsigned long long b = (unsigned long long)__double_as_longlong(x);
-  int e = (int)((b >> 52) & 0x7ffull) - 1023 + 127;
-  const unsigned long long m = b & ((1ull << 52) - 1ull), rem = m & ((1ull << 45) - 1ull), half = 1ull << 44;
-  unsigned q = (unsigned)(m >> 45);
-  if (rem > half || (rem == half && (q & 1u))) q += 1u;
-  if (q >= 128u) { q = 0u; e += 1; }
-  return (bf16_t)(((unsigned)e << 7) | q);
 }
 
 __global__ void __launch_bounds__(NB_TPB) k_li_weights(const LayerCounts* __restrict__ cnt, const int* __restrict__ b_indptr,

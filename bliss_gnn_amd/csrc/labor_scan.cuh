@@ -1,5 +1,6 @@
-// What the two LABOR samplers share (csrc/labor.hip, csrc/labor_is.hip) in front of the source-numbering tail: the per-source key,
-// the clamped seed count, and the one-workgroup scan behind their counting kernels.
+// What the LABOR samplers share (csrc/labor.hip, csrc/labor_is.hip, csrc/labor_w.hip) in front of the source-numbering tail: the
+// per-source key, the clamped seed count, the one-workgroup scan behind their counting kernels; for the two with per-edge
+// probabilities also a seed's column, the column-size paths of their scale solves and the one-rounding fp64 -> bf16 of the weights.
 //   k_lb_scan    one workgroup: seg_ptr (degrees), indptr (c_s), S / E / B, clamps and error bits, the rest of the counts record
 #pragma once
 #include "neighbor_tail.cuh"
@@ -18,6 +19,33 @@ __device__ __forceinline__ unsigned lb_key(unsigned long long mk, const unsigned
 __device__ __forceinline__ int lb_seed_count(int S_host, const int* __restrict__ S_dev, int cap_s) {
   const int S = S_host >= 0 ? S_host : *S_dev;
   return S > cap_s ? cap_s : (S < 0 ? 0 : S);
+}
+
+#define LI_ONE (1ull << 32)
+#define LI_WAVE_D 256         // a wave solves a column up to this degree from registers: four positions per lane
+#define LI_STAGE 2048         // the workgroup stages a column's importances in LDS up to this degree
+#define LI_COLS 4             // columns per workgroup and trip in the wave-per-column kernels (= waves per workgroup)
+
+// column s: first CSC position and degree; an empty column for a seed id outside [0, V)
+__device__ __forceinline__ void li_column(const long long* __restrict__ g_indptr, const int* __restrict__ seeds, int V, int s, int* a,
+                                          int* d) {
+  const int nid = seeds[s];
+  *a = 0; *d = 0;
+  if ((unsigned)nid < (unsigned)V) {
+    const long long a64 = g_indptr[nid];
+    *a = (int)a64; *d = (int)(g_indptr[nid + 1] - a64);
+  }
+}
+__device__ __forceinline__ bool li_whole(int fanout, int d) { return fanout < 0 || d <= fanout; }
+// fp64 -> bf16, ONE rounding to nearest even (positive normal values in bf16's range: the weights)
+__device__ __forceinline__ bf16_t li_d2bf(double x) {
+  const unsigned long long b = (unsigned long long)__double_as_longlong(x);
+  int e = (int)((b >> 52) & 0x7ffull) - 1023 + 127;
+  const unsigned long long m = b & ((1ull << 52) - 1ull), rem = m & ((1ull << 45) - 1ull), half = 1ull << 44;
+  unsigned q = (unsigned)(m >> 45);
+  if (rem > half || (rem == half && (q & 1u))) q += 1u;
+  if (q >= 128u) { q = 0u; e += 1; }
+  return (bf16_t)(((unsigned)e << 7) | q);
 }
 
 __global__ void __launch_bounds__(NB_SCAN_TPB) k_lb_scan(const long long* __restrict__ g_indptr, int V, const int* __restrict__ seeds,

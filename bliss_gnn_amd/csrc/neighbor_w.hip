@@ -30,12 +30,6 @@ namespace {
 
 #define WN_INF_BITS 0x7f800000u
 
-// q of the edge at CSC position pos; cf = the column's (bf16 sum, fp32 bits of the eta / n term) in EXP3 mode
-__device__ __forceinline__ bf16_t wn_q(int mode, const bf16_t* __restrict__ prob, int pos, uint2 cf, float ome_f) {
-  const bf16_t x = prob[pos];
-  return mode == BLISS_WN_EXP3 ? edge_q_pre(x, (bf16_t)(cf.x & 0xffffu), __uint_as_float(cf.y), ome_f) : x;
-}
-
 // the race key's fp32 bits: non-negative, so they order as unsigned integers
 __device__ __forceinline__ unsigned wn_key_bits(unsigned long long mk, int pos, bf16_t qb) {
   const float q = bf2f(qb);
@@ -44,28 +38,6 @@ __device__ __forceinline__ unsigned wn_key_bits(unsigned long long mk, int pos, 
   const float u = (float)((k32 >> 8) + 1u) * 5.9604644775390625e-8f;      // (0, 1], exact in fp32
   const float key = (float)(-log((double)u) / (double)q);           // one fp64 quotient, rounded once
   return __float_as_uint(key) & 0x7fffffffu;                        // (u = 1: -0.0)
-}
-
-__device__ __forceinline__ long long wn_block_sum_i64(long long v, long long* sh) {
-  v = wave_total_i64(v);
-  __syncthreads();                                                  // sh free again
-  if (lane_id() == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  long long t = 0;
-#pragma unroll
-  for (int w = 0; w < NB_TPB / BLISS_WAVE; ++w) t += sh[w];
-  return t;
-}
-
-__device__ __forceinline__ int wn_block_max_u31(int v, long long* sh) {
-  v = wave_max_u31(v);
-  __syncthreads();                                                  // sh free again
-  if (lane_id() == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  int t = 0;
-#pragma unroll
-  for (int w = 0; w < NB_TPB / BLISS_WAVE; ++w) t = max(t, (int)sh[w]);
-  return t;
 }
 
 __global__ void __launch_bounds__(NB_TPB) k_wn_keys(const long long* __restrict__ g_indptr, int V, const int* __restrict__ seeds,
@@ -88,19 +60,7 @@ __global__ void __launch_bounds__(NB_TPB) k_wn_keys(const long long* __restrict_
     if (d == 0) continue;
     uint2 cf = make_uint2(0u, 0u);
     if (mode == BLISS_WN_EXP3) {
-      // sum_j w_ij exactly (csrc/sampler.hip:k_col_sums' block-floating form: integer adds, any order gives the same bits)
-      int emax = 1;
-      for (int i = tid; i < d; i += NB_TPB) emax = max(emax, bf_exp_field(prob[a + i]));
-      emax = wn_block_max_u31(emax, sh);
-      const int wfrac = rel_frac(FRAC_DST, emax);
-      long long part = 0, part_lo = 0;
-      int sticky = 0;
-      for (int i = tid; i < d; i += NB_TPB) part += bf_to_fixed_wide(prob[a + i], wfrac, &part_lo, &sticky, &bad);
-      const long long hi = wn_block_sum_i64(part, sh);
-      const long long lo = wn_block_sum_i64(part_lo, sh);
-      const long long st = wn_block_sum_i64(sticky, sh);
-      const bf16_t wsum = fixed_wide_to_bf(hi, lo, st != 0, wfrac, &bad);
-      cf = make_uint2((unsigned)wsum, __float_as_uint(rbf((1.0f / (float)d) * eta_f)));
+      cf = wn_col_record<NB_TPB>(prob, a, d, eta_f, sh, &bad);         // the exact column sum and the eta / n term (edge_q.cuh)
       if (tid == 0) coef[s] = cf;
     }
     if (fanout < 0 || d <= fanout) continue;                        // a whole column: no key

@@ -12,6 +12,8 @@ pytorch_lightning, reduced to plain loops -- Lightning / torchmetrics / tensorbo
     (csrc/labor.hip) -- the sampler the reference's training script was derived from and dropped.
     ``ImportanceLaborSampler``: LABOR-i, the same draw after i fixed-point iterations over per-vertex importances
     (csrc/labor_is.hip).
+    ``WeightedLaborSampler``: LABOR-0 with edge probabilities (DGL's ``prob=``), and ``BanditLaborSampler``: the same draw over the
+    EXP3 edge probabilities with ``BanditLadiesSampler``'s state and reward update (csrc/labor_w.hip).
   * ``fit``: epochs of TrainStep, ``StepLR(gamma=0.01, step_size=5)`` stepped per epoch (:205-216), validation with the same
     sampler (:179-203, :410-422), best-``val_acc`` checkpoint (:620-625), early stop on ``val_acc_target`` / patience
     (:627-634), then the best checkpoint reloaded for the layer-wise full-neighbour inference and the Final Accuracy of the
@@ -244,6 +246,9 @@ class LaborSampler(NeighborSampler):
 
     _iterations = 0                                         # (ImportanceLaborSampler: LABOR-i layers, csrc/labor_is.hip)
 
+    def _lb_prob(self, eng):
+        return None                                         # (WeightedLaborSampler: the engine's probability record)
+
     def __init__(self, fanouts, edge_dir="in", prob=None, importance_sampling=0, layer_dependency=False, batch_dependency=1, seed=0,
                  **_ignored):
         if importance_sampling != 0:
@@ -271,12 +276,13 @@ class LaborSampler(NeighborSampler):
         fan = list(reversed(self.fanouts))
         return self._blocks(eng.enqueue_static(None, seed_nodes, fan, 0, 0.0, slot=slot, draw_state=self._draw_state_on(eng.g.device),
                                                labor=True, layer_dependency=self.layer_dependency,
-                                               labor_iterations=self._iterations, **split), seed_nodes)
+                                               labor_iterations=self._iterations, lb_prob=self._lb_prob(eng), **split), seed_nodes)
 
     def sample_blocks(self, g, seed_nodes, exclude_eids=None):
         g = as_graph(g, self.__dict__.setdefault("_graphs", {}))
-        blks = self._bind(g).sample_blocks_labor(seed_nodes, list(reversed(self.fanouts)), self._draw_state_on(g.device),
-                                                 self.layer_dependency, iterations=self._iterations)
+        eng = self._bind(g)
+        blks = eng.sample_blocks_labor(seed_nodes, list(reversed(self.fanouts)), self._draw_state_on(g.device),
+                                       self.layer_dependency, iterations=self._iterations, lb_prob=self._lb_prob(eng))
         return self._blocks(blks, seed_nodes)
 
 
@@ -308,11 +314,98 @@ class ImportanceLaborSampler(LaborSampler):
         return eng
 
 
+class WeightedLaborSampler(LaborSampler):
+    """``dgl.dataloading.LaborSampler(fanouts, prob=...)`` with ``importance_sampling=0``: LABOR-0's one variate r_u per source
+    vertex, the edge u -> s kept iff r_u < p_us with p_us proportional to the edge's probability inside its column, scaled so
+    that the column keeps ``fanout`` edges in expectation and clamped below 1 (the scale then rises for the other edges).  No
+    parity claim: a defined mode in unsigned integers from the bf16 bits of the probabilities, csrc/labor_w.hip restated by
+    tests/wlabor_ref.py.  A column with fewer than ``fanout`` edges of comparable weight (within about
+    2^-8 of its largest) keeps fewer than ``fanout`` edges in expectation; an edge whose probability is not positive and finite, or
+    below 2^-32 of the column's largest, is never kept unless the column is kept whole (DGL's behaviour; the weighted neighbor
+    draw's filler rule does not apply).
+
+    ``prob``: unnormalised edge probabilities, a tensor [|E|] by EDGE ID or the name of an entry of ``g.edata``, converted to bf16
+    by CSC position once per graph.  Blocks carry ``edge_weights`` (the Hajek weights under the mean aggregation, from the true
+    inclusion probabilities), ``edata["q_ij"]`` (the edge probabilities) and ``edata["p_ij"]`` (the inclusion probabilities, 1 in
+    a column kept whole).  Everything else is ``LaborSampler``'s: always the device draw, ``layer_dependency``, ``reset_draw`` /
+    ``draw_step`` / ``sample_blocks_static`` / ``finish_static`` / ``check_errors``; it runs inside a captured train step."""
+
+    def __init__(self, fanouts, prob, layer_dependency=False, seed=0, **_ignored):
+        if prob is None:
+            raise ValueError("WeightedLaborSampler needs edge probabilities (prob=); without them it is LaborSampler")
+        super().__init__(fanouts, layer_dependency=layer_dependency, seed=seed)
+        self.prob = prob
+
+    def _lb_prob(self, eng):
+        return self._nb_prob(eng)
+
+    def _blocks(self, blks, seed_nodes):
+        for blk in blks:
+            blk.edata["p_ij"] = blk._p
+        return super()._blocks(blks, seed_nodes)
+
+
+class BanditLaborSampler(BanditLadiesSampler):
+    """LABOR with learned edge probabilities: ``WeightedLaborSampler``'s draw over the EXP3 edge probabilities q_ij = eta / n_i +
+    (1 - eta) * w_ij / sum_j w_ij -- csrc/labor_w.hip in EXP3 mode, layer ``b``'s row of the EXP3 weights for
+    block ``b``.  Unlike ``BanditNeighborSampler``'s blocks, these shrink as the probabilities concentrate: one variate per source
+    vertex is shared by all seeds of a layer.  No parity claim: a defined mode restated by tests/wlabor_ref.py.
+
+    The EXP3 state (``exp3_weights`` [L, |E|] by edge id, exact row sums), ``exp3(mfgs, g)`` (also ``model="gat"``) and
+    ``check_errors`` are ``BanditLadiesSampler``'s; blocks carry ``edge_weights`` (Hajek weights under the mean aggregation),
+    ``q_ij`` (what the reward divides by), ``p_ij`` (the inclusion probabilities) and ``node_prob`` = 1.  Always ``draw="device"``:
+    ``reset_draw`` / ``draw_step`` / ``sample_blocks_static`` / ``finish_static`` as ``LaborSampler`` has them, it runs inside a
+    captured train step, and the pipelined two-stream loop refuses it."""
+
+    def __init__(self, fanouts, eta=0.4, num_steps=5000, model="sage", layer_dependency=False, seed=0, **_ignored):
+        super().__init__(list(fanouts), eta=eta, num_steps=num_steps, model=model, draw="device")
+        self.fanouts = list(fanouts)
+        self.layer_dependency = bool(layer_dependency)
+        self._draw_init = (seed, 0)
+
+    def _bind(self, g):
+        g = self._graph(g)
+        if self._engine is None or self._engine.g is not g:
+            self._engine = LayerEngine(g)                   # (exact_b stays False: a column's kept count is data dependent)
+        return self._engine
+
+    def _sample(self, g, seed_nodes, static, **kw):
+        g = self._graph(g)
+        eng = self._bind(g)
+        self._ensure_weights(g)
+        order = list(reversed(range(len(self.fanouts))))   # sampling order: the last block first
+        fan = [self.fanouts[b] for b in order]
+        prob = eng.neighbor_prob([self._w_pos[b] for b in order], eta=self.eta)
+        ds = self._draw_state_on(g.device)
+        if static:
+            blks = eng.enqueue_static(None, seed_nodes, fan, 0, 0.0, draw_state=ds, labor=True,
+                                      layer_dependency=self.layer_dependency, lb_prob=prob, **kw)
+        else:
+            blks = eng.sample_blocks_labor(seed_nodes, fan, ds, self.layer_dependency, lb_prob=prob)
+        blocks = []
+        for blk in blks:
+            blk.edata[self.output_weight] = blk._edge_weights
+            blk.edata["q_ij"] = blk._q
+            blk.edata["p_ij"] = blk._p
+            blk.srcdata[self.node_prob] = blk._node_prob
+            blocks.insert(0, blk)
+        return blocks[0].srcdata[NID], seed_nodes, blocks
+
+    def sample_blocks(self, g, seed_nodes, exclude_eids=None):
+        return self._sample(g, seed_nodes, False)
+
+    def sample_blocks_static(self, g, seed_nodes, slot=0, **split):
+        """sample_blocks with capacity-padded blocks, only ENQUEUED; whole calls only: any split / external-generator keyword
+        raises.  A step over its calibrated capacities is reported by ``finish_static``."""
+        return self._sample(g, seed_nodes, True, slot=slot, **split)
+
+
 def make_sampler(name, fanouts, importance_sampling=1, num_steps=5000, eta=0.1, model="sage", draw="host"):
     """The sampler-name dispatch of DataModule.__init__ (train_lightning.py:348-370).  ``draw``: where the two multinomial
     samplers ("ladies", "bandit") and "neighbor" draw -- "host" (torch.multinomial / torch tensor ops) or "device" (the keyed
     draws, graph-capturable).  "labor" and "labor-<i>" (i in 1 .. 8: ``ImportanceLaborSampler`` with i iterations) always draw on
-    the device.  "neighbor-exp3": ``BanditNeighborSampler`` (EXP3-weighted node-wise draw, always on the device)."""
+    the device.  "neighbor-exp3": ``BanditNeighborSampler`` (EXP3-weighted node-wise draw, always on the device); "labor-exp3":
+    ``BanditLaborSampler`` (EXP3-weighted LABOR draw, always on the device)."""
     from . import BanditLadiesSampler, LadiesSampler, PoissonBanditLadiesSampler, PoissonLadiesSampler as PLS
     if name == "full":
         return MultiLayerFullNeighborSampler(len(fanouts))
@@ -320,6 +413,8 @@ def make_sampler(name, fanouts, importance_sampling=1, num_steps=5000, eta=0.1, 
         return NeighborSampler(fanouts, draw=draw)
     if name == "neighbor-exp3":                             # the node-wise bandit sampler; always the device draw
         return BanditNeighborSampler(fanouts, eta=eta, num_steps=num_steps, model=model)
+    if name == "labor-exp3":                                # LABOR over the EXP3 edge probabilities; always the device draw
+        return BanditLaborSampler(fanouts, eta=eta, num_steps=num_steps, model=model)
     if name == "labor":
         return LaborSampler(fanouts)                        # (LABOR-0; always the device draw)
     if name.startswith("labor-"):                           # "labor-1" .. "labor-8": LABOR-i

@@ -306,7 +306,43 @@ int bliss_labor_is_layer(const bliss_graph_t* g, const int32_t* seeds, int32_t n
                          int bump_step, int layer_dependency, int32_t iterations, const bliss_layer_ws_t* ws,
                          const bliss_block_out_t* out, void* scratch, void* stream);
 
-/* generate_block     bandit_sampler.py:269-339 (BANDIT: Hajek weights) / ladies_sampler.py:71-107.
+/* LABOR WITH EDGE PROBABILITIES ON THE DEVICE, one layer (fit.WeightedLaborSampler -- dgl.dataloading.LaborSampler(fanouts, prob=...),
+ * importance_sampling = 0 -- and fit.BanditLaborSampler; bliss_labor_layer's keyed per-source draw with a per-edge inclusion
+ * probability proportional to q, clamped below ONE = 2^32; a defined mode restated on the CPU by tests/wlabor_ref.py; DESIGN.md
+ * section 19).  Unsigned integers from the bf16 bits of q up to the weights:
+ *   q_pos   = bliss_wneighbor_layer's: prob_pos[pos] (mode BLISS_WN_RAW: bf16 [num_edges] by CSC position, unnormalised), or the EXP3
+ *             edge probability eta / n_i + (1 - eta) * w_pos / sum_col(w) with that entry point's roundings (mode BLISS_WN_EXP3)
+ *   seed column s, CSC positions [a, b), d = b - a, is WHOLE if fanout < 0 or d <= fanout: every edge is kept, no key is computed.
+ *   An edge of a non-whole column is VALID iff q_pos is positive and finite.  From the bf16 bits of q_pos (exponent field E, 7-bit
+ *             mantissa M): m = E ? 128 + M : M, e = max(E, 1); e_max = the largest e over the column's valid edges;
+ *             a_pos = (m << 24) >> (e_max - e), 0 when the shift is >= 32 and for an invalid edge (a_pos < ONE)
+ *   p_pos(c) = min(ONE - 1, (c * a_pos) >> 24) in 64 bits; c_s = the largest c in [0, ONE - 1] with sum_pos p_pos(c) <= fanout * ONE,
+ *             by 32 bisection steps from bit 31 down (the sum is nondecreasing in c; for c_s < ONE - 1 it exceeds
+ *             fanout * ONE - 256 d).  A column with fewer than `fanout` edges whose a_pos reaches 2^24 ends at c_s = ONE - 1 and keeps
+ *             fewer than `fanout` edges in expectation
+ *   draw:     the edge at pos is kept iff (uint64)key(u) < p_pos(c_s), u = g->indices[pos], key = bliss_labor_layer's (keys_override by
+ *             NODE ID, layer_dependency as there).  An edge with a_pos = 0 is never kept in a non-whole column (no filler rule)
+ *   block, sources, counts record, capacity padding, clamps, BLISS_ERR_CAP_* bits, ws->kept_map, bump_step: bliss_labor_layer's.
+ *   q_ij = q_pos for every kept edge, whole columns included; p_ij (bf16 [out->cap_b], a buffer of the caller's beside out->q_ij)
+ *             = bf16(fp32(p_pos) * 2^-32), both roundings to nearest even, 1 in whole columns; edge_weights = the Hajek weight under
+ *             the mean aggregation from the TRUE inclusion probability, W_e = (ONE / p_e) * k_s / sum_{kept e' of column s} (ONE / p_e'),
+ *             in fp64 with bliss_labor_is_layer's order of summation, rounded once to bf16, 1 in whole columns; node_prob = 1.
+ *             EXP3 mode: a non-finite weight raises BLISS_ERR_NONFINITE.
+ * scratch: bliss_wlabor_scratch_bytes(num_nodes, cap_s, cap_b) bytes for cap_b = out->cap_b, 16-byte aligned, zero-initialised ONCE:
+ * bliss_neighbor_layer's words (tickets, here also word 2 for pending error bits, and bitmap: all left zero by every call, also a
+ * replayed one, one that flagged an overflow and one with a seed id out of range; one offset per 1024 bitmap words), then per seed
+ * the (sum, eta / n) record, the (c_s, e_max) record and the kept count, and cap_b words of p_e, rewritten by every call before they
+ * are read.  9 launches in raw mode, 10 in EXP3 mode; no host round trip.  BLISS_EINVAL before any launch: the sets
+ * bliss_labor_layer and bliss_wneighbor_layer refuse (prob_pos NULL or not 2-byte aligned, a mode other than the two,
+ * keys_override not 4-byte aligned, eta or one_minus_eta negative or NaN in EXP3 mode), p_ij NULL or not 2-byte aligned; the
+ * scratch size: num_nodes <= 0, cap_s <= 0, cap_b < 0. */
+int64_t bliss_wlabor_scratch_bytes(int32_t num_nodes, int32_t cap_s, int32_t cap_b);
+int bliss_wlabor_layer(const bliss_graph_t* g, const int32_t* seeds, int32_t n_seeds, const int32_t* n_seeds_dev, int32_t cap_s,
+                       int32_t fanout, const uint32_t* keys_override, uint64_t seed, int64_t* step_dev, int32_t layer, int bump_step,
+                       int layer_dependency, int32_t mode, const void* prob_pos, float eta, float one_minus_eta,
+                       const bliss_layer_ws_t* ws, const bliss_block_out_t* out, void* p_ij, void* scratch, void* stream);
+
+/* generate_block    bandit_sampler.py:269-339 (BANDIT: Hajek weights) / ladies_sampler.py:71-107.
  * Same g, maps, w_pos, seeds, eta as the matching bliss_frontier_prob call.  Out: counts{B}, the block;
  * leaves the node maps clean. */
 int bliss_build_block(const bliss_graph_t* g, const bliss_node_maps_t* maps, const void* w_pos,
