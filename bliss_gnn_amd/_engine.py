@@ -705,7 +705,7 @@ class LayerEngine:
 
     def enqueue_static(self, w_rows, seeds, fanouts, mode, eta, eps=0.9999, slot=0, chain_rng=False, external_rng=False, part=None,
                        last_block=True, ready_flag=0, draw_state=None, neighbor=False, labor=False, layer_dependency=False,
-                       labor_iterations=0, nb_prob=None, lb_prob=None):
+                       labor_iterations=0, nb_prob=None, lb_prob=None, n_live_dev=None):
         """Enqueue one sample_blocks on the current stream with capacity-padded outputs and NO sync.  Returns the
         blocks (sampling order); sizes, errors and the generator state are read back by finish().
 
@@ -724,7 +724,22 @@ class LayerEngine:
         layers (csrc/labor.hip; the same conditions), with one variate per vertex for all layers when ``layer_dependency``; ``labor_iterations`` > 0:
         LABOR-i layers (csrc/labor_is.hip).  ``nb_prob`` (with ``neighbor``): the weighted draw of csrc/neighbor_w.hip, from
         ``neighbor_prob(...)``.  ``lb_prob`` (with ``labor``, ``labor_iterations`` = 0): LABOR layers with edge probabilities
-        (csrc/labor_w.hip), from the same record; the blocks then carry ``_p``, the inclusion probabilities."""
+        (csrc/labor_w.hip), from the same record; the blocks then carry ``_p``, the inclusion probabilities.
+        ``n_live_dev`` (an int32 word on the device): ``seeds`` is a buffer of CAPACITY length -- the
+        capacity the static shapes were fixed for -- of which only the first ``n_live_dev[0]`` slots are this batch's seeds.
+        The first-sampled layer is then launched like every later one, with its seed count read on the device, so a captured
+        call serves every batch size up to the capacity; the output block's counts record holds the live S.  Slots past the
+        live count are read for no result (they hold valid node ids: zero, or an earlier batch's).  Whole calls only."""
+        if n_live_dev is not None:
+            if part is not None or external_rng or chain_rng:
+                raise NotImplementedError("a live seed count has no split / external-generator enqueue (the pipelined two-stream "
+                                          "loop is out of scope)")
+            if not (torch.is_tensor(n_live_dev) and n_live_dev.dtype == torch.int32 and n_live_dev.numel() == 1
+                    and n_live_dev.device == self.g.device):
+                raise ValueError("n_live_dev: one int32 word on the graph's device")
+            if self.caps is None or int(seeds.numel()) != self.caps[0]["S"] or seeds.dtype != torch.int32 or not seeds.is_contiguous():
+                raise ValueError("a live seed count needs a contiguous int32 seed buffer of exactly the static seed capacity (%s), "
+                                 "got %d slots" % (None if self.caps is None else self.caps[0]["S"], int(seeds.numel())))
         if nb_prob is not None and not neighbor:
             raise ValueError("nb_prob belongs to the neighbor layers")
         if lb_prob is not None and not labor:
@@ -744,7 +759,7 @@ class LayerEngine:
         out = self._enqueue(w_rows, seeds, fanouts, mode, eta, eps, None, True, slot=slot, chain_rng=chain_rng,
                             external_rng=external_rng, part=part, last_block=last_block, ready_flag=ready_flag, draw_state=draw_state,
                             neighbor=neighbor, labor=labor, layer_dependency=layer_dependency, labor_iterations=labor_iterations,
-                            nb_prob=nb_prob, lb_prob=lb_prob)
+                            nb_prob=nb_prob, lb_prob=lb_prob, n_live_dev=n_live_dev)
         self._static_draw[slot] = draw_state is not None
         counts_dev, layers = out
         if slot not in self._slot_counts_host:
@@ -790,7 +805,7 @@ class LayerEngine:
 
     def _enqueue(self, w_rows, seeds, fanouts, mode, eta, eps, uniforms, snapshot, slot=None, chain_rng=False, external_rng=False,
                  part=None, last_block=True, ready_flag=0, draw_state=None, neighbor=False, labor=False, layer_dependency=False,
-                 labor_iterations=0, nb_prob=None, lb_prob=None):
+                 labor_iterations=0, nb_prob=None, lb_prob=None, n_live_dev=None):
         if lb_prob is not None and (labor_iterations > 0 or self.labor_is):
             raise NotImplementedError("LABOR-i with edge probabilities is out of scope")
         dev, st = self.g.device, _stream()
@@ -814,6 +829,8 @@ class LayerEngine:
         layers = []
         self._wl_out = []                       # the p_ij outputs of weighted LABOR layers, in sampling order
         cur_seeds, n_seeds, n_seeds_dev = seeds, int(seeds.numel()), 0
+        if n_live_dev is not None:              # the first-sampled layer reads its seed count on the device, like the others
+            n_seeds, n_seeds_dev = -1, n_live_dev.data_ptr()
         for n in range(L):
             cap = self.caps[n]
             cs, ws = cap["S"], self.ws[n]

@@ -165,6 +165,13 @@ def ledger_dict(rec):
     return out
 
 
+BATCH_STATS_PUSH, BATCH_STATS_CLEAR = 0, 1
+
+
+class BatchStats(C.Structure):                         # bliss_batch_stats' record (BLISS_BATCH_STATS_BYTES)
+    _fields_ = [("n", C.c_uint64), ("m", C.c_double), ("s", C.c_double), ("reserved", C.c_uint64)]
+
+
 class BlockOut(C.Structure):
     _fields_ = [("indptr", C.c_void_p), ("src", C.c_void_p), ("dst", C.c_void_p), ("pos", C.c_void_p),
                 ("eid", C.c_void_p), ("edge_weights", C.c_void_p), ("q_ij", C.c_void_p), ("t_indptr", C.c_void_p),
@@ -209,6 +216,8 @@ SIGNATURES = {
     "bliss_cross_entropy": [_P, _I64, _P, _I32, _I32, _P, _P, _I64, _P, _P, _P, _P],
     "bliss_cross_entropy_sum": [_P, _I64, _P, _I64, _P, _P, _I32, _I32, _P, _P, _I64, _P, _P, _P, _P],
     "bliss_cross_entropy_masked": [_P, _I64, _P, _I64, _P, _I32, _P, _I32, _I32, _P, _F, _I32, _P, _P, _I64, _P, _P, _P, _P],
+    "bliss_cross_entropy_live": [_P, _I64, _P, _I64, _P, _P, _I32, _P, _I32, _P, _P, _I64, _P, _P, _P, _P],
+    "bliss_bce_logits_live": [_P, _I64, _P, _I64, _P, _P, _I32, _P, _I32, _P, _P, _I64, _P, _P, _P, _P],
     "bliss_bce_logits": [_P, _I64, _P, _I32, _I32, _P, _P, _I64, _P, _P, _P, _P],
     "bliss_bce_logits_sum": [_P, _I64, _P, _I64, _P, _P, _I32, _I32, _P, _P, _I64, _P, _P, _P, _P],
     "bliss_bce_logits_masked": [_P, _I64, _P, _I64, _P, _I32, _P, _I32, _I32, _P, _F, _I32, _P, _P, _I64, _P, _P, _P, _P],
@@ -217,6 +226,7 @@ SIGNATURES = {
     "bliss_adam_step": [C.POINTER(AdamTensors), _P, _F, _F, _F, _F, _P],
     "bliss_step_ledger_bytes": [C.c_int],
     "bliss_step_ledger": [C.c_int, _P, C.c_int, _P, C.c_int, C.POINTER(C.c_int32), _D, _D, _P, _P],
+    "bliss_batch_stats": [C.c_int, _P, C.c_int, _P, _P],
     "bliss_cand_importance": [_P, _I32, C.c_int, _P, _P, _P],
     "bliss_poisson_scale": [_P, _P, _I32, _D, _P, _P],
     "bliss_keyed_select": [_P, _P, _P, _I32, _P, C.c_uint64, C.c_uint64, _I32, _P, _P, _P],
@@ -311,6 +321,7 @@ def _load():
     assert lib.bliss_layer_counts_bytes() == C.sizeof(LayerCounts), "LayerCounts layout mismatch"
     assert all(lib.bliss_step_ledger_bytes(n) == C.sizeof(ledger_struct(n)) for n in range(1, LEDGER_MAX_LAYERS + 1)), \
         "step ledger layout mismatch"
+    assert C.sizeof(BatchStats) == 32, "batch statistics layout mismatch"
     return lib
 
 

@@ -191,7 +191,8 @@ class BanditLadiesSampler(DeviceDraw, BlockSampler):
             blocks.insert(0, blk)                                       # :366
         return blocks[0].srcdata[NID], output_nodes, blocks             # :364,:367
 
-    def sample_blocks_static(self, g, seed_nodes, slot=0, chain_rng=False, external_rng=False, part=None, last_block=True, ready_flag=0):
+    def sample_blocks_static(self, g, seed_nodes, slot=0, chain_rng=False, external_rng=False, part=None, last_block=True, ready_flag=0,
+                             n_live_dev=None):
         """sample_blocks with capacity-padded (static-shape) blocks and no host round trip: everything is only
         ENQUEUED, so the whole train step can be recorded into a HIP graph.  Call ``engine.stage_rng_from_torch()``
         before and ``finish_static()`` after the stream has been synchronised.  Padded rows / edges are inert:
@@ -205,7 +206,7 @@ class BanditLadiesSampler(DeviceDraw, BlockSampler):
         order = list(reversed(range(len(self.nodes_per_layer))))
         blks = eng.enqueue_static([self._w_pos[b] for b in order], seed_nodes, [self.nodes_per_layer[b] for b in order],
                                   self._mode(), self.eta, self.eps, slot=slot, chain_rng=chain_rng, external_rng=external_rng, part=part,
-                                  last_block=last_block, ready_flag=ready_flag, draw_state=self._draw_state_on(g.device))
+                                  last_block=last_block, ready_flag=ready_flag, draw_state=self._draw_state_on(g.device), n_live_dev=n_live_dev)
         blocks = []
         for blk in blks:
             blk.edata[self.output_weight] = blk._edge_weights

@@ -89,6 +89,38 @@ __global__ void __launch_bounds__(64) k_ledger_mode(int mode, char* __restrict__
   }
 }
 
+// The running mean / variance of the input layer's size (train_lightning.py:437-441, BatchSizeCallback.push) as a device record:
+// lane 0 of one wave folds x = K of `layer`'s counts record.  Four separate fp64 operations per fold (-ffp-contract=off), the
+// bits of the same statements in Python floats (tests/batch_stats_ref.py).
+struct BatchStats {
+  unsigned long long n;
+  double m, s;
+  unsigned long long reserved;
+};
+static_assert(sizeof(BatchStats) == BLISS_BATCH_STATS_BYTES, "batch statistics layout");
+
+__global__ void __launch_bounds__(64) k_batch_stats(int mode, const int* __restrict__ counts, int layer, BatchStats* __restrict__ rec) {
+  if (threadIdx.x != 0) return;
+  if (mode == BLISS_BATCH_STATS_CLEAR) {
+    rec->n = 0;
+    rec->m = 0.0;
+    rec->s = 0.0;
+    rec->reserved = 0;
+    return;
+  }
+  const double x = (double)counts[10 * layer + 3];           // LayerCounts: S E C K ...
+  const unsigned long long n = rec->n + 1;
+  const double m_old = rec->m;
+  const double d_old = x - m_old;
+  const double q = d_old / (double)n;
+  const double m_new = m_old + q;
+  const double d_new = x - m_new;
+  const double prod = d_old * d_new;
+  rec->n = n;
+  rec->m = m_new;
+  rec->s = rec->s + prod;
+}
+
 bool layers_ok(int n_layers) { return n_layers >= 1 && n_layers <= BLISS_LEDGER_MAX_LAYERS; }
 
 }  // namespace
@@ -113,5 +145,12 @@ extern "C" int bliss_step_ledger(int mode, const void* loss, int loss_dtype, con
     c.b[n] = n < n_layers ? caps[3 * n + 1] : 0;
   }
   k_step_ledger<<<1, 64, 0, (hipStream_t)stream>>>(loss, loss_dtype, (const int*)counts, n_layers, c, w, regrow_at, (char*)ledger);
+  return (int)hipGetLastError();
+}
+
+extern "C" int bliss_batch_stats(int mode, const int32_t* counts, int layer, void* record, void* stream) {
+  if (!record || (mode != BLISS_BATCH_STATS_PUSH && mode != BLISS_BATCH_STATS_CLEAR)) return BLISS_EINVAL;
+  if (mode == BLISS_BATCH_STATS_PUSH && (!counts || layer < 0 || layer >= BLISS_LEDGER_MAX_LAYERS)) return BLISS_EINVAL;
+  k_batch_stats<<<1, 64, 0, (hipStream_t)stream>>>(mode, (const int*)counts, layer, (BatchStats*)record);
   return (int)hipGetLastError();
 }

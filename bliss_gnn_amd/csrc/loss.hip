@@ -49,14 +49,15 @@ __global__ void __launch_bounds__(CE_TPB) k_cross_entropy(const bf16_t* __restri
                                                           const int* __restrict__ label_ids,
                                                           int n_rows, int n_cls, float* __restrict__ row_loss, bf16_t* __restrict__ dlogits,
                                                           long long d_stride, float* __restrict__ loss_out, unsigned* ticket, int* err,
-                                                          const int* __restrict__ n_rows_dev, float denom, int id_off, int n_table) {
+                                                          const int* __restrict__ n_rows_dev, float denom, int id_off, int n_table, int live) {
   // masked form (bliss_cross_entropy_masked): only the first *n_rows_dev rows count (the others get a zero gradient row and no
   // loss), the divisor is `denom` (a global batch, not this rank's rows), label ids are node ids minus id_off into a table of
-  // n_table rows
+  // n_table rows.  live form (bliss_cross_entropy_live): the same mask, the divisor is the live count itself -- the bits of a
+  // launch with n_rows = that count (rows past it add +0 to the fixed-order sum); no live row: loss 0, not 0 * inf
   const int lane = lane_id(), wave = threadIdx.x >> 6;
-  const float inv_n = 1.0f / (denom > 0.f ? denom : (float)n_rows);
   int n_valid = n_rows;
   if (n_rows_dev) { const int v = *n_rows_dev; n_valid = v < n_rows ? (v < 0 ? 0 : v) : n_rows; }
+  const float inv_n = live ? (n_valid > 0 ? 1.0f / (float)n_valid : 0.f) : 1.0f / (denom > 0.f ? denom : (float)n_rows);
   for (int r = blockIdx.x * (CE_TPB / 64) + wave; r < n_rows; r += gridDim.x * (CE_TPB / 64)) {
     if (r >= n_valid) {                                 // (wave-uniform)
       bf16_t* g0 = dlogits + (long long)r * d_stride;
@@ -105,11 +106,12 @@ __global__ void __launch_bounds__(CE_TPB) k_bce_logits(const bf16_t* __restrict_
                                                        const int* __restrict__ label_ids, int n_rows, int n_cls,
                                                        float* __restrict__ row_loss, bf16_t* __restrict__ dlogits, long long d_stride,
                                                        float* __restrict__ loss_out, unsigned* ticket, int* err,
-                                                       const int* __restrict__ n_rows_dev, float denom, int id_off, int n_table) {
+                                                       const int* __restrict__ n_rows_dev, float denom, int id_off, int n_table, int live) {
+  // live (bliss_bce_logits_live): the divisor is the live count x n_cls, formed as the host forms it for that many rows
   const int lane = lane_id(), wave = threadIdx.x >> 6;
-  const float inv = 1.0f / denom;
   int n_valid = n_rows;
   if (n_rows_dev) { const int v = *n_rows_dev; n_valid = v < n_rows ? (v < 0 ? 0 : v) : n_rows; }
+  const float inv = live ? (n_valid > 0 ? 1.0f / ((float)n_valid * (float)n_cls) : 0.f) : 1.0f / denom;
   for (int r = blockIdx.x * (CE_TPB / 64) + wave; r < n_rows; r += gridDim.x * (CE_TPB / 64)) {
     bf16_t* g = dlogits + (long long)r * d_stride;
     long long li = r;
@@ -151,13 +153,13 @@ __global__ void __launch_bounds__(CE_TPB) k_bce_logits(const bf16_t* __restrict_
 static int ce_launch(const void* logits, int64_t stride, const void* logits2, int64_t stride2, const int64_t* labels, const int32_t* label_ids,
                      int32_t n_rows, int32_t n_cls, float* row_loss, void* dlogits, int64_t d_stride, float* loss_out, uint32_t* ticket,
                      int32_t* err, void* stream, const int32_t* n_rows_dev = nullptr, float denom = 0.f, int32_t id_off = 0,
-                     int32_t n_table = 0) {
+                     int32_t n_table = 0, int live = 0) {
   if (!logits || !labels || !row_loss || !dlogits || !loss_out || !ticket || !err || n_rows <= 0 || n_cls <= 0) return BLISS_EINVAL;
   int grid = (n_rows + CE_TPB / 64 - 1) / (CE_TPB / 64);
   if (grid > 1024) grid = 1024;
   k_cross_entropy<<<grid, CE_TPB, 0, (hipStream_t)stream>>>((const bf16_t*)logits, stride, (const bf16_t*)logits2, stride2, (const long long*)labels,
                                                             label_ids, n_rows, n_cls, row_loss, (bf16_t*)dlogits, d_stride, loss_out, ticket, err,
-                                                            n_rows_dev, denom, id_off, n_table);
+                                                            n_rows_dev, denom, id_off, n_table, live);
   return (int)hipGetLastError();
 }
 
@@ -184,17 +186,25 @@ extern "C" int bliss_cross_entropy_masked(const void* logits, int64_t stride, co
                    stream, n_rows_dev, denom, id_off, n_table);
 }
 
+extern "C" int bliss_cross_entropy_live(const void* logits, int64_t stride, const void* logits2, int64_t stride2, const int64_t* label_table,
+                                        const int32_t* label_ids, int32_t n_rows, const int32_t* n_rows_dev, int32_t n_cls, float* row_loss,
+                                        void* dlogits, int64_t d_stride, float* loss_out, uint32_t* ticket, int32_t* err, void* stream) {
+  if ((!logits2 && !label_ids) || !n_rows_dev) return BLISS_EINVAL;
+  return ce_launch(logits, stride, logits2, stride2, label_table, label_ids, n_rows, n_cls, row_loss, dlogits, d_stride, loss_out, ticket, err,
+                   stream, n_rows_dev, 0.f, 0, 0, 1);
+}
+
 static int bce_launch(const void* logits, int64_t stride, const void* logits2, int64_t stride2, const float* targets, const int32_t* label_ids,
                       int32_t n_rows, int32_t n_cls, float denom, float* row_loss, void* dlogits, int64_t d_stride, float* loss_out,
                       uint32_t* ticket, int32_t* err, void* stream, const int32_t* n_rows_dev = nullptr, int32_t id_off = 0,
-                      int32_t n_table = 0) {
+                      int32_t n_table = 0, int live = 0) {
   if (!logits || !targets || !row_loss || !dlogits || !loss_out || !ticket || !err || n_rows <= 0 || n_cls <= 0 || !(denom > 0.f))
     return BLISS_EINVAL;
   int grid = (n_rows + CE_TPB / 64 - 1) / (CE_TPB / 64);
   if (grid > 1024) grid = 1024;
   k_bce_logits<<<grid, CE_TPB, 0, (hipStream_t)stream>>>((const bf16_t*)logits, stride, (const bf16_t*)logits2, stride2, targets, label_ids, n_rows,
                                                          n_cls, row_loss, (bf16_t*)dlogits, d_stride, loss_out, ticket, err, n_rows_dev, denom,
-                                                         id_off, n_table);
+                                                         id_off, n_table, live);
   return (int)hipGetLastError();
 }
 
@@ -219,4 +229,13 @@ extern "C" int bliss_bce_logits_masked(const void* logits, int64_t stride, const
   if (!label_ids || !n_rows_dev || n_table <= 0 || !(denom > 0.f)) return BLISS_EINVAL;
   return bce_launch(logits, stride, logits2, stride2, target_table, label_ids, n_rows, n_cls, denom, row_loss, dlogits, d_stride, loss_out,
                     ticket, err, stream, n_rows_dev, id_off, n_table);
+}
+
+extern "C" int bliss_bce_logits_live(const void* logits, int64_t stride, const void* logits2, int64_t stride2, const float* target_table,
+                                     const int32_t* label_ids, int32_t n_rows, const int32_t* n_rows_dev, int32_t n_cls, float* row_loss,
+                                     void* dlogits, int64_t d_stride, float* loss_out, uint32_t* ticket, int32_t* err, void* stream) {
+  if ((!logits2 && !label_ids) || !n_rows_dev) return BLISS_EINVAL;
+  // (the host-side divisor only has to pass bce_launch's check: the kernel forms its own from the live count)
+  return bce_launch(logits, stride, logits2, stride2, target_table, label_ids, n_rows, n_cls, (float)n_rows * (float)n_cls, row_loss, dlogits,
+                    d_stride, loss_out, ticket, err, stream, n_rows_dev, 0, 0, 1);
 }

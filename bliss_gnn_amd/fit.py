@@ -490,6 +490,50 @@ class EarlyStopping:
         return val_acc > self.threshold or self.bad >= self.patience
 
 
+class BatchSizeController:
+    """``BatchSizeCallback(limit, factor)`` (``--vertex-limit``, train_lightning.py:425-486): steers the batch size towards
+    ``limit`` input-layer vertices per step.  Every step's ``mfgs[0].num_src_nodes()`` goes through ``push`` (a running mean
+    ``m`` and sum of squared deviations ``s`` over ``n`` steps; the device keeps the same three words, ``load`` takes them from
+    ``GraphedTrainStep.batch_stats()``).  At an epoch's end ``propose(batch_size)`` answers with a new size once the mean is at
+    least ``factor`` standard errors away from the limit,
+
+        limit > 0  and  n >= 2  and  |limit - m| * n >= sqrt(s / (n - 1)) * factor,
+
+    namely ``int(batch_size * limit / m)`` -- and only then are the statistics cleared; otherwise they keep accumulating
+    across epochs.  The reference lets that size reach 0 or pass the split and then fails; here it is clamped to
+    ``[1, max_size]`` and ``clamped`` says whether the clamp changed it."""
+
+    def __init__(self, limit, factor=3):
+        self.limit, self.factor, self.clamped = limit, factor, False
+        self.clear()
+
+    def clear(self):
+        self.n, self.m, self.s = 0, 0.0, 0.0
+
+    def push(self, x):
+        self.n += 1
+        m = self.m
+        self.m += (x - m) / self.n
+        self.s += (x - m) * (x - self.m)
+
+    def load(self, n, m, s):
+        self.n, self.m, self.s = int(n), float(m), float(s)
+
+    def propose(self, batch_size, max_size=None):
+        """The batch size of the next epoch, or None for "keep it"."""
+        if not (self.limit > 0 and self.n >= 2):
+            return None
+        if abs(self.limit - self.m) * self.n < math.sqrt(self.s / (self.n - 1)) * self.factor:
+            return None
+        want = int(batch_size * self.limit / self.m)
+        new = max(want, 1)
+        if max_size is not None:
+            new = min(new, int(max_size))
+        self.clamped = new != want
+        self.clear()
+        return new
+
+
 class ModelCheckpoint:
     """``ModelCheckpoint(monitor='val_acc', save_top_k=1, mode='max')`` (:620-625): keep the best parameters (in memory, and
     on disk when a path is given; the EXP3 state is NOT part of it, as in the reference -- bandit_sampler.py:43).
@@ -555,24 +599,41 @@ def evaluate(g, sampler, model, ids, batch_size, multilabel=False, loss_fn=None,
 
 def fit(g, sampler, model, train_nid, val_nid, test_nid=None, batch_size=1024, lr=0.002, max_epochs=10, max_steps=None,
         multilabel=False, val_acc_target=1.0, early_stopping_patience=1000, checkpoint_path=None, seed=0, log=None,
-        eval_step="eager", train_metric=False, train_step="eager"):
+        eval_step="eager", train_metric=False, train_step="eager", vertex_limit=-1, limit_factor=3, batch_capacity=None):
     """One run of ``trainer.fit`` + the final evaluation (train_lightning.py:640-705).  Returns a dict of metrics.
     ``eval_step``: "eager" (``evaluate`` as it stands) or "graphed" (one train.GraphedEvalStep serves every epoch's validation;
     the sampler needs a static-shape path).  ``train_metric``: keep train_acc (:143) on the device beside every step and add it,
     reset per epoch, to the history entries.  ``train_step``: "eager" (TrainStep, a loss read back per step) or "graphed" (the
     epoch's steps replayed from one captured train.GraphedTrainStep whose ledger keeps the epoch's statistics on the device,
     DESIGN.md section 18: the same batches, random streams and bits; the sampler needs a static-shape path and the model the
-    one-launch Adam); its history entries also carry ``sampled_nodes`` / ``sampled_edges``."""
+    one-launch Adam); its history entries also carry ``sampled_nodes`` / ``sampled_edges``.
+
+    ``vertex_limit`` > 0 (``--vertex-limit``, train_lightning.py:425-486): a ``BatchSizeController(vertex_limit,
+    limit_factor)`` sees every step's input-layer size and, at each epoch's end, may set the batch size of the following epochs
+    (training and validation), clamped to ``[1, min(len(train_nid), batch_capacity)]``.  The history entries then carry
+    ``batch_size`` (the epoch's), ``batch_size_clamped``, ``input_nodes`` (the controller's ``n``, ``m``, ``s`` at the epoch's end)
+    and ``sampled_nodes`` / ``sampled_edges`` in both loops.  The graphed loop runs under ``batch_capacity`` seeds (default twice
+    the batch size): one captured step serves every size, nothing is re-captured, and the statistics come with the epoch's one
+    read-back.  ``-1`` (and no ``batch_capacity``): the loops as they were."""
     if eval_step not in ("eager", "graphed"):
         raise ValueError("eval_step must be 'eager' or 'graphed', not %r" % (eval_step,))
     if train_step not in ("eager", "graphed"):
         raise ValueError("train_step must be 'eager' or 'graphed', not %r" % (train_step,))
     g = as_graph(g)
+    ctl = BatchSizeController(vertex_limit, limit_factor) if vertex_limit > 0 else None
+    if batch_capacity is not None and not int(batch_size) <= int(batch_capacity):
+        raise ValueError("batch_capacity (%d) must be at least the batch size (%d)" % (int(batch_capacity), int(batch_size)))
     if train_step == "graphed":
         return _fit_graphed(g, sampler, model, train_nid, val_nid, test_nid, batch_size, lr, max_epochs, max_steps, multilabel,
-                            val_acc_target, early_stopping_patience, checkpoint_path, seed, log, eval_step, train_metric)
+                            val_acc_target, early_stopping_patience, checkpoint_path, seed, log, eval_step, train_metric, ctl,
+                            batch_capacity)
     step = TrainStep(g, sampler, model, lr=lr, multilabel=multilabel, train_metric=train_metric)
-    ev = GraphedEvalStep(g, sampler, model, batch_size, multilabel, loss_fn=step.loss_fn) if eval_step == "graphed" else None
+    ev_cap = batch_capacity
+    if ev_cap is None and ctl is not None and eval_step == "graphed":
+        ev_cap = 2 * int(batch_size)                  # (the replayed validation follows the batch size inside a capacity)
+    max_bs = int(train_nid.numel()) if ev_cap is None else min(int(train_nid.numel()), int(ev_cap))
+    cur_bs, clamped = int(batch_size), False
+    ev = GraphedEvalStep(g, sampler, model, batch_size, multilabel, loss_fn=step.loss_fn, batch_capacity=ev_cap) if eval_step == "graphed" else None
     sched, stopper, ckpt = StepLR(step.opt, 5, 0.01), EarlyStopping(val_acc_target, early_stopping_patience), ModelCheckpoint(checkpoint_path)
     loader = BatchLoader(train_nid, batch_size, shuffle=True, drop_last=True, seed=seed)
     history, n_steps = [], 0
@@ -581,15 +642,28 @@ def fit(g, sampler, model, train_nid, val_nid, test_nid=None, batch_size=1024, l
         tot, cnt = 0.0, 0
         for seeds in loader:
             tot += float(step(seeds)); cnt += 1; n_steps += 1
+            if ctl is not None:
+                ctl.push(step.last["mfgs"][0].num_src_nodes())                   # :467
             if max_steps is not None and n_steps >= max_steps:
                 break
-        val_acc, val_loss = evaluate(g, sampler, model, val_nid, batch_size, multilabel, step.loss_fn, step=ev)
+        val_acc, val_loss = evaluate(g, sampler, model, val_nid, cur_bs, multilabel, step.loss_fn, step=ev)
         ckpt.update(val_acc, model, epoch)
         history.append(dict(epoch=epoch, train_loss=tot / max(cnt, 1), val_acc=val_acc, val_loss=val_loss, lr=step.opt.param_groups[0]["lr"]))
         if train_metric:
             history[-1]["train_acc"] = step.train_acc.compute()                 # (one read-back per epoch)
             step.train_acc.reset()
             step.train_acc.check_errors()
+        if ctl is not None:
+            L = len(sampler.nodes_per_layer)
+            history[-1].update(batch_size=cur_bs, batch_size_clamped=clamped, input_nodes=dict(n=ctl.n, m=ctl.m, s=ctl.s),
+                               sampled_nodes=[step.num_sampled_nodes(i) for i in range(L + 1)],
+                               sampled_edges=[step.num_sampled_edges(i) for i in range(L)])
+            new = ctl.propose(cur_bs, max_bs)                                    # on_train_epoch_end, :472-486
+            if new is not None:
+                cur_bs, clamped = new, ctl.clamped
+                loader.set_batch_size(new)
+                if ev is not None:
+                    ev.set_batch_size(new)
         if log:
             log(history[-1])
         sched.step()                                                             # per epoch (:205-216)
@@ -614,7 +688,7 @@ def _final_metrics(g, model, ckpt, train_nid, val_nid, test_nid, multilabel):
 
 
 def _fit_graphed(g, sampler, model, train_nid, val_nid, test_nid, batch_size, lr, max_epochs, max_steps, multilabel, val_acc_target,
-                 early_stopping_patience, checkpoint_path, seed, log, eval_step, train_metric):
+                 early_stopping_patience, checkpoint_path, seed, log, eval_step, train_metric, ctl=None, batch_capacity=None):
     """``fit`` with the epoch's steps replayed from one captured train step (train.GraphedTrainStep with its ledger): the same
     protocol, batches, random streams and bits as the eager loop; the host reads one ledger record per epoch."""
     static = hasattr(sampler, "sample_blocks_static") and (getattr(sampler, "_poisson", False) or getattr(sampler, "draw", "host") == "device")
@@ -623,12 +697,20 @@ def _fit_graphed(g, sampler, model, train_nid, val_nid, test_nid, batch_size, lr
                                   "samplers have one, and the samplers that draw on the device: draw='device', labor, neighbor-exp3)"
                                   % (type(sampler).__name__, " with draw='host'" if hasattr(sampler, "draw") else ""))
     from .optim import Adam
-    step = GraphedTrainStep(g, sampler, model, batch_size, lr=lr, multilabel=multilabel, train_metric=train_metric, ledger=True)
+    # a batch-size controller needs room to move: the step is captured once for ``cap`` seeds and runs any live count below it
+    cap = batch_capacity
+    if cap is None and ctl is not None:
+        cap = 2 * int(batch_size)
+    if cap is not None:
+        cap = max(min(int(cap), int(train_nid.numel())), int(batch_size))
+    cur_bs, clamped = int(batch_size), False
+    step = GraphedTrainStep(g, sampler, model, batch_size, lr=lr, multilabel=multilabel, train_metric=train_metric, ledger=True,
+                            batch_capacity=cap)
     if not isinstance(step.opt, Adam):
         raise TypeError("fit(train_step='graphed') needs the one-launch Adam of bliss_gnn_amd.optim (contiguous bf16 parameters on the "
                         "GPU, at most %d tensors): a replayed step runs no Python, so the learning rate StepLR rewrites must live on "
                         "the device; this model's parameters get %s" % (_lib.ADAM_MAX_TENSORS, type(step.opt).__name__))
-    ev = GraphedEvalStep(g, sampler, model, batch_size, multilabel, loss_fn=step.loss_fn) if eval_step == "graphed" else None
+    ev = GraphedEvalStep(g, sampler, model, batch_size, multilabel, loss_fn=step.loss_fn, batch_capacity=cap) if eval_step == "graphed" else None
     sched, stopper, ckpt = StepLR(step.opt, 5, 0.01), EarlyStopping(val_acc_target, early_stopping_patience), ModelCheckpoint(checkpoint_path)
     loader = BatchLoader(train_nid, batch_size, shuffle=True, drop_last=True, seed=seed)
     L = len(sampler.nodes_per_layer)
@@ -638,20 +720,21 @@ def _fit_graphed(g, sampler, model, train_nid, val_nid, test_nid, batch_size, lr
         # capacities from a second loader with the same ids and seed, leaving torch's generator and the draw step where they
         # were: the epoch's batches and the sampler's random stream stay those of the eager loop
         with _rng_kept(sampler, g):
-            step.calibrate(BatchLoader(train_nid, batch_size, shuffle=True, drop_last=True, seed=seed).forever())
+            step.calibrate(BatchLoader(train_nid, batch_size if cap is None else cap, shuffle=True, drop_last=True, seed=seed).forever())
         eng = sampler._engine
         for epoch in range(max_epochs):
             model.train()
+            batches = iter(loader)                                               # (a new batch size takes effect here)
             n = len(loader) if max_steps is None else min(len(loader), max_steps - n_steps)
-            step.run(iter(loader), n)                                            # (the first one captures: its steps are epoch 0's)
+            step.run(batches, n)                                                 # (the first one captures: its steps are epoch 0's)
             n_steps += n
             rec = step.ledger()                                                  # THE read-back of the epoch
             step.reset_epoch()
             if ev is not None:
-                val_acc, val_loss = evaluate(g, sampler, model, val_nid, batch_size, multilabel, step.loss_fn, step=ev)
+                val_acc, val_loss = evaluate(g, sampler, model, val_nid, cur_bs, multilabel, step.loss_fn, step=ev)
             else:
                 with _keep_static_caps(eng):                                     # (eager sampling beside the captured train graph)
-                    val_acc, val_loss = evaluate(g, sampler, model, val_nid, batch_size, multilabel, step.loss_fn)
+                    val_acc, val_loss = evaluate(g, sampler, model, val_nid, cur_bs, multilabel, step.loss_fn)
             ckpt.update(val_acc, model, epoch)
             history.append(dict(epoch=epoch, train_loss=rec["loss_sum"] / max(rec["steps_epoch"], 1), val_acc=val_acc, val_loss=val_loss,
                                 lr=step.opt.param_groups[0]["lr"]))
@@ -661,6 +744,16 @@ def _fit_graphed(g, sampler, model, train_nid, val_nid, test_nid, batch_size, lr
                 step.train_acc.check_errors()
             history[-1]["sampled_nodes"] = [step.num_sampled_nodes(i, rec) for i in range(L + 1)]
             history[-1]["sampled_edges"] = [step.num_sampled_edges(i, rec) for i in range(L)]
+            if ctl is not None:
+                ctl.load(**step.batch_stats(rec))                                # the device's n, m, s: came with the read-back above
+                history[-1].update(batch_size=cur_bs, batch_size_clamped=clamped, input_nodes=dict(n=ctl.n, m=ctl.m, s=ctl.s))
+                new = ctl.propose(cur_bs, min(int(train_nid.numel()), cap))      # on_train_epoch_end, :472-486
+                if new is not None:                                              # the loader's size; the live count follows the
+                    cur_bs, clamped = new, ctl.clamped                           # batches -- no re-capture
+                    loader.set_batch_size(new)
+                    step.clear_batch_stats()
+                    if ev is not None:
+                        ev.set_batch_size(new)
             if log:
                 log(history[-1])
             sched.step()                                                         # per epoch (:205-216)

@@ -70,7 +70,8 @@ class LadiesSampler(DeviceDraw, BlockSampler):
             self._engine.exact_k = self.draw == "device"
         return self._engine
 
-    def sample_blocks_static(self, g, seed_nodes, slot=0, chain_rng=False, external_rng=False, part=None, last_block=True, ready_flag=0):
+    def sample_blocks_static(self, g, seed_nodes, slot=0, chain_rng=False, external_rng=False, part=None, last_block=True, ready_flag=0,
+                             n_live_dev=None):
         if not self._poisson and self.draw != "device":
             raise NotImplementedError(self._NO_STATIC)
         g = self._graph(g)
@@ -79,7 +80,7 @@ class LadiesSampler(DeviceDraw, BlockSampler):
         order = list(reversed(range(len(self.nodes_per_layer))))
         blks = eng.enqueue_static([w_pos] * len(order), seed_nodes, [self.nodes_per_layer[b] for b in order], self._mode(), 0.0,
                                   self.eps, slot=slot, chain_rng=chain_rng, external_rng=external_rng, part=part, last_block=last_block, ready_flag=ready_flag,
-                                  draw_state=self._draw_state_on(g.device))
+                                  draw_state=self._draw_state_on(g.device), n_live_dev=n_live_dev)
         blocks = []
         for blk in blks:
             blk.edata[self.output_weight] = blk._edge_weights

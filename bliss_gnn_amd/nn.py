@@ -94,12 +94,44 @@ def sage_epilogue(self_out, neigh, p, ctr, seed):
 
 
 # ------------------------------------------------------------------------------------------------ loss (csrc/loss.hip)
+_row_ids = {}
+
+
+def _identity_ids(n, device):
+    """int32 [n] = 0 .. n-1: the label ids of a live launch whose labels are gathered already (the live entry points take
+    bliss_cross_entropy_sum's arguments, which name the labels through ids); built once per size and device."""
+    key = (int(n), str(device))
+    if key not in _row_ids:
+        _row_ids[key] = torch.arange(int(n), dtype=torch.int32, device=device)
+    return _row_ids[key]
+
+
+def _live_word(n_rows_dev, device):
+    """The live row count of a capacity-padded batch as the kernels take it: one int32 word on ``device``."""
+    if not (torch.is_tensor(n_rows_dev) and n_rows_dev.dtype == torch.int32 and n_rows_dev.numel() == 1 and n_rows_dev.device == device):
+        raise ValueError("n_rows_dev: one int32 word on the logits' device")
+    return n_rows_dev
+
+
+def _live_kw(n_rows_dev):
+    """The launch helpers' keyword for a live row count; nothing without one: their calls are then the ones they were."""
+    return {} if n_rows_dev is None else {"n_rows_dev": n_rows_dev}
+
+
+_NO_LIVE = ("a live row count (n_rows_dev) needs the one-launch loss kernel -- bf16 logits [rows, classes] on the GPU with unit "
+            "column stride and labels on the same device; there is no masked form of torch's functional loss here")
+
+
 class _CrossEntropy(torch.autograd.Function):
     """nn.CrossEntropyLoss() (mean) on bf16 logits, forward and gradient in one launch (train_lightning.py:77-79, :142)."""
 
     @staticmethod
-    def forward(ctx, logits, labels, state):
+    def forward(ctx, logits, labels, state, n_rows_dev=None):
         x = logits if logits.stride(1) == 1 else logits.contiguous()
+        if n_rows_dev is not None:
+            loss, dx = _ce_launch(x, labels, state, n_rows_dev=n_rows_dev)
+            ctx.save_for_backward(dx)
+            return loss.to(logits.dtype)
         n, c = x.shape
         dx = torch.empty(n, c, dtype=torch.bfloat16, device=x.device)
         rows = torch.empty(n, dtype=torch.float32, device=x.device)
@@ -112,15 +144,23 @@ class _CrossEntropy(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         (dx,) = ctx.saved_tensors
-        return dx * g.to(dx.dtype), None, None
+        return dx * g.to(dx.dtype), None, None, None
 
 
-def _ce_launch(x, labels, state, x2=None, label_ids=None):
+def _ce_launch(x, labels, state, x2=None, label_ids=None, n_rows_dev=None):
     n, c = x.shape
     dx = torch.empty(n, c, dtype=torch.bfloat16, device=x.device)
     rows = torch.empty(n, dtype=torch.float32, device=x.device)
     loss = torch.empty((), dtype=torch.float32, device=x.device)
-    if x2 is None and label_ids is None:
+    if n_rows_dev is not None:                  # n is the capacity; the divisor is the device's count (bliss_cross_entropy_live)
+        if x2 is None and label_ids is None:
+            label_ids = _identity_ids(n, x.device)
+        _lib.check(_lib.lib.bliss_cross_entropy_live(x.data_ptr(), x.stride(0), 0 if x2 is None else x2.data_ptr(),
+                                                     0 if x2 is None else x2.stride(0), labels.data_ptr(),
+                                                     0 if label_ids is None else label_ids.data_ptr(), n, n_rows_dev.data_ptr(), c,
+                                                     rows.data_ptr(), dx.data_ptr(), dx.stride(0), loss.data_ptr(), state.data_ptr(),
+                                                     state.data_ptr() + 4, _stream()), "bliss_cross_entropy_live")
+    elif x2 is None and label_ids is None:
         _lib.check(_lib.lib.bliss_cross_entropy(x.data_ptr(), x.stride(0), labels.data_ptr(), n, c, rows.data_ptr(), dx.data_ptr(),
                                                 dx.stride(0), loss.data_ptr(), state.data_ptr(), state.data_ptr() + 4, _stream()),
                    "bliss_cross_entropy")
@@ -149,13 +189,23 @@ def _check_loss_errors(module, name):
 
 class CrossEntropyLoss(nn.Module):
     """``nn.CrossEntropyLoss()`` as the reference builds it (train_lightning.py:77-79): mean over the batch, class-index
-    targets.  bf16 logits on the GPU take the one-launch kernel; anything else goes to torch's functional form."""
+    targets.  bf16 logits on the GPU take the one-launch kernel; anything else goes to torch's functional form.
 
-    def forward(self, logits, target):
+    ``n_rows_dev`` (``forward``, ``backward_from``, ``backward_from_parts``): the logits are a capacity-padded batch and only the
+    first ``n_rows_dev[0]`` rows (an int32 word on the device) are live -- the mean is over those, the other rows get a zero
+    gradient and nothing of them is read (csrc/loss.hip: bliss_cross_entropy_live).  Kernel path only: anything else raises."""
+
+    def forward(self, logits, target, n_rows_dev=None):
         if logits.is_cuda and logits.dtype == torch.bfloat16 and logits.dim() == 2 and target.dtype == torch.int64 and target.dim() == 1:
             if getattr(self, "_state", None) is None or self._state.device != logits.device:
                 self._state = torch.zeros(2, dtype=torch.int32, device=logits.device)       # [0] ticket, [1] error word
+            if n_rows_dev is not None:
+                if target.device != logits.device or target.shape[0] != logits.shape[0]:
+                    raise NotImplementedError(_NO_LIVE)
+                return _CrossEntropy.apply(logits, target.contiguous(), self._state, _live_word(n_rows_dev, logits.device))
             return _CrossEntropy.apply(logits, target.contiguous(), self._state)
+        if n_rows_dev is not None:
+            raise NotImplementedError(_NO_LIVE)
         return torch.nn.functional.cross_entropy(logits, target)
 
     def _eligible(self, logits, target):
@@ -166,22 +216,28 @@ class CrossEntropyLoss(nn.Module):
         loss and no one-hot).  This reads the word, clears it and raises."""
         _check_loss_errors(self, "CrossEntropyLoss")
 
-    def backward_from(self, logits, target):
+    def backward_from(self, logits, target, n_rows_dev=None):
         """loss.backward() without the loss node: the kernel produces d loss / d logits with the loss, so the train loops call
         ``logits.backward(that)`` directly (saves the ones-fill, the scalar cast and the elementwise product of the generic
         route).  Returns the loss (fp32 scalar, detached)."""
         if not self._eligible(logits, target):
+            if n_rows_dev is not None:
+                raise NotImplementedError(_NO_LIVE)
             loss = self.forward(logits, target)
             loss.backward()
             return loss.detach()
         if getattr(self, "_state", None) is None or self._state.device != logits.device:
             self._state = torch.zeros(2, dtype=torch.int32, device=logits.device)
         x = logits.detach()
-        loss, dx = _ce_launch(x if x.stride(1) == 1 else x.contiguous(), target.contiguous(), self._state)
+        if n_rows_dev is not None:
+            if target.device != logits.device or target.shape[0] != logits.shape[0]:
+                raise NotImplementedError(_NO_LIVE)
+            n_rows_dev = _live_word(n_rows_dev, logits.device)
+        loss, dx = _ce_launch(x if x.stride(1) == 1 else x.contiguous(), target.contiguous(), self._state, **_live_kw(n_rows_dev))
         logits.backward(dx)
         return loss
 
-    def backward_from_parts(self, a, b, label_table, label_ids):
+    def backward_from_parts(self, a, b, label_table, label_ids, n_rows_dev=None):
         """backward_from for logits = a + b that are never formed (the output layer's fc_self + h_neigh) and labels
         = label_table[label_ids] that are never gathered: one launch, then the same gradient into both addends."""
         ok = (a.is_cuda and a.dtype == torch.bfloat16 and b.dtype == torch.bfloat16 and a.shape == b.shape and a.dim() == 2
@@ -189,10 +245,12 @@ class CrossEntropyLoss(nn.Module):
               and label_table.is_contiguous() and label_ids.dtype == torch.int32 and label_ids.is_contiguous()
               and label_ids.numel() == a.shape[0])
         if not ok:
-            return self.backward_from(a + b, torch.index_select(label_table, 0, label_ids.long()))
+            return self.backward_from(a + b, torch.index_select(label_table, 0, label_ids.long()), n_rows_dev)
         if getattr(self, "_state", None) is None or self._state.device != a.device:
             self._state = torch.zeros(2, dtype=torch.int32, device=a.device)
-        loss, dx = _ce_launch(a.detach(), label_table, self._state, x2=b.detach(), label_ids=label_ids)
+        if n_rows_dev is not None:
+            n_rows_dev = _live_word(n_rows_dev, a.device)
+        loss, dx = _ce_launch(a.detach(), label_table, self._state, x2=b.detach(), label_ids=label_ids, **_live_kw(n_rows_dev))
         torch.autograd.backward([a, b], [dx, dx])
         return loss
 
@@ -201,23 +259,31 @@ class _BCEWithLogits(torch.autograd.Function):
     """nn.BCEWithLogitsLoss() (mean) on bf16 logits and fp32 targets, forward and gradient in one launch (train_lightning.py:77-79)."""
 
     @staticmethod
-    def forward(ctx, logits, target, state):
-        loss, dx = _bce_launch(logits, target, state)
+    def forward(ctx, logits, target, state, n_rows_dev=None):
+        loss, dx = _bce_launch(logits, target, state, **_live_kw(n_rows_dev))
         ctx.save_for_backward(dx)
         return loss
 
     @staticmethod
     def backward(ctx, g):
         (dx,) = ctx.saved_tensors
-        return dx * g.to(dx.dtype), None, None
+        return dx * g.to(dx.dtype), None, None, None
 
 
-def _bce_launch(x, targets, state, x2=None, label_ids=None):
+def _bce_launch(x, targets, state, x2=None, label_ids=None, n_rows_dev=None):
     n, c = x.shape
     dx = torch.empty(n, c, dtype=torch.bfloat16, device=x.device)
     rows = torch.empty(n, dtype=torch.float32, device=x.device)
     loss = torch.empty((), dtype=torch.float32, device=x.device)
-    if x2 is None and label_ids is None:
+    if n_rows_dev is not None:                  # n is the capacity; the divisor is the device's count (bliss_bce_logits_live)
+        if x2 is None and label_ids is None:
+            label_ids = _identity_ids(n, x.device)
+        _lib.check(_lib.lib.bliss_bce_logits_live(x.data_ptr(), x.stride(0), 0 if x2 is None else x2.data_ptr(),
+                                                  0 if x2 is None else x2.stride(0), targets.data_ptr(),
+                                                  0 if label_ids is None else label_ids.data_ptr(), n, n_rows_dev.data_ptr(), c,
+                                                  rows.data_ptr(), dx.data_ptr(), dx.stride(0), loss.data_ptr(), state.data_ptr(),
+                                                  state.data_ptr() + 4, _stream()), "bliss_bce_logits_live")
+    elif x2 is None and label_ids is None:
         _lib.check(_lib.lib.bliss_bce_logits(x.data_ptr(), x.stride(0), targets.data_ptr(), n, c, rows.data_ptr(), dx.data_ptr(),
                                              dx.stride(0), loss.data_ptr(), state.data_ptr(), state.data_ptr() + 4, _stream()),
                    "bliss_bce_logits")
@@ -234,7 +300,8 @@ class BCEWithLogitsLoss(nn.Module):
     """``nn.BCEWithLogitsLoss()`` as the reference builds it for the multi-label dataset (train_lightning.py:77-79): mean over
     all (row, class) pairs, no ``weight``, no ``pos_weight``.  bf16 logits on the GPU with fp32 targets take the one-launch
     kernel (csrc/loss.hip: k_bce_logits; the loss is an fp32 scalar, as torch's is for these dtypes); anything else goes to
-    torch's functional form."""
+    torch's functional form.  ``n_rows_dev``: a live row count, as ``CrossEntropyLoss`` takes it (bliss_bce_logits_live: the mean
+    is over the live rows x classes); kernel path only."""
 
     def _eligible(self, logits, target):
         return (logits.is_cuda and logits.dtype == torch.bfloat16 and logits.dim() == 2 and logits.stride(1) == 1 and logits.numel() > 0
@@ -250,22 +317,30 @@ class BCEWithLogitsLoss(nn.Module):
         """A label id outside the target table (backward_from_parts) sets a word; this reads it, clears it and raises."""
         _check_loss_errors(self, "BCEWithLogitsLoss")
 
-    def forward(self, logits, target):
+    def forward(self, logits, target, n_rows_dev=None):
         if self._eligible(logits, target):
+            if n_rows_dev is not None:
+                return _BCEWithLogits.apply(logits, target, self._state_on(logits.device), _live_word(n_rows_dev, logits.device))
             return _BCEWithLogits.apply(logits, target, self._state_on(logits.device))
+        if n_rows_dev is not None:
+            raise NotImplementedError(_NO_LIVE)
         return torch.nn.functional.binary_cross_entropy_with_logits(logits, target)
 
-    def backward_from(self, logits, target):
+    def backward_from(self, logits, target, n_rows_dev=None):
         """loss.backward() without the loss node (see CrossEntropyLoss.backward_from).  Returns the loss (fp32 scalar, detached)."""
         if not self._eligible(logits, target):
+            if n_rows_dev is not None:
+                raise NotImplementedError(_NO_LIVE)
             loss = self.forward(logits, target)
             loss.backward()
             return loss.detach()
-        loss, dx = _bce_launch(logits.detach(), target, self._state_on(logits.device))
+        if n_rows_dev is not None:
+            n_rows_dev = _live_word(n_rows_dev, logits.device)
+        loss, dx = _bce_launch(logits.detach(), target, self._state_on(logits.device), **_live_kw(n_rows_dev))
         logits.backward(dx)
         return loss
 
-    def backward_from_parts(self, a, b, label_table, label_ids):
+    def backward_from_parts(self, a, b, label_table, label_ids, n_rows_dev=None):
         """backward_from for logits = a + b that are never formed (the output layer's fc_self + h_neigh) and targets
         = label_table[label_ids] ([V, n_cls] fp32) that are never gathered: one launch, then the same gradient into both addends."""
         ok = (a.is_cuda and a.dtype == torch.bfloat16 and b.dtype == torch.bfloat16 and a.shape == b.shape and a.dim() == 2
@@ -275,8 +350,10 @@ class BCEWithLogitsLoss(nn.Module):
               and label_ids.dtype == torch.int32 and label_ids.is_contiguous() and label_ids.numel() == a.shape[0]
               and label_ids.device == a.device)
         if not ok:
-            return self.backward_from(a + b, torch.index_select(label_table, 0, label_ids.long()))
-        loss, dx = _bce_launch(a.detach(), label_table, self._state_on(a.device), x2=b.detach(), label_ids=label_ids)
+            return self.backward_from(a + b, torch.index_select(label_table, 0, label_ids.long()), n_rows_dev)
+        if n_rows_dev is not None:
+            n_rows_dev = _live_word(n_rows_dev, a.device)
+        loss, dx = _bce_launch(a.detach(), label_table, self._state_on(a.device), x2=b.detach(), label_ids=label_ids, **_live_kw(n_rows_dev))
         torch.autograd.backward([a, b], [dx, dx])
         return loss
 

@@ -28,19 +28,33 @@ class BatchLoader:
 
     def __init__(self, ids, batch_size, shuffle=True, drop_last=True, seed=2):
         self.ids, self.bs, self.shuffle, self.drop_last = ids, int(batch_size), shuffle, drop_last
+        self._next_bs = None
         self.gen = torch.Generator(device=ids.device)
         self.gen.manual_seed(seed)
+
+    def set_batch_size(self, bs):
+        """``datamodule.batch_size = bs`` + ``loop.setup_data()`` (train_lightning.py:478-485): the size of the batches from the
+        next ``__iter__`` on.  A pass in progress keeps its slices, and ``len`` the count of the pass last started."""
+        bs = int(bs)
+        if bs < 1:
+            raise ValueError("batch size must be at least 1, got %d" % bs)
+        self._next_bs = bs
 
     def __len__(self):
         n = self.ids.numel()
         return n // self.bs if self.drop_last else (n + self.bs - 1) // self.bs
 
     def __iter__(self):
+        if self._next_bs is not None:
+            self.bs, self._next_bs = self._next_bs, None
+        return self._batches(self.bs, len(self))
+
+    def _batches(self, bs, count):
         ids = self.ids
         if self.shuffle:
             ids = ids[torch.randperm(ids.numel(), generator=self.gen, device=ids.device)]
-        for i in range(len(self)):
-            yield ids[i * self.bs:(i + 1) * self.bs]
+        for i in range(count):
+            yield ids[i * bs:(i + 1) * bs]
 
     def forever(self):
         while True:
@@ -80,10 +94,16 @@ def _bce_loss():
     return BCEWithLogitsLoss()
 
 
-def _loss_backward(loss_fn, pred, labels, opt):
+def _loss_backward(loss_fn, pred, labels, opt, n_rows_dev=None):
     """loss = loss_fn(pred, labels); opt.zero_grad(); loss.backward() (train_lightning.py:142 + Lightning).  The one-launch
-    losses of csrc/loss.hip hand d loss / d pred over with the loss, so their route skips the loss node.  Returns the detached loss."""
+    losses of csrc/loss.hip hand d loss / d pred over with the loss, so their route skips the loss node.  Returns the detached loss.
+    ``n_rows_dev``: the live row count of a capacity-padded batch (one-launch losses only)."""
     opt.zero_grad(set_to_none=True)
+    if n_rows_dev is not None:
+        if not hasattr(loss_fn, "backward_from"):
+            raise NotImplementedError("a batch capacity needs the one-launch losses of csrc/loss.hip (BLISS_FUSED_CE / "
+                                      "BLISS_FUSED_BCE are off): torch's losses have no live row count")
+        return loss_fn.backward_from(pred, labels, n_rows_dev=n_rows_dev)
     if hasattr(loss_fn, "backward_from"):
         return loss_fn.backward_from(pred, labels)
     loss = loss_fn(pred, labels)
@@ -91,16 +111,44 @@ def _loss_backward(loss_fn, pred, labels, opt):
     return loss.detach()
 
 
-def _update_metric(metric, pred, mfgs):
+def _update_metric(metric, pred, mfgs, n_rows_dev=None):
     """``metric.update`` for a batch: the output block's labels as (label table, destination ids) -- the pair the one-launch
-    losses take, so nothing is gathered for the metric -- or, for a block without a parent table, its own labels."""
+    losses take, so nothing is gathered for the metric -- or, for a block without a parent table, its own labels.
+    ``n_rows_dev``: the live row count of a capacity-padded batch."""
     lab = mfgs[-1].dstdata
     parent = getattr(lab, "_parent", None)
     if parent is not None and "labels" in parent:
         from .graph import NID
-        metric.update(pred, label_table=parent["labels"], label_ids=lab[NID])
+        metric.update(pred, label_table=parent["labels"], label_ids=lab[NID], n_rows_dev=n_rows_dev)
     else:
-        metric.update(pred, lab["labels"])
+        metric.update(pred, lab["labels"], n_rows_dev=n_rows_dev)
+
+
+def _live_refusal(model):
+    """Why ``model`` cannot run on a capacity-padded OUTPUT block, or None if it can.  Rows past the live
+    count hold whatever the buffers held: only a path whose every row loop is bounded by the block's device-side counts keeps
+    them out of the weight gradients (0 * NaN is NaN)."""
+    from .model import SAGE
+    from .nn import _mfma_bwd_on
+    if not isinstance(model, SAGE):
+        return ("%s has no live path: its layers run over all capacity rows of the output block (only SAGE on its MFMA path bounds "
+                "every row loop by the block's device-side counts)" % type(model).__name__)
+    ps = list(model.parameters())
+    if not ps or not model._mfma_ok(ps[0]) or not _mfma_bwd_on():
+        return ("SAGE runs live on its MFMA path only (bf16 on the GPU, ReLU, layers within the tile kernel's limits, "
+                "BLISS_SAGE_MFMA / BLISS_SAGE_MFMA_BWD not 0): the library-GEMM path multiplies stale capacity rows into the "
+                "weight gradients")
+    return None
+
+
+def _check_capacity(batch_size, batch_capacity, model, what):
+    cap = int(batch_capacity)
+    if cap < int(batch_size) or int(batch_size) < 1:
+        raise ValueError("%s: batch_capacity (%d) must be at least the batch size (%d)" % (what, cap, int(batch_size)))
+    why = _live_refusal(model)
+    if why is not None:
+        raise NotImplementedError("%s(batch_capacity=...): %s" % (what, why))
+    return cap
 
 
 def _train_metric(train_metric, multilabel):
@@ -207,16 +255,26 @@ class GraphedTrainStep:
     blocks are padded to capacities learned from a few eager steps (``calibrate``); true sizes stay on the device
     and come back with the step's single end-of-step sync.  Results are bit-identical to the eager path."""
 
-    def __init__(self, g, sampler, model, batch_size, lr=0.002, multilabel=False, distributed=False, train_metric=False, ledger=False):
+    def __init__(self, g, sampler, model, batch_size, lr=0.002, multilabel=False, distributed=False, train_metric=False, ledger=False,
+                 batch_capacity=None):
         self.g, self.sampler, self.model, self.bs = g, sampler, model, int(batch_size)
         self.distributed = distributed          # replicas: gradient all-reduce + EXP3 exchange recorded in the graph too
+        # batch_capacity (DESIGN.md section 20): the seed buffer has that many slots and a device word says how many are live, so
+        # ONE captured graph serves every batch size 1 .. capacity; None: the step and its graph are exactly the ones without it
+        self.capacity = None
+        if batch_capacity is not None:
+            if distributed:
+                raise NotImplementedError("batch_capacity is the single-process step's (every rank would need the same live count)")
+            self.capacity = _check_capacity(batch_size, batch_capacity, model, type(self).__name__)
         # ledger: one more launch at the end of the step (csrc/ledger.hip) folds it into a device-resident record -- what ``run``
         # needs to leave the host out of the loop; False: the step and its graph are exactly the ones without it
         self._ledger_on, self._ledger, self.w = bool(ledger), None, 0.99
         self.regrows, self._want_regrow, self._ledger_regrow_at = 0, False, None
         if self._ledger_on:
             rec = _lib.ledger_new(len(sampler.nodes_per_layer))
-            self._ledger = torch.frombuffer(bytearray(bytes(rec)), dtype=torch.int64).to(g.device)
+            # (with a capacity the 32-byte batch statistics record of bliss_batch_stats follows the ledger's: one read-back has both)
+            raw = bytearray(bytes(rec)) + (bytearray(C.sizeof(_lib.BatchStats)) if self.capacity is not None else bytearray())
+            self._ledger = torch.frombuffer(raw, dtype=torch.int64).to(g.device)
         self.loss_fn = _bce_loss() if multilabel else _ce_loss()
         # train_acc: one more launch inside the captured graph (metrics.MicroF1: counts stay on the device); None unless asked
         # for, and the graph is then exactly the one without it
@@ -224,18 +282,42 @@ class GraphedTrainStep:
         # ONE launch for all parameter tensors (csrc/optim.hip; torch's foreach path is ~40 launches of >= 5 us inside a graph,
         # its fused multi-tensor kernel ~50 us)
         self.opt = make_adam(model, lr, capturable=True)
-        self.seeds = torch.zeros(self.bs, dtype=torch.int32, device=g.device)
+        self._cap_s = self.bs if self.capacity is None else self.capacity        # slots of the seed buffer = the static seed capacity
+        self.seeds = torch.zeros(self._cap_s, dtype=torch.int32, device=g.device)
+        self.n_live, self._n_enqueued = None, None
+        if self.capacity is not None:
+            self.n_live = torch.full((1,), self.bs, dtype=torch.int32, device=g.device)
+            self._n_enqueued = self.bs
         self.graph = None
         self.num_steps = 0
         self.last_counts = None
         self.loss = None
 
+    def _load_batch(self, seeds):
+        """Enqueue the batch: the seed copy and, with a capacity, the live count -- the latter only when it changed.  No sync.
+        Sizes outside 1 .. capacity are refused here, on the host, before anything is enqueued."""
+        if self.capacity is None:
+            self.seeds.copy_(seeds)
+            return
+        n = int(seeds.numel())
+        if not 1 <= n <= self.capacity:
+            raise ValueError("a batch of %d seeds does not fit this step: 1 .. %d (batch_capacity)" % (n, self.capacity))
+        self.seeds[:n].copy_(seeds)
+        if n != self._n_enqueued:
+            self.n_live.fill_(n)
+            self._n_enqueued = n
+
     def calibrate(self, loader, steps=8, k_margin=1.5, b_margin=3.0):
-        """Run eager sampling to learn per-layer sizes, then fix the static capacities."""
+        """Run eager sampling to learn per-layer sizes, then fix the static capacities.  With a batch capacity ``loader`` yields
+        batches of ``batch_capacity`` seeds: the capacities are those of the largest batch the step serves."""
         L = len(self.sampler.nodes_per_layer)
         mx = [dict(K=0, B=0, E=0) for _ in range(L)]
         for _ in range(steps):
-            _, _, blocks = self.sampler.sample_blocks(self.g, next(loader))
+            seeds = next(loader)
+            if self.capacity is not None and int(seeds.numel()) != self.capacity:
+                raise ValueError("calibrate: with batch_capacity=%d the loader must yield batches of that many seeds, got %d"
+                                 % (self.capacity, int(seeds.numel())))
+            _, _, blocks = self.sampler.sample_blocks(self.g, seeds)
             for n, b in enumerate(reversed(blocks)):                      # sampling order
                 mx[n]["K"] = max(mx[n]["K"], b.num_src_nodes())
                 mx[n]["B"] = max(mx[n]["B"], b.num_edges())
@@ -247,16 +329,17 @@ class GraphedTrainStep:
             mx = [dict(K=int(k), B=int(b), E=int(e)) for k, b, e in t.tolist()]
         fan = [self.sampler.nodes_per_layer[b] for b in reversed(range(L))]
         self._margins, self._hw = (k_margin, b_margin), [dict(m) for m in mx]
-        self.sampler._engine.set_static_caps(self.bs, fan, mx, k_margin, b_margin)
+        self.sampler._engine.set_static_caps(self._cap_s, fan, mx, k_margin, b_margin)
 
     def _body(self):
-        input_nodes, output_nodes, mfgs = self.sampler.sample_blocks_static(self.g, self.seeds)
+        live = {} if self.capacity is None else dict(n_live_dev=self.n_live)
+        input_nodes, output_nodes, mfgs = self.sampler.sample_blocks_static(self.g, self.seeds, **live)
         x = _inputs(self.model, mfgs)
         y = mfgs[-1].dstdata["labels"]
         pred = self.model(mfgs, x)
         if self.train_acc is not None:
-            _update_metric(self.train_acc, pred, mfgs)             # train_lightning.py:143
-        loss = _loss_backward(self.loss_fn, pred, y, self.opt)
+            _update_metric(self.train_acc, pred, mfgs, self.n_live)    # train_lightning.py:143
+        loss = _loss_backward(self.loss_fn, pred, y, self.opt, self.n_live)
         bandit = hasattr(self.sampler, "exp3")                     # train_lightning.py:469: only for the bandit samplers
         if self.distributed:
             from . import dist as bdist
@@ -291,7 +374,7 @@ class GraphedTrainStep:
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             for _ in range(warmup):
-                self.seeds.copy_(next(loader))
+                self._load_batch(next(loader))
                 eng.stage_rng_from_torch()
                 self.loss = self._body()
                 self._finish()
@@ -306,7 +389,7 @@ class GraphedTrainStep:
         import gc
         gc.collect()
         torch.cuda.synchronize()
-        self.seeds.copy_(next(loader))
+        self._load_batch(next(loader))
         self.sampler._engine.stage_rng_from_torch()
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph, **_cap_kw()):
@@ -316,7 +399,7 @@ class GraphedTrainStep:
         self._finish()
 
     def __call__(self, seeds):
-        self.seeds.copy_(seeds)
+        self._load_batch(seeds)
         self.sampler._engine.stage_rng_from_torch()
         self.graph.replay()
         self._finish()
@@ -324,7 +407,7 @@ class GraphedTrainStep:
 
     def eager_step(self, seeds):
         """The same static-shape step launched kernel by kernel (used to time individual kernels)."""
-        self.seeds.copy_(seeds)
+        self._load_batch(seeds)
         self.sampler._engine.stage_rng_from_torch()
         loss = self._body()
         self._finish()
@@ -361,6 +444,27 @@ class GraphedTrainStep:
         _lib.check(_lib.lib.bliss_step_ledger(_lib.LEDGER_STEP, loss.data_ptr(), code, self.sampler._engine._slot_counts[0].data_ptr(),
                                               self._n_layers(), self._ledger_caps(), self.w, self._ledger_regrow_at,
                                               self._ledger.data_ptr(), torch.cuda.current_stream().cuda_stream), "bliss_step_ledger")
+        if self.capacity is not None:              # the input layer (the LAST-sampled one) into the running mean / variance
+            _lib.check(_lib.lib.bliss_batch_stats(_lib.BATCH_STATS_PUSH, self.sampler._engine._slot_counts[0].data_ptr(),
+                                                  self._n_layers() - 1, self._stats_ptr(), torch.cuda.current_stream().cuda_stream),
+                       "bliss_batch_stats")
+
+    def _stats_ptr(self):
+        return self._ledger.data_ptr() + int(_lib.lib.bliss_step_ledger_bytes(self._n_layers()))
+
+    def batch_stats(self, rec=None):
+        """The running statistics of the input layer's size, ``dict(n=, m=, s=)`` -- what ``fit.BatchSizeController.load`` takes
+        (``rec``: a ledger record read already; else one read-back behind everything enqueued)."""
+        if not self._ledger_on or self.capacity is None:
+            raise RuntimeError("this step keeps no batch statistics (ledger=True and a batch_capacity)")
+        return dict((rec if rec is not None else self.ledger())["batch_stats"])
+
+    def clear_batch_stats(self):
+        """Enqueue the clear of the batch statistics (after a change of the batch size: train_lightning.py:486)."""
+        if not self._ledger_on or self.capacity is None:
+            raise RuntimeError("this step keeps no batch statistics (ledger=True and a batch_capacity)")
+        _lib.check(_lib.lib.bliss_batch_stats(_lib.BATCH_STATS_CLEAR, None, 0, self._stats_ptr(), torch.cuda.current_stream().cuda_stream),
+                   "bliss_batch_stats")
 
     def _ledger_mode(self, mode):
         _lib.check(_lib.lib.bliss_step_ledger(mode, None, 0, None, self._n_layers(), None, 0.0, 0.0, self._ledger.data_ptr(),
@@ -368,7 +472,12 @@ class GraphedTrainStep:
 
     def _parse(self, buf):
         """A host copy of the record (an int64 tensor) as a dict."""
-        return _lib.ledger_dict(_lib.ledger_struct(self._n_layers()).from_buffer_copy(buf.numpy().tobytes()))
+        raw = buf.numpy().tobytes()
+        out = _lib.ledger_dict(_lib.ledger_struct(self._n_layers()).from_buffer_copy(raw))
+        if self.capacity is not None:
+            st = _lib.BatchStats.from_buffer_copy(raw[int(_lib.lib.bliss_step_ledger_bytes(self._n_layers())):])
+            out["batch_stats"] = dict(n=int(st.n), m=float(st.m), s=float(st.s))
+        return out
 
     def ledger(self):
         """The record as a dict, behind everything enqueued on the current stream (one read-back)."""
@@ -419,7 +528,7 @@ class GraphedTrainStep:
             mx = [dict(K=max(h.get("K", 0), rec["hw_K"][n]), B=max(h.get("B", 0), rec["hw_B"][n]), E=max(h.get("E", 0), rec["hw_E"][n]))
                   for n, h in enumerate(self._hw)]
             fan = [self.sampler.nodes_per_layer[b] for b in reversed(range(L))]
-            eng.set_static_caps(self.bs, fan, mx, *self._margins)
+            eng.set_static_caps(self._cap_s, fan, mx, *self._margins)
             self._hw = mx
             self._ledger_mode(_lib.LEDGER_REARM)
             self._want_regrow = False
@@ -491,7 +600,7 @@ class GraphedTrainStep:
                 self._regrow_now(loader, refix=self._want_regrow)
                 done += 1
                 continue
-            self.seeds.copy_(next(loader))
+            self._load_batch(next(loader))
             if free:
                 self.graph.replay()
                 self.num_steps += 1
@@ -595,7 +704,11 @@ class PipelinedTrainStep(GraphedTrainStep):
     One call = two optimiser steps on two batches; the batch sampled last is trained by the next call (``drain``
     trains the final one)."""
 
-    def __init__(self, g, sampler, model, batch_size, lr=0.002, multilabel=False, distributed=False, train_metric=False):
+    def __init__(self, g, sampler, model, batch_size, lr=0.002, multilabel=False, distributed=False, train_metric=False,
+                 batch_capacity=None):
+        if batch_capacity is not None:
+            raise NotImplementedError("PipelinedTrainStep has no batch_capacity: its sampler is split over streams around a "
+                                      "host-known seed count (use GraphedTrainStep)")
         if train_metric:
             raise NotImplementedError("PipelinedTrainStep keeps no train_acc (its forward pass is split over two graphs and two "
                                       "streams): use TrainStep or GraphedTrainStep with train_metric=True")
@@ -1188,11 +1301,17 @@ class GraphedEvalStep:
     captured train graph depends on them); otherwise ``calibrate`` fixes them, from the split's own batches, the first time
     ``run`` needs them.  The ragged last batch runs eagerly through ``sampler.sample`` into the same accumulators, and so does a
     batch whose replay exceeded a capacity (``finish_static`` raised): its per-batch buffer is dropped, torch's generator and the
-    draw step are put back, and the batch is sampled again by the engine's regrowing eager loop (``fallbacks`` counts these)."""
+    draw step are put back, and the batch is sampled again by the engine's regrowing eager loop (``fallbacks`` counts these).
+
+    ``batch_capacity``: the seed buffer has that many slots and a device word says how many are live --
+    EVERY batch of 1 .. capacity seeds is then replayed from the one graph, the ragged last batch of a split included
+    (``replays`` counts them), the eager path remains only as the capacity-overflow fallback, the static capacities are those
+    of ``batch_capacity`` seeds (shared with a train step of the same capacity) and ``set_batch_size`` changes the batch size
+    without a re-capture."""
 
     SLOT = 2                                   # (0 and 1 are the training loops')
 
-    def __init__(self, g, sampler, model, batch_size, multilabel=False, loss_fn=None):
+    def __init__(self, g, sampler, model, batch_size, multilabel=False, loss_fn=None, batch_capacity=None):
         static = hasattr(sampler, "sample_blocks_static") and (getattr(sampler, "_poisson", False)
                                                                or getattr(sampler, "draw", "host") == "device")
         if not static:
@@ -1203,7 +1322,16 @@ class GraphedEvalStep:
         self.g, self.sampler, self.model, self.bs, self.multilabel = g, sampler, model, int(batch_size), bool(multilabel)
         self.loss_fn = loss_fn if loss_fn is not None else (_bce_loss() if multilabel else _ce_loss())
         dev = g.device
-        self.seeds = torch.zeros(self.bs, dtype=torch.int32, device=dev)
+        self.capacity = None if batch_capacity is None else _check_capacity(batch_size, batch_capacity, model, type(self).__name__)
+        if self.capacity is not None and not hasattr(self.loss_fn, "backward_from"):
+            raise NotImplementedError("a batch capacity needs the one-launch losses of csrc/loss.hip: torch's have no live row count")
+        self._cap_s = self.bs if self.capacity is None else self.capacity
+        self.seeds = torch.zeros(self._cap_s, dtype=torch.int32, device=dev)
+        self.n_live, self._n_enqueued = None, None
+        if self.capacity is not None:
+            self.n_live = torch.full((1,), self.bs, dtype=torch.int32, device=dev)
+            self._n_enqueued = self.bs
+        self.replays = 0
         self.metric, self._batch_metric = MicroF1(multilabel), MicroF1(multilabel)
         self.metric._state_on(dev)
         self._batch_metric._state_on(dev)
@@ -1221,10 +1349,33 @@ class GraphedEvalStep:
         L = len(self.sampler.nodes_per_layer)
         if caps is None or len(caps) != L or not all("E" in c for c in caps):
             return False
-        if caps[0]["S"] != self.bs:
+        if caps[0]["S"] != self._cap_s:
             raise ValueError("the sampler's static capacities were fixed for batches of %d, not %d: a GraphedEvalStep shares them "
-                             "with the train step that fixed them and needs its batch size" % (caps[0]["S"], self.bs))
+                             "with the train step that fixed them and needs its batch size%s"
+                             % (caps[0]["S"], self._cap_s, "" if self.capacity is None else " (its batch_capacity)"))
         return True
+
+    def set_batch_size(self, bs):
+        """The batch size of the next ``run`` (``val_dataloader`` follows ``datamodule.batch_size``, train_lightning.py:410-422);
+        needs a capacity, and stays within it."""
+        if self.capacity is None:
+            raise RuntimeError("a GraphedEvalStep without batch_capacity is captured for one batch size")
+        if not 1 <= int(bs) <= self.capacity:
+            raise ValueError("batch size %d outside 1 .. %d (batch_capacity)" % (int(bs), self.capacity))
+        self.bs = int(bs)
+
+    def _load_batch(self, seeds):
+        """Enqueue the seed copy and, with a capacity, the live count when it changed.  No sync."""
+        if self.capacity is None:
+            self.seeds.copy_(seeds)
+            return
+        n = int(seeds.numel())
+        if not 1 <= n <= self.capacity:
+            raise ValueError("a batch of %d seeds does not fit this step: 1 .. %d (batch_capacity)" % (n, self.capacity))
+        self.seeds[:n].copy_(seeds)
+        if n != self._n_enqueued:
+            self.n_live.fill_(n)
+            self._n_enqueued = n
 
     def _rng_kept(self):
         return _rng_kept(self.sampler, self.g)
@@ -1239,7 +1390,7 @@ class GraphedEvalStep:
         with self._rng_kept():
             for _ in range(steps):
                 seeds = next(loader)
-                if seeds.numel() != self.bs:
+                if seeds.numel() != self._cap_s and self.capacity is None:
                     continue
                 _, _, blocks = self.sampler.sample_blocks(self.g, seeds)
                 for n, b in enumerate(reversed(blocks)):                  # sampling order
@@ -1247,11 +1398,19 @@ class GraphedEvalStep:
                     mx[n]["B"] = max(mx[n]["B"], b.num_edges())
                     mx[n]["E"] = max(mx[n]["E"], b._counts.E)
         fan = [self.sampler.nodes_per_layer[b] for b in reversed(range(L))]
-        self._engine().set_static_caps(self.bs, fan, mx, k_margin, b_margin)
+        self._engine().set_static_caps(self._cap_s, fan, mx, k_margin, b_margin)
 
     # -- the batch --------------------------------------------------------------------------------------------------------
     def _body(self):
         self._batch_metric._counts.zero_()
+        if self.capacity is not None:
+            _, _, mfgs = self.sampler.sample_blocks_static(self.g, self.seeds, slot=self.SLOT, n_live_dev=self.n_live)
+            with torch.no_grad():
+                pred = self.model(mfgs, _inputs(self.model, mfgs))
+                loss = self.loss_fn(pred, mfgs[-1].dstdata["labels"], n_rows_dev=self.n_live)
+                _update_metric(self._batch_metric, pred, mfgs, self.n_live)
+                self._batch_loss.copy_(loss.float() * self.n_live[0].float())      # loss * n, n from the device word
+            return
         _, _, mfgs = self.sampler.sample_blocks_static(self.g, self.seeds, slot=self.SLOT)
         with torch.no_grad():
             pred = self.model(mfgs, _inputs(self.model, mfgs))
@@ -1282,7 +1441,7 @@ class GraphedEvalStep:
             with torch.cuda.stream(side):
                 for _ in range(warmup):
                     with self._rng_kept():
-                        self.seeds.copy_(seeds)
+                        self._load_batch(seeds)
                         eng.stage_rng_from_torch()
                         self._body()
                         side.synchronize()
@@ -1293,7 +1452,7 @@ class GraphedEvalStep:
             torch.cuda.current_stream().wait_stream(side)
             gc.collect()
             torch.cuda.synchronize()
-            self.seeds.copy_(seeds)
+            self._load_batch(seeds)
             eng.stage_rng_from_torch()
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph, **_cap_kw()):
@@ -1307,9 +1466,10 @@ class GraphedEvalStep:
             self.capture(seeds)
         state = torch.get_rng_state()
         ds = self.sampler._draw_state_on(self.g.device) if hasattr(self.sampler, "_draw_state_on") else None
-        self.seeds.copy_(seeds)
+        self._load_batch(seeds)
         eng.stage_rng_from_torch()
         self.graph.replay()
+        self.replays += 1
         torch.cuda.current_stream().synchronize()
         try:
             self.sampler.finish_static(self.SLOT)
@@ -1341,10 +1501,13 @@ class GraphedEvalStep:
         try:
             self.metric.reset()
             self._loss_sum.zero_()
-            if ids.numel() >= self.bs and not self.has_static_caps():
+            if self.capacity is not None:
+                if ids.numel() and not self.has_static_caps():      # from batches of `capacity` seeds (the whole split if it is smaller)
+                    self.calibrate(BatchLoader(ids, min(self.capacity, ids.numel()), shuffle=False, drop_last=True).forever())
+            elif ids.numel() >= self.bs and not self.has_static_caps():
                 self.calibrate(BatchLoader(ids, self.bs, shuffle=False, drop_last=True).forever())
             for seeds in BatchLoader(ids, self.bs, shuffle=False, drop_last=False):
-                if seeds.numel() == self.bs:
+                if seeds.numel() == self.bs or self.capacity is not None:
                     self._replayed(seeds)
                 else:
                     self._eager(seeds)

@@ -533,6 +533,17 @@ int bliss_cross_entropy_masked(const void* logits, int64_t stride, const void* l
                                float denom, int32_t n_cls, float* row_loss, void* dlogits, int64_t d_stride, float* loss_out,
                                uint32_t* ticket, int32_t* err, void* stream);
 
+/* The same under a LIVE row count: n_rows is the capacity (the launch bound) and, with
+ * n = min(max(*n_rows_dev, 0), n_rows), rows r < n get exactly the loss term and gradient row bliss_cross_entropy_sum produces
+ * when called with n_rows = n -- the divisor is n, formed on the device; the rounding points and the fixed order of the final sum
+ * are the same, so *loss_out and gradient rows 0 .. n-1 are bit-equal to that call.  Rows r >= n get a zero gradient row and
+ * nothing of their logits, label ids or labels is read.  n == 0: *loss_out = 0 and all-zero gradients, no NaN.  One launch, no
+ * host read, capturable: one captured launch serves every batch size up to n_rows.  Error bits and BLISS_EINVAL cases are
+ * bliss_cross_entropy_sum's; n_rows_dev == NULL is BLISS_EINVAL too. */
+int bliss_cross_entropy_live(const void* logits, int64_t stride, const void* logits2, int64_t stride2, const int64_t* label_table,
+                             const int32_t* label_ids, int32_t n_rows, const int32_t* n_rows_dev, int32_t n_cls, float* row_loss,
+                             void* dlogits, int64_t d_stride, float* loss_out, uint32_t* ticket, int32_t* err, void* stream);
+
 /* nn.BCEWithLogitsLoss() (mean; no weight, no pos_weight: train_lightning.py:77-79 for the multi-label dataset, load_graph.py:69-71)
  * on bf16 logits [n_rows, n_cls] and fp32 targets [n_rows, n_cls] (rows contiguous), forward and gradient in one launch, in fp32 from
  * e = exp(-|x|): *loss_out = mean (max(x, 0) - x y + log1p(e)), dlogits = bf16((sigmoid(x) - y) / (n_rows n_cls)), one rounding.
@@ -555,6 +566,14 @@ int bliss_bce_logits_masked(const void* logits, int64_t stride, const void* logi
                             int32_t n_table, const int32_t* label_ids, int32_t id_off, int32_t n_rows, const int32_t* n_rows_dev,
                             float denom, int32_t n_cls, float* row_loss, void* dlogits, int64_t d_stride, float* loss_out,
                             uint32_t* ticket, int32_t* err, void* stream);
+
+/* The same under a LIVE row count, as bliss_cross_entropy_live: with n = min(max(*n_rows_dev, 0), n_rows), rows r < n get the
+ * loss terms and gradient row of bliss_bce_logits_sum called with n_rows = n (divisor (float)n * (float)n_cls, formed on the
+ * device as the host forms it), bit for bit; rows r >= n get a zero gradient row and nothing of theirs is read; n == 0: loss 0,
+ * zero gradients, no NaN.  Error bits and BLISS_EINVAL cases are bliss_bce_logits_sum's; n_rows_dev == NULL is BLISS_EINVAL too. */
+int bliss_bce_logits_live(const void* logits, int64_t stride, const void* logits2, int64_t stride2, const float* target_table,
+                          const int32_t* label_ids, int32_t n_rows, const int32_t* n_rows_dev, int32_t n_cls, float* row_loss,
+                          void* dlogits, int64_t d_stride, float* loss_out, uint32_t* ticket, int32_t* err, void* stream);
 
 /* Micro-F1 (torchmetrics Multiclass / MultilabelF1Score(average='micro'), train_lightning.py:68-70, :143, :179-203) as counts on
  * the device: one launch ADDS this batch's {tp, fp, fn, n} to counts[0..3] (int64; never overwritten) with 64-bit integer atomics,
@@ -647,6 +666,26 @@ int bliss_adam_step(const bliss_adam_t* tensors, float* state, float beta1, floa
 int bliss_step_ledger_bytes(int n_layers);
 int bliss_step_ledger(int mode, const void* loss, int loss_dtype, const int32_t* counts, int n_layers, const int32_t* caps,
                       double w, double regrow_at, void* ledger, void* stream);
+
+/* Batch statistics (csrc/ledger.hip): ONE launch of one wave folds the finished step's input-layer source
+ * count into a 32-byte device record -- the running mean and variance BatchSizeCallback keeps on the host
+ * (train_lightning.py:425-486), so that a loop of replayed steps can steer its batch size from one read per epoch.
+ *
+ * The record (8-byte aligned, BLISS_BATCH_STATS_BYTES):  0 uint64 n    8 double m    16 double s    24 uint64 reserved (zero)
+ * A fresh record is all zero.
+ *
+ * The rule (normative; restated by tests/batch_stats_ref.py) -- mode BLISS_BATCH_STATS_PUSH, counts = bliss_layer_counts_t[],
+ * x = (double)K of record `layer` (the LAST-sampled layer is the input layer: mfgs[0].num_src_nodes(), :467):
+ *   n += 1;  m_old = m;  m += (x - m_old) / (double)n;  s += (x - m_old) * (x - m)
+ * -- a difference, a quotient, a sum, a difference, a product, a sum: separate fp64 operations, never fused (:437-441 in Python
+ * floats give the same bits).  mode BLISS_BATCH_STATS_CLEAR: the record is zeroed (only `record` is read).
+ * The step ledger's record, its size and bliss_step_ledger are untouched by this.
+ * BLISS_EINVAL before any launch: record NULL; an unknown mode; in mode PUSH counts NULL or layer outside
+ * 0 .. BLISS_LEDGER_MAX_LAYERS - 1. */
+#define BLISS_BATCH_STATS_BYTES 32
+#define BLISS_BATCH_STATS_PUSH 0
+#define BLISS_BATCH_STATS_CLEAR 1
+int bliss_batch_stats(int mode, const int32_t* counts, int layer, void* record, void* stream);
 
 /* normalized_edata    bandit_sampler.py:20-27: w_pos[p] = bf16(1 / bf16(indeg(dst(p)))). */
 int bliss_normalized_edata(const bliss_graph_t* g, void* w_pos, void* stream);
