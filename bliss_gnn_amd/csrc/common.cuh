@@ -155,6 +155,31 @@ __device__ __forceinline__ bf16_t fixed_wide_to_bf(int64_t hi, int64_t lo, int s
   return (bf16_t)(sign | ((uint32_t)e << 7) | ((uint32_t)q & 0x7f));
 }
 
+// ---- straight-line form of the two converters (bf_to_fixed, bf_to_fixed_wide) for their common case.  A term b is PLAIN for
+// `frac` when it is non-negative, finite and its shift  max(e, 1) - 134 + frac  lies in [0, 55].  For a plain term
+//   bf_to_fixed(b, frac, bad) == bf_to_fixed_wide(b, frac, lo, sticky, bad) == bf_fixed_plain(b, frac),
+// nothing is added to `lo`, `sticky` and `bad` stay as they were: both converters take their `shift >= 0` branch with the sign
+// clear.  With the sign clear the exponent field is b >> 7, so "plain" is one range test on the 16 bits (bf_plain_range, uniform
+// per column).  A caller ORs "not plain" over its terms, takes one vote per wave or workgroup and runs the branch-free sum when
+// nobody objects -- the lost-bits vote of the wide form is then known to be zero -- and the generic converters otherwise.
+// bf_fixed_plain of a term that is NOT plain is some harmless number (no trap, no out-of-range shift); of +0 it is 0.
+struct PlainRange { unsigned lo, span; };
+__device__ __forceinline__ PlainRange bf_plain_range(int frac) {
+  int e_lo = 134 - frac, e_hi = 189 - frac;          // bounds of max(e, 1)
+  if (e_hi > 254) e_hi = 254;                          // finite
+  PlainRange r;
+  r.lo = e_lo <= 1 ? 0u : (unsigned)e_lo << 7;         // (e_lo <= 1: zero and the subnormals, which shift like e = 1, are in)
+  const unsigned end = e_hi < 1 ? 0u : (unsigned)(e_hi + 1) << 7;
+  r.span = end > r.lo ? end - r.lo : 0u;
+  return r;
+}
+__device__ __forceinline__ bool bf_is_plain(bf16_t b, PlainRange r) { return (unsigned)b - r.lo < r.span; }
+__device__ __forceinline__ long long bf_fixed_plain(bf16_t b, int frac) {
+  const unsigned ef = (unsigned)b >> 7, m = (b & 0x7fu) | (ef ? 0x80u : 0u);
+  const int shift = (int)(ef ? ef : 1u) - 134 + frac;
+  return (long long)((uint64_t)m << (shift & 63));
+}
+
 __device__ __forceinline__ int lane_id() { return threadIdx.x & (BLISS_WAVE - 1); }
 
 __device__ __forceinline__ int64_t shfl_up_i64(int64_t v, int d) {

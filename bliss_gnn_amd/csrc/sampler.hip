@@ -41,6 +41,15 @@ namespace {
 #define SPAN (64 * ITEMS)
 #define SEG_ZERO_WGS 8
 #define LONG_COL 1024                     // = COL_BIG below: columns longer than this get a workgroup in k_col_sums
+#define LONG_FIRST 4096                   // ... and those longer than this are listed first: their workgroups start first
+
+// One long column as k_col_sums takes it: everything the consumer needs in one load (seed index, length, first CSC position),
+// so its chain is count -> entry -> weights.  The list is ColEnt[cap_s], filled from both ends -- columns of more than
+// LONG_FIRST edges from the front, the other long ones from the back -- followed by the two counts (int[2]).
+struct alignas(8) ColEnt {
+  int k, n;
+  long long p0;
+};
 
 struct EdgeAt {
   int k;          // seed index (local destination id); valid iff e < E
@@ -86,14 +95,14 @@ __device__ __forceinline__ void seg_scan_body(const int64_t* __restrict__ indptr
                                               int* __restrict__ local_id, int num_nodes, int* __restrict__ src_cnt, int cap_k,
                                               int* __restrict__ bin_cursor, int n_bins, long long* __restrict__ col_base,
                                               int* __restrict__ span_seg, long long frontier_cap, int* entry_flag,
-                                              int wg, int n_wgs, bool keep_sums, int* sh, int* st_sh, int* hub_count = nullptr) {
+                                              int wg, int n_wgs, bool keep_sums, int* sh, int* st_sh, ColEnt* long_list = nullptr) {
   // This kernel runs <=> everything enqueued before this layer has completed (stream / graph order): tell a consumer on
   // another stream (bliss_flag_wait) without an event, i.e. without cutting a captured graph in two.
   if (entry_flag && wg == 0 && threadIdx.x == 0) __hip_atomic_store(entry_flag, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-  // hub_count (optional): int[cap_s + 1] -- the columns of more than COL_BIG edges, in no particular order, count last: k_col_sums
-  // gives each of them a workgroup without walking over the short ones
-  __shared__ int sh_long;
-  if (hub_count && threadIdx.x == 0) sh_long = 0;     // (appended to behind the first block_excl_scan's barriers)
+  // long_list (optional): the columns of more than COL_BIG edges as ColEnt records, longest class first (no order inside a
+  // class): k_col_sums gives each of them a workgroup without walking over the short ones, and starts the longest ones first
+  __shared__ int sh_long[2];
+  if (long_list && threadIdx.x < 2) sh_long[threadIdx.x] = 0;     // (appended to behind the first block_excl_scan's barriers)
   int S = S_host >= 0 ? S_host : *S_dev;
   int bad = 0;
   if (S > cap_s) { S = cap_s; bad |= BLISS_ERR_CAP_SEEDS; }         // clamp: results invalid but in bounds
@@ -138,14 +147,22 @@ __device__ __forceinline__ void seg_scan_body(const int64_t* __restrict__ indptr
         // what every frontier pass needs to find its edges without a search and without chasing seeds -> indptr:
         col_base[k] = deg > 0 ? cols[i] - start : 0;    // CSC position = col_base[k] + frontier position
       }
-      if (hub_count) {
-        const bool is_long = k < S && deg > LONG_COL;
-        const unsigned long long mask = __ballot(is_long);
-        if (mask) {
-          int base_l = 0;
-          if (lane_id() == 0) base_l = atomicAdd(&sh_long, __popcll(mask));
-          base_l = __shfl(base_l, 0);
-          if (is_long) hub_count[base_l + __popcll(mask & ((1ull << lane_id()) - 1ull))] = k;
+      if (long_list) {
+        const bool is_long = k < S && deg > LONG_COL, is_first = is_long && deg > LONG_FIRST;
+        const unsigned long long m_first = __ballot(is_first), m_rest = __ballot(is_long && !is_first);
+        if (m_first | m_rest) {
+          int b_first = 0, b_rest = 0;
+          if (lane_id() == 0) {
+            if (m_first) b_first = atomicAdd(&sh_long[0], __popcll(m_first));
+            if (m_rest) b_rest = atomicAdd(&sh_long[1], __popcll(m_rest));
+          }
+          b_first = __shfl(b_first, 0); b_rest = __shfl(b_rest, 0);
+          if (is_long) {                                // at most S <= cap_s entries in all: the two ends never meet
+            const unsigned long long below = (1ull << lane_id()) - 1ull;
+            const int slot = is_first ? b_first + __popcll(m_first & below) : cap_s - 1 - (b_rest + __popcll(m_rest & below));
+            ColEnt ent; ent.k = k; ent.n = deg; ent.p0 = cols[i];
+            long_list[slot] = ent;
+          }
         }
       }
       // span_seg[sp] = the seed column holding frontier position sp * 256.  Done by the whole workgroup over the round's
@@ -170,7 +187,7 @@ __device__ __forceinline__ void seg_scan_body(const int64_t* __restrict__ indptr
   }
   int any_bad = __syncthreads_or(bad);
   if (threadIdx.x == 0) {
-    if (hub_count) hub_count[cap_s] = sh_long;
+    if (long_list) { int* n_long = (int*)(long_list + cap_s); n_long[0] = sh_long[0]; n_long[1] = sh_long[1]; }
     seg_ptr[S] = (int)run;
     cnt->S = S; cnt->E = (any_bad & BLISS_ERR_CAP_FRONTIER) ? 0 : (int)run;
     cnt->C = 0; cnt->K = 0; cnt->B = 0; cnt->iters = 0; cnt->all_one = 0; cnt->c = 1.0;
@@ -184,11 +201,11 @@ __global__ void __launch_bounds__(1024) k_seg_scan(const int64_t* __restrict__ i
                                                    int* __restrict__ local_id, int num_nodes, int* __restrict__ src_cnt, int cap_k,
                                                    int* __restrict__ bin_cursor, int n_bins, long long* __restrict__ col_base,
                                                    int* __restrict__ span_seg, long long frontier_cap, int* entry_flag,
-                                                   int keep_sums, int* hub_count) {
+                                                   int keep_sums, ColEnt* long_list) {
   __shared__ int sh[17];
   __shared__ int st_sh[1024];
   seg_scan_body(indptr, seeds, cnt, S_host, S_dev, cap_s, seed_acc, seg_ptr, local_id, num_nodes, src_cnt, cap_k, bin_cursor, n_bins,
-                col_base, span_seg, frontier_cap, entry_flag, blockIdx.x, gridDim.x, keep_sums != 0, sh, st_sh, hub_count);
+                col_base, span_seg, frontier_cap, entry_flag, blockIdx.x, gridDim.x, keep_sums != 0, sh, st_sh, long_list);
 }
 
 // ---------------------------------------------------------------- K_b: first appearance + sum_j w_ij
@@ -432,6 +449,9 @@ __global__ void __launch_bounds__(FIN_TPB) k_cand_finalize(const int* __restrict
 #ifndef COL_RB
 #define COL_RB 8
 #endif
+#ifndef COL_BLOCK_WGS
+#define COL_BLOCK_WGS 512                 // workgroups that take whole columns, two per CU: each strides over k_seg_scan's list (2048: no faster)
+#endif
 #define COL_BIG (COL_R * 64)              // a wave keeps a whole column of up to 1024 edges in registers
 static_assert(LONG_COL == COL_BIG, "k_seg_scan lists the columns k_col_sums treats as long");
 #ifndef BINRED_TPB
@@ -477,6 +497,23 @@ __device__ __forceinline__ long long block_sum_i64(long long v, long long* sh) {
   return t;
 }
 
+// N bf16 values of a thread, two per 32-bit register (indices are compile-time constants once the loops are unrolled): the
+// column a thread holds between the two sums costs half the registers, which is what keeps k_col_sums at two workgroups per CU
+template <int N>
+struct PackedBf {
+  unsigned v[N / 2];
+  __device__ __forceinline__ void set(int r, bf16_t x) { v[r >> 1] = (r & 1) ? (v[r >> 1] | ((unsigned)x << 16)) : (unsigned)x; }
+  __device__ __forceinline__ bf16_t get(int r) const { return (bf16_t)((r & 1) ? v[r >> 1] >> 16 : v[r >> 1] & 0xffffu); }
+};
+
+// a wave-uniform pointer, held in scalar registers: the column's base stays ONE scalar base + a 32-bit lane offset in every
+// load (left to itself the compiler re-associates base + lane + constant into per-lane 64-bit addresses kept across the kernel)
+__device__ __forceinline__ const bf16_t* uniform_ptr(const bf16_t* p) {
+  const unsigned long long v = (unsigned long long)p;
+  const unsigned lo = __builtin_amdgcn_readfirstlane((int)(unsigned)v), hi = __builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
+  return (const bf16_t*)(((unsigned long long)hi << 32) | lo);
+}
+
 // one WAVE per seed column (typical columns hold a few hundred to a few thousand edges: several columns in flight per
 // workgroup hide the pointer-chasing latency, and the two sums are DPP wave reductions with no barrier); columns longer
 // than COL_BIG are left to a second loop in which the whole workgroup shares one column
@@ -496,110 +533,198 @@ __device__ __forceinline__ void col_store(int k, long long ws_fixed, long long q
 // long columns is MORE threads each: 1024-thread workgroups holding 8 edges per thread in registers took the launch from
 // 47 to 34 us on average over the three layers (512 x 32: 47, 256 x 32: 56, 1024 x 16: 35, 1024 x 32: 43), the step from
 // 0.816 to 0.789 ms, same box.)
-__global__ void __launch_bounds__(COL_TPB) k_col_sums(const int64_t* __restrict__ indptr, const bf16_t* __restrict__ w,
+// Round 7: two workgroups per CU (<= 64 registers: the held column is packed two bf16 per
+// register, the column's base is scalar, the generic converters run from rolled loops), the list in classes with one record per
+// column, the branch-free sums of plain terms with one vote per wave / workgroup, register slots past the column's end skipped
+// by scalar branches, and no load behind a test that does not need it.
+__global__ void __launch_bounds__(COL_TPB, 8) k_col_sums(const int64_t* __restrict__ indptr, const bf16_t* __restrict__ w,
                                                       const int* __restrict__ seeds, const int* __restrict__ seg_ptr,
                                                       const long long* __restrict__ col_base, const int* __restrict__ span_seg,
                                                       LayerCounts* cnt, unsigned long long* __restrict__ acc_w,
                                                       unsigned long long* __restrict__ acc_q, float eta_f, float ome_f,
-                                                      uint2* __restrict__ seed_coef, int n_wave_wgs,
-                                                      const int* __restrict__ long_list, int cap_s) {
+                                                      uint2* __restrict__ seed_coef, int n_block_wgs,
+                                                      const ColEnt* __restrict__ long_list, int cap_s) {
   __shared__ long long sh[COL_TPB / 64];
   __shared__ long long sh2[2 * COL_TPB / 64];
-  const int S = cnt->S, tid = threadIdx.x, lane = lane_id();
-  if (cnt->E == 0) return;
+  const int tid = threadIdx.x, lane = lane_id();
+  // (every level of dependent loads costs a microsecond or more here: the list's counts are asked for together with the layer's
+  // counts, not behind the test on them -- k_seg_scan writes both in every case)
+  const int* n_long = (const int*)(long_list + cap_s);
+  const int S = cnt->S, E = cnt->E, n_first = n_long[0], n_all = n_first + n_long[1];
+  if (E == 0) return;
   int bad = 0;
-  // the first n_wave_wgs workgroups take the short columns (one per wave), the others the long ones (one per workgroup):
-  // both kinds are latency chains, so they run side by side instead of one after the other
-  const int n_block_wgs = (int)gridDim.x - n_wave_wgs;
+  // the first workgroups take the short columns (one per wave), the last n_block_wgs the long ones (one per workgroup, in the
+  // list's order: the longest class first, since the launch lasts as long as its last workgroup): both kinds are latency
+  // chains, so they run side by side instead of one after the other.  (Measured the other way round as well, the whole-column
+  // workgroups at the low block indices: the ones that find nothing in the list then hold the slots the one-wave workgroups
+  // wait for, and the launch is no faster on any layer -- DESIGN.md section 6 item 23.)
+  const int bid_wave = (int)blockIdx.x, bid_block = (int)blockIdx.x - ((int)gridDim.x - n_block_wgs);
   // ---- columns up to COL_BIG edges: one per wave
-  if ((int)blockIdx.x < n_wave_wgs)
-  for (int k = blockIdx.x * (COL_TPB / 64) + (tid >> 6); k < S; k += n_wave_wgs * (COL_TPB / 64)) {
-    const int s0 = seg_ptr[k], n = seg_ptr[k + 1] - s0;
-    if (n == 0 || n > COL_BIG) continue;              // wave-uniform
-    const long long p0 = col_base[k] + s0;
-    bf16_t wr[COL_R];
+  if (bid_block < 0) {
+  // (the launch has a wave for every seed.  The wave's index as a scalar: the column's bounds and base address then live in
+  // scalar registers)
+  const int k = bid_wave * (COL_TPB / 64) + __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int s0 = k < S ? seg_ptr[k] : 0, n = k < S ? seg_ptr[k + 1] - s0 : 0;
+  const long long cb = k < S ? col_base[k] : 0;       // (asked for beside the bounds, not behind the test on them)
+  if (n > 0 && n <= COL_BIG) {                        // wave-uniform
+    const bf16_t* wc = uniform_ptr(w + (cb + s0));
+    PackedBf<COL_R> wr;
     long long part = 0;
     int emax = 1;
+    {
+      bf16_t x[COL_R];                                // (packed only after all the loads are out)
 #pragma unroll
-    for (int r = 0; r < COL_R; ++r) {
-      const int i = lane + r * 64;
-      wr[r] = 0;
-      if (i < n) wr[r] = w[p0 + i];
+      for (int r = 0; r < COL_R; ++r) {
+        const int i = lane + r * 64;
+        x[r] = 0;
+        if (i < n) x[r] = wc[i];
+      }
+#pragma unroll
+      for (int r = 0; r < COL_R; ++r) wr.set(r, x[r]);
     }
 #pragma unroll
     for (int r = 0; r < COL_R; ++r)
-      if (lane + r * 64 < n) emax = max(emax, bf_exp_field(wr[r]));
+      if (lane + r * 64 < n) emax = max(emax, bf_exp_field(wr.get(r)));
     const int wfrac = rel_frac(FRAC_DST, wave_max_u31(emax));      // block-floating: exact relative to the column's largest weight
-    long long part_lo = 0;
-    int sticky = 0;
+    // :129 copy_e_sum over exp3 weights.  Branch-free while every term is plain (common.cuh: the padding's +0 adds 0); one vote
+    const PlainRange wr_ok = bf_plain_range(wfrac);
+    bool odd = false;
 #pragma unroll
     for (int r = 0; r < COL_R; ++r)
-      if (lane + r * 64 < n) part += bf_to_fixed_wide(wr[r], wfrac, &part_lo, &sticky, &bad);  // :129 copy_e_sum over exp3 weights
-    const long long ws_fixed = wave_total_i64(part);
+      if (r * 64 < n) {                                // (scalar branch: register slots past the column's end cost nothing)
+        odd |= lane + r * 64 < n && !bf_is_plain(wr.get(r), wr_ok);
+        part += bf_fixed_plain(wr.get(r), wfrac);
+      }
+    long long ws_fixed;
     bf16_t wsum;
-    if (__ballot(part_lo != 0 || sticky) == 0ull) wsum = fixed_to_bf(ws_fixed, wfrac, &bad);   // nothing lost below the last bit
-    else wsum = fixed_wide_to_bf(ws_fixed, wave_total_i64(part_lo), __ballot(sticky) != 0ull, wfrac, &bad);
+    if (__ballot(odd) == 0ull) {                       // nothing below the last bit, nothing negative or non-finite
+      ws_fixed = wave_total_i64(part);
+      wsum = fixed_to_bf(ws_fixed, wfrac, &bad);
+    } else {
+      long long part_lo = 0;
+      int sticky = 0;
+      part = 0;
+      // (the generic converters run from a rolled loop over the column in L2, not over the registers: unrolled beside the
+      // plain form they cost the registers that keep two workgroups on a CU, and 16 inlined copies of their branches)
+#pragma unroll 4
+      for (int i = lane; i < n; i += 64) part += bf_to_fixed_wide(wc[i], wfrac, &part_lo, &sticky, &bad);
+      ws_fixed = wave_total_i64(part);
+      if (__ballot(part_lo != 0 || sticky) == 0ull) wsum = fixed_to_bf(ws_fixed, wfrac, &bad);   // nothing lost below the last bit
+      else wsum = fixed_wide_to_bf(ws_fixed, wave_total_i64(part_lo), __ballot(sticky) != 0ull, wfrac, &bad);
+    }
     const float a = rbf((1.0f / (float)n) * eta_f);
-    part = 0;
+    // :67 copy_e_sum(insg, edge_prob): the same, q plain <=> 2^-33 <= q < 2^23
+    const PlainRange q_ok = bf_plain_range(FRAC_DST);
+    part = 0; odd = false;
 #pragma unroll
-    for (int r = 0; r < COL_R; ++r) {
-      const int i = lane + r * 64;
-      if (i < n) part += bf_to_fixed(edge_q_pre(wr[r], wsum, a, ome_f), FRAC_DST, &bad);     // :67 copy_e_sum(insg, edge_prob)
+    for (int r = 0; r < COL_R; ++r)
+      if (r * 64 < n) {
+        const bool in = lane + r * 64 < n;
+        const bf16_t q = edge_q_pre(wr.get(r), wsum, a, ome_f);
+        odd |= in && !bf_is_plain(q, q_ok);
+        part += in ? bf_fixed_plain(q, FRAC_DST) : 0ll;
+      }
+    if (__ballot(odd) != 0ull) {
+      part = 0;
+#pragma unroll 4
+      for (int i = lane; i < n; i += 64) part += bf_to_fixed(edge_q_pre(wc[i], wsum, a, ome_f), FRAC_DST, &bad);
     }
     const long long qs_fixed = wave_total_i64(part);
     if (lane == 0) col_store(k, ws_fixed, qs_fixed, wsum, n, eta_f, acc_w, acc_q, seed_coef, &bad);
   }
+  }
   // ---- the long columns: one per workgroup, the first COL_RB * COL_TPB edges held in registers between the two sums
-  if ((int)blockIdx.x >= n_wave_wgs)
-  for (int li = (int)blockIdx.x - n_wave_wgs, n_long = long_list[cap_s]; li < n_long; li += n_block_wgs) {
-    const int k = long_list[li];                      // (k_seg_scan's list: no workgroup walks over short columns)
-    const int s0 = seg_ptr[k], n = seg_ptr[k + 1] - s0;
-    if (n <= COL_BIG) continue;                       // block-uniform (cannot happen: the list holds exactly the long ones)
-    const long long p0 = col_base[k] + s0;
-    bf16_t wr[COL_RB];
+  if (bid_block >= 0) {
+  for (int li = bid_block; li < n_all; li += n_block_wgs) {
+    // (k_seg_scan's list: no workgroup walks over short columns; one record holds the column's place and length)
+    const ColEnt ent = long_list[li < n_first ? li : cap_s - 1 - (li - n_first)];
+    const int k = ent.k, n = ent.n;
+    const bf16_t* wc = uniform_ptr(w + ent.p0);
+    // (the thread index behind an optimisation barrier: otherwise its multiples and the tail loops' offsets are computed once
+    // before this loop and kept in registers across it, which costs the registers of the second workgroup on the CU)
+    int t = tid;
+    asm volatile("" : "+v"(t));
+    const int wave0 = __builtin_amdgcn_readfirstlane(t & ~63);      // the wave's first thread, as a scalar
+    PackedBf<COL_RB> wr;
     long long part = 0;
     int emax = 1;
+    {
+      bf16_t x[COL_RB];
 #pragma unroll
-    for (int r = 0; r < COL_RB; ++r) {
-      const int i = tid + r * COL_TPB;
-      wr[r] = 0;
-      if (i < n) wr[r] = w[p0 + i];
+      for (int r = 0; r < COL_RB; ++r) {
+        const int i = t + r * COL_TPB;
+        x[r] = 0;
+        if (i < n) x[r] = wc[i];
+      }
+#pragma unroll
+      for (int r = 0; r < COL_RB; ++r) wr.set(r, x[r]);
     }
 #pragma unroll
     for (int r = 0; r < COL_RB; ++r)
-      if (tid + r * COL_TPB < n) emax = max(emax, bf_exp_field(wr[r]));
+      if (t + r * COL_TPB < n) emax = max(emax, bf_exp_field(wr.get(r)));
 #pragma unroll 8
-    for (int i = tid + COL_RB * COL_TPB; i < n; i += COL_TPB) emax = max(emax, bf_exp_field(w[p0 + i]));
+    for (int i = t + COL_RB * COL_TPB; i < n; i += COL_TPB) emax = max(emax, bf_exp_field(wc[i]));
     const int wfrac = rel_frac(FRAC_DST, block_max_u31<COL_TPB>(emax, sh));
-    long long part_lo = 0;
-    int sticky = 0;
+    // branch-free while every term of the column is plain (common.cuh); the vote rides through the SAME pair of barriers as the sum
+    const PlainRange wr_ok = bf_plain_range(wfrac);
+    bool odd = false;
 #pragma unroll
     for (int r = 0; r < COL_RB; ++r)
-      if (tid + r * COL_TPB < n) part += bf_to_fixed_wide(wr[r], wfrac, &part_lo, &sticky, &bad);
+      if (wave0 + r * COL_TPB < n) {                   // (scalar branch: a wave skips the register slots it holds nothing in)
+        odd |= t + r * COL_TPB < n && !bf_is_plain(wr.get(r), wr_ok);
+        part += bf_fixed_plain(wr.get(r), wfrac);
+      }
 #pragma unroll 8
-    for (int i = tid + COL_RB * COL_TPB; i < n; i += COL_TPB)
-      part += bf_to_fixed_wide(w[p0 + i], wfrac, &part_lo, &sticky, &bad);
-    // (lost bits anywhere in the column? the count rides through the SAME pair of barriers as the sum)
+    for (int i = t + COL_RB * COL_TPB; i < n; i += COL_TPB) {
+      const bf16_t b = wc[i];
+      odd |= !bf_is_plain(b, wr_ok);
+      part += bf_fixed_plain(b, wfrac);
+    }
     long long lost;
-    const long long ws_fixed = block_sum2_i64<COL_TPB>(part, (part_lo != 0 || sticky) ? 1 : 0, sh2, &lost);
+    long long ws_fixed = block_sum2_i64<COL_TPB>(part, odd ? 1 : 0, sh2, &lost);
     bf16_t wsum;
     if (lost == 0) wsum = fixed_to_bf(ws_fixed, wfrac, &bad);
-    else {
-      const long long lo_tot = block_sum_i64<COL_TPB>(part_lo, sh);
-      const long long st_tot = block_sum_i64<COL_TPB>(sticky, sh);
-      wsum = fixed_wide_to_bf(ws_fixed, lo_tot, st_tot != 0, wfrac, &bad);
+    else {                                             // block-uniform: some term needs the generic converter
+      long long part_lo = 0;
+      int sticky = 0;
+      part = 0;
+#pragma unroll 4
+      for (int i = t; i < n; i += COL_TPB) part += bf_to_fixed_wide(wc[i], wfrac, &part_lo, &sticky, &bad);   // (rolled, from L2: as above)
+      // (lost bits anywhere in the column? the count rides through the same pair of barriers as the sum)
+      ws_fixed = block_sum2_i64<COL_TPB>(part, (part_lo != 0 || sticky) ? 1 : 0, sh2, &lost);
+      if (lost == 0) wsum = fixed_to_bf(ws_fixed, wfrac, &bad);
+      else {
+        const long long lo_tot = block_sum_i64<COL_TPB>(part_lo, sh);
+        const long long st_tot = block_sum_i64<COL_TPB>(sticky, sh);
+        wsum = fixed_wide_to_bf(ws_fixed, lo_tot, st_tot != 0, wfrac, &bad);
+      }
     }
     const float a = rbf((1.0f / (float)n) * eta_f);
-    part = 0;
+    const PlainRange q_ok = bf_plain_range(FRAC_DST);
+    part = 0; odd = false;
 #pragma unroll
-    for (int r = 0; r < COL_RB; ++r) {
-      const int i = tid + r * COL_TPB;
-      if (i < n) part += bf_to_fixed(edge_q_pre(wr[r], wsum, a, ome_f), FRAC_DST, &bad);
-    }
+    for (int r = 0; r < COL_RB; ++r)
+      if (wave0 + r * COL_TPB < n) {
+        const bool in = t + r * COL_TPB < n;
+        const bf16_t q = edge_q_pre(wr.get(r), wsum, a, ome_f);
+        odd |= in && !bf_is_plain(q, q_ok);
+        part += in ? bf_fixed_plain(q, FRAC_DST) : 0ll;
+      }
 #pragma unroll 8
-    for (int i = tid + COL_RB * COL_TPB; i < n; i += COL_TPB) part += bf_to_fixed(edge_q_pre(w[p0 + i], wsum, a, ome_f), FRAC_DST, &bad);
-    const long long qs_fixed = block_sum_i64<COL_TPB>(part, sh);
-    if (tid == 0) col_store(k, ws_fixed, qs_fixed, wsum, n, eta_f, acc_w, acc_q, seed_coef, &bad);
+    for (int i = t + COL_RB * COL_TPB; i < n; i += COL_TPB) {
+      const bf16_t q = edge_q_pre(wc[i], wsum, a, ome_f);
+      odd |= !bf_is_plain(q, q_ok);
+      part += bf_fixed_plain(q, FRAC_DST);
+    }
+    long long qs_fixed = block_sum2_i64<COL_TPB>(part, odd ? 1 : 0, sh2, &lost);
+    if (lost != 0) {                                   // block-uniform
+      part = 0;
+#pragma unroll 4
+      for (int i = t; i < n; i += COL_TPB) part += bf_to_fixed(edge_q_pre(wc[i], wsum, a, ome_f), FRAC_DST, &bad);
+      qs_fixed = block_sum_i64<COL_TPB>(part, sh);
+    }
+    if (t == 0) col_store(k, ws_fixed, qs_fixed, wsum, n, eta_f, acc_w, acc_q, seed_coef, &bad);
+  }
   }
   if (bad) atomicOr(&cnt->err, bad);
 }
@@ -1444,7 +1569,7 @@ int bliss_frontier_prob(const bliss_graph_t* g, const bliss_node_maps_t* m, cons
   const long long fcap = (long long)(g->num_edges < 0x7fffffffll ? g->num_edges : 0x7fffffffll);
   // the bandit's column sums write the first two per-seed accumulators themselves: the scan's zeroing leaves them alone
   const bool col_sums = binned && mode == BLISS_MODE_BANDIT;
-  int* long_list = (int*)(acc_w + 7 * (size_t)cap_s);                      // [cap_s + 1], written by k_seg_scan
+  ColEnt* long_list = (ColEnt*)(acc_w + 7 * (size_t)cap_s);                // [cap_s] + int[2], written by k_seg_scan
   PROF_LAUNCH(BK_SEG_SCAN, st, k_seg_scan<<<1 + SEG_ZERO_WGS, 1024, 0, st>>>(g->indptr, seeds, cnt, n_seeds, n_seeds_dev, cap_s, acc_w, ws->seg_ptr,
                                                             m->local_id, g->num_nodes, ws->src_cnt, ws->cap_k,
                                                             binned ? ws->bin_cursor : nullptr, ws->n_bins, (long long*)col_base, ws->span_seg,
@@ -1454,9 +1579,9 @@ int bliss_frontier_prob(const bliss_graph_t* g, const bliss_node_maps_t* m, cons
     uint2* seed_coef = (uint2*)(acc_w + 6 * (size_t)cap_s);               // [cap_s], written by k_col_sums
     unsigned long long* bin_rec = (unsigned long long*)ws->bin_rec;
     const int gb = grid_for(frontier_bound, BIN_BATCH);
-    const int n_wave_wgs = grid_for(cap_s, COL_TPB / 64, 2048);
+    const int n_wave_wgs = (cap_s + COL_TPB / 64 - 1) / (COL_TPB / 64), n_block_wgs = cap_s < COL_BLOCK_WGS ? cap_s : COL_BLOCK_WGS;   // a wave per seed
     if (col_sums)                                        // (the block passes need sum_j w_ij even when p_j does not)
-      PROF_LAUNCH(BK_COL_SUMS, st, k_col_sums<<<n_wave_wgs + (cap_s < 2048 ? cap_s : 2048), COL_TPB, 0, st>>>(g->indptr, w, seeds, ws->seg_ptr, col_base, ws->span_seg, cnt, acc_w, acc_q, eta_f, one_minus_eta_f, seed_coef, n_wave_wgs, long_list, cap_s));
+      PROF_LAUNCH(BK_COL_SUMS, st, k_col_sums<<<n_block_wgs + n_wave_wgs, COL_TPB, 0, st>>>(g->indptr, w, seeds, ws->seg_ptr, col_base, ws->span_seg, cnt, acc_w, acc_q, eta_f, one_minus_eta_f, seed_coef, n_block_wgs, long_list, cap_s));
     if (mode == BLISS_MODE_BANDIT)
       PROF_LAUNCH(BK_BIN_SCATTER, st, k_bin_scatter<true><<<gb, BIN_TPB, 0, st>>>(g->indptr, g->indices, w, seeds, ws->seg_ptr, col_base, ws->span_seg, cnt, acc_w, acc_q, eta_f, one_minus_eta_f, uniform_nodes, ws->n_bins, log2_bins, ws->bin_cap, ws->bin_cursor, bin_rec, ws->bitmap, seed_coef));
     else

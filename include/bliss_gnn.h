@@ -70,7 +70,7 @@ typedef struct {
 typedef struct {
   void* counts;             /* bliss_layer_counts_t */
   int32_t* seg_ptr;         /* [cap_s + 1] start of every seed's column in the frontier */
-  void* seed_acc;           /* [56 * cap_s bytes] exact per-seed accumulators, column bases, per-seed coefficients */
+  void* seed_acc;           /* [72 * cap_s + 64 bytes] exact per-seed accumulators, column bases, per-seed coefficients, long-column list */
   int32_t* chunk_cnt;       /* [max(frontier_bound, cap_c) / 1024 + 2] */
   int32_t* cand_nid;        /* [cap_c] global id of every candidate, seeds first (ndata[NID]) */
   void* p;                  /* bf16 [cap_c] LADIES importance p_j */
