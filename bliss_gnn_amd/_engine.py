@@ -56,8 +56,8 @@ class _LayerWs:
 
 
 class DrawState:
-    """Seed and step counter of the keyed multinomial draw (``draw="device"``).  The counter lives on the device: the last
-    layer of every sampler call bumps it, also when the call is a replayed HIP graph."""
+    """Seed and step counter of the keyed draws (``draw="device"``: multinomial, neighbor, LABOR, keyed Poisson).  The counter
+    lives on the device: the last layer of every sampler call bumps it, also when the call is a replayed HIP graph."""
 
     def __init__(self, seed, step, device):
         self.seed = int(seed) & ((1 << 64) - 1)
@@ -220,19 +220,27 @@ class LayerEngine:
         torch.set_rng_state(snapshot)
 
     # ------------------------------------------------------------------ one sample_blocks call
-    def sample_blocks(self, w_rows, seeds, fanouts, mode, eta, eps=0.9999, uniforms=None):
+    def sample_blocks(self, w_rows, seeds, fanouts, mode, eta, eps=0.9999, uniforms=None, draw_state=None, layer_dependency=False):
         """The ``for block_id in reversed(range(L))`` loop of bandit_sampler.py:350-366 /
         ladies_sampler.py:112-122.  ``w_rows[n]`` / ``fanouts[n]`` are in SAMPLING order (last block
         first).  Returns the blocks in sampling order.
 
         ``uniforms``: optional list of fp32 vectors replacing the draws from torch's global CPU
-        generator (the stream ATen's CPU ``torch.bernoulli`` consumes)."""
+        generator (the stream ATen's CPU ``torch.bernoulli`` consumes).
+        ``draw_state`` (a DrawState): the keyed Poisson draw instead -- candidate ``nid`` of sampling layer n
+        is kept iff ``keyed_uniform(seed, step, n, nid) < P`` (layer 0 for every n with ``layer_dependency``); torch's generator
+        and the staged MT state are neither read nor advanced, and the call bumps the draw step once."""
+        if draw_state is not None and uniforms is not None:
+            raise ValueError("uniforms= replaces the stream draw; the keyed draw (draw_state=) has no uniforms to replace")
+        if layer_dependency and draw_state is None:
+            raise ValueError("layer_dependency belongs to the keyed draw (draw_state=)")
         seeds = seeds.to(torch.int32).contiguous()
         L = len(fanouts)
         self._ensure(int(seeds.numel()), fanouts)
-        snapshot = torch.get_rng_state() if uniforms is None else None
+        snapshot = torch.get_rng_state() if uniforms is None and draw_state is None else None
         while True:
-            out = self._enqueue(w_rows, seeds, fanouts, mode, eta, eps, uniforms, snapshot)
+            out = self._enqueue(w_rows, seeds, fanouts, mode, eta, eps, uniforms, snapshot, draw_state=draw_state,
+                                poisson=draw_state is not None, layer_dependency=layer_dependency)
             counts_dev = out[0]
             self.counts_host.copy_(counts_dev, non_blocking=True)
             if snapshot is not None:
@@ -252,6 +260,8 @@ class LayerEngine:
                 raise RuntimeError("candidate capacity exceeded / seed id out of range")
             if bad == 0:
                 break
+            if draw_state is not None:
+                draw_state.step_dev.sub_(1)                            # the repeated call is the same draw step
             self._grow(errs)
             self._ensure(int(seeds.numel()), fanouts)
         if snapshot is not None:
@@ -705,7 +715,7 @@ class LayerEngine:
 
     def enqueue_static(self, w_rows, seeds, fanouts, mode, eta, eps=0.9999, slot=0, chain_rng=False, external_rng=False, part=None,
                        last_block=True, ready_flag=0, draw_state=None, neighbor=False, labor=False, layer_dependency=False,
-                       labor_iterations=0, nb_prob=None, lb_prob=None, n_live_dev=None):
+                       labor_iterations=0, nb_prob=None, lb_prob=None, n_live_dev=None, poisson=False):
         """Enqueue one sample_blocks on the current stream with capacity-padded outputs and NO sync.  Returns the
         blocks (sampling order); sizes, errors and the generator state are read back by finish().
 
@@ -719,7 +729,9 @@ class LayerEngine:
         (its draw is done); part "last_block" = only that block, behind a bliss_flag_wait on ``flags[L]``; ``ready_flag``
         (address of a device flag) is raised as soon as the block's forward arrays are final, before its by-source index.
         ``draw_state`` (a DrawState): the layers draw with the device-side multinomial draw instead of the Poisson chain
-        (whole calls only; no generator is involved).  ``neighbor``: the layers are neighbor layers (csrc/neighbor.hip; needs
+        (whole calls only; no generator is involved); with ``poisson``: the Poisson chain itself with the keyed draw of
+        bliss_poisson_select_keyed (whole calls only, no generator, no staging; ``layer_dependency``: one
+        variate per node for all layers).  ``neighbor``: the layers are neighbor layers (csrc/neighbor.hip; needs
         ``draw_state``, whole calls only; ``w_rows`` / ``mode`` / ``eta`` / ``eps`` are ignored).  ``labor``: the layers are LABOR-0
         layers (csrc/labor.hip; the same conditions), with one variate per vertex for all layers when ``layer_dependency``; ``labor_iterations`` > 0:
         LABOR-i layers (csrc/labor_is.hip).  ``nb_prob`` (with ``neighbor``): the weighted draw of csrc/neighbor_w.hip, from
@@ -750,16 +762,18 @@ class LayerEngine:
         if neighbor and (draw_state is None or part is not None or external_rng or chain_rng):
             raise NotImplementedError("the device-side neighbor sampler needs a draw_state and has no split / external-generator "
                                       "enqueue (the pipelined two-stream loop is out of scope)")
+        if poisson and (neighbor or labor or draw_state is None):
+            raise ValueError("poisson=True selects the keyed Poisson draw of the layer-wise samplers: it needs a draw_state")
         if draw_state is not None and (part is not None or external_rng or chain_rng):
-            raise NotImplementedError("the device-side multinomial draw has no split / external-generator enqueue "
-                                      "(the pipelined two-stream loop is out of scope)")
+            raise NotImplementedError("the device-side draws (multinomial, keyed Poisson) have no split / external-generator "
+                                      "enqueue (the pipelined two-stream loop is out of scope)")
         if part is not None and (self.scratch_sets < len(fanouts) or not external_rng):
             raise ValueError("split enqueue needs one scratch set per layer and an external generator")
         L = len(fanouts)
         out = self._enqueue(w_rows, seeds, fanouts, mode, eta, eps, None, True, slot=slot, chain_rng=chain_rng,
                             external_rng=external_rng, part=part, last_block=last_block, ready_flag=ready_flag, draw_state=draw_state,
                             neighbor=neighbor, labor=labor, layer_dependency=layer_dependency, labor_iterations=labor_iterations,
-                            nb_prob=nb_prob, lb_prob=lb_prob, n_live_dev=n_live_dev)
+                            nb_prob=nb_prob, lb_prob=lb_prob, n_live_dev=n_live_dev, poisson=poisson)
         self._static_draw[slot] = draw_state is not None
         counts_dev, layers = out
         if slot not in self._slot_counts_host:
@@ -805,7 +819,7 @@ class LayerEngine:
 
     def _enqueue(self, w_rows, seeds, fanouts, mode, eta, eps, uniforms, snapshot, slot=None, chain_rng=False, external_rng=False,
                  part=None, last_block=True, ready_flag=0, draw_state=None, neighbor=False, labor=False, layer_dependency=False,
-                 labor_iterations=0, nb_prob=None, lb_prob=None, n_live_dev=None):
+                 labor_iterations=0, nb_prob=None, lb_prob=None, n_live_dev=None, poisson=False):
         if lb_prob is not None and (labor_iterations > 0 or self.labor_is):
             raise NotImplementedError("LABOR-i with edge probabilities is out of scope")
         dev, st = self.g.device, _stream()
@@ -851,7 +865,7 @@ class LayerEngine:
             w_pos = w_rows[n]
             if part == "main":                  # layer n raises flag n when it starts (= everything before it has completed)
                 c_ws.entry_flag = self.flags.data_ptr() + 4 * n
-            if draw_state is not None:          # multinomial samplers, keyed draw: 1 + 5 + 4 launches, then the block
+            if draw_state is not None and not poisson:   # multinomial samplers, keyed draw: 1 + 5 + 4 launches, then the block
                 _lib.check(_lib.lib.bliss_frontier_prob(C.byref(self.c_graph), C.byref(self._set(n)["c_maps"]), w_pos.data_ptr(),
                                                         cur_seeds.data_ptr(), n_seeds, n_seeds_dev, cs, mode, eta_f, ome_f,
                                                         cap.get("E", self.Eg), C.byref(c_ws), st), "bliss_frontier_prob")
@@ -871,7 +885,11 @@ class LayerEngine:
                 _lib.check(_lib.lib.bliss_frontier_prob(C.byref(self.c_graph), C.byref(self._set(n)["c_maps"]), w_pos.data_ptr(),
                                                         cur_seeds.data_ptr(), n_seeds, n_seeds_dev, cs, mode, eta_f, ome_f,
                                                         cap.get("E", self.Eg), C.byref(c_ws), st), "bliss_frontier_prob")
-                if use_rng:
+                if poisson:                     # keyed Poisson draw: no generator, no uniforms buffer; the last select bumps the step
+                    _lib.check(_lib.lib.bliss_poisson_select_keyed(C.byref(c_ws), int(fanouts[n]), float(eps), draw_state.seed,
+                                                                   draw_state.step_dev.data_ptr(), 0 if layer_dependency else n,
+                                                                   int(last), cap["C"], st), "bliss_poisson_select_keyed")
+                elif use_rng:
                     off_ptr = self.rng_ctl.data_ptr() + 4 * (8 + n)
                     _lib.check(_lib.lib.bliss_poisson_select(C.byref(c_ws), int(fanouts[n]), float(eps), self.rng_out.data_ptr(),
                                                              off_ptr, self.rng_ctl.data_ptr(), int(n == L - 1), self.rng_cap,

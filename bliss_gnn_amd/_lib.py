@@ -199,6 +199,7 @@ SIGNATURES = {
     "bliss_pack_lists": [C.POINTER(PackLists), _P, _P],
     "bliss_mt19937_uniform": [_P, _P, _I32, _P, _I32, _P],
     "bliss_poisson_select": [C.POINTER(LayerWs), _I32, _D, _P, _P, _P, C.c_int, _I32, _I64, _P],
+    "bliss_poisson_select_keyed": [C.POINTER(LayerWs), _I32, _D, C.c_uint64, _P, _I32, C.c_int, _I64, _P],
     "bliss_multinomial_select": [C.POINTER(LayerWs), _P, _I32, _P],
     "bliss_multinomial_draw": [_P, _P, _P, _I32, _I32, _P, C.c_uint64, _P, _I32, C.c_int, _P, _P, _P, _P],
     "bliss_multinomial_select_marked": [C.POINTER(LayerWs), _P],

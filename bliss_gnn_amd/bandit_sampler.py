@@ -57,18 +57,25 @@ class DeviceDraw:
     reference's draw, one sync per layer.  ``"device"``: the keyed exponential race of csrc/mn_draw.hip
     -- no host round trip, so ``sample_blocks_static`` exists and the sampler can run inside a captured train step; the
     draw is a function of (seed, draw step, layer, node id) and consumes nothing from torch's generator.
-    (fit.NeighborSampler shares the keyword and the draw state: its device draw is csrc/neighbor.hip, keyed by the edge.)"""
+    (fit.NeighborSampler shares the keyword and the draw state: its device draw is csrc/neighbor.hip, keyed by the edge.)
+
+    The two Poisson samplers share the keyword.  ``"host"`` (default): the Bernoulli draw against torch's
+    CPU MT19937 stream, regenerated on the device -- the reference's bits, at the price of the host staging the generator state
+    around every step.  ``"device"``: the keyed Bernoulli draw of bliss_poisson_select_keyed -- candidate ``nid`` of sampling
+    layer n is kept iff ``keyed_uniform(seed, draw step, n, nid) < P``; no generator, no staging, so a captured train step runs
+    free.  ``layer_dependency=True`` (device draw only): layer 0's variate for every layer, i.e. one variate per node and step."""
 
     _NO_STATIC = "the multinomial draw is torch.multinomial on the host: no static-shape variant (use draw='device')"
 
-    def _init_draw(self, draw, replace):
+    def _init_draw(self, draw, replace, layer_dependency=False):
         if draw not in ("host", "device"):
             raise ValueError("draw must be 'host' or 'device', not %r" % (draw,))
-        if draw == "device" and self._poisson:
-            raise ValueError("draw='device' is the multinomial samplers' draw; the Poisson samplers always draw on the device")
+        if layer_dependency and not (self._poisson and draw == "device"):
+            raise ValueError("layer_dependency=True belongs to the Poisson samplers' keyed draw (draw='device')")
         if draw == "device" and replace:
             raise NotImplementedError("the device draw is without replacement only (replace=True needs draw='host')")
         self.draw = draw
+        self.layer_dependency = bool(layer_dependency)
         self._draw_init, self._draw_state = (None, 0), None
 
     def reset_draw(self, seed=None, step=0):
@@ -97,9 +104,9 @@ class BanditLadiesSampler(DeviceDraw, BlockSampler):
 
     def __init__(self, nodes_per_layer, importance_sampling=True, weight="w", out_weight="edge_weights",
                  node_embedding="nfeat", node_prob="node_prob", replace=False, eta=0.4, num_steps=5000,
-                 model="sage", *, draw="host"):
+                 model="sage", *, draw="host", layer_dependency=False):
         super().__init__()
-        self._init_draw(draw, replace)
+        self._init_draw(draw, replace, layer_dependency)
         self.nodes_per_layer = nodes_per_layer
         self.importance_sampling = importance_sampling
         self.edge_weight = weight
@@ -131,7 +138,7 @@ class BanditLadiesSampler(DeviceDraw, BlockSampler):
         g = self._graph(g)
         if self._engine is None or self._engine.g is not g:
             self._engine = LayerEngine(g)
-            self._engine.exact_k = self.draw == "device"
+            self._engine.exact_k = self.draw == "device" and not self._poisson     # (a Poisson layer's K is not bounded by its fanout)
         return self._engine
 
     def _ensure_weights(self, g):
@@ -179,7 +186,8 @@ class BanditLadiesSampler(DeviceDraw, BlockSampler):
         order = list(reversed(range(len(self.nodes_per_layer))))          # :350
         rows, fan = [self._w_pos[b] for b in order], [self.nodes_per_layer[b] for b in order]
         if self._poisson:
-            blks = eng.sample_blocks(rows, seed_nodes, fan, self._mode(), self.eta, self.eps, uniforms)
+            blks = eng.sample_blocks(rows, seed_nodes, fan, self._mode(), self.eta, self.eps, uniforms,
+                                     draw_state=self._draw_state_on(g.device), layer_dependency=self.layer_dependency)
         else:                                                             # select_neighbors :84-99 (torch.multinomial)
             blks = eng.sample_blocks_multinomial(rows, seed_nodes, fan, self._mode(), self.eta, self.replace, draw=self.draw,
                                                  draw_state=self._draw_state_on(g.device))
@@ -206,7 +214,8 @@ class BanditLadiesSampler(DeviceDraw, BlockSampler):
         order = list(reversed(range(len(self.nodes_per_layer))))
         blks = eng.enqueue_static([self._w_pos[b] for b in order], seed_nodes, [self.nodes_per_layer[b] for b in order],
                                   self._mode(), self.eta, self.eps, slot=slot, chain_rng=chain_rng, external_rng=external_rng, part=part,
-                                  last_block=last_block, ready_flag=ready_flag, draw_state=self._draw_state_on(g.device), n_live_dev=n_live_dev)
+                                  last_block=last_block, ready_flag=ready_flag, draw_state=self._draw_state_on(g.device), n_live_dev=n_live_dev,
+                                  poisson=self._poisson and self.draw == "device", layer_dependency=self.layer_dependency)
         blocks = []
         for blk in blks:
             blk.edata[self.output_weight] = blk._edge_weights
@@ -316,6 +325,6 @@ class BanditLadiesSampler(DeviceDraw, BlockSampler):
 
 
 class PoissonBanditLadiesSampler(BanditLadiesSampler):
-    """bandit_sampler.py:369-425."""
+    """bandit_sampler.py:369-425.  ``draw="device"`` (with ``layer_dependency``): the keyed Bernoulli draw, DeviceDraw."""
 
     _poisson = True

@@ -10,6 +10,7 @@
 //
 //   k_seg_scan -> [k_col_sums] -> k_bin_scatter -> k_bin_reduce -> k_bitmap_tiles -> k_cand_number     bliss_frontier_prob
 //   k_poisson_scale -> k_select_fused                                                                  bliss_poisson_select
+//   k_poisson_scale -> k_select_keyed   (the same select, its uniforms hashed from the node ids)       bliss_poisson_select_keyed
 //   k_block_pass1 -> k_block_scans -> k_block_pass2 -> k_tr_sort_lists (+ map cleanup)                 bliss_build_block
 // (k_frontier_pass1/2/3 + k_cand_finalize: the same candidate stage with memory-side atomics, for graphs whose node
 // slots do not fit the LDS bins.)
@@ -24,6 +25,7 @@
 #include "bliss_gnn.h"
 #include "prof.h"
 #include "edge_q.cuh"                // edge_q / edge_q_pre: q_ij with the reference's bf16 roundings (shared with neighbor_w.hip)
+#include "keyed_uniform.cuh"         // keyed_mix / keyed_u24: the counter-based uniform of the keyed Poisson select
 #include <cstdlib>
 
 #ifndef TPB
@@ -1062,19 +1064,42 @@ __device__ __forceinline__ bf16_t incl_prob(const bf16_t* __restrict__ p, int j,
 // Saves two launches (>= 4 us each inside a graph) per layer over pass1 + chunk scan + pass2.
 #define SEL_AGG 1
 #define SEL_PFX 2
-__global__ void __launch_bounds__(TPB) k_select_fused(const bf16_t* __restrict__ p, const float* __restrict__ uniforms_base,
-                                                      const int* __restrict__ u_off, LayerCounts* cnt, bf16_t* __restrict__ P,
-                                                      int* state, const int* __restrict__ cand_nid, int* __restrict__ new_id,
-                                                      int* __restrict__ kept_nid, bf16_t* __restrict__ node_prob, int cap_c, int cap_k,
-                                                      int* __restrict__ kept_map) {
+// KEYED (bliss_poisson_select_keyed): the uniform of candidate j is keyed_u24 of (seed, *step_dev, layer,
+// cand_nid[j]) instead of uniforms[j] -- no generator, no buffer.  The step is read by ONE thread per workgroup, before that
+// workgroup takes its chunk ticket; the tickets count every workgroup of the launch, so the one that draws the last ticket knows
+// that every workgroup has read the step, and (bump_step: the last select of a sampler call) writes step + 1 -- k_nb_select's
+// bump on the ticket this kernel takes anyway.  The word is not read again in this launch.
+struct KeyedDraw { unsigned long long seed; long long* step_dev; int layer, bump_step; };
+template <bool KEYED>
+__device__ __forceinline__ void select_fused_body(const bf16_t* __restrict__ p, const float* __restrict__ uniforms_base,
+                                                  const int* __restrict__ u_off, LayerCounts* cnt, bf16_t* __restrict__ P,
+                                                  int* state, const int* __restrict__ cand_nid, int* __restrict__ new_id,
+                                                  int* __restrict__ kept_nid, bf16_t* __restrict__ node_prob, int cap_c, int cap_k,
+                                                  int* __restrict__ kept_map, const KeyedDraw kd) {
   __shared__ int sh4[TPB / 64];
   __shared__ int sh_chunk, sh_base, sh_K;
-  const float* __restrict__ uniforms = uniforms_base + (u_off ? *u_off : 0);
+  const float* __restrict__ uniforms = KEYED ? nullptr : uniforms_base + (u_off ? *u_off : 0);
   const int S = cnt->S, C = min(cnt->C, cap_c), all_one = cnt->all_one;
   const float c32 = (float)cnt->c;
   const int nchunks = (C + CHUNK - 1) / CHUNK;
-  if (threadIdx.x == 0) sh_chunk = atomicAdd(state, 1);
-  __syncthreads();
+  unsigned long long key = 0;
+  if constexpr (KEYED) {
+    __shared__ unsigned long long sh_key;
+    if (threadIdx.x == 0) {
+      const unsigned long long step = (unsigned long long)*kd.step_dev;
+      // the step is in registers before the ticket is taken (the operands make the wait a data dependence, not only an order)
+      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::"v"((unsigned)step), "v"((unsigned)(step >> 32)) : "memory");
+      const int ticket = atomicAdd(state, 1);
+      sh_chunk = ticket;
+      sh_key = keyed_mix(kd.seed, step, kd.layer);
+      if (kd.bump_step && ticket == (int)gridDim.x - 1) *kd.step_dev = (long long)(step + 1);
+    }
+    __syncthreads();
+    key = sh_key;
+  } else {
+    if (threadIdx.x == 0) sh_chunk = atomicAdd(state, 1);
+    __syncthreads();
+  }
   const int chunk = sh_chunk;
   if (chunk >= nchunks) return;
   unsigned long long mask[ITEMS];
@@ -1088,8 +1113,9 @@ __global__ void __launch_bounds__(TPB) k_select_fused(const bf16_t* __restrict__
     if (j < C) {
       Pv[i] = incl_prob(p, j, S, all_one, c32);
       P[j] = Pv[i];
+      if constexpr (KEYED) keep = keyed_u24(key, cand_nid[j]) < bf2f(Pv[i]);     // (cand_nid: an earlier launch wrote it)
       // the numbers may come from a generator kernel that is still running: agent-scope (sc1) load
-      keep = __hip_atomic_load(uniforms + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < bf2f(Pv[i]);   // :422-424  u24 < float(P)
+      else keep = __hip_atomic_load(uniforms + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < bf2f(Pv[i]);   // :422-424  u24 < float(P)
     }
     mask[i] = __ballot(keep);
     wave_total += __popcll(mask[i]);
@@ -1150,6 +1176,22 @@ __global__ void __launch_bounds__(TPB) k_select_fused(const bf16_t* __restrict__
   // capacity padding (by the workgroup that knows K): ids past K stay valid node ids (0) so that padded feature gathers are harmless
   if (chunk == nchunks - 1)
     for (int r = sh_K + threadIdx.x; r < cap_k; r += TPB) { kept_nid[r] = 0; node_prob[r] = 0x3f80; }
+}
+
+__global__ void __launch_bounds__(TPB) k_select_fused(const bf16_t* __restrict__ p, const float* __restrict__ uniforms_base,
+                                                      const int* __restrict__ u_off, LayerCounts* cnt, bf16_t* __restrict__ P,
+                                                      int* state, const int* __restrict__ cand_nid, int* __restrict__ new_id,
+                                                      int* __restrict__ kept_nid, bf16_t* __restrict__ node_prob, int cap_c, int cap_k,
+                                                      int* __restrict__ kept_map) {
+  select_fused_body<false>(p, uniforms_base, u_off, cnt, P, state, cand_nid, new_id, kept_nid, node_prob, cap_c, cap_k, kept_map,
+                           KeyedDraw{0ull, nullptr, 0, 0});
+}
+
+__global__ void __launch_bounds__(TPB) k_select_keyed(const bf16_t* __restrict__ p, const KeyedDraw kd, LayerCounts* cnt,
+                                                      bf16_t* __restrict__ P, int* state, const int* __restrict__ cand_nid,
+                                                      int* __restrict__ new_id, int* __restrict__ kept_nid,
+                                                      bf16_t* __restrict__ node_prob, int cap_c, int cap_k, int* __restrict__ kept_map) {
+  select_fused_body<true>(p, nullptr, nullptr, cnt, P, state, cand_nid, new_id, kept_nid, node_prob, cap_c, cap_k, kept_map, kd);
 }
 
 // ---------------------------------------------------------------- multinomial variants (BanditLadiesSampler / LadiesSampler)
@@ -1637,6 +1679,21 @@ int bliss_poisson_select(const bliss_layer_ws_t* ws, int32_t fanout, double eps,
   PROF_LAUNCH(BK_SELECT2, st, k_select_fused<<<grid_for(cand_bound, CHUNK, 1 << 20), TPB, 0, st>>>(
       (const bf16_t*)ws->p, uniforms, uniforms_offset_dev, cnt, (bf16_t*)ws->P, ws->chunk_cnt, ws->cand_nid, ws->new_id, ws->kept_nid,
       (bf16_t*)ws->node_prob, ws->cap_c, ws->cap_k, ws->kept_map));
+  return (int)hipGetLastError();
+}
+
+int bliss_poisson_select_keyed(const bliss_layer_ws_t* ws, int32_t fanout, double eps, uint64_t seed, int64_t* step_dev,
+                               int32_t layer, int bump_step, int64_t cand_bound, void* stream_) {
+  if (!ws || !step_dev || fanout < 0 || layer < 0 || layer > 255) return BLISS_EINVAL;
+  hipStream_t st = (hipStream_t)stream_;
+  LayerCounts* cnt = (LayerCounts*)ws->counts;
+  if (cand_bound < 1) cand_bound = 1;
+  if (cand_bound > ws->cap_c) cand_bound = ws->cap_c;
+  if (!ws->fs_ticket)                                  // (else k_cand_number's last workgroup has computed the scale)
+    PROF_LAUNCH(BK_POISSON_SCALE, st, k_poisson_scale<<<1, 1024, 0, st>>>(ws->hist, cnt, fanout, eps, nullptr, nullptr, 0, 0, ws->chunk_cnt));
+  PROF_LAUNCH(BK_SELECT2, st, k_select_keyed<<<grid_for(cand_bound, CHUNK, 1 << 20), TPB, 0, st>>>(
+      (const bf16_t*)ws->p, KeyedDraw{(unsigned long long)seed, (long long*)step_dev, (int)layer, bump_step ? 1 : 0}, cnt, (bf16_t*)ws->P,
+      ws->chunk_cnt, ws->cand_nid, ws->new_id, ws->kept_nid, (bf16_t*)ws->node_prob, ws->cap_c, ws->cap_k, ws->kept_map));
   return (int)hipGetLastError();
 }
 

@@ -405,8 +405,15 @@ def make_sampler(name, fanouts, importance_sampling=1, num_steps=5000, eta=0.1, 
     samplers ("ladies", "bandit") and "neighbor" draw -- "host" (torch.multinomial / torch tensor ops) or "device" (the keyed
     draws, graph-capturable).  "labor" and "labor-<i>" (i in 1 .. 8: ``ImportanceLaborSampler`` with i iterations) always draw on
     the device.  "neighbor-exp3": ``BanditNeighborSampler`` (EXP3-weighted node-wise draw, always on the device); "labor-exp3":
-    ``BanditLaborSampler`` (EXP3-weighted LABOR draw, always on the device)."""
+    ``BanditLaborSampler`` (EXP3-weighted LABOR draw, always on the device).  The Poisson names ignore ``draw`` (they keep the
+    draw against torch's stream); their keyed draw on the device has names of its own:
+    "poisson-bandit-keyed" and "poisson-ladies-keyed"."""
     from . import BanditLadiesSampler, LadiesSampler, PoissonBanditLadiesSampler, PoissonLadiesSampler as PLS
+    if name == "poisson-ladies-keyed":
+        return PLS(fanouts, draw="device")
+    if name == "poisson-bandit-keyed":
+        return PoissonBanditLadiesSampler(fanouts, importance_sampling=importance_sampling, node_embedding="features",
+                                          num_steps=num_steps, eta=eta, model=model, draw="device")
     if name == "full":
         return MultiLayerFullNeighborSampler(len(fanouts))
     if name == "neighbor":

@@ -17,9 +17,9 @@ class LadiesSampler(DeviceDraw, BlockSampler):
     _poisson = False
 
     def __init__(self, nodes_per_layer, importance_sampling=True, weight="w", out_weight="edge_weights",
-                 replace=False, allow_zero_in_degree=False, *, draw="host"):
+                 replace=False, allow_zero_in_degree=False, *, draw="host", layer_dependency=False):
         super().__init__()
-        self._init_draw(draw, replace)
+        self._init_draw(draw, replace, layer_dependency)
         self.nodes_per_layer = nodes_per_layer
         self.importance_sampling = importance_sampling
         self.edge_weight = weight
@@ -43,7 +43,8 @@ class LadiesSampler(DeviceDraw, BlockSampler):
         order = list(reversed(range(len(self.nodes_per_layer))))         # :112
         fan = [self.nodes_per_layer[b] for b in order]
         if self._poisson:
-            blks = self._engine.sample_blocks([w_pos] * len(order), seed_nodes, fan, self._mode(), 0.0, self.eps, uniforms)
+            blks = self._engine.sample_blocks([w_pos] * len(order), seed_nodes, fan, self._mode(), 0.0, self.eps, uniforms,
+                                              draw_state=self._draw_state_on(g.device), layer_dependency=self.layer_dependency)
         else:                                                            # select_neighbors :54-69 (torch.multinomial)
             blks = self._engine.sample_blocks_multinomial([w_pos] * len(order), seed_nodes, fan, self._mode(), 0.0, self.replace,
                                                           fp32_importance=not self.importance_sampling, draw=self.draw,
@@ -67,7 +68,7 @@ class LadiesSampler(DeviceDraw, BlockSampler):
         g = self._graph(g)
         if self._engine is None or self._engine.g is not g:
             self._engine = LayerEngine(g)
-            self._engine.exact_k = self.draw == "device"
+            self._engine.exact_k = self.draw == "device" and not self._poisson     # (a Poisson layer's K is not bounded by its fanout)
         return self._engine
 
     def sample_blocks_static(self, g, seed_nodes, slot=0, chain_rng=False, external_rng=False, part=None, last_block=True, ready_flag=0,
@@ -80,7 +81,8 @@ class LadiesSampler(DeviceDraw, BlockSampler):
         order = list(reversed(range(len(self.nodes_per_layer))))
         blks = eng.enqueue_static([w_pos] * len(order), seed_nodes, [self.nodes_per_layer[b] for b in order], self._mode(), 0.0,
                                   self.eps, slot=slot, chain_rng=chain_rng, external_rng=external_rng, part=part, last_block=last_block, ready_flag=ready_flag,
-                                  draw_state=self._draw_state_on(g.device), n_live_dev=n_live_dev)
+                                  draw_state=self._draw_state_on(g.device), n_live_dev=n_live_dev,
+                                  poisson=self._poisson and self.draw == "device", layer_dependency=self.layer_dependency)
         blocks = []
         for blk in blks:
             blk.edata[self.output_weight] = blk._edge_weights
@@ -95,10 +97,11 @@ class LadiesSampler(DeviceDraw, BlockSampler):
 
 
 class PoissonLadiesSampler(LadiesSampler):
-    """ladies_sampler.py:125-183."""
+    """ladies_sampler.py:125-183.  ``draw="device"`` (with ``layer_dependency``): the keyed Bernoulli draw, DeviceDraw."""
 
     _poisson = True
 
     def __init__(self, nodes_per_layer, importance_sampling=True, weight="w", out_weight="edge_weights",
-                 allow_zero_in_degree=False):
-        super().__init__(nodes_per_layer, importance_sampling, weight, out_weight, False, allow_zero_in_degree)
+                 allow_zero_in_degree=False, *, draw="host", layer_dependency=False):
+        super().__init__(nodes_per_layer, importance_sampling, weight, out_weight, False, allow_zero_in_degree, draw=draw,
+                         layer_dependency=layer_dependency)

@@ -554,7 +554,8 @@ class GraphedTrainStep:
         pinned buffers, each with an event, after looking at the copies that have landed (never the one just enqueued; a buffer
         about to be reused is waited for, so the host stays at most ``ring`` polls ahead).  The stream is synchronised once, at
         the end.  The Poisson samplers draw from torch's CPU generator, which the host stages per step and takes back after it:
-        they keep the per-step protocol (stage, replay, one sync, ``finish_static``) and use the ledger for everything else.
+        they keep the per-step protocol (stage, replay, one sync, ``finish_static``) and use the ledger for everything else
+        -- unless they too draw on the device (``draw="device"``, the keyed Poisson draw of DESIGN.md section 21).
 
         A record with an error word stops the enqueueing: the device finishes and RuntimeError names ``first_bad_step``.  A
         record with ``near`` set (or ``regrow()``) makes the loop finish what is enqueued, re-fix the capacities, re-capture

@@ -166,6 +166,21 @@ int bliss_poisson_select(const bliss_layer_ws_t* ws, int32_t fanout, double eps,
                          int32_t* uniforms_offset_dev, int32_t* rng_ctl, int is_last, int32_t rng_cap_total,
                          int64_t cand_bound, void* stream);
 
+/* bliss_poisson_select with a KEYED draw (draw="device" of the two Poisson samplers): the same two launches
+ * (the scale, unless fs_ticket has it computed by bliss_frontier_prob; the select with its ordered look-back compaction), but the
+ * uniform of candidate j is not read from a buffer:
+ *   u_j = keyed_uniform(seed, *step_dev, layer, cand_nid[j])     SplitMix64 finaliser, top 24 bits, u = r * 2^-24 in [0, 1)
+ *   j is kept iff u_j < float(P_j), P_j exactly bliss_poisson_select's (seeds and the all_one early-out: P = 1, always kept)
+ * (oracle/bliss_oracle.py:keyed_uniform; the draw bliss_keyed_select makes for the sharded samplers).  No generator, rng_ctl or
+ * uniforms offset takes part: with fs_ticket set, fs_rng_ctl and fs_layer_off must be NULL.  `layer`: the sampling layer mixed
+ * into the key, 0 .. 255 (pass 0 for every layer to draw one variate per node and step: layer dependency).  bump_step != 0 (the
+ * LAST select of a sampler call): the workgroup that draws the launch's last ticket -- every workgroup has read the step by then
+ * -- writes *step_dev + 1, so a replayed graph advances the draw step; no extra launch, wait or spin.  step_dev: int64 device
+ * word.  Everything else (outputs, clamps, error bits, cand_bound) as bliss_poisson_select.
+ * BLISS_EINVAL, before any launch: ws or step_dev NULL, fanout < 0, layer outside 0 .. 255. */
+int bliss_poisson_select_keyed(const bliss_layer_ws_t* ws, int32_t fanout, double eps, uint64_t seed, int64_t* step_dev,
+                               int32_t layer, int bump_step, int64_t cand_bound, void* stream);
+
 /* The non-Poisson samplers: `chosen` [n_chosen] = candidate-local ids drawn by select_neighbors
  * (torch.multinomial(prob, min(num, C)), bandit_sampler.py:98 / ladies_sampler.py:68 -- its random stream is MKL's
  * inside ATen's CPU kernel, so the draw itself stays with torch on the host, on the device-computed ws->p).  Marks
