@@ -1467,9 +1467,13 @@ __device__ __forceinline__ void maps_cleanup(LayerCounts* cnt, const int* __rest
 }
 
 // ---------------------------------------------------------------- by-source lists into ascending edge order
-// One wave per source.  A source has at most one edge per destination, so an edge's rank inside its list is the
-// number of list members with a smaller destination: short lists (<= 64) rank in registers, longer ones through a
+// One wave per source; t_edge is the stable argsort of src, i.e. every list in ascending edge index.  Block edges are in
+// frontier order (destination-major), so on a list with at most one edge per destination an edge's rank is the number of
+// list members with a smaller destination: short lists (<= 64) rank in registers by edge index, longer ones through a
 // per-wave LDS bitmap over the destinations (popcount prefix) -- O(len + S/32) per list, no comparison sort.
+// Parallel edges are supported input (prepare_graph keeps repeats): two members with one destination would share a bitmap
+// rank, so a long list in which a destination bit was already set is ranked by edge index like the short ones, in rounds
+// of 64 -- O(len^2 / 64), exact for any list; lists without a repeat never take that branch.
 #define TSORT_MAX_S 32768
 __global__ void __launch_bounds__(TPB) k_tr_sort_lists(const int* __restrict__ t_indptr, const int* __restrict__ t_unsorted,
                                                        const int* __restrict__ dst, LayerCounts* cnt, int cap_k, int cap_s,
@@ -1493,8 +1497,25 @@ __global__ void __launch_bounds__(TPB) k_tr_sort_lists(const int* __restrict__ t
     }
     for (int w = lane; w <= words; w += 64) bm[w] = 0;
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier();
-    for (int i = lane; i < len; i += 64) { const int d = dst[t_unsorted[beg + i]]; atomicOr(bm + (d >> 5), 1u << (d & 31)); }
+    int repeat = 0;                                      // (LDS atomics serialise: of two members with one destination, one sees the bit)
+    for (int i = lane; i < len; i += 64) {
+      const int d = dst[t_unsorted[beg + i]];
+      repeat |= (atomicOr(bm + (d >> 5), 1u << (d & 31)) >> (d & 31)) & 1u;
+    }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier();
+    if (__ballot(repeat) != 0ull) {                      // parallel edges (wave-uniform): rank by edge index, 64 members a round
+      for (int i0 = 0; i0 < len; i0 += 64) {
+        const int v = i0 + lane < len ? t_unsorted[beg + i0 + lane] : 0x7fffffff;
+        int rank = 0;
+        for (int k0 = 0; k0 < len; k0 += 64) {
+          const int u = k0 + lane < len ? t_unsorted[beg + k0 + lane] : 0x7fffffff;
+          const int n = min(64, len - k0);
+          for (int k = 0; k < n; ++k) rank += (__shfl(u, k) < v);
+        }
+        if (i0 + lane < len) t_edge[beg + rank] = v;
+      }
+      continue;
+    }
     // exclusive prefix of popcounts, kept in place in a second word array would double LDS: do it in registers
     int carry = 0;
     for (int base = 0; base < words; base += 64) {
