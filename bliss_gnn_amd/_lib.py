@@ -112,6 +112,15 @@ class GatFused(C.Structure):                           # bliss_gat_fused_t
                 ("err", C.c_void_p)]
 
 
+class GatGlue(C.Structure):                            # bliss_gat_glue_t
+    _fields_ = [("rst", C.c_void_p), ("rst_stride", C.c_int64), ("res", C.c_void_p), ("res_stride", C.c_int64),
+                ("n_rows", C.c_int32), ("n_rows_dev", C.c_void_p),
+                ("heads", C.c_int32), ("head_dim", C.c_int32), ("act", C.c_int32), ("head_mean", C.c_int32),
+                ("drop_p", C.c_float), ("drop_seed", C.c_uint32), ("drop_ctr", C.c_void_p), ("drop_ctr_used", C.c_void_p),
+                ("out", C.c_void_p), ("out_stride", C.c_int64), ("pre", C.c_void_p), ("pre_stride", C.c_int64),
+                ("dout", C.c_void_p), ("dout_stride", C.c_int64), ("din", C.c_void_p), ("din_stride", C.c_int64)]
+
+
 ADAM_MAX_TENSORS = 32
 F1_MAX_WORKGROUPS, F1_ROWS_PER_WORKGROUP, F1_PAIRS_PER_WORKGROUP = 1024, 4, 256    # BLISS_F1_MAX_WORKGROUPS; csrc/metrics.hip
 
@@ -253,6 +262,10 @@ SIGNATURES = {
     "bliss_gat_logits": [_P, _P, _P, _I32, _P, _I64, _P, _I32, _I32, _F, _P, _P],
     "bliss_sage_dgrad": [C.POINTER(DGrad), _P],
     "bliss_sage_wgrad": [C.POINTER(WGrad), _I32, _P, _I64, _P],
+    "bliss_gat_dgrad": [C.POINTER(DGrad), _P],
+    "bliss_gat_glue_fwd": [C.POINTER(GatGlue), _P],
+    "bliss_gat_glue_bwd": [C.POINTER(GatGlue), _P],
+    "bliss_gat_head_mean": [_P, _I32, _I32, _P, _P, _P],
     "bliss_shard_local_seeds": [_P, _I32, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P],
     "bliss_shard_scatter_partials": [_P, _P, _P, _P, _P, _P, _P, _I32, _P, _P],
     "bliss_shard_zero_dense": [_P, _I32, _P],

@@ -356,13 +356,9 @@ bool wgrad_plan(const bliss_wgrad_t* a, int n_probs, WGradLaunch* L, long long* 
   return true;
 }
 
-}  // namespace
-
-extern "C" {
-
-int bliss_sage_dgrad(const bliss_dgrad_t* a, void* stream) {
-  if (!a || !a->a1 || !a->w1 || !a->out || a->k1 <= 0 || a->k1 > 256 || a->n <= 0 || a->m_bound <= 0) return BLISS_EINVAL;
-  if (a->k2 < 0 || a->k2 > 256 || (a->k2 > 0 && (!a->a2 || !a->w2 || a->m2_bound <= 0))) return BLISS_EINVAL;
+int dgrad_launch(const bliss_dgrad_t* a, int k_max, void* stream) {
+  if (!a || !a->a1 || !a->w1 || !a->out || a->k1 <= 0 || a->k1 > k_max || a->n <= 0 || a->m_bound <= 0) return BLISS_EINVAL;
+  if (a->k2 < 0 || a->k2 > k_max || (a->k2 > 0 && (!a->a2 || !a->w2 || a->m2_bound <= 0))) return BLISS_EINVAL;
   DGrad p;
   p.a1 = (const bf16_t*)a->a1; p.a1_stride = a->a1_stride; p.w1 = (const bf16_t*)a->w1; p.w1_stride = a->w1_stride; p.k1 = a->k1;
   p.a2 = (const bf16_t*)a->a2; p.a2_stride = a->a2_stride; p.w2 = (const bf16_t*)a->w2; p.w2_stride = a->w2_stride; p.k2 = a->k2;
@@ -372,6 +368,7 @@ int bliss_sage_dgrad(const bliss_dgrad_t* a, void* stream) {
   const size_t stage = ((size_t)DG_M * (dg_astride(a->k1) + (a->k2 ? dg_astride(a->k2) : 0)) + (size_t)DG_SLAB * DG_WSTRIDE) * sizeof(bf16_t);
   const size_t outt = (size_t)DG_M * (256 + 8) * sizeof(bf16_t);
   const size_t lds = stage > outt ? stage : outt;
+  if (lds > 160 * 1024) return BLISS_EINVAL;
   static size_t lds_set = 0;
   if (lds > lds_set) {
     if (hipFuncSetAttribute((const void*)k_dgrad, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return BLISS_EINVAL;
@@ -381,6 +378,17 @@ int bliss_sage_dgrad(const bliss_dgrad_t* a, void* stream) {
   k_dgrad<<<grid, DG_TPB, lds, (hipStream_t)stream>>>(p);
   return (int)hipGetLastError();
 }
+
+}  // namespace
+
+extern "C" {
+
+int bliss_sage_dgrad(const bliss_dgrad_t* a, void* stream) { return dgrad_launch(a, 256, stream); }
+
+// The same kernel with its k-loop run further: k1, k2 <= 1024 (a GATv2 layer's H*D gradient columns).  k_dgrad
+// walks k in 64-row slabs of W and keeps all of a row tile's k columns in LDS, so the limit is the LDS a workgroup may hold:
+// BLISS_EINVAL when the two staged operands and a W slab pass 160 KiB (k1 + k2 above ~1900: the caller then launches twice).
+int bliss_gat_dgrad(const bliss_dgrad_t* a, void* stream) { return dgrad_launch(a, 1024, stream); }
 
 int64_t bliss_sage_wgrad_workspace(const bliss_wgrad_t* probs, int32_t n_probs) {
   WGradLaunch L;

@@ -282,13 +282,18 @@ class GATv2(nn.Module):
     that the bandit's calculate_alpha consumes (model.py:211-213, 224-227)."""
 
     def __init__(self, num_layers, in_dim, num_hidden, num_classes, heads, activation, feat_drop, attn_drop, negative_slope,
-                 residual):
+                 residual, transforms="library"):
         super().__init__()
-        from .nn import GATv2Conv
+        from .nn import GAT_TRANSFORMS, GATv2Conv
+        if transforms not in GAT_TRANSFORMS:
+            raise ValueError("transforms must be one of %r, not %r" % (GAT_TRANSFORMS, transforms))
+        # "tile" (DESIGN.md section 22): the dense transforms on the MFMA tile kernels and the glue between the layers in one
+        # bounded launch per direction -- the path that runs under a batch capacity; "library": the launches and bits of before
+        self.transforms = transforms
         self.num_layers, self.activation = num_layers, activation
         self.num_hidden, self.num_classes, self.heads = num_hidden, num_classes, heads
         mk = lambda i, o, h, res, act: GATv2Conv(i, o, h, feat_drop, attn_drop, negative_slope, res, act, bias=False,
-                                                 share_weights=True, allow_zero_in_degree=True)
+                                                 share_weights=True, allow_zero_in_degree=True, transforms=transforms)
         self.gatv2_layers = nn.ModuleList()
         if num_layers > 1:
             self.gatv2_layers.append(mk(in_dim, num_hidden, heads[0], False, activation))                     # :141-155
@@ -300,7 +305,45 @@ class GATv2(nn.Module):
         for l, layer in enumerate(self.gatv2_layers):              # the attention-dropout stream of layer l (nn.GATv2Conv._fused_state)
             layer._drop_salt = l + 1
 
+    def tile_refusal(self):
+        """Why this model cannot take the tile path (a layer outside its limits), or None."""
+        for l, layer in enumerate(self.gatv2_layers):
+            why = layer.tile_refusal("GATv2 layer %d" % l)
+            if why is not None:
+                return why
+        return None
+
+    def _forward_tile(self, blocks, inputs):
+        """``forward`` on the bounded kernels: per layer the two Linears (one or two tile launches), the fused message passing, the
+        head mean of the logits and ONE glue launch (residual, activation, flatten / head mean, the next layer's feat_drop)."""
+        from .nn import _block_words, _glue_act, gat_glue, gat_head_mean
+        if len(blocks) != len(self.gatv2_layers):
+            raise ValueError("%d blocks for %d layers" % (len(blocks), len(self.gatv2_layers)))
+        why = self.tile_refusal()
+        if why is None and not (inputs.is_cuda and inputs.dtype == torch.bfloat16):
+            why = 'GATv2: transforms="tile" takes bf16 features on the GPU'
+        if why is not None:
+            raise NotImplementedError(why)
+        n = len(blocks)
+        norm = _gathered_norm(blocks, inputs)
+        h = inputs                                                                   # the layer input before its feat_drop
+        h_drop = self.gatv2_layers[0].tile_feat_drop(blocks[0], h)
+        for l, block in enumerate(blocks):
+            layer, last = self.gatv2_layers[l], l == n - 1
+            block.srcdata["embed_norm"] = embed_norm(h) if (l > 0 or norm is None) else norm                   # :211-213
+            rst, res, e = layer.tile_parts(block, h_drop, "GATv2 layer %d" % l)
+            dst_dev, _, edges_dev = _block_words(block)
+            block.edata["a_ij"] = gat_head_mean(e, block.num_edges(), edges_dev)                               # :224-227
+            nxt = None if last else self.gatv2_layers[l + 1]
+            p = float(nxt.feat_drop.p) if (nxt is not None and self.training) else 0.0
+            h_drop, h = gat_glue(rst, res, layer._num_heads, layer._out_feats, act=_glue_act(layer.activation, "GATv2 layer %d" % l),
+                                 head_mean=last, p=p, state=nxt._feat_state(rst.device) if p > 0 else None,
+                                 n_rows=block.num_dst_nodes(), rows_dev=dst_dev, want_pre=True)                 # :101-106, :228-232, :66
+        return h_drop
+
     def forward(self, blocks, inputs):
+        if self.transforms == "tile":
+            return self._forward_tile(blocks, inputs)
         h = inputs.bfloat16()
         norm = _gathered_norm(blocks, h)
         for l, block in enumerate(blocks):

@@ -996,6 +996,239 @@ class _GatFusedMP(torch.autograd.Function):
         return d_feat, d_attn.to(ctx.attn_dtype).view(ctx.attn_shape), None, None, None, None, None, None
 
 
+# ------------------------------------------------------------------------------------------------ GATv2 on bounded kernels
+# transforms="tile" (DESIGN.md section 22): fc_src / res_fc on the MFMA tile kernels, the glue around the message passing in one
+# launch per direction (csrc/gat_glue.hip) -- every loop that crosses rows is bounded by the block's device-side counts, so the
+# layers run on a capacity-padded output block (train.GraphedTrainStep(batch_capacity=...)).
+GAT_TRANSFORMS = ("library", "tile")
+
+
+def _block_words(block):
+    """Addresses of the block's live (S, K, B) words for the kernels' ``*_dev`` arguments; (0, 0, 0) for an exact-size block."""
+    if block._nnz_ptr and getattr(block, "_counts_dev", None) is not None:
+        cd = block._counts_dev.data_ptr()
+        return cd, cd + 12, cd + 16
+    return 0, 0, 0
+
+
+def _col_blocks(n):
+    return [(c, min(n, c + TILE_GEMM_MAX_N)) for c in range(0, n, TILE_GEMM_MAX_N)]
+
+
+def _dgrad_fits(k1, k2):
+    """Do both staged operands and a W slab of bliss_gat_dgrad fit a workgroup's 160 KiB of LDS (csrc/sage_bwd.hip)?"""
+    st = lambda k: (((k + 15) & ~15) + 8) if k else 0
+    return 2 * (32 * (st(k1) + st(k2)) + 64 * (256 + 32)) <= 160 * 1024
+
+
+def gat_dgrad(a1, w1, m_bound, m_dev=0, a2=None, w2=None, m2_bound=0, m2_dev=0):
+    """sage_dgrad for gradient rows of up to 1024 columns (bliss_gat_dgrad): out[r] = a1[r] @ w1 (+ a2[r] @ w2 for r < m2), fp32
+    accumulation over all of it, one rounding; zero rows at or past the counts."""
+    import ctypes as C
+    out = torch.empty(m_bound, w1.shape[1], dtype=torch.bfloat16, device=a1.device)
+    t = _lib.DGrad()
+    t.a1, t.a1_stride, t.w1, t.w1_stride, t.k1 = a1.data_ptr(), a1.stride(0), w1.data_ptr(), w1.stride(0), w1.shape[0]
+    if a2 is not None:
+        t.a2, t.a2_stride, t.w2, t.w2_stride, t.k2 = a2.data_ptr(), a2.stride(0), w2.data_ptr(), w2.stride(0), w2.shape[0]
+        t.m2_bound, t.m2_dev = int(m2_bound), int(m2_dev)
+    t.m_bound, t.m_dev, t.n = int(m_bound), int(m_dev), w1.shape[1]
+    t.out, t.out_stride = out.data_ptr(), out.stride(0)
+    _lib.check(_lib.lib.bliss_gat_dgrad(C.byref(t), _stream()), "bliss_gat_dgrad")
+    return out
+
+
+def _zero_rows(n, like):
+    # (a fill kernel, not torch.zeros: memset nodes of a captured HIP graph were seen stale on replay, DESIGN.md 7.3)
+    return torch.empty(n, like.shape[1], dtype=like.dtype, device=like.device).fill_(0)
+
+
+def _wgrad_blocks(problems):
+    """[(d [R, N], x [R, k_in], rows_bound, rows_dev, want_bias)] -> [(dW [N, k_in], db or None)] for N of any size: one
+    bliss_sage_wgrad problem per block of 256 output rows (a column slice of d, a row slice of dW), two problems per launch."""
+    import ctypes as C
+    outs, recs = [], []
+    for d, x, rb, rdev, want_b in problems:
+        dw = torch.empty(d.shape[1], x.shape[1], dtype=torch.bfloat16, device=d.device)
+        db = torch.empty(d.shape[1], dtype=torch.bfloat16, device=d.device) if want_b else None
+        outs.append((dw, db))
+        for c0, c1 in _col_blocks(d.shape[1]):
+            recs.append((d[:, c0:c1], x, rb, rdev, dw[c0:c1], None if db is None else db[c0:c1]))
+    for i in range(0, len(recs), 2):
+        pair = recs[i:i + 2]
+        arr = (_lib.WGrad * len(pair))()
+        for a, (d, x, rb, rdev, dw, db) in zip(arr, pair):
+            a.d, a.d_stride, a.n_out = d.data_ptr(), d.stride(0), d.shape[1]
+            a.x, a.x_stride, a.k_in = x.data_ptr(), x.stride(0), x.shape[1]
+            a.rows_bound, a.rows_dev = int(rb), int(rdev)
+            a.dw, a.dw_stride, a.db = dw.data_ptr(), dw.stride(0), 0 if db is None else db.data_ptr()
+        need = int(_lib.lib.bliss_sage_wgrad_workspace(arr, len(pair)))
+        if need < 0:
+            raise RuntimeError("bliss_sage_wgrad: invalid problem description")
+        ws = torch.empty(max(need, 4), dtype=torch.float32, device=pair[0][0].device)
+        _lib.check(_lib.lib.bliss_sage_wgrad(arr, len(pair), ws.data_ptr(), ws.numel(), _stream()), "bliss_sage_wgrad")
+    return outs
+
+
+class _GatLinear(torch.autograd.Function):
+    """y1 = x[:n1] @ w1^T (+ b1) and, with a second weight, y2 = x[:n2] @ w2^T (+ b2), n2 <= n1 -- fc_src over a block's source
+    rows and res_fc over its destination rows (model.py:66-72, :101-103) -- on bliss_tile_gemm in output-column blocks of at most
+    256 (a row slice of W, an offset ``out`` pointer with the full row stride), two blocks per launch.  ``dev1`` / ``dev2``: the
+    block's live row words (0: the bounds are exact); rows at or past them come out as zeros.  Backward: the weight (and bias)
+    gradients on bliss_sage_wgrad, one problem per column block; the input gradient on bliss_gat_dgrad (both Linears into one
+    fp32 accumulator when they fit)."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, n1, dev1, w2, b2, n2, dev2):
+        ctx.set_materialize_grads(False)
+        x, w1 = _bf16c(x), _bf16c(w1)
+        w2 = None if w2 is None else _bf16c(w2)
+        if x.shape[1] > TILE_GEMM_MAX_K or x.shape[0] < n1 or (w2 is not None and n2 > n1):
+            raise ValueError("_GatLinear: in_feats <= %d, n2 <= n1 <= rows" % TILE_GEMM_MAX_K)
+        y1 = torch.empty(n1, w1.shape[0], dtype=torch.bfloat16, device=x.device)
+        y2 = None if w2 is None else torch.empty(n2, w2.shape[0], dtype=torch.bfloat16, device=x.device)
+        sets = [_tg_args(x, w1[c0:c1], y1[:, c0:c1], n1, bias=None if b1 is None else b1[c0:c1], m_dev=dev1) for c0, c1 in _col_blocks(w1.shape[0])]
+        if w2 is not None:
+            sets += [_tg_args(x, w2[c0:c1], y2[:, c0:c1], n2, bias=None if b2 is None else b2[c0:c1], m_dev=dev2) for c0, c1 in _col_blocks(w2.shape[0])]
+        for i in range(0, len(sets), 2):
+            _tile_gemm(sets[i], sets[i + 1] if i + 1 < len(sets) else None)
+        ctx.save_for_backward(x, w1, w2)
+        ctx.n1, ctx.dev1, ctx.n2, ctx.dev2, ctx.has_b1, ctx.has_b2 = n1, dev1, n2, dev2, b1 is not None, b2 is not None
+        return y1, y2
+
+    @staticmethod
+    def backward(ctx, d1, d2):
+        x, w1, w2 = ctx.saved_tensors
+        d1 = None if d1 is None else _bf16c(d1)
+        d2 = None if (d2 is None or w2 is None) else _bf16c(d2)
+        probs = []
+        if d1 is not None:
+            probs.append((d1, x, ctx.n1, ctx.dev1, ctx.has_b1))
+        if d2 is not None:
+            probs.append((d2, x, ctx.n2, ctx.dev2, ctx.has_b2))
+        outs = _wgrad_blocks(probs) if probs else []
+        dw1, db1 = outs[0] if d1 is not None else (None, None)
+        dw2, db2 = outs[-1] if d2 is not None else (None, None)
+        dx = None
+        if ctx.needs_input_grad[0] and probs:
+            if d1 is not None and d2 is not None and _dgrad_fits(w1.shape[0], w2.shape[0]):
+                dx = gat_dgrad(d1, w1, ctx.n1, ctx.dev1, a2=d2, w2=w2, m2_bound=ctx.n2, m2_dev=ctx.dev2)
+            else:
+                dx = gat_dgrad(d1, w1, ctx.n1, ctx.dev1) if d1 is not None else None
+                if d2 is not None:
+                    dx2 = gat_dgrad(d2, w2, ctx.n2, ctx.dev2)                # (zero rows at or past the count)
+                    if dx is None:
+                        dx = torch.cat([dx2, _zero_rows(ctx.n1 - ctx.n2, dx2)])
+                    else:
+                        dx[: ctx.n2] += dx2
+            if x.shape[0] > ctx.n1:
+                dx = torch.cat([dx, _zero_rows(x.shape[0] - ctx.n1, dx)])
+        return dx, dw1, db1, None, None, dw2, db2, None, None
+
+
+def gat_linear(x, w, b, n_rows, rows_dev=0, w2=None, b2=None, n2_rows=0, rows2_dev=0):
+    """``_GatLinear``: (x[:n_rows] @ w^T + b, x[:n2_rows] @ w2^T + b2 or None)."""
+    return _GatLinear.apply(x, w, b, int(n_rows), int(rows_dev), w2, b2, int(n2_rows), int(rows2_dev))
+
+
+def gat_drop_state(salt, device):
+    """The feat_drop stream of one GATv2 layer: its launch counter (device uint64[2]) and seed -- a function of torch's CUDA seed
+    and of the layer's ordinal, like the attention dropout's (GATv2Conv._fused_state)."""
+    return dict(ctr=torch.zeros(2, dtype=torch.int64, device=device),
+                seed=(torch.cuda.initial_seed() ^ (0x85EBCA77 * (int(salt) + 1))) & 0xFFFFFFFF)
+
+
+def _glue_args(H, D, act, head_mean, p, n_rows, rows_dev, state, ctr_used):
+    t = _lib.GatGlue()
+    t.n_rows, t.n_rows_dev, t.heads, t.head_dim, t.act, t.head_mean = int(n_rows), int(rows_dev), int(H), int(D), int(act), int(bool(head_mean))
+    if p > 0:
+        t.drop_p, t.drop_seed, t.drop_ctr, t.drop_ctr_used = float(p), int(state["seed"]) & 0xFFFFFFFF, state["ctr"].data_ptr(), ctr_used.data_ptr()
+    return t
+
+
+class _GatGlue(torch.autograd.Function):
+    """csrc/gat_glue.hip: out = dropout_p(flatten-or-head-mean(act(rst (+ res)))) over the rows below the live count, zeros past
+    it; ``pre`` (with ``want_pre``) is the value before the dropout, for the row norms the next layer stores."""
+
+    @staticmethod
+    def forward(ctx, rst, res, H, D, act, head_mean, p, state, n_rows, rows_dev, want_pre):
+        import ctypes as C
+        ctx.set_materialize_grads(False)
+        rst = _bf16c(rst)
+        res = None if res is None else _bf16c(res)
+        HD, dev = H * D, rst.device
+        if rst.dim() != 2 or rst.shape[1] != HD or rst.shape[0] < n_rows or (res is not None and (res.shape[1] != HD or res.shape[0] < n_rows)):
+            raise ValueError("gat_glue: rst (and res) are [rows >= n_rows, heads * head_dim]")
+        width = D if head_mean else HD
+        out = torch.empty(n_rows, width, dtype=torch.bfloat16, device=dev)
+        pre = torch.empty(n_rows, width, dtype=torch.bfloat16, device=dev) if (want_pre and p > 0) else None
+        ctr_used = torch.empty(1, dtype=torch.int32, device=dev) if p > 0 else None
+        t = _glue_args(H, D, act, head_mean, p, n_rows, rows_dev, state, ctr_used)
+        t.rst, t.rst_stride = rst.data_ptr(), rst.stride(0)
+        if res is not None:
+            t.res, t.res_stride = res.data_ptr(), res.stride(0)
+        t.out, t.out_stride = out.data_ptr(), out.stride(0)
+        if pre is not None:
+            t.pre, t.pre_stride = pre.data_ptr(), pre.stride(0)
+        _lib.check(_lib.lib.bliss_gat_glue_fwd(C.byref(t), _stream()), "bliss_gat_glue_fwd")
+        ctx.save_for_backward(rst if act else None, res if act else None, ctr_used)
+        ctx.cfg = (H, D, act, head_mean, float(p), state, n_rows, rows_dev, res is not None)
+        if pre is not None:
+            ctx.mark_non_differentiable(pre)
+        return out, pre
+
+    @staticmethod
+    def backward(ctx, dout, _dpre):
+        import ctypes as C
+        rst, res, ctr_used = ctx.saved_tensors
+        H, D, act, head_mean, p, state, n_rows, rows_dev, has_res = ctx.cfg
+        if dout is None:
+            return (None,) * 11
+        dout = _bf16c(dout)
+        din = torch.empty(n_rows, H * D, dtype=torch.bfloat16, device=dout.device)
+        t = _glue_args(H, D, act, head_mean, p, n_rows, rows_dev, state, ctr_used)
+        if act:
+            t.rst, t.rst_stride = rst.data_ptr(), rst.stride(0)
+            if res is not None:
+                t.res, t.res_stride = res.data_ptr(), res.stride(0)
+        t.dout, t.dout_stride, t.din, t.din_stride = dout.data_ptr(), dout.stride(0), din.data_ptr(), din.stride(0)
+        _lib.check(_lib.lib.bliss_gat_glue_bwd(C.byref(t), _stream()), "bliss_gat_glue_bwd")
+        return (din, din if has_res else None) + (None,) * 9
+
+
+GLUE_ACT_NONE, GLUE_ACT_ELU = 0, 1
+
+
+def gat_glue(rst, res, heads, head_dim, act=GLUE_ACT_NONE, head_mean=False, p=0.0, state=None, n_rows=None, rows_dev=0, want_pre=False):
+    """The glue behind a GATv2 layer's message passing (see ``_GatGlue``) -> (out, pre or None)."""
+    n_rows = rst.shape[0] if n_rows is None else int(n_rows)
+    if p > 0 and state is None:
+        raise ValueError("gat_glue: dropout needs the stream's state (gat_drop_state)")
+    out, pre = _GatGlue.apply(rst, res, int(heads), int(head_dim), int(act), bool(head_mean), float(p), state, n_rows, int(rows_dev), bool(want_pre))
+    return out, (out.detach() if (want_pre and pre is None) else pre)
+
+
+def gat_feat_drop(x, p, state, n_rows=None, rows_dev=0):
+    """feat_drop (model.py:66) on the rows below the live count with the keyed mask; zeros past it."""
+    return gat_glue(x, None, 1, x.shape[1], p=p, state=state, n_rows=n_rows, rows_dev=rows_dev)[0]
+
+
+def gat_head_mean(e, n_edges=None, edges_dev=0):
+    """a_ij = e.mean(1) (model.py:224-227) over the live edges: bf16 [B]; entries past the count are left as allocated."""
+    e = _bf16c(e.detach())
+    B, H = (e.shape[0] if n_edges is None else int(n_edges)), e.shape[1]
+    out = torch.empty(B, dtype=torch.bfloat16, device=e.device)
+    _lib.check(_lib.lib.bliss_gat_head_mean(e.data_ptr(), H, B, int(edges_dev), out.data_ptr(), _stream()), "bliss_gat_head_mean")
+    return out
+
+
+def _glue_act(act, what):
+    if act is None:
+        return GLUE_ACT_NONE
+    if act is torch.nn.functional.elu or (isinstance(act, nn.ELU) and float(act.alpha) == 1.0):
+        return GLUE_ACT_ELU
+    raise NotImplementedError('%s: transforms="tile" covers the activations ELU (alpha 1) and None, not %r' % (what, act))
+
+
 def edge_softmax(graph, logits):
     """``dglnn.functional.edge_softmax(graph, e)`` (model.py:88-90): softmax over the in-edges of every destination,
     per head; ``logits`` [B, H, 1] (or [B, H])."""
@@ -1035,10 +1268,13 @@ class GATv2Conv(nn.Module):
     res_fc Linear(in, H*D, bias) when residual and in != H*D, identity when equal; xavier_normal(gain('relu'))."""
 
     def __init__(self, in_feats, out_feats, num_heads, feat_drop=0.0, attn_drop=0.0, negative_slope=0.2, residual=False,
-                 activation=None, allow_zero_in_degree=False, bias=True, share_weights=False):
+                 activation=None, allow_zero_in_degree=False, bias=True, share_weights=False, transforms="library"):
         super().__init__()
         if not share_weights:
             raise NotImplementedError("the reference always builds share_weights=True (model.py:152,170,186,202)")
+        if transforms not in GAT_TRANSFORMS:
+            raise ValueError("transforms must be one of %r, not %r" % (GAT_TRANSFORMS, transforms))
+        self.transforms = transforms
         self._num_heads, self._out_feats, self._in = num_heads, out_feats, in_feats
         self._allow_zero_in_degree = allow_zero_in_degree
         self.fc_src = nn.Linear(in_feats, out_feats * num_heads, bias=bias)
@@ -1079,8 +1315,75 @@ class GATv2Conv(nn.Module):
         if st is not None and int(st["err"].item()):
             raise RuntimeError("GATv2 fused kernels: error 0x%x (%s)" % (int(st["err"].item()), _lib.err_string(int(st["err"].item()))))
 
+    # -- transforms="tile"  -------------------------------------------------------------------------
+    def _feat_state(self, device):
+        st = getattr(self, "_dstate", None)
+        if st is None or st["ctr"].device != device:
+            st = self._dstate = gat_drop_state(getattr(self, "_drop_salt", 0), device)
+        return st
+
+    def tile_refusal(self, what="GATv2Conv"):
+        """Why this layer cannot take the tile path, or None: the limits that do not depend on the input tensor."""
+        H, D = self._num_heads, self._out_feats
+        if self._in > TILE_GEMM_MAX_K:
+            return ('%s: transforms="tile" takes in_feats <= %d (the tile kernel keeps a row tile\'s K columns in LDS), this layer '
+                    'has %d; build it with transforms="library"' % (what, TILE_GEMM_MAX_K, self._in))
+        if not _gat_fused_on(H, D):
+            return ('%s: transforms="tile" runs on the fused message-passing kernels (bliss_gat_fused_supported(%d, %d) is false or '
+                    'BLISS_GAT_FUSED=0)' % (what, H, D))
+        if not _mfma_bwd_on():
+            return "%s: transforms=\"tile\" needs the MFMA backward (BLISS_SAGE_MFMA_BWD=0 is set)" % what
+        try:
+            _glue_act(self.activation, what)
+        except NotImplementedError as e:
+            return str(e)
+        return None
+
+    def _tile_check(self, feat, what):
+        why = self.tile_refusal(what)
+        if why is None and not (feat.is_cuda and feat.dtype == torch.bfloat16 and self.fc_src.weight.dtype == torch.bfloat16):
+            why = '%s: transforms="tile" takes bf16 features and parameters on the GPU' % what
+        if why is not None:
+            raise NotImplementedError(why)
+
+    def tile_feat_drop(self, graph, feat):
+        """feat_drop over the block's live source rows (identity in evaluation or with p = 0)."""
+        p = float(self.feat_drop.p) if self.training else 0.0
+        if p <= 0:
+            return feat
+        return gat_feat_drop(feat, p, self._feat_state(feat.device), graph.num_src_nodes(), _block_words(graph)[1])
+
+    def tile_parts(self, graph, h_src, what="GATv2Conv"):
+        """(rst [S, H*D], res [S, H*D] or None, e [B, H]) from the feat-dropped input rows: fc_src / res_fc on the tile kernels,
+        model.py:82-99 on the fused kernels; every row past the block's live counts is zero."""
+        H, D, S, K = self._num_heads, self._out_feats, graph.num_dst_nodes(), graph.num_src_nodes()
+        self._tile_check(h_src, what)
+        if h_src.shape[0] < K or h_src.shape[1] != self._in:
+            raise ValueError("%s: %d x %d input rows for a block of %d sources and in_feats %d" % (what, h_src.shape[0], h_src.shape[1], K, self._in))
+        if not self._allow_zero_in_degree and not torch.cuda.is_current_stream_capturing() and bool((graph.in_degrees() == 0).any()):
+            raise RuntimeError("There are 0-in-degree nodes in the graph (model.py:49-61); build the layer with "
+                               "allow_zero_in_degree=True or add self loops")      # (a host read: not taken inside a captured step)
+        dst_dev, src_dev, _ = _block_words(graph)
+        lin = isinstance(self.res_fc, nn.Linear)
+        feat_src, res = gat_linear(h_src, self.fc_src.weight, self.fc_src.bias, K, src_dev,
+                                   self.res_fc.weight if lin else None, self.res_fc.bias if lin else None, S if lin else 0, dst_dev if lin else 0)
+        if self.res_fc is not None and not lin:
+            res = h_src[:S]                                                      # nn.Identity (in_feats == H * D)
+        p_drop = float(self.attn_drop.p) if self.training else 0.0
+        rst, e = _GatFusedMP.apply(feat_src, self.attn, graph, H, D, self.negative_slope, p_drop, self._fused_state(feat_src.device))
+        return rst, res, e
+
+    def _forward_tile(self, graph, feat, get_attention):
+        H, D, S = self._num_heads, self._out_feats, graph.num_dst_nodes()
+        self._tile_check(feat, "GATv2Conv")
+        rst, res, e = self.tile_parts(graph, self.tile_feat_drop(graph, feat))
+        out = gat_glue(rst, res, H, D, act=_glue_act(self.activation, "GATv2Conv"), n_rows=S, rows_dev=_block_words(graph)[0])[0].view(S, H, D)
+        return (out, e.view(-1, H, 1)) if get_attention else out
+
     def forward(self, graph, feat, edge_weight=None, get_attention=False):
         H, D, S = self._num_heads, self._out_feats, graph.num_dst_nodes()
+        if self.transforms == "tile":
+            return self._forward_tile(graph, feat, get_attention)
         if not self._allow_zero_in_degree and bool((graph.in_degrees() == 0).any()):
             raise RuntimeError("There are 0-in-degree nodes in the graph (model.py:49-61); build the layer with "
                                "allow_zero_in_degree=True or add self loops")

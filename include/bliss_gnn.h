@@ -516,6 +516,10 @@ typedef struct {
   void* out; int64_t out_stride;
 } bliss_dgrad_t;
 int bliss_sage_dgrad(const bliss_dgrad_t* args, void* stream);
+/* bliss_sage_dgrad with k1, k2 <= 1024: the input gradient of a GATv2 layer's fc_src / res_fc, whose gradient rows have
+ * heads * head_dim columns (csrc/sage_bwd.hip: the same kernel, its k-loop run further; the existing entry point and its bits are
+ * untouched).  BLISS_EINVAL when both staged operands and a W slab do not fit a workgroup's 160 KiB of LDS. */
+int bliss_gat_dgrad(const bliss_dgrad_t* args, void* stream);
 typedef struct {
   const void* d; int64_t d_stride; int32_t n_out;
   const void* x; int64_t x_stride; int32_t k_in;
@@ -921,6 +925,35 @@ int bliss_gat_rows(int which, const int32_t* row_ptr, int32_t n_rows, const int3
                    int32_t heads, int32_t head_dim, float negative_slope, void* out, int64_t out_stride, float* partials,
                    float* d_attn, void* stream);
 int bliss_gat_alpha(const int32_t* indptr, int32_t n_dst, const void* q_ij, const void* a_ij, void* alpha_out, int32_t* err, void* stream);
+
+/* The element-wise glue around a GATv2 layer's message passing in ONE launch per direction, bounded by a device-side row count
+ * (csrc/gat_glue.hip).  For rows r < min(n_rows, *n_rows_dev)  (n_rows_dev NULL: n_rows):
+ *   x = rst[r, h, d] (+ res[r, h, d], rounded to bf16);  y = ELU(x) rounded to bf16 (act = 1) or x (act = 0);
+ *   z = y as [heads * head_dim] (head_mean = 0) or bf16((sum_h y[h, d]) * (1 / heads)) as [head_dim] (head_mean = 1: fp32 sum,
+ *   one rounding);  pre = z (optional);  out = z, or with drop_p > 0:  keep ? bf16(z / (1 - p)) : 0  where keep comes from the
+ *   keyed hash of (drop_seed, launch counter, r * width + column) -- the stream of bliss_sage_epilogue_fwd.  drop_ctr: device
+ *   uint64[2], zero-initialised once (bumped behind every launch with drop_p > 0); drop_ctr_used: device uint32, receives the
+ *   counter the launch used (the backward reads it there).
+ * Rows at or past the live count are written as zeros and nothing of their inputs is read.  heads = 1, act = 0, res = NULL is a
+ * dropout-only pass over [n_rows, head_dim].
+ * _bwd: din [n_rows, heads * head_dim] = the gradient w.r.t. rst (and, unchanged, w.r.t. res) from dout [n_rows, width]: mask and
+ * scale, the transpose of the flatten / head mean, the ELU derivative taken from x (g * exp(x) for x <= 0, as torch's elu does),
+ * each rounded to bf16 where the tensor ops round; zero rows at or past the count.  rst / res are read only when act = 1.
+ * bliss_gat_head_mean: out[e] = bf16((sum_h x[e, h]) * (1 / heads)) for e < min(n_edges, *n_edges_dev); the tail is left alone. */
+typedef struct {
+  const void* rst; int64_t rst_stride;
+  const void* res; int64_t res_stride;
+  int32_t n_rows; const int32_t* n_rows_dev;
+  int32_t heads; int32_t head_dim; int32_t act; int32_t head_mean;
+  float drop_p; uint32_t drop_seed; uint64_t* drop_ctr; uint32_t* drop_ctr_used;
+  void* out; int64_t out_stride;
+  void* pre; int64_t pre_stride;
+  const void* dout; int64_t dout_stride;
+  void* din; int64_t din_stride;
+} bliss_gat_glue_t;
+int bliss_gat_glue_fwd(const bliss_gat_glue_t* args, void* stream);
+int bliss_gat_glue_bwd(const bliss_gat_glue_t* args, void* stream);
+int bliss_gat_head_mean(const void* x, int32_t heads, int32_t n_edges, const int32_t* n_edges_dev, void* out, void* stream);
 
 /* Per-kernel timing with HIP events recorded on the launching stream (bench.py's roofline object).
  * bliss_prof_enable(id): -2 off (default), -1 every kernel, >= 0 one kernel id; names via
