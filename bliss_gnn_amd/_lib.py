@@ -112,6 +112,15 @@ class GatFused(C.Structure):                           # bliss_gat_fused_t
                 ("err", C.c_void_p)]
 
 
+class GatInfer(C.Structure):                           # bliss_gat_infer_t
+    _fields_ = [("indptr", C.c_void_p), ("indices", C.c_void_p), ("row0", C.c_int32), ("n_rows", C.c_int32), ("n_edges", C.c_int64),
+                ("feat", C.c_void_p), ("feat_stride", C.c_int64), ("attn", C.c_void_p), ("heads", C.c_int32), ("head_dim", C.c_int32),
+                ("negative_slope", C.c_float), ("res", C.c_void_p), ("res_stride", C.c_int64), ("act", C.c_int32),
+                ("out", C.c_void_p), ("out_stride", C.c_int64),
+                ("wg_row", C.c_void_p), ("n_wg_dev", C.c_void_p), ("cap_wg", C.c_int32), ("row_ws", C.c_void_p), ("seg_part", C.c_void_p),
+                ("err", C.c_void_p)]
+
+
 class GatGlue(C.Structure):                            # bliss_gat_glue_t
     _fields_ = [("rst", C.c_void_p), ("rst_stride", C.c_int64), ("res", C.c_void_p), ("res_stride", C.c_int64),
                 ("n_rows", C.c_int32), ("n_rows_dev", C.c_void_p),
@@ -280,6 +289,7 @@ SIGNATURES = {
     "bliss_gat_segments": [_P, _I32, _I32, _P, _P, _P, _P],
     "bliss_gat_fused_fwd": [C.POINTER(GatFused), _P],
     "bliss_gat_fused_bwd_dst": [C.POINTER(GatFused), _P, _P, _P, _P],
+    "bliss_gat_infer_fwd": [C.POINTER(GatInfer), _P],
     "bliss_gat_rows_src_fused": [_P, _I32, _P, _P, _P, _P, _I32, _P, _P, _P, _I64, _P, _I64, _P, _I32, _I32, _F, _P, _I64, _P, _P],
     "bliss_gat_logits_f32": [_P, _P, _P, _I32, _P, _I64, _P, _I32, _I32, _F, _P, _P],
     "bliss_gat_edge_dot": [_P, _P, _P, _I32, _P, _I64, _P, _I64, _I32, _I32, _P, _P],

@@ -18,6 +18,8 @@
 // fixtures of tests/golden/gat*_model_exp3.npz hold for both paths.  bf16 conversions use the hardware's
 // v_cvt_pk_bf16_f32 (round to nearest even, like common.cuh:f2bf on every finite input).
 // Where a workgroup's time goes is measured by the kernels themselves (bliss_gat_fused_stamps, scratch/gatbench.py).
+// The same forward, forward only, serves GATv2.inference on destination ranges of the whole graph (bliss_gat_infer_fwd: the INFER
+// instantiation of k_gat_fwd off the graph's int64 indptr, no edge-sized output, residual + ELU in the launch).
 #include "common.cuh"
 #include "bliss_gnn.h"
 
@@ -94,6 +96,11 @@ struct GatFused {
   unsigned* rowws;                                     // [n_dst, GF_ROWWS] zero-initialised, self-cleaning: arrive counters, max, sum
   float* seg_part;                                     // [n_wg, H*D] partial rows of the segments; [n_wg, GF_MAXH] behind it for t
   int* err;
+  // full-neighbour inference off the graph's own CSC (k_gat_fwd<.., .., true>, bliss_gat_infer_fwd): the
+  // destination range row0 .. row0 + n_dst - 1 of a graph whose int64 indptr the descriptors were cut from (k_gat_segments<int64>:
+  // edge offsets relative to indptr[row0]); src then is the graph's `indices`, feat holds ALL nodes' rows
+  const long long* indptr64; int row0;
+  const bf16_t* res; long long res_stride; int act;    // the epilogue of the workgroup that finishes a row (gat_glue.hip's rounding points)
 };
 
 // A row of one edge as the lane's NG column groups, still packed (two registers per group of four bf16).
@@ -200,10 +207,16 @@ __device__ __forceinline__ int4 gf_desc(int row, int rbeg, int rend, int G, int 
   const int beg = rbeg + seg_i * GF_SEG;
   return make_int4(row, beg, G > 1 ? min(rend, beg + GF_SEG) : rend, (G << 16) | seg_i);
 }
-__global__ void __launch_bounds__(1024) k_gat_segments(const int* __restrict__ indptr, int n_dst, int cap_wg, int4* __restrict__ wg_row,
+// IT = int: a block's own indptr.  IT = long long: the graph's indptr from the first row of a destination range on (the pointer is
+// &indptr[row0]); the descriptors then hold edge offsets relative to indptr[row0], which the caller keeps below 2^31
+template <typename IT>
+__global__ void __launch_bounds__(1024) k_gat_segments(const IT* __restrict__ indptr_g, int n_dst, int cap_wg, int4* __restrict__ wg_row,
                                                         int* __restrict__ n_wg_dev, int* err) {
   __shared__ int sh[17];
   int run = 0;
+  struct { const IT* q; IT base; __device__ __forceinline__ int operator[](int i) const { return (int)(q[i] - base); } } indptr;
+  indptr.q = indptr_g;
+  indptr.base = sizeof(IT) == 8 ? indptr_g[0] : (IT)0;
   if (n_dst <= 1024 * GF_SEG_R) {
     // one sweep: a thread owns R consecutive rows, all their degrees loaded up front (the launch sits on the forward's critical
     // path: 15 us as two scanning loops over 9 K rows, a third of that like this)
@@ -304,7 +317,21 @@ __device__ __forceinline__ RowSeg row_segment(const GatFused& p, int vwg) {
 // Forward.  A workgroup holds at most GF_SEG = 256 edges (longer rows are shared), so the logits and the softmax coefficients of
 // its edges live in LDS between the passes (the global copies are outputs only: nothing is re-read from memory, no wait for a
 // store, no agent-scope load) and a wave's source ids are ONE coalesced load kept in registers for both gather passes.
-template <bool VEC4, int HG>
+// INFER (bliss_gat_infer_fwd): the same passes on a destination range of the whole graph -- no edge-sized output (the logits and
+// coefficients only ever live in LDS), no dropout, and the residual add / ELU of gat_glue.hip applied by the workgroup that
+// finishes the row.  Nothing else differs: the bits of a row are the training forward's with p_drop = 0.
+template <bool INFER>
+__device__ __forceinline__ void gf_put_row(const GatFused& p, int row, int col, float s) {
+  bf16_t o = f2bf(s);
+  if (INFER) {
+    float x = bf2f(o);
+    if (p.res) x = rbf(x + bf2f(p.res[(long long)row * p.res_stride + col]));      // the tensor add, rounded
+    if (p.act) x = x <= 0.f ? rbf(expm1f(x)) : x;                                   // ELU (alpha 1), rounded
+    o = f2bf(x);
+  }
+  p.rst[(long long)row * p.rst_stride + col] = o;
+}
+template <bool VEC4, int HG, bool INFER = false>
 __global__ void __launch_bounds__(GF_TPB, 4) k_gat_fwd(GatFused p) {
   constexpr int W = VEC4 ? 4 : 1;
   // HG > 0: "a column group is a head" (VEC4, D == 256: group c of 64 lanes x 4 columns IS head c, H == HG <= 4) -- the Reddit
@@ -319,12 +346,15 @@ __global__ void __launch_bounds__(GF_TPB, 4) k_gat_fwd(GatFused p) {
   __shared__ int sh_last;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int vwg = blockIdx.x;
-  long long* stamps = g_gf_stamps;
+  long long* stamps = INFER ? nullptr : g_gf_stamps;
   GF_STAMP(0);
   if (vwg >= *p.n_wg_dev) return;
   int S = p.n_dst;
   if (p.n_dst_dev) { const int t = *p.n_dst_dev; S = t < S ? t : S; }
   const int H = HG ? HG : p.H, D = p.D, HD = H * D;
+  if (INFER) { p.drop_thresh = 0u; p.src += p.indptr64[p.row0]; }
+  // row r's own feature row (shared weights): the block's destinations are its first source rows, the range's are rows row0 ..
+  const bf16_t* feat_dst = INFER ? p.feat + (long long)p.row0 * p.feat_stride : p.feat;
   const uint32_t ctr = p.drop_thresh ? (uint32_t)__hip_atomic_load(p.ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
   if (vwg == 0 && tid == 0 && p.drop_thresh && p.ctr_used) *p.ctr_used = ctr;
   const RowSeg rs = row_segment(p, vwg);
@@ -336,7 +366,11 @@ __global__ void __launch_bounds__(GF_TPB, 4) k_gat_fwd(GatFused p) {
   }
   unsigned* ws = p.rowws + (long long)row * GF_ROWWS;
   const int my_e = beg + (lane >> 3) * GF_CHUNK + (lane & 7) * GF_WAVES + wave;
-  const int my_s = (lane < GF_NCH * GF_EW && my_e < end) ? p.src[my_e] : 0;
+  int my_s;
+  if (INFER) {                                          // (a graph range: beg + 255 may pass 2^31 there -- offsets are compared, not positions)
+    const int my_off = (lane >> 3) * GF_CHUNK + (lane & 7) * GF_WAVES + wave;
+    my_s = (lane < GF_NCH * GF_EW && my_off < end - beg) ? p.src[(long long)beg + my_off] : 0;
+  } else my_s = (lane < GF_NCH * GF_EW && my_e < end) ? p.src[my_e] : 0;
   const int n_edges = end - beg, n_chunks = (n_edges + GF_CHUNK - 1) / GF_CHUNK;
   // this lane's columns: group c covers columns c*64*W + lane*W .. +W-1 (one head per group when VEC4: D % 4 == 0)
   float acc[NG][W];
@@ -354,7 +388,7 @@ __global__ void __launch_bounds__(GF_TPB, 4) k_gat_fwd(GatFused p) {
   g4f er_at = g4f{{0.f, 0.f, 0.f, 0.f}};
   {
     const int col = (tid & 255) * W;
-    if (col < HD) er_at = ldrow<VEC4>((tid >> 8) ? p.attn + col : p.feat + (long long)row * p.feat_stride + col);
+    if (col < HD) er_at = ldrow<VEC4>((tid >> 8) ? p.attn + col : feat_dst + (long long)row * p.feat_stride + col);
   }
   if (tid < GF_MAXH) sh_sum[tid] = 0ull;
   if (tid == 0) sh_bad = 0;
@@ -415,7 +449,7 @@ __global__ void __launch_bounds__(GF_TPB, 4) k_gat_fwd(GatFused p) {
       for (int j = 0; j < GF_EW; ++j) {
         if (j < n_mine && lane < H) {
           const int eidx = k * GF_CHUNK + j * GF_WAVES + wave;
-          p.e[(long long)(beg + eidx) * H + lane] = (bf16_t)(__float_as_uint(mine[j]) >> 16);
+          if (!INFER) p.e[(long long)(beg + eidx) * H + lane] = (bf16_t)(__float_as_uint(mine[j]) >> 16);
           sh_e[eidx][lane] = mine[j];
         }
       }
@@ -455,7 +489,7 @@ __global__ void __launch_bounds__(GF_TPB, 4) k_gat_fwd(GatFused p) {
             mx[h] = max_raw(mx[h], eb);
           }
         }
-        if (lane < H) { p.e[(long long)(beg + eidx) * H + lane] = (bf16_t)(__float_as_uint(mine) >> 16); sh_e[eidx][lane] = mine; }
+        if (lane < H) { if (!INFER) p.e[(long long)(beg + eidx) * H + lane] = (bf16_t)(__float_as_uint(mine) >> 16); sh_e[eidx][lane] = mine; }
       }
     }
   };
@@ -523,7 +557,7 @@ __global__ void __launch_bounds__(GF_TPB, 4) k_gat_fwd(GatFused p) {
     if (sh_bad) ssum = __builtin_nanf("");             // a non-finite logit: the reference's sum, and with it the row, is NaN
     const long long o = (long long)beg * H + i;
     const bf16_t av = f2bf(sh_e[eidx][h] / ssum);
-    p.a[o] = av;
+    if (!INFER) p.a[o] = av;
     bf16_t cv = av;
     if (p.drop_thresh) {                               // nn.Dropout on a bf16 tensor: a * mask / (1 - p), one rounding
       const bool keep = gf_drop_hash(p.seed, ctr, (uint32_t)o) >= p.drop_thresh;
@@ -572,7 +606,7 @@ __global__ void __launch_bounds__(GF_TPB, 4) k_gat_fwd(GatFused p) {
       float s = sh_acc[0][col];
 #pragma unroll
       for (int w2 = 1; w2 < GF_WAVES; ++w2) s += sh_acc[w2][col];   // fixed order: bitwise reproducible
-      p.rst[(long long)row * p.rst_stride + col] = f2bf(s);
+      gf_put_row<INFER>(p, row, col, s);
     }
     GF_STAMP(7);
     return;
@@ -589,7 +623,7 @@ __global__ void __launch_bounds__(GF_TPB, 4) k_gat_fwd(GatFused p) {
     for (int col = tid; col < HD; col += GF_TPB) {
       float s = 0.f;
       for (int q = 0; q < G; ++q) s += __hip_atomic_load(p.seg_part + (v0 + q) * HD + col, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      p.rst[(long long)row * p.rst_stride + col] = f2bf(s);
+      gf_put_row<INFER>(p, row, col, s);
     }
     for (int i = tid; i < GF_ROWWS; i += GF_TPB) ws[i] = 0u;          // the row's words back to zero for the next launch
   }
@@ -870,6 +904,7 @@ bool gf_fill(const bliss_gat_fused_t* a, GatFused* p, bool* vec4) {
   p->d_er = (bf16_t*)a->d_er; p->der_stride = a->d_er_stride; p->dattn_part = a->dattn_part;
   p->wg_row = reinterpret_cast<const int4*>(a->wg_row); p->n_wg_dev = a->n_wg_dev; p->rowws = (unsigned*)a->row_ws; p->seg_part = a->seg_part; p->err = a->err;
   if (!a->wg_row || !a->n_wg_dev || !a->row_ws || !a->seg_part || a->cap_wg < a->n_dst) return false;
+  p->indptr64 = nullptr; p->row0 = 0; p->res = nullptr; p->res_stride = 0; p->act = 0;
   *vec4 = v4;
   return true;
 }
@@ -892,7 +927,7 @@ int bliss_gat_fused_stamps(long long* stamps, long long* stamps_bwd) {
 
 int bliss_gat_segments(const int32_t* indptr, int32_t n_dst, int32_t cap_wg, int32_t* wg_row, int32_t* n_wg_dev, int32_t* err, void* stream) {
   if (!indptr || !wg_row || !n_wg_dev || n_dst <= 0 || cap_wg < n_dst) return BLISS_EINVAL;
-  k_gat_segments<<<1, 1024, 0, (hipStream_t)stream>>>(indptr, n_dst, cap_wg, reinterpret_cast<int4*>(wg_row), n_wg_dev, err);
+  k_gat_segments<int><<<1, 1024, 0, (hipStream_t)stream>>>(indptr, n_dst, cap_wg, reinterpret_cast<int4*>(wg_row), n_wg_dev, err);
   return (int)hipGetLastError();
 }
 
@@ -911,6 +946,44 @@ int bliss_gat_fused_fwd(const bliss_gat_fused_t* args, void* stream) {
   else if (v4) k_gat_fwd<true, 0><<<grid, GF_TPB, 0, st>>>(p);
   else k_gat_fwd<false, 0><<<grid, GF_TPB, 0, st>>>(p);
   if (p.drop_thresh) k_gat_bump<<<1, 64, 0, st>>>(p.ctr);
+  return (int)hipGetLastError();
+}
+
+// Full-neighbour inference for the destination range row0 .. row0 + n_rows - 1 of the graph's own CSC: the
+// range's descriptors (k_gat_segments on &indptr[row0]: offsets relative to indptr[row0], which the forward adds to `indices`
+// itself -- the host's n_edges only sizes the scratch and is refused when a 32-bit offset could not hold it), then the forward
+// with no edge-sized output and the glue's epilogue on the finishing workgroup.
+int bliss_gat_infer_fwd(const bliss_gat_infer_t* a, void* stream) {
+  if (!a || !a->indptr || !a->indices || !a->feat || !a->attn || !a->out) return BLISS_EINVAL;
+  if (a->heads <= 0 || a->heads > GF_MAXH || a->head_dim <= 0 || !bliss_gat_fused_supported(a->heads, a->head_dim)) return BLISS_EINVAL;
+  if (a->n_rows < 0 || a->row0 < 0 || a->n_edges < 0 || a->n_edges >= (1ll << 31) || (a->act != 0 && a->act != 1)) return BLISS_EINVAL;
+  const int HD = a->heads * a->head_dim;
+  const bool v4 = a->head_dim % 4 == 0 && a->feat_stride % 4 == 0 && ((uintptr_t)a->feat) % 8 == 0 && ((uintptr_t)a->attn) % 8 == 0;
+  if (HD > GF_ITER * 64 * (v4 ? 4 : 1)) return BLISS_EINVAL;               // the 4-column path's alignment, where the width needs it
+  if (((uintptr_t)a->feat) % 2 || ((uintptr_t)a->attn) % 2 || ((uintptr_t)a->out) % 2 || ((uintptr_t)a->res) % 2) return BLISS_EINVAL;
+  if (a->feat_stride < HD || a->out_stride < HD || (a->res && a->res_stride < HD)) return BLISS_EINVAL;
+  if (((uintptr_t)a->indptr) % 8 || ((uintptr_t)a->indices) % 4) return BLISS_EINVAL;
+  if (a->n_rows == 0) return 0;                                            // an empty range: nothing is launched or written
+  const long long need_wg = (long long)a->n_rows + a->n_edges / GF_SEG;
+  if (!a->wg_row || ((uintptr_t)a->wg_row) % 16 || !a->n_wg_dev || !a->row_ws || !a->seg_part || a->cap_wg < need_wg) return BLISS_EINVAL;
+  GatFused p = {};
+  p.indptr64 = (const long long*)a->indptr; p.row0 = a->row0; p.src = a->indices; p.n_dst = a->n_rows;
+  p.feat = (const bf16_t*)a->feat; p.feat_stride = a->feat_stride; p.attn = (const bf16_t*)a->attn;
+  p.H = a->heads; p.D = a->head_dim; p.slope = a->negative_slope; p.drop_scale = 1.0f;
+  p.rst = (bf16_t*)a->out; p.rst_stride = a->out_stride; p.res = (const bf16_t*)a->res; p.res_stride = a->res_stride; p.act = a->act;
+  p.wg_row = reinterpret_cast<const int4*>(a->wg_row); p.n_wg_dev = a->n_wg_dev; p.rowws = (unsigned*)a->row_ws; p.seg_part = a->seg_part;
+  p.err = a->err;
+  hipStream_t st = (hipStream_t)stream;
+  // (the grid is what the host's edge count allows: more descriptors than that -- a count that was not this range's -- are cut
+  // off with BLISS_ERR_CAP_EDGES in *err instead of running past the scratch)
+  const int grid = (int)need_wg;
+  k_gat_segments<long long><<<1, 1024, 0, st>>>(p.indptr64 + a->row0, a->n_rows, grid, reinterpret_cast<int4*>(a->wg_row), a->n_wg_dev, a->err);
+  const int hg = (v4 && p.D == 256 && (p.H == 1 || p.H == 2 || p.H == 4)) ? p.H : 0;
+  if (hg == 4) k_gat_fwd<true, 4, true><<<grid, GF_TPB, 0, st>>>(p);
+  else if (hg == 2) k_gat_fwd<true, 2, true><<<grid, GF_TPB, 0, st>>>(p);
+  else if (hg == 1) k_gat_fwd<true, 1, true><<<grid, GF_TPB, 0, st>>>(p);
+  else if (v4) k_gat_fwd<true, 0, true><<<grid, GF_TPB, 0, st>>>(p);
+  else k_gat_fwd<false, 0, true><<<grid, GF_TPB, 0, st>>>(p);
   return (int)hipGetLastError();
 }
 

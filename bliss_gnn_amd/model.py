@@ -354,14 +354,94 @@ class GATv2(nn.Module):
             h = h.flatten(1) if l < len(blocks) - 1 else h.mean(1)                                             # :228-232
         return h
 
+    INFERENCE_PATHS = ("auto", "blocks", "csc")
+    csc_min_rows = 1 << 16          # "csc": a destination range holds at least this many rows (``node_chunk`` may ask for more) ...
+    csc_max_edges = 1 << 22         # ... and about this many edges at most: the fp32 partial rows of the scratch grow with edges / 256
+    last_inference_path = None      # the path the last ``inference`` call took
+
+    def csc_refusal(self, g, h):
+        """Why ``inference(path="csc")`` cannot run on this graph and these features, or None."""
+        if not (g.device.type == "cuda" and h.is_cuda):
+            return "GATv2.inference: the CSC path runs on the GPU (graph on %s, features on %s)" % (g.device, h.device)
+        for l, layer in enumerate(self.gatv2_layers):
+            why = layer.infer_refusal(h, "GATv2 layer %d" % l)
+            if why is not None:
+                return why
+        return None
+
+    def _csc_ranges(self, g, node_chunk):
+        """Destination ranges of the CSC path: [(row0, row1, edges)], contiguous, each at most max(node_chunk, csc_min_rows) rows
+        and (a single longer row aside) csc_max_edges + one row's edges -- cut on the device, read by the host ONCE per call."""
+        V, E = g.num_nodes(), g.num_edges()
+        rows = max(int(node_chunk), int(self.csc_min_rows), 1)
+        cuts = [torch.arange(0, V, rows, device=g.device, dtype=torch.int64), torch.tensor([V], device=g.device, dtype=torch.int64)]
+        if E > self.csc_max_edges:
+            targets = g.indptr[0] + torch.arange(1, E // int(self.csc_max_edges) + 1, device=g.device, dtype=torch.int64) * int(self.csc_max_edges)
+            cuts.append((torch.searchsorted(g.indptr, targets, right=True) - 1).clamp_(0, V))      # the last row starting at or before a target
+        cuts = torch.unique(torch.cat(cuts))                                                      # (sorted)
+        both = torch.stack([cuts, g.indptr[cuts]]).tolist()                                       # the call's one host read
+        ranges = [(r0, r1, e1 - e0) for r0, r1, e0, e1 in zip(both[0][:-1], both[0][1:], both[1][:-1], both[1][1:])]
+        if any(e >= 2 ** 31 for _, _, e in ranges):
+            raise NotImplementedError("GATv2.inference: a node with 2^31 or more in-edges is beyond the CSC path")
+        return ranges
+
+    def _inference_csc(self, g, h, node_chunk):
+        """Per layer: fc_src (and a Linear res_fc) ONCE over all rows, then one launch pair per destination range off the graph's
+        own indptr / indices -- finished rows (residual, ELU, flatten) out of the message-passing kernel; the last layer's head
+        mean is one glue launch per range."""
+        from .nn import gat_glue, gat_infer_state
+        ranges = self._csc_ranges(g, node_chunk)
+        state = gat_infer_state(h.device)
+        V, n = g.num_nodes(), len(self.gatv2_layers)
+        for l, layer in enumerate(self.gatv2_layers):
+            H, D = layer._num_heads, layer._out_feats
+            feat_src, res = layer.infer_transform(h)
+            last = l == n - 1
+            y = torch.empty(V, D if last else H * D, dtype=torch.bfloat16, device=h.device)
+            rows = torch.empty(max(r1 - r0 for r0, r1, _ in ranges), H * D, dtype=torch.bfloat16, device=h.device) if last else None
+            for r0, r1, edges in ranges:
+                out = rows[: r1 - r0] if last else y[r0:r1]
+                layer.infer_rows(g, r0, r1, edges, feat_src, res, out, state)
+                if last:
+                    y[r0:r1] = gat_glue(out, None, H, D, head_mean=True)[0]                         # :282-285
+            del feat_src, res
+            h = y
+            g.ndata["h"] = h
+        err = int(state["err"].item())
+        if err:
+            from . import _lib
+            raise RuntimeError("GATv2.inference (csc): error 0x%x (%s)" % (err, _lib.err_string(err)))
+        return h
+
     @torch.no_grad()
-    def inference(self, g, device=None, batch_size=128, use_uva=False, num_workers=0, node_chunk=4096):
+    def inference(self, g, device=None, batch_size=128, use_uva=False, num_workers=0, node_chunk=4096, path="auto"):
         """model.py:236-289.  Every output row depends only on its own in-edges (edge softmax is per destination), so the
-        nodes are walked ``node_chunk`` at a time instead of the reference loader's ``batch_size``; the rows are the same."""
+        nodes are walked in contiguous ranges instead of the reference loader's ``batch_size``; the rows are the same.
+
+        ``path="blocks"``: the full-neighbour block of ``node_chunk`` nodes at a time through the layers' ``forward``.
+        ``path="csc"``: straight off the graph's CSC -- each layer's transforms once over all nodes, one
+        forward-only message-passing launch per destination range; ``node_chunk`` only sizes the ranges (with the floor
+        ``csc_min_rows``) and never changes the result.  Raises NotImplementedError naming the reason when it cannot run.
+        ``path="auto"``: "csc" for a ``transforms="tile"`` model within the CSC path's limits, "blocks" otherwise.
+        The path taken is left in ``last_inference_path``."""
+        if path not in self.INFERENCE_PATHS:
+            raise ValueError("path must be one of %r, not %r" % (self.INFERENCE_PATHS, path))
+        h = g.ndata["features"].bfloat16()
+        if path != "blocks":
+            why = self.csc_refusal(g, h)
+            if path == "csc" and why is not None:
+                raise NotImplementedError(why)
+            path = "csc" if (why is None and (path == "csc" or self.transforms == "tile")) else "blocks"
         was_training = self.training
         self.eval()                                                                                            # :265
-        n = len(self.gatv2_layers)
-        h = _blockwise_inference(self.gatv2_layers, g, g.ndata["features"].bfloat16(), int(node_chunk),
-                                 lambda l, out: out.flatten(1) if l < n - 1 else out.mean(1))                  # :282-285
-        self.train(was_training)
+        try:
+            if path == "csc":
+                h = self._inference_csc(g, h, int(node_chunk))
+            else:
+                n = len(self.gatv2_layers)
+                h = _blockwise_inference(self.gatv2_layers, g, h, int(node_chunk),
+                                         lambda l, out: out.flatten(1) if l < n - 1 else out.mean(1))          # :282-285
+        finally:
+            self.train(was_training)
+        self.last_inference_path = path
         return h

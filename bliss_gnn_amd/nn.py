@@ -996,6 +996,66 @@ class _GatFusedMP(torch.autograd.Function):
         return d_feat, d_attn.to(ctx.attn_dtype).view(ctx.attn_shape), None, None, None, None, None, None
 
 
+def gat_infer_state(device):
+    """Scratch of ``gat_infer_layer``: the error word and the buffers that grow with the largest range seen."""
+    return dict(err=torch.zeros(1, dtype=torch.int32, device=device), n_wg=torch.empty(1, dtype=torch.int32, device=device),
+                wg_row=None, row_ws=None, seg_part=None)
+
+
+def _gat_infer_refusal(feat, H, D, what="gat_infer_layer"):
+    """Why the CSC inference kernel cannot take these rows, or None."""
+    if not (feat.is_cuda and feat.dtype == torch.bfloat16):
+        return "%s: the CSC inference path takes bf16 rows on the GPU, not %s on %s" % (what, feat.dtype, feat.device)
+    if not _gat_fused_on(H, D):
+        return ("%s: the CSC inference path runs on the fused message-passing kernel (bliss_gat_fused_supported(%d, %d) is false "
+                "or BLISS_GAT_FUSED=0)" % (what, H, D))
+    return None
+
+
+def gat_infer_layer(indptr, indices, row0, row1, n_edges, feat, attn, H, D, slope, out, res=None, act=0, state=None):
+    """model.py:82-106 for the destinations ``row0 .. row1 - 1`` of the WHOLE graph in one launch pair (bliss_gat_infer_fwd,
+    DESIGN.md section 23): ``out[r - row0] = act(rst_r + res[r - row0])`` with ``rst`` the fused kernel's bits on the range's
+    full-neighbour block, read straight off the graph's int64 ``indptr`` / int32 ``indices``.  ``feat`` = fc_src(h) of ALL nodes
+    [V, H*D]; ``res`` the range's residual rows or None; ``out`` [row1 - row0, H*D] bf16 (a view of the layer's rows);
+    ``n_edges`` = indptr[row1] - indptr[row0] as the host read it (below 2^31).  ``state`` (``gat_infer_state``) owns the
+    scratch and regrows it by range; no host read, nothing of edge size allocated."""
+    import ctypes as C
+    why = _gat_infer_refusal(feat, H, D)
+    if why is not None:
+        raise NotImplementedError(why)
+    n_rows, HD, dev = int(row1) - int(row0), H * D, feat.device
+    V = indptr.numel() - 1
+    if not (0 <= row0 <= row1 <= V) or feat.shape[0] < V or feat.shape[1] != HD or feat.stride(1) != 1:
+        raise ValueError("gat_infer_layer: rows %d .. %d of %d nodes, feat %r for H*D = %d" % (row0, row1, V, tuple(feat.shape), HD))
+    if indptr.dtype != torch.int64 or indices.dtype != torch.int32 or not (indptr.is_contiguous() and indices.is_contiguous()):
+        raise ValueError("gat_infer_layer: the graph's CSC is int64 indptr / int32 indices, contiguous")
+    if out.dtype != torch.bfloat16 or out.shape != (n_rows, HD) or out.stride(1) != 1 or out.device != dev:
+        raise ValueError("gat_infer_layer: out is bf16 [%d, %d] on %s" % (n_rows, HD, dev))
+    if res is not None and (res.dtype != torch.bfloat16 or res.shape != (n_rows, HD) or res.stride(1) != 1 or res.device != dev):
+        raise ValueError("gat_infer_layer: res is bf16 [%d, %d] on %s" % (n_rows, HD, dev))
+    if n_rows == 0:
+        return out
+    st = gat_infer_state(dev) if state is None else state
+    cap_wg = n_rows + int(n_edges) // int(_lib.lib.bliss_gat_segment_edges())
+    if st["wg_row"] is None or st["wg_row"].shape[0] < cap_wg:
+        st["wg_row"] = torch.empty(cap_wg, 4, dtype=torch.int32, device=dev)
+    if st["seg_part"] is None or st["seg_part"].numel() < cap_wg * HD:
+        st["seg_part"] = torch.empty(cap_wg * HD, dtype=torch.float32, device=dev)
+    if st["row_ws"] is None or st["row_ws"].numel() < n_rows * 32:
+        st["row_ws"] = torch.zeros(n_rows * 32, dtype=torch.int32, device=dev)        # (zero once: the kernel returns it to zero)
+    attn_f = attn.detach().reshape(-1).contiguous()
+    t = _lib.GatInfer()
+    t.indptr, t.indices, t.row0, t.n_rows, t.n_edges = indptr.data_ptr(), indices.data_ptr(), int(row0), n_rows, int(n_edges)
+    t.feat, t.feat_stride, t.attn, t.heads, t.head_dim, t.negative_slope = feat.data_ptr(), feat.stride(0), attn_f.data_ptr(), H, D, float(slope)
+    if res is not None:
+        t.res, t.res_stride = res.data_ptr(), res.stride(0)
+    t.act, t.out, t.out_stride = int(act), out.data_ptr(), out.stride(0)
+    t.wg_row, t.n_wg_dev, t.cap_wg = st["wg_row"].data_ptr(), st["n_wg"].data_ptr(), cap_wg
+    t.row_ws, t.seg_part, t.err = st["row_ws"].data_ptr(), st["seg_part"].data_ptr(), st["err"].data_ptr()
+    _lib.check(_lib.lib.bliss_gat_infer_fwd(C.byref(t), _stream()), "bliss_gat_infer_fwd")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ GATv2 on bounded kernels
 # transforms="tile" (DESIGN.md section 22): fc_src / res_fc on the MFMA tile kernels, the glue around the message passing in one
 # launch per direction (csrc/gat_glue.hip) -- every loop that crosses rows is bounded by the block's device-side counts, so the
@@ -1372,6 +1432,43 @@ class GATv2Conv(nn.Module):
         p_drop = float(self.attn_drop.p) if self.training else 0.0
         rst, e = _GatFusedMP.apply(feat_src, self.attn, graph, H, D, self.negative_slope, p_drop, self._fused_state(feat_src.device))
         return rst, res, e
+
+    # -- full-neighbour inference off the graph's CSC -------------------------------------------------
+    def infer_refusal(self, h_all, what="GATv2Conv"):
+        """Why ``infer_transform`` / ``infer_rows`` cannot run on these input rows, or None."""
+        why = _gat_infer_refusal(h_all, self._num_heads, self._out_feats, what)
+        if why is None and self.fc_src.weight.dtype != torch.bfloat16:
+            why = "%s: the CSC inference path takes bf16 parameters" % what
+        if why is None and self.transforms == "tile" and self._in > TILE_GEMM_MAX_K:
+            why = self.tile_refusal(what)
+        if why is None:
+            try:
+                _glue_act(self.activation, what)
+            except NotImplementedError:
+                why = "%s: the CSC inference kernel's epilogue has the activations ELU (alpha 1) and None, not %r" % (what, self.activation)
+        return why
+
+    def infer_transform(self, h_all):
+        """(fc_src(h) [V, H*D], res [V, H*D] or None) over ALL rows, once per layer: on the tile kernels for a
+        ``transforms="tile"`` layer (a row's bits do not depend on how many rows the launch has), on nn.Linear otherwise.
+        An identity residual is the input itself."""
+        lin = isinstance(self.res_fc, nn.Linear)
+        if self.transforms == "tile":
+            V = h_all.shape[0]
+            feat_src, res = gat_linear(h_all, self.fc_src.weight, self.fc_src.bias, V, 0, self.res_fc.weight if lin else None,
+                                       self.res_fc.bias if lin else None, V if lin else 0, 0)
+        else:
+            feat_src, res = self.fc_src(h_all), (self.res_fc(h_all) if lin else None)
+        if self.res_fc is not None and not lin:
+            res = h_all                                                          # nn.Identity (in_feats == H * D)
+        return feat_src, res
+
+    def infer_rows(self, g, row0, row1, n_edges, feat_src_all, res_all, out, state):
+        """The finished rows ``row0 .. row1 - 1`` of this layer in evaluation mode, flattened [rows, H*D], into ``out`` (see
+        ``gat_infer_layer``): message passing over all in-edges, residual and activation in one launch pair."""
+        return gat_infer_layer(g.indptr, g.indices, row0, row1, n_edges, feat_src_all, self.attn, self._num_heads, self._out_feats,
+                               self.negative_slope, out, None if res_all is None else res_all[row0:row1],
+                               _glue_act(self.activation, "GATv2Conv"), state)
 
     def _forward_tile(self, graph, feat, get_attention):
         H, D, S = self._num_heads, self._out_feats, graph.num_dst_nodes()

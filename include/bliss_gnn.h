@@ -910,6 +910,40 @@ int bliss_gat_rows_src_fused(const int32_t* t_indptr, int32_t n_src, const int32
                              void* out, int64_t out_stride, float* partials, void* stream);
 int bliss_gat_fused_fwd(const bliss_gat_fused_t* args, void* stream);
 int bliss_gat_fused_bwd_dst(const bliss_gat_fused_t* args, float* block_sums, float* d_attn, uint32_t* ticket, void* stream);
+/* Full-neighbour inference of one GATv2 layer straight off the graph's CSC (custom_GATv2Conv under model.py:236-289; DESIGN.md
+ * section 23): finished layer rows for the destinations row0 .. row0 + n_rows - 1, two launches (the range's workgroup
+ * descriptors, then the forward), no block, no id remapping, nothing of edge size written.
+ *   indptr  int64 [V + 1], 8-byte aligned; indices int32 [E], 4-byte aligned: the source of CSC position pos is feat[indices[pos]],
+ *           row r of the range owns the positions indptr[row0 + r] .. indptr[row0 + r + 1] - 1 and its own feature row is
+ *           feat[row0 + r] (shared weights).  row0 >= 0, n_rows >= 0, row0 + n_rows <= V and indices[] < V are the caller's.
+ *   n_edges indptr[row0 + n_rows] - indptr[row0] as the host knows it: it sizes the scratch (below) and must be < 2^31 (offsets
+ *           inside a range are 32-bit; everything added to a pointer is 64-bit).  The kernels read the offsets from indptr itself;
+ *           a range that holds more edges than stated is cut off with BLISS_ERR_CAP_EDGES in *err, never run past the scratch.
+ *   feat    bf16 [V, heads*head_dim] = fc_src(h) of ALL nodes, row stride feat_stride >= heads*head_dim elements; attn bf16
+ *           [heads, head_dim].  Limits: bliss_gat_fused_supported(heads, head_dim).  feat, attn, res, out 2-byte aligned; a width
+ *           above 256 runs on 8-byte loads and needs head_dim % 4 == 0, feat and attn 8-byte aligned, feat_stride % 4 == 0.
+ *   res     bf16 [n_rows, heads*head_dim] (row r of the RANGE, stride res_stride) or NULL; act 0 = none, 1 = ELU (alpha 1).
+ *   out     bf16 [n_rows, heads*head_dim], stride out_stride >= heads*head_dim:
+ *           out[r] = act(bf16(rst[r] + res[r])) rounded to bf16, with rst the bits bliss_gat_fused_fwd(drop_p = 0) gives on the
+ *           full-neighbour block of the range and the add / ELU rounded where bliss_gat_glue_fwd rounds them.  A row without
+ *           in-edges has rst = 0.  Rows outside the range are not touched.
+ *   scratch wg_row int32 [4 * cap_wg], 16-byte aligned, and n_wg_dev int32 [1]: written by the call; cap_wg >= n_rows + n_edges /
+ *           bliss_gat_segment_edges(); seg_part float [cap_wg * heads*head_dim]; row_ws uint32 [32 * n_rows], zero-initialised
+ *           once (the kernel returns it to zero: launches follow each other without a memset); err (optional) int32, receives
+ *           BLISS_ERR_FLAG_TIMEOUT if the workgroups of a shared row fail to meet within the spin bound, as for the fused kernels.
+ * n_rows == 0 launches nothing and returns 0 (the scratch may then be NULL).  BLISS_EINVAL, before any launch: args, indptr,
+ * indices, feat, attn or out NULL; heads outside 1 .. 8, head_dim <= 0 or a pair bliss_gat_fused_supported refuses; n_rows, row0
+ * or n_edges negative; n_edges >= 2^31; act not 0 or 1; a pointer or stride that breaks the alignment above (a width above 256
+ * without the 8-byte alignment included); a stride below heads*head_dim; with n_rows > 0 missing or misaligned scratch or a
+ * cap_wg below the bound. */
+typedef struct {
+  const int64_t* indptr; const int32_t* indices; int32_t row0; int32_t n_rows; int64_t n_edges;
+  const void* feat; int64_t feat_stride; const void* attn; int32_t heads; int32_t head_dim; float negative_slope;
+  const void* res; int64_t res_stride; int32_t act;
+  void* out; int64_t out_stride;
+  int32_t* wg_row; int32_t* n_wg_dev; int32_t cap_wg; void* row_ws; float* seg_part; int32_t* err;
+} bliss_gat_infer_t;
+int bliss_gat_infer_fwd(const bliss_gat_infer_t* args, void* stream);
 /* bliss_gat_logits without the intermediate bf16 roundings, float result (the north star's 1e-4 check against fp32 math);
  * likewise bliss_gat_edge_softmax with backward == 2 (float logits in, float out) and bliss_gat_rows with which == 4 (the
  * forward aggregation with float coefficients and float output rows, out_stride in floats). */
