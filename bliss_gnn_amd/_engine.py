@@ -51,6 +51,7 @@ class _LayerWs:
         # device-side multinomial draw (csrc/mn_draw.hip): race keys + bins / ticket / tie counts (zero once, left zero by every call)
         self.keys = torch.empty(cap_c, dtype=torch.float32, device=dev)
         self.draw_scr = torch.zeros(int(_lib.lib.bliss_multinomial_draw_scratch_bytes(cap_c)) // 4, dtype=torch.int32, device=dev)
+        self.rdraw_scr = None               # csrc/replace_draw.hip's layer-wise draw: ticket, per-chunk and per-candidate prefixes (zero once)
         self.src_cnt = None
         self.tr_temp = None                 # neighbor layers: bliss_block_transpose's temporary, (capacities, bytes, tensor)
 
@@ -111,6 +112,8 @@ class LayerEngine:
         self._static_draw = {}
         self.exact_k = False                # device-drawn multinomial layers keep at most fanout + S nodes: K capacities are that bound
         self.exact_b = False                # neighbor layers keep at most fanout edges per seed: B capacities are that bound
+        self.nb_replace = False             # neighbor layers drawn WITH replacement hold exactly fanout edges per non-empty column: B <= S * fanout, not |E|
+        self._nr_scr = None                 # csrc/replace_draw.hip's node-wise draw: csrc/neighbor.hip's words
         self._nb_scr = None                 # csrc/neighbor.hip: tickets + node bitmap (zero once, left zero by every call)
         self._wn_scr = None                 # csrc/neighbor_w.hip: the same words + a record per seed and a staged key per CSC position
         self._lb_scr = None                 # csrc/labor.hip: the same words + one kept count per seed column; (cap_s, tensor)
@@ -280,10 +283,8 @@ class LayerEngine:
         ``draw="device"`` (with ``draw_state``, a DrawState): the keyed draw of csrc/mn_draw.hip instead -- frontier_prob,
         multinomial_draw, multinomial_select_marked and build_block of all L layers are only enqueued and the call synchronises
         once, at the end, like sample_blocks; torch's CPU generator is not touched."""
-        if draw == "device":
-            if replace:
-                raise NotImplementedError("the device draw is without replacement only (replace=True needs draw='host')")
-            return self._sample_blocks_mn_device(w_rows, seeds, fanouts, mode, eta, draw_state)
+        if draw == "device":                   # (``replace``: the keyed draw WITH replacement of csrc/replace_draw.hip, section 24)
+            return self._sample_blocks_mn_device(w_rows, seeds, fanouts, mode, eta, draw_state, replace=bool(replace))
         if draw != "host":
             raise ValueError("draw must be 'host' or 'device', not %r" % (draw,))
         seeds = seeds.to(torch.int32).contiguous()
@@ -349,7 +350,7 @@ class LayerEngine:
                 self.caps[n + 1]["S"] = self.caps[n]["K"]
                 self.ws = None
 
-    def _sample_blocks_mn_device(self, w_rows, seeds, fanouts, mode, eta, draw_state):
+    def _sample_blocks_mn_device(self, w_rows, seeds, fanouts, mode, eta, draw_state, replace=False):
         if draw_state is None:
             raise ValueError("draw='device' needs a draw_state")
         seeds = seeds.to(torch.int32).contiguous()
@@ -358,7 +359,7 @@ class LayerEngine:
         self._mn_exact_caps(fanouts)
         self._ensure(int(seeds.numel()), fanouts)
         while True:
-            out = self._enqueue(w_rows, seeds, fanouts, mode, eta, 0.0, None, None, draw_state=draw_state)
+            out = self._enqueue(w_rows, seeds, fanouts, mode, eta, 0.0, None, None, draw_state=draw_state, replace=replace)
             self.counts_host.copy_(out[0], non_blocking=True)
             torch.cuda.current_stream().synchronize()                 # the one sync of the call
             raw = self.counts_host.numpy().tobytes()
@@ -369,7 +370,7 @@ class LayerEngine:
             if bad & ~_CAP_ERRS or bad & 1 or (bad & 2 and not self.n_bins):
                 raise RuntimeError(f"sampler kernel error 0x{bad:x}: {_lib.err_string(bad)}")
             if bad == 0:
-                return self._finish(out, cnts, keys=True)
+                return self._finish(out, cnts, keys=not replace)
             draw_state.step_dev.sub_(1)                                # the repeated call is the same draw step
             self._grow([c.err for c in cnts])
             self._ensure(int(seeds.numel()), fanouts)
@@ -384,7 +385,9 @@ class LayerEngine:
         for f in fanouts:
             f = int(f)
             b = int(min(self.Eg, s * f)) if f >= 0 else int(min(self.Eg, max(1 << 16, 48 * s)))
-            k = int(min(self.V, s + b)) if f >= 0 else self.V
+            if self.nb_replace and f >= 0:      # (a column of fewer than f edges holds f block edges: |E| is no bound)
+                b = int(min(2 ** 31 - 1, s * f))
+            k = int(min(self.V, s + min(b, self.Eg))) if f >= 0 else self.V
             caps.append(dict(S=s, C=self.V, K=k, B=b))
             s = k
         return caps
@@ -397,17 +400,22 @@ class LayerEngine:
             self.caps, self.ws = fresh, None
         self._ensure(S0, fan)
 
-    def sample_blocks_neighbor(self, seeds, fanouts, draw_state, nb_prob=None):
+    def sample_blocks_neighbor(self, seeds, fanouts, draw_state, nb_prob=None, replace=False):
         """fit.NeighborSampler with ``draw="device"`` (csrc/neighbor.hip): the L layers (``fanouts`` in
         SAMPLING order) are only enqueued and the call synchronises once, at the end; torch's generators are not touched.
-        ``nb_prob``: the weighted draw of csrc/neighbor_w.hip -- ``neighbor_prob(...)``'s record."""
+        ``nb_prob``: the weighted draw of csrc/neighbor_w.hip -- ``neighbor_prob(...)``'s record.
+        ``replace``: the draw WITH replacement of csrc/replace_draw.hip, uniform or over a raw-mode
+        ``nb_prob``."""
         if draw_state is None:
             raise ValueError("draw='device' needs a draw_state")
         seeds = seeds.to(torch.int32).contiguous()
         L = len(fanouts)
+        if bool(replace) != self.nb_replace:
+            self.nb_replace, self.caps, self.ws = bool(replace), None, None
         self._ensure_neighbor(int(seeds.numel()), fanouts)
         while True:
-            out = self._enqueue(None, seeds, fanouts, 0, 0.0, 0.0, None, None, draw_state=draw_state, neighbor=True, nb_prob=nb_prob)
+            out = self._enqueue(None, seeds, fanouts, 0, 0.0, 0.0, None, None, draw_state=draw_state, neighbor=True, nb_prob=nb_prob,
+                                nb_replace=bool(replace))
             self.counts_host.copy_(out[0], non_blocking=True)
             torch.cuda.current_stream().synchronize()                 # the one sync of the call
             raw = self.counts_host.numpy().tobytes()
@@ -533,12 +541,29 @@ class LayerEngine:
         return self._wn_scr
 
     def _enqueue_neighbor_layer(self, n, fanout, cur_seeds, n_seeds, n_seeds_dev, draw_state, last, c_ws, c_out, lay, cnt_ptr, st,
-                                labor=False, layer_dependency=False, labor_iterations=0, nb_prob=None, lb_prob=None, p_out=None):
+                                labor=False, layer_dependency=False, labor_iterations=0, nb_prob=None, lb_prob=None, p_out=None,
+                                nb_replace=False):
         """One bliss_neighbor_layer (``labor``: one bliss_labor_layer, or one bliss_labor_is_layer when ``labor_iterations`` > 0, or
         one bliss_wlabor_layer with ``lb_prob``, its p_ij into ``p_out``; ``nb_prob``: one bliss_wneighbor_layer) + the by-source
-        index of its block (bliss_block_transpose on the device-resident B)."""
+        index of its block (bliss_block_transpose on the device-resident B).  ``nb_replace``: one bliss_neighbor_replace_layer,
+        uniform or over the raw-mode ``nb_prob``."""
         cap, ws = self.caps[n], self.ws[n]
-        if labor and lb_prob is not None:
+        if nb_replace:
+            if labor or (nb_prob is not None and nb_prob["mode"] != _lib.WN_RAW):
+                raise NotImplementedError("the draw with replacement is the neighbor layers', uniform or over raw probabilities")
+            f = int(fanout)
+            if f == 0 or f > _lib.NR_MAX_FANOUT:
+                raise ValueError("the draw with replacement takes fanouts of 1 .. %d (or negative: whole columns), not %d"
+                                 % (_lib.NR_MAX_FANOUT, f))
+            if self._nr_scr is None:
+                nbytes = int(_lib.lib.bliss_neighbor_replace_scratch_bytes(self.V, 1))
+                self._nr_scr = torch.zeros(nbytes // 4, dtype=torch.int32, device=self.g.device)
+            row = None if nb_prob is None else nb_prob["rows"][n if len(nb_prob["rows"]) > 1 else 0]
+            _lib.check(_lib.lib.bliss_neighbor_replace_layer(C.byref(self.c_graph), cur_seeds.data_ptr(), n_seeds, n_seeds_dev, cap["S"],
+                                                             f, 0, draw_state.seed, draw_state.step_dev.data_ptr(), n, int(last),
+                                                             _ptr(row), 0, C.byref(c_ws), C.byref(c_out), self._nr_scr.data_ptr(), st),
+                       "bliss_neighbor_replace_layer")
+        elif labor and lb_prob is not None:
             row = lb_prob["rows"][n if len(lb_prob["rows"]) > 1 else 0]
             _lib.check(_lib.lib.bliss_wlabor_layer(C.byref(self.c_graph), cur_seeds.data_ptr(), n_seeds, n_seeds_dev, cap["S"],
                                                    int(fanout), 0, draw_state.seed, draw_state.step_dev.data_ptr(), n, int(last),
@@ -655,7 +680,7 @@ class LayerEngine:
                 k = min(self.V, int(f) + s)
             b = int(min(self.Eg, int(b_margin * max_sizes[n]["B"]) + 4096))
             if self.exact_b and int(f) >= 0:    # (neighbor layer: the exact bound, such a step cannot overflow B)
-                b = int(min(self.Eg, s * int(f)))
+                b = int(min(2 ** 31 - 1, s * int(f))) if self.nb_replace else int(min(self.Eg, s * int(f)))
             # E only sizes launch grids (every kernel strides over the true count): a tight bound lets the hardware balance
             # the workgroups instead of a capped grid looping unevenly
             e = int(min(self.Eg, int(1.5 * max_sizes[n].get("E", self.Eg)) + 65536))
@@ -715,7 +740,8 @@ class LayerEngine:
 
     def enqueue_static(self, w_rows, seeds, fanouts, mode, eta, eps=0.9999, slot=0, chain_rng=False, external_rng=False, part=None,
                        last_block=True, ready_flag=0, draw_state=None, neighbor=False, labor=False, layer_dependency=False,
-                       labor_iterations=0, nb_prob=None, lb_prob=None, n_live_dev=None, poisson=False):
+                       labor_iterations=0, nb_prob=None, lb_prob=None, n_live_dev=None, poisson=False, replace=False,
+                       nb_replace=False):
         """Enqueue one sample_blocks on the current stream with capacity-padded outputs and NO sync.  Returns the
         blocks (sampling order); sizes, errors and the generator state are read back by finish().
 
@@ -741,7 +767,16 @@ class LayerEngine:
         capacity the static shapes were fixed for -- of which only the first ``n_live_dev[0]`` slots are this batch's seeds.
         The first-sampled layer is then launched like every later one, with its seed count read on the device, so a captured
         call serves every batch size up to the capacity; the output block's counts record holds the live S.  Slots past the
-        live count are read for no result (they hold valid node ids: zero, or an earlier batch's).  Whole calls only."""
+        live count are read for no result (they hold valid node ids: zero, or an earlier batch's).  Whole calls only.
+        ``replace`` (with ``draw_state``, the multinomial layers) / ``nb_replace`` (with ``neighbor``): the draws WITH replacement of
+        csrc/replace_draw.hip in place of bliss_multinomial_draw / bliss_neighbor_layer."""
+        if replace and (draw_state is None or poisson or neighbor or labor):
+            raise ValueError("replace=True selects the multinomial layers' keyed draw with replacement: it needs a draw_state")
+        if nb_replace and not neighbor:
+            raise ValueError("nb_replace belongs to the neighbor layers")
+        if neighbor and bool(nb_replace) != self.nb_replace:
+            raise ValueError("the capacities of this engine were fixed %s replacement (LayerEngine.nb_replace)"
+                             % ("with" if self.nb_replace else "without"))
         if n_live_dev is not None:
             if part is not None or external_rng or chain_rng:
                 raise NotImplementedError("a live seed count has no split / external-generator enqueue (the pipelined two-stream "
@@ -773,7 +808,8 @@ class LayerEngine:
         out = self._enqueue(w_rows, seeds, fanouts, mode, eta, eps, None, True, slot=slot, chain_rng=chain_rng,
                             external_rng=external_rng, part=part, last_block=last_block, ready_flag=ready_flag, draw_state=draw_state,
                             neighbor=neighbor, labor=labor, layer_dependency=layer_dependency, labor_iterations=labor_iterations,
-                            nb_prob=nb_prob, lb_prob=lb_prob, n_live_dev=n_live_dev, poisson=poisson)
+                            nb_prob=nb_prob, lb_prob=lb_prob, n_live_dev=n_live_dev, poisson=poisson, replace=replace,
+                            nb_replace=nb_replace)
         self._static_draw[slot] = draw_state is not None
         counts_dev, layers = out
         if slot not in self._slot_counts_host:
@@ -819,7 +855,7 @@ class LayerEngine:
 
     def _enqueue(self, w_rows, seeds, fanouts, mode, eta, eps, uniforms, snapshot, slot=None, chain_rng=False, external_rng=False,
                  part=None, last_block=True, ready_flag=0, draw_state=None, neighbor=False, labor=False, layer_dependency=False,
-                 labor_iterations=0, nb_prob=None, lb_prob=None, n_live_dev=None, poisson=False):
+                 labor_iterations=0, nb_prob=None, lb_prob=None, n_live_dev=None, poisson=False, replace=False, nb_replace=False):
         if lb_prob is not None and (labor_iterations > 0 or self.labor_is):
             raise NotImplementedError("LABOR-i with edge probabilities is out of scope")
         dev, st = self.g.device, _stream()
@@ -858,7 +894,7 @@ class LayerEngine:
                 self._enqueue_neighbor_layer(n, fanouts[n], cur_seeds, n_seeds, n_seeds_dev, draw_state, last, c_ws, c_out, lay,
                                              cnt_ptr, st, labor=labor, layer_dependency=layer_dependency,
                                              labor_iterations=labor_iterations, nb_prob=nb_prob if neighbor else None,
-                                             lb_prob=lb_prob if labor else None, p_out=p_out)
+                                             lb_prob=lb_prob if labor else None, p_out=p_out, nb_replace=nb_replace and neighbor)
                 layers.append(lay)
                 cur_seeds, n_seeds, n_seeds_dev = kept_nid, -1, cnt_ptr + 12
                 continue
@@ -869,10 +905,19 @@ class LayerEngine:
                 _lib.check(_lib.lib.bliss_frontier_prob(C.byref(self.c_graph), C.byref(self._set(n)["c_maps"]), w_pos.data_ptr(),
                                                         cur_seeds.data_ptr(), n_seeds, n_seeds_dev, cs, mode, eta_f, ome_f,
                                                         cap.get("E", self.Eg), C.byref(c_ws), st), "bliss_frontier_prob")
-                _lib.check(_lib.lib.bliss_multinomial_draw(ws.cand_nid.data_ptr(), ws.p.data_ptr(), cnt_ptr, cap["C"], int(fanouts[n]), 0,
-                                                           draw_state.seed, draw_state.step_dev.data_ptr(), n, int(last),
-                                                           ws.draw_scr.data_ptr(), ws.keys.data_ptr(), ws.new_id.data_ptr(), st),
-                           "bliss_multinomial_draw")
+                if replace:                     # the keyed categorical draw with replacement: 3 launches, the same mark format
+                    if ws.rdraw_scr is None:
+                        nbytes = int(_lib.lib.bliss_multinomial_draw_replace_scratch_bytes(cap["C"]))
+                        ws.rdraw_scr = torch.zeros(nbytes // 8, dtype=torch.int64, device=dev)
+                    _lib.check(_lib.lib.bliss_multinomial_draw_replace(ws.p.data_ptr(), cnt_ptr, cap["C"], int(fanouts[n]), 0,
+                                                                       draw_state.seed, draw_state.step_dev.data_ptr(), n, int(last),
+                                                                       ws.rdraw_scr.data_ptr(), ws.new_id.data_ptr(), 0, st),
+                               "bliss_multinomial_draw_replace")
+                else:
+                    _lib.check(_lib.lib.bliss_multinomial_draw(ws.cand_nid.data_ptr(), ws.p.data_ptr(), cnt_ptr, cap["C"], int(fanouts[n]), 0,
+                                                               draw_state.seed, draw_state.step_dev.data_ptr(), n, int(last),
+                                                               ws.draw_scr.data_ptr(), ws.keys.data_ptr(), ws.new_id.data_ptr(), st),
+                               "bliss_multinomial_draw")
                 _lib.check(_lib.lib.bliss_multinomial_select_marked(C.byref(c_ws), st), "bliss_multinomial_select_marked")
             elif part in (None, "main"):        # candidates, probabilities, draw: all the next layer needs (its seeds = kept_nid)
                 if self.n_bins and self.fuse_scale:

@@ -11,6 +11,7 @@ LIB_PATH = os.path.join(_HERE, "libbliss_gnn.so")
 
 EINVAL = -1
 MODE_BANDIT, MODE_LADIES, MODE_UNIFORM_NODES, MODE_PARTIALS = 0, 1, 4, 8
+NR_MAX_FANOUT = 1024                   # BLISS_NR_MAX_FANOUT: bliss_neighbor_replace_layer orders a column's draws in LDS
 WN_RAW, WN_EXP3 = 0, 1                 # bliss_wneighbor_layer / bliss_wlabor_layer: probabilities as given / EXP3 weights
 
 ERR_BITS = {
@@ -225,6 +226,9 @@ SIGNATURES = {
                              C.POINTER(BlockOut), _P, _P],
     "bliss_wneighbor_layer": [C.POINTER(Graph), _P, _I32, _P, _I32, _I32, _P, C.c_uint64, _P, _I32, C.c_int, _I32, _P, _F, _F, _P,
                               C.POINTER(LayerWs), C.POINTER(BlockOut), _P, _P],
+    "bliss_neighbor_replace_layer": [C.POINTER(Graph), _P, _I32, _P, _I32, _I32, _P, C.c_uint64, _P, _I32, C.c_int, _P, _P,
+                                     C.POINTER(LayerWs), C.POINTER(BlockOut), _P, _P],
+    "bliss_multinomial_draw_replace": [_P, _P, _I32, _I32, _P, C.c_uint64, _P, _I32, C.c_int, _P, _P, _P, _P],
     "bliss_labor_layer": [C.POINTER(Graph), _P, _I32, _P, _I32, _I32, _P, C.c_uint64, _P, _I32, C.c_int, C.c_int, C.POINTER(LayerWs),
                           C.POINTER(BlockOut), _P, _P],
     "bliss_labor_is_layer": [C.POINTER(Graph), _P, _I32, _P, _I32, _I32, _P, C.c_uint64, _P, _I32, C.c_int, C.c_int, _I32,
@@ -306,7 +310,8 @@ SIGNATURES = {
 SPECIAL_SIGNATURES = ("bliss_prof_kernel_name", "bliss_block_transpose_temp_bytes", "bliss_graph_prepare_capacity",
                       "bliss_graph_prepare_temp_bytes", "bliss_rng_stream_handle", "bliss_sage_wgrad_workspace",
                       "bliss_multinomial_draw_scratch_bytes", "bliss_neighbor_scratch_bytes", "bliss_wneighbor_scratch_bytes",
-                      "bliss_labor_scratch_bytes", "bliss_labor_is_scratch_bytes", "bliss_wlabor_scratch_bytes")   # non-int return types, set in _load()
+                      "bliss_labor_scratch_bytes", "bliss_labor_is_scratch_bytes", "bliss_wlabor_scratch_bytes",
+                      "bliss_neighbor_replace_scratch_bytes", "bliss_multinomial_draw_replace_scratch_bytes")   # non-int return types, set in _load()
 
 
 def _load():
@@ -338,6 +343,10 @@ def _load():
     lib.bliss_labor_is_scratch_bytes.restype = C.c_int64
     lib.bliss_wlabor_scratch_bytes.argtypes = [_I32, _I32, _I32]
     lib.bliss_wlabor_scratch_bytes.restype = C.c_int64
+    lib.bliss_neighbor_replace_scratch_bytes.argtypes = [_I32, _I32]
+    lib.bliss_neighbor_replace_scratch_bytes.restype = C.c_int64
+    lib.bliss_multinomial_draw_replace_scratch_bytes.argtypes = [_I32]
+    lib.bliss_multinomial_draw_replace_scratch_bytes.restype = C.c_int64
     lib.bliss_rng_stream_handle.argtypes = []
     lib.bliss_rng_stream_handle.restype = C.c_int64
     lib.bliss_prof_kernel_name.argtypes = [C.c_int]

@@ -63,18 +63,29 @@ class DeviceDraw:
     CPU MT19937 stream, regenerated on the device -- the reference's bits, at the price of the host staging the generator state
     around every step.  ``"device"``: the keyed Bernoulli draw of bliss_poisson_select_keyed -- candidate ``nid`` of sampling
     layer n is kept iff ``keyed_uniform(seed, draw step, n, nid) < P``; no generator, no staging, so a captured train step runs
-    free.  ``layer_dependency=True`` (device draw only): layer 0's variate for every layer, i.e. one variate per node and step."""
+    free.  ``layer_dependency=True`` (device draw only): layer 0's variate for every layer, i.e. one variate per node and step.
+
+    ``"device-replace"`` (the multinomial samplers only): the reference's ``replace=True`` on the device --
+    ``min(num, C)`` keyed categorical draws WITH replacement over the importances (csrc/replace_draw.hip, integers only), the
+    duplicates dropped by the union as the reference drops them.  It sets ``draw = "device"`` and ``replace = True``: everything
+    that holds for ``draw="device"`` holds for it."""
 
     _NO_STATIC = "the multinomial draw is torch.multinomial on the host: no static-shape variant (use draw='device')"
 
     def _init_draw(self, draw, replace, layer_dependency=False):
-        if draw not in ("host", "device"):
-            raise ValueError("draw must be 'host' or 'device', not %r" % (draw,))
+        if draw == "device-replace":
+            if self._poisson:
+                raise ValueError("draw='device-replace' belongs to the multinomial samplers: a Poisson draw has no replacement")
+            draw, replace = "device", True
+        elif draw not in ("host", "device"):
+            raise ValueError("draw must be 'host', 'device' or 'device-replace', not %r" % (draw,))
+        elif draw == "device" and replace:
+            raise NotImplementedError("draw='device' is the draw without replacement; the device draw with replacement is "
+                                      "draw='device-replace' (replace=True otherwise needs draw='host')")
         if layer_dependency and not (self._poisson and draw == "device"):
             raise ValueError("layer_dependency=True belongs to the Poisson samplers' keyed draw (draw='device')")
-        if draw == "device" and replace:
-            raise NotImplementedError("the device draw is without replacement only (replace=True needs draw='host')")
         self.draw = draw
+        self.replace = bool(replace)
         self.layer_dependency = bool(layer_dependency)
         self._draw_init, self._draw_state = (None, 0), None
 
@@ -113,7 +124,6 @@ class BanditLadiesSampler(DeviceDraw, BlockSampler):
         self.output_weight = out_weight
         self.node_prob = node_prob
         self.node_embedding = node_embedding
-        self.replace = replace
         self.eta = eta
         self.T = num_steps
         self.model = model
@@ -215,7 +225,8 @@ class BanditLadiesSampler(DeviceDraw, BlockSampler):
         blks = eng.enqueue_static([self._w_pos[b] for b in order], seed_nodes, [self.nodes_per_layer[b] for b in order],
                                   self._mode(), self.eta, self.eps, slot=slot, chain_rng=chain_rng, external_rng=external_rng, part=part,
                                   last_block=last_block, ready_flag=ready_flag, draw_state=self._draw_state_on(g.device), n_live_dev=n_live_dev,
-                                  poisson=self._poisson and self.draw == "device", layer_dependency=self.layer_dependency)
+                                  poisson=self._poisson and self.draw == "device", layer_dependency=self.layer_dependency,
+                                  replace=self.replace and self.draw == "device")
         blocks = []
         for blk in blks:
             blk.edata[self.output_weight] = blk._edge_weights

@@ -74,15 +74,31 @@ class NeighborSampler(DeviceDraw, BlockSampler):
     ``prob`` (DGL's keyword; ``draw="device"`` only, the host draw raises): unnormalised edge probabilities, a tensor [|E|] by EDGE ID
     or the name of an entry of ``g.edata``, converted to bf16 by CSC position once per graph.  The draw is then the weighted one of
     csrc/neighbor_w.hip (a keyed exponential race per column, an edge with probability <= 0 taken only as
-    a filler); ``edge_weights`` carry the Hajek weights under the mean aggregation and ``edata["q_ij"]`` the probabilities."""
+    a filler); ``edge_weights`` carry the Hajek weights under the mean aggregation and ``edata["q_ij"]`` the probabilities.
+
+    ``replace=True`` (DGL's keyword; ``draw="device"`` only, the host draw raises): every destination with an in-edge gets exactly
+    ``fanout`` edges, drawn WITH replacement -- also when it has fewer in-edges than that -- uniformly or with ``prob``: the keyed
+    categorical draw of csrc/replace_draw.hip (integers only, a function of seed, draw step, layer, the
+    destination's node id and the draw's index).  Repeats are separate block edges; with ``prob`` the weights are
+    ``(1 / q_e) * fanout / sum (1 / q_e')`` over the column's edges, the exact per-draw importance weights.  Fanouts are limited to
+    ``NeighborSampler.MAX_REPLACE_FANOUT``."""
 
     _poisson = False                                       # (DeviceDraw's Poisson / replace checks have no subject here)
+    MAX_REPLACE_FANOUT = _lib.NR_MAX_FANOUT
 
-    def __init__(self, fanouts, seed=0, *, draw="host", prob=None, **_ignored):
+    def __init__(self, fanouts, seed=0, *, draw="host", prob=None, replace=False, **_ignored):
         super().__init__()
+        if draw not in ("host", "device"):
+            raise ValueError("draw must be 'host' or 'device', not %r" % (draw,))
         self._init_draw(draw, False)
         if prob is not None and draw != "device":
             raise NotImplementedError("NeighborSampler: edge probabilities (prob=) need draw='device'; the host draw is uniform")
+        if replace and draw != "device":
+            raise NotImplementedError("NeighborSampler: replace=True needs draw='device'; the host draw is without replacement")
+        if replace and any(int(f) == 0 or int(f) > self.MAX_REPLACE_FANOUT for f in fanouts):
+            raise ValueError("NeighborSampler(replace=True): fanouts must be negative (whole columns) or 1 .. %d, got %r"
+                             % (self.MAX_REPLACE_FANOUT, list(fanouts)))
+        self.replace = bool(replace)
         self.prob, self._prob_pos = prob, None
         self._draw_init = (seed, 0)
         self.fanouts, self.nodes_per_layer = list(fanouts), list(fanouts)
@@ -95,6 +111,7 @@ class NeighborSampler(DeviceDraw, BlockSampler):
         if self._engine is None or self._engine.g is not g:
             self._engine = LayerEngine(g)
             self._engine.exact_b = True
+            self._engine.nb_replace = self.replace
         return self._engine
 
     def _nb_prob(self, eng):
@@ -126,7 +143,7 @@ class NeighborSampler(DeviceDraw, BlockSampler):
         eng = self._bind(g)
         fan = list(reversed(self.fanouts))
         return self._blocks(eng.enqueue_static(None, seed_nodes, fan, 0, 0.0, slot=slot, draw_state=self._draw_state_on(eng.g.device),
-                                               neighbor=True, nb_prob=self._nb_prob(eng), **split), seed_nodes)
+                                               neighbor=True, nb_prob=self._nb_prob(eng), nb_replace=self.replace, **split), seed_nodes)
 
     def finish_static(self, slot=0, commit=True):
         return self._engine.finish(slot, commit)
@@ -139,7 +156,7 @@ class NeighborSampler(DeviceDraw, BlockSampler):
         if self.draw == "device":
             eng = self._bind(g)
             blks = eng.sample_blocks_neighbor(seed_nodes, list(reversed(self.fanouts)), self._draw_state_on(g.device),
-                                              nb_prob=self._nb_prob(eng))
+                                              nb_prob=self._nb_prob(eng), replace=self.replace)
             return self._blocks(blks, seed_nodes)
         dev = g.device
         if self._gen is None:
@@ -188,7 +205,12 @@ class BanditNeighborSampler(BanditLadiesSampler):
     ``finish_static`` as ``NeighborSampler(draw="device")`` has them, it runs inside a captured train step, and the pipelined
     two-stream loop refuses it."""
 
-    def __init__(self, fanouts, eta=0.4, num_steps=5000, model="sage", seed=0, **_ignored):
+    def __init__(self, fanouts, eta=0.4, num_steps=5000, model="sage", seed=0, replace=False, **_ignored):
+        if replace:
+            raise NotImplementedError("BanditNeighborSampler(replace=True): the EXP3 update rewrites w[pos] once per block edge and "
+                                      "relies on a position occurring at most once per block; a draw with replacement repeats "
+                                      "positions (NeighborSampler(draw='device', replace=True, prob=...) draws from fixed "
+                                      "probabilities)")
         super().__init__(list(fanouts), eta=eta, num_steps=num_steps, model=model, draw="device")
         self.fanouts = list(fanouts)
         self._draw_init = (seed, 0)
@@ -357,7 +379,11 @@ class BanditLaborSampler(BanditLadiesSampler):
     ``reset_draw`` / ``draw_step`` / ``sample_blocks_static`` / ``finish_static`` as ``LaborSampler`` has them, it runs inside a
     captured train step, and the pipelined two-stream loop refuses it."""
 
-    def __init__(self, fanouts, eta=0.4, num_steps=5000, model="sage", layer_dependency=False, seed=0, **_ignored):
+    def __init__(self, fanouts, eta=0.4, num_steps=5000, model="sage", layer_dependency=False, seed=0, replace=False, **_ignored):
+        if replace:
+            raise NotImplementedError("BanditLaborSampler(replace=True): the EXP3 update rewrites w[pos] once per block edge and "
+                                      "relies on a position occurring at most once per block; LABOR keeps an edge at most once "
+                                      "and has no draw with replacement")
         super().__init__(list(fanouts), eta=eta, num_steps=num_steps, model=model, draw="device")
         self.fanouts = list(fanouts)
         self.layer_dependency = bool(layer_dependency)
@@ -400,15 +426,25 @@ class BanditLaborSampler(BanditLadiesSampler):
         return self._sample(g, seed_nodes, True, slot=slot, **split)
 
 
-def make_sampler(name, fanouts, importance_sampling=1, num_steps=5000, eta=0.1, model="sage", draw="host"):
+def make_sampler(name, fanouts, importance_sampling=1, num_steps=5000, eta=0.1, model="sage", draw="host", replace=False):
     """The sampler-name dispatch of DataModule.__init__ (train_lightning.py:348-370).  ``draw``: where the two multinomial
     samplers ("ladies", "bandit") and "neighbor" draw -- "host" (torch.multinomial / torch tensor ops) or "device" (the keyed
     draws, graph-capturable).  "labor" and "labor-<i>" (i in 1 .. 8: ``ImportanceLaborSampler`` with i iterations) always draw on
     the device.  "neighbor-exp3": ``BanditNeighborSampler`` (EXP3-weighted node-wise draw, always on the device); "labor-exp3":
     ``BanditLaborSampler`` (EXP3-weighted LABOR draw, always on the device).  The Poisson names ignore ``draw`` (they keep the
     draw against torch's stream); their keyed draw on the device has names of its own:
-    "poisson-bandit-keyed" and "poisson-ladies-keyed"."""
+    "poisson-bandit-keyed" and "poisson-ladies-keyed".  ``replace=True``: the draws with replacement, on
+    the device only -- "ladies" and "bandit" with ``draw="device"`` (built with ``draw="device-replace"``) and "neighbor" (which
+    gets ``replace=True``); every other name raises."""
     from . import BanditLadiesSampler, LadiesSampler, PoissonBanditLadiesSampler, PoissonLadiesSampler as PLS
+    if replace:
+        if name == "neighbor":
+            return NeighborSampler(fanouts, draw=draw, replace=True)
+        if name not in ("ladies", "bandit"):
+            raise ValueError("replace=True: only 'ladies', 'bandit' and 'neighbor' draw with replacement, not %r" % (name,))
+        if draw != "device":
+            raise ValueError("replace=True with %r needs draw='device' (the keyed draw with replacement)" % (name,))
+        draw = "device-replace"
     if name == "poisson-ladies-keyed":
         return PLS(fanouts, draw="device")
     if name == "poisson-bandit-keyed":

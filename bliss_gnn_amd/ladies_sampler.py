@@ -24,7 +24,6 @@ class LadiesSampler(DeviceDraw, BlockSampler):
         self.importance_sampling = importance_sampling
         self.edge_weight = weight
         self.output_weight = out_weight
-        self.replace = replace
         self.allow_zero_in_degree = allow_zero_in_degree
         self.eps = 0.9999
         self._engine = None
@@ -82,7 +81,8 @@ class LadiesSampler(DeviceDraw, BlockSampler):
         blks = eng.enqueue_static([w_pos] * len(order), seed_nodes, [self.nodes_per_layer[b] for b in order], self._mode(), 0.0,
                                   self.eps, slot=slot, chain_rng=chain_rng, external_rng=external_rng, part=part, last_block=last_block, ready_flag=ready_flag,
                                   draw_state=self._draw_state_on(g.device), n_live_dev=n_live_dev,
-                                  poisson=self._poisson and self.draw == "device", layer_dependency=self.layer_dependency)
+                                  poisson=self._poisson and self.draw == "device", layer_dependency=self.layer_dependency,
+                                  replace=self.replace and self.draw == "device")
         blocks = []
         for blk in blks:
             blk.edata[self.output_weight] = blk._edge_weights

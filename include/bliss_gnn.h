@@ -268,6 +268,60 @@ int bliss_wneighbor_layer(const bliss_graph_t* g, const int32_t* seeds, int32_t 
                           int bump_step, int32_t mode, const void* prob_pos, float eta, float one_minus_eta, uint32_t* keys_out,
                           const bliss_layer_ws_t* ws, const bliss_block_out_t* out, void* scratch, void* stream);
 
+/* Draws WITH REPLACEMENT (csrc/replace_draw.hip; a defined-mode keyed categorical draw in integers only, restated on the CPU by
+ * tests/replace_ref.py).  Shared by the two entry points below:
+ *   fin(z)  = the SplitMix64 finaliser of bliss_neighbor_layer's key; mk = its mix(seed, *step_dev, layer)
+ *   h       = fin(mk ^ (uint64)(uint32)ident); r_j = fin(h ^ ((uint64)(j + 1) * 0x9E3779B97F4A7C15)), the variate of draw j = 0, 1, ...
+ *   weights of a group of bf16 probabilities: E = floor(log2(largest positive finite value)); w_i = floor(x_i * 2^(23 - E)) for a
+ *             positive finite x_i, else 0 (<= 0, NaN, +-inf); the largest lands in [2^23, 2^24), values below 2^(E - 23) become 0 and
+ *             are never drawn (the mode's resolution); W = sum w_i in uint64
+ *   one draw over a group of m entries: W > 0: t = mulhi64(r_j, W), the pick is the smallest i whose inclusive prefix sum of w
+ *             exceeds t (an entry of weight zero is never picked); W == 0, or no probabilities: the pick is mulhi64(r_j, m).
+ *
+ * bliss_neighbor_replace_layer: dgl.dataloading.NeighborSampler(fanouts, replace=True) on the device, one layer
+ * (fit.NeighborSampler(draw="device", replace=True)), uniform (prob_pos == NULL) or with edge probabilities (prob_pos: bf16
+ * [num_edges] by CSC position, unnormalised, as bliss_wneighbor_layer's raw mode).  ident = the node id of the seed column, so a
+ * column's draws depend on (seed, step, layer, node id, j) and on nothing else.
+ *   seed column s, CSC positions [a, a + d):  k_s = d if fanout < 0 (a WHOLE column: no draw), 0 if d == 0, else fanout -- also
+ *             when d <= fanout; the drawn positions are a + pick_j, j < fanout
+ *   block:     edges column by column in seed order, inside a column in ascending (position, j): repeats are separate, adjacent
+ *             edges with the same pos and eid; indptr[s + 1] - indptr[s] = k_s, so B = sum k_s is known before the draw
+ *   sources, eid / pos / dst, the counts record {S, E = sum d, C = K, K, B, err}, capacity padding, clamps, BLISS_ERR_CAP_* bits,
+ *             ws->kept_map, node_prob = 1 and bump_step (the last workgroup of the draw kernel): bliss_neighbor_layer's.
+ *   with prob_pos: q_ij = prob_pos[pos] on every edge; edge_weights W_e = (1 / q_e) * k_s / sum over the column's edges e', repeats
+ *             counted, of (1 / q_e'), fp64 in a fixed order, rounded once to bf16 (1 / q is the exact per-draw importance weight);
+ *             exactly 1 in a whole column and in a column that fell back to the uniform pick.  Without: edge_weights = q_ij = 1.
+ * r_override (optional, a test hook that plants variates): uint64 [cap_s * fanout], r_j of column s at s * fanout + j.  picks_out
+ * (optional, a test hook: NULL in every product path): int32 [cap_b], pick_j of every block edge (the index inside a whole column).
+ * scratch: bliss_neighbor_replace_scratch_bytes(num_nodes, cap_s) bytes, 16-byte aligned, zero-initialised ONCE:
+ * bliss_neighbor_layer's words, left idle by every call, also a replayed one and one that flagged an overflow.  Six launches, seven
+ * with probabilities; no host round trip.
+ * BLISS_EINVAL before any launch: the set bliss_neighbor_layer refuses (step_dev may be NULL only with r_override and without
+ * bump_step), fanout > BLISS_NR_MAX_FANOUT (a column's draws are ordered in LDS), prob_pos / r_override / picks_out not aligned to
+ * their element size (2 / 8 / 4 bytes). */
+#define BLISS_NR_MAX_FANOUT 1024
+int64_t bliss_neighbor_replace_scratch_bytes(int32_t num_nodes, int32_t cap_s);
+int bliss_neighbor_replace_layer(const bliss_graph_t* g, const int32_t* seeds, int32_t n_seeds, const int32_t* n_seeds_dev,
+                                 int32_t cap_s, int32_t fanout, const uint64_t* r_override, uint64_t seed, int64_t* step_dev,
+                                 int32_t layer, int bump_step, const void* prob_pos, int32_t* picks_out, const bliss_layer_ws_t* ws,
+                                 const bliss_block_out_t* out, void* scratch, void* stream);
+
+/* bliss_multinomial_draw WITH replacement (LadiesSampler / BanditLadiesSampler with draw="device-replace";
+ * torch.multinomial(p, min(num, C), replacement=True) followed by the reference's union, which drops the duplicates): the rule
+ * above over ONE group, the layer's C = counts->C candidates in the order of the candidate list with importances p_bf16, ident =
+ * 0xFFFFFFFF (no node id), n = min(fanout, C) draws.
+ * Out: drawn int32 [cap_c], entries [0, C): 1 if any draw picked the candidate, else 0 -- the mark format
+ * bliss_multinomial_select_marked reads from ws->new_id.  r_override (optional, a test hook): uint64 [fanout].  picks_out
+ * (optional, a test hook): int32 [fanout], entries [0, n) written.  bump_step: *step_dev is read once, by the one workgroup that
+ * then increments it.  scratch: bliss_multinomial_draw_replace_scratch_bytes(cap_c) bytes, 16-byte aligned, zero-initialised ONCE;
+ * every call leaves it ready for the next (also when replayed from a captured graph).  Three launches, no host round trip.
+ * BLISS_EINVAL: a null pointer (r_override and picks_out may be NULL; step_dev only with r_override and without bump_step),
+ * fanout < 0, cap_c <= 0, misaligned scratch, r_override / picks_out / drawn not aligned to their element size. */
+int64_t bliss_multinomial_draw_replace_scratch_bytes(int32_t cap_c);
+int bliss_multinomial_draw_replace(const void* p_bf16, const void* counts, int32_t cap_c, int32_t fanout, const uint64_t* r_override,
+                                   uint64_t seed, int64_t* step_dev, int32_t layer, int bump_step, void* scratch, int32_t* drawn,
+                                   int32_t* picks_out, void* stream);
+
 /* dgl.dataloading.LaborSampler(fanouts, importance_sampling=0) ON THE DEVICE, one layer (fit.LaborSampler; LABOR-0: a defined-mode
  * keyed draw like bliss_neighbor_layer with the key on the edge's SOURCE NODE and a per-column threshold instead of a per-column
  * select, restated on the CPU by tests/labor_ref.py).  Integers only:
