@@ -344,6 +344,37 @@ __device__ __forceinline__ int wave_segment(const int* __restrict__ seg_ptr, int
   return k;
 }
 
+// Segments of a wave's whole span of N * 64 CONSECUTIVE frontier positions wbase .. wbase + N*64 - 1 (item j, lane l: position
+// wbase + j*64 + l) from ONE window of 64 boundaries after k_hint, instead of N carried wave_segment() calls: one load, then
+// N six-shuffle searches that depend on nothing else, so the caller can issue the N loads of every later level together.
+// k_hint (wave-uniform, in [0, S)): a segment known to start at or before wbase.  Positions are clamped to `last` (= E - 1,
+// wbase <= last), so every k[j] is a non-empty column that holds a real edge and k[j] < S: lanes past the frontier's end
+// decode its last edge and the caller discards their results.
+// Returns false (wave-uniform), k[] unset, when the window does not reach past the span -- more than 64 column starts inside
+// it, runs of empty columns, a hint 64 or more columns behind: the caller then walks the span with wave_segment().
+// On true k[j] is exactly what wave_segment() returns: the LAST column that starts at or before the position.
+template <int N>
+__device__ __forceinline__ bool span_segments(const int* __restrict__ seg_ptr, int S, int wbase, int last, int k_hint, int (&k)[N]) {
+  const int lane = lane_id();
+  const int idx = k_hint + 1 + lane;
+  const int v = seg_ptr[idx < S ? idx : S];           // unconditional, clamped
+  const int b = idx <= S ? v : 0x7fffffff;            // non-decreasing over lanes
+  if (__shfl(b, 63) - wbase <= N * 64 - 1) return false;
+#pragma unroll
+  for (int j = 0; j < N; ++j) {
+    const int e = wbase + j * 64 + lane, p = e < last ? e : last;
+    int c = 0;                                        // boundaries at or before p: < 64, the window's last one lies beyond
+#pragma unroll
+    for (int step = 32; step >= 1; step >>= 1) {
+      const int t = __shfl(b, c + step - 1);
+      if (t <= p) c += step;
+    }
+    const int kk = k_hint + c;
+    k[j] = kk < S ? kk : S - 1;                       // (already so when seg_ptr[S] = E: no address from an unclamped value)
+  }
+  return true;
+}
+
 // One lane: wait until the streaming generator (rng.hip) has produced the numbers a layer needs, hand the layer its
 // offset into the stream and account for the numbers it will consume.  ctl: [0] progress, [1] stop_at, [2] pos,
 // [3] error, [4] base.  Bounded spin: never hangs the GPU.

@@ -73,6 +73,36 @@ __device__ __forceinline__ EdgeAt decode(int base, int E, int S, const int* __re
   return r;
 }
 
+// decode() for a wave's whole SPAN at once: item j, lane l holds the edge at frontier position wbase + j * 64 + l.
+// The ITEMS carried decode() calls are a chain of ~5 dependent global loads EACH (window after the hint, window after k0,
+// col_base, indices, then the caller's gathers), one item after the other; here one window serves all items and the loads
+// of a level -- ITEMS x col_base, then ITEMS x indices -- are unconditional and issued together, and so are the caller's
+// (w, seed_coef, kept_map ...) when it issues them before it masks.
+// wbase < E required (wave-uniform).  Every address is clamped and valid: lanes at or past E decode the frontier's last edge
+// E - 1 and the caller discards what they computed (`e < E`) -- the rule of sage.hip's stage_rows.
+// false (wave-uniform): the window does not cover the span (span_segments), walk it with decode().
+struct SpanAt {
+  int k[ITEMS];          // seed index
+  int64_t pos[ITEMS];    // CSC position
+  int src[ITEMS];        // global source id
+};
+__device__ __forceinline__ bool decode_span(int wbase, int E, int S, const int* __restrict__ seg_ptr,
+                                            const long long* __restrict__ col_base, const int* __restrict__ indices, int k_hint,
+                                            SpanAt& r) {
+  k_hint = k_hint < 0 ? 0 : (k_hint < S ? k_hint : S - 1);
+  if (!span_segments<ITEMS>(seg_ptr, S, wbase, E - 1, k_hint, r.k)) return false;
+  long long cb[ITEMS];
+#pragma unroll
+  for (int j = 0; j < ITEMS; ++j) cb[j] = col_base[r.k[j]];
+#pragma unroll
+  for (int j = 0; j < ITEMS; ++j) {
+    const int e = wbase + j * 64 + lane_id();
+    r.pos[j] = cb[j] + (e < E ? e : E - 1);
+    r.src[j] = indices[r.pos[j]];
+  }
+  return true;
+}
+
 // exclusive rank of this wave's span inside its chunk + chunk total, from per-wave totals (one barrier)
 __device__ __forceinline__ int chunk_wave_offset(int wave_total, int* sh4, int* chunk_total) {
   const int wave = threadIdx.x >> 6;
@@ -755,6 +785,35 @@ __global__ void __launch_bounds__(BIN_TPB) k_bin_scatter(const int64_t* __restri
     bf16_t ts[BIN_ITEMS];
     const int wbase = batch * BIN_BATCH + (tid >> 6) * (64 * BIN_ITEMS);
     int hint = span_seg[wbase >> 8];       // a wave owns 256 consecutive positions
+    SpanAt sp;
+    if (wbase < E && decode_span(wbase, E, S, seg_ptr, col_base, indices, hint, sp)) {       // wave-uniform
+      // the span's twelve loads -- indices (decode_span), w, seed_coef -- are in flight together; only then mask
+      bf16_t wv[BIN_ITEMS];
+      uint2 cf[BIN_ITEMS];
+      if (!uniform_nodes) {
+#pragma unroll
+        for (int j = 0; j < BIN_ITEMS; ++j) {
+          wv[j] = w[sp.pos[j]];
+          if (BANDIT) cf[j] = seed_coef[sp.k[j]];
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < BIN_ITEMS; ++j) {
+        bf16_t t;
+        if (uniform_nodes) {
+          t = (bf16_t)0x3f80;
+        } else if (BANDIT) {
+          bf16_t q = edge_q_pre(wv[j], (bf16_t)(cf[j].x & 0xffffu), __uint_as_float(cf[j].y), ome_f);
+          float r = rbf(bf2f(q) / bf2f((bf16_t)(cf[j].x >> 16)));
+          t = f2bf(r * r);
+        } else {
+          float x = bf2f(wv[j]);
+          t = f2bf(x * x);
+        }
+        srcs[j] = sp.src[j]; ts[j] = t;
+        ranks[j] = wbase + j * 64 + lane_id() < E ? atomicAdd(&hist[sp.src[j] & bmask], 1) : -1;
+      }
+    } else {                                            // the walk item by item, each with its own lookup
 #pragma unroll
     for (int j = 0; j < BIN_ITEMS; ++j) {
       ranks[j] = -1; srcs[j] = 0; ts[j] = 0;
@@ -777,6 +836,7 @@ __global__ void __launch_bounds__(BIN_TPB) k_bin_scatter(const int64_t* __restri
         srcs[j] = a.src; ts[j] = t;
         ranks[j] = atomicAdd(&hist[a.src & bmask], 1);
       }
+    }
     }
     __syncthreads();
     for (int b = tid; b < n_bins; b += BIN_TPB) {
@@ -825,6 +885,8 @@ __global__ void __launch_bounds__(BINRED_TPB) k_bin_reduce(LayerCounts* cnt, int
   if (n > bin_cap) n = bin_cap;
   const unsigned long long* rec = bin_rec + (size_t)b * (size_t)bin_cap;
   int bad = 0;
+  // (several records per thread requested together -- 4 or 8, clamped index, masked afterwards -- was measured and moves
+  // nothing: 13.4 / 19.8 / 23.6 us per layer against 13.9 / 20.0 / 22.8 and 14.1 / 20.2 / 23.9)
   for (long long i = tid; i < n; i += BINRED_TPB) {
     const unsigned long long r = rec[i];
     const int li = (int)(((unsigned)r) >> 15);
@@ -1268,9 +1330,34 @@ __device__ __forceinline__ int span_collect(int chunk, int E, int S, const int* 
                                             const int* __restrict__ indices, const int* __restrict__ kept_map,
                                             const int* __restrict__ local_id, const int* __restrict__ new_id, KeptRec* buf) {
   int n = 0, hint = span_seg[chunk * ITEMS + (threadIdx.x >> 6)];
+  const int wbase = chunk * CHUNK + (threadIdx.x >> 6) * SPAN;
+  SpanAt sp;
+  if (wbase < E && decode_span(wbase, E, S, seg_ptr, col_base, indices, hint, sp)) {          // wave-uniform
+    int lid[ITEMS], nid[ITEMS];
+    // one more level (two without kept_map) of ITEMS gathers in flight together; lanes past E gather for the last real edge
+    if (kept_map) {
+#pragma unroll
+      for (int i = 0; i < ITEMS; ++i) { lid[i] = 0; nid[i] = kept_map[sp.src[i]]; }
+    } else {
+#pragma unroll
+      for (int i = 0; i < ITEMS; ++i) lid[i] = local_id[sp.src[i]];
+#pragma unroll
+      for (int i = 0; i < ITEMS; ++i) nid[i] = new_id[lid[i]];
+    }
+#pragma unroll
+    for (int i = 0; i < ITEMS; ++i) {                   // ballots and compaction in item order: frontier order is kept
+      const bool kept = wbase + i * 64 + lane_id() < E && nid[i] >= 0;
+      const unsigned long long mask = __ballot(kept);
+      if (kept) {
+        KeptRec r; r.k = sp.k[i]; r.pos = (int)sp.pos[i]; r.nid = nid[i]; r.lid = lid[i];
+        buf[n + __popcll(mask & ((1ull << lane_id()) - 1ull))] = r;
+      }
+      n += __popcll(mask);
+    }
+  } else {
 #pragma unroll
   for (int i = 0; i < ITEMS; ++i) {
-    const int base = chunk * CHUNK + (threadIdx.x >> 6) * SPAN + i * 64;
+    const int base = wbase + i * 64;
     if (base >= E) break;                               // wave-uniform
     EdgeAt a = decode(base, E, S, seg_ptr, col_base, indices, &hint);
     int lid = 0, nid = -1;
@@ -1284,6 +1371,7 @@ __device__ __forceinline__ int span_collect(int chunk, int E, int S, const int* 
       buf[n + __popcll(mask & ((1ull << lane_id()) - 1ull))] = r;
     }
     n += __popcll(mask);
+  }
   }
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier();
   return n;
