@@ -10,9 +10,9 @@ Buffers are sized by per-layer capacities; if a capacity is exceeded the kernels
 and the whole call is repeated with larger buffers from the same generator snapshot (steady state:
 never).  PyTorch is used for device memory and the current stream only.
 """
-import contextlib
 import ctypes as C
 import os
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -34,6 +34,146 @@ def _stream():
 
 def _up8(n):
     return (int(n) + 7) & ~7
+
+
+# ---------------------------------------------------------------------- the kinds of layer an engine runs
+class _Kind(NamedTuple):
+    """What the host driver knows about one kind of layer; an engine runs one kind (``LayerEngine.kind``)."""
+    family: str                 # "layer": frontier_prob -> draw -> build_block; "node": one *_layer call + the by-source index
+    k_slack: int = None         # K capacity >= fanout + S + this; 0: K is exactly bounded (``exact_k``).  None: no such floor
+    b_limit: int = None         # B capacity = S * fanout (fanout >= 0) capped by this, 0 = |E| (``exact_b``).  None: B may overflow
+    fatal: int = 3              # error bits that end the exact-shape call instead of growing the buffers ...
+    fatal_no_bins: int = 0      # ... and those that do so only on the atomic passes (n_bins == 0)
+    own_messages: bool = False  # bits 1 and 2 raise with messages of their own
+    keyed: bool = True          # draws from a DrawState; a repeated call rolls the draw step back
+    torch_rng: bool = False     # consumes torch's CPU generator (snapshot, stage, commit) unless uniforms are given
+    split: bool = False         # split enqueue, external and chained generator exist
+    keys: bool = False          # the race keys go into the blocks' _trace
+    prob: str = None            # probability record (neighbor_prob): None = takes none, "raw" = optional raw-mode, "any" = required
+    entry: str = None           # node-wise: the C entry point, ...
+    scratch: object = None      # ... its scratch: (engine, cap_s, cap_b) -> zeroed int32 tensor, ...
+    tail: object = None         # ... its own arguments after the eleven shared ones: (draw record, probability row) -> tuple
+    p_out: bool = False         # ... and whether it writes p_ij (the blocks' _p)
+
+
+def _prob_args(d, row):
+    return d.prob["mode"], row.data_ptr(), d.prob["eta_f"], d.prob["ome_f"]
+
+
+def _dep(d):
+    return int(bool(d.layer_dependency))
+
+
+KINDS = {
+    # Poisson from the MT stream (or explicit uniforms) / keyed Poisson
+    "stream": _Kind("layer", fatal=1, fatal_no_bins=2, own_messages=True, keyed=False, torch_rng=True, split=True),
+    "poisson_keyed": _Kind("layer", fatal=1, fatal_no_bins=2, own_messages=True),
+    # torch.multinomial on the host / the keyed race of csrc/mn_draw.hip / the draw with replacement of csrc/replace_draw.hip
+    "multinomial_host": _Kind("layer", k_slack=64, fatal=2, keyed=False),
+    "multinomial": _Kind("layer", k_slack=0, fatal=1, fatal_no_bins=2, keys=True),
+    "multinomial_replace": _Kind("layer", k_slack=0, fatal=1, fatal_no_bins=2),
+    # node-wise: csrc/neighbor.hip, neighbor_w.hip, replace_draw.hip, labor.hip, labor_is.hip, labor_w.hip
+    "neighbor": _Kind("node", b_limit=0, entry="bliss_neighbor_layer", tail=lambda d, row: (),
+                      scratch=lambda e, s, b: e._scratch_once("_nb_scr", "bliss_neighbor_scratch_bytes", 1)),
+    "wneighbor": _Kind("node", b_limit=0, prob="any", entry="bliss_wneighbor_layer", tail=lambda d, row: _prob_args(d, row) + (0,),
+                       scratch=lambda e, s, b: e._scratch_once("_wn_scr", "bliss_wneighbor_scratch_bytes", e.V, e.Eg)),
+    # (a column of fewer than fanout edges holds fanout block edges: |E| is no bound on B)
+    "neighbor_replace": _Kind("node", b_limit=2 ** 31 - 1, prob="raw", entry="bliss_neighbor_replace_layer",
+                              tail=lambda d, row: (_ptr(row), 0),
+                              scratch=lambda e, s, b: e._scratch_once("_nr_scr", "bliss_neighbor_replace_scratch_bytes", 1)),
+    "labor": _Kind("node", entry="bliss_labor_layer", tail=lambda d, row: (_dep(d),),
+                   scratch=lambda e, s, b: e._scratch_grown("_lb_scr", "bliss_labor_scratch_bytes", s)),
+    "labor_is": _Kind("node", entry="bliss_labor_is_layer", tail=lambda d, row: (_dep(d), int(d.iterations)),
+                      scratch=lambda e, s, b: e._scratch_grown("_li_scr", "bliss_labor_is_scratch_bytes", s, b)),
+    "wlabor": _Kind("node", prob="any", entry="bliss_wlabor_layer", tail=lambda d, row: (_dep(d),) + _prob_args(d, row), p_out=True,
+                    scratch=lambda e, s, b: e._scratch_grown("_wl_scr", "bliss_wlabor_scratch_bytes", s, b)),
+}
+
+
+class _Draw(NamedTuple):
+    """The per-call values of a layer that are not its kind."""
+    state: object = None        # DrawState of the keyed draws
+    prob: dict = None           # neighbor_prob(...)'s record
+    layer_dependency: bool = False
+    iterations: int = 0         # LABOR-i
+
+
+# caller-owned outputs of one layer, capacity-sized (LayerEngine._layer_buffers)
+_LayerOut = NamedTuple("_LayerOut", [(name, object) for name in
+                                     "indptr src dst pos eid w q kept_nid node_prob counts t_indptr t_edge".split()])
+
+
+def _exact_b(rule, Eg, s, f):
+    """The exact edge bound of a neighbor layer: at most ``fanout`` edges per seed."""
+    return int(min(rule.b_limit or Eg, s * f))
+
+
+def layer_caps(kind, V, Eg, S0, fanouts, have=None):
+    """Per-layer capacities (sampling order) of ``kind`` for S0 seeds on a graph of V nodes and Eg edges.  ``have``: the
+    capacities so far; they are kept while they hold S0 seeds, else merged (max) with fresh ones.  Pure: returns ``have`` itself
+    when nothing changes, new dicts otherwise."""
+    rule = KINDS[kind]
+    if have is not None and len(have) != len(fanouts):
+        have = None
+    if have is not None and have[0]["S"] >= S0:
+        if rule.k_slack is None:
+            return have
+        caps = [dict(c) for c in have]
+    else:
+        caps, s = [], int(S0)
+        for f in fanouts:
+            f = int(f)
+            if rule.family == "layer":
+                k = min(V, int(1.25 * (f + s)) + 64)
+                b = int(min(Eg, max(1 << 16, 48 * k)))
+            elif f < 0:                     # whole columns: nothing bounds K or B
+                k, b = V, int(min(Eg, max(1 << 16, 48 * s)))
+            else:                           # besides its seeds a layer keeps at most one new source per kept edge
+                # (LABOR keeps fanout edges per column in expectation, not at most: twice that, the regrow loop covers the rest)
+                b = _exact_b(rule, Eg, s, f) if rule.b_limit is not None else int(min(Eg, 2 * s * f + 4096))
+                k = int(min(V, s + min(b, Eg)))
+            caps.append(dict(S=s, C=V, K=k, B=b))
+            s = k
+        if have is not None:
+            caps = [{k: max(a.get(k, 0), b[k]) for k in b} for a, b in zip(have, caps)]
+    if rule.k_slack is not None:            # a multinomial draw keeps union(drawn, seeds): make room
+        for n, f in enumerate(fanouts):
+            caps[n]["K"] = max(caps[n]["K"], min(V, int(f) + caps[n]["S"] + rule.k_slack))
+            if n + 1 < len(caps):           # a layer's seeds are the previous layer's kept nodes
+                caps[n + 1]["S"] = max(caps[n + 1]["S"], caps[n]["K"])
+    return have if caps == have else caps
+
+
+def static_caps(kind, V, Eg, S0, fanouts, max_sizes, k_margin=1.5, b_margin=3.0):
+    """Capacities fixed from sizes observed in exact mode (``LayerEngine.set_static_caps``); exact bounds where ``kind`` has them."""
+    rule = KINDS[kind]
+    caps, s = [], int(S0)
+    for n, f in enumerate(fanouts):
+        k = min(V, int(k_margin * max_sizes[n]["K"]) + 256)
+        if rule.k_slack == 0:               # (device-drawn multinomial layer: the exact bound, such a step cannot overflow K)
+            k = min(V, int(f) + s)
+        b = int(min(Eg, int(b_margin * max_sizes[n]["B"]) + 4096))
+        if rule.b_limit is not None and int(f) >= 0:    # (neighbor layer: the exact bound, such a step cannot overflow B)
+            b = _exact_b(rule, Eg, s, int(f))
+        # E only sizes launch grids (every kernel strides over the true count): a tight bound lets the hardware balance
+        # the workgroups instead of a capped grid looping unevenly
+        e = int(min(Eg, int(1.5 * max_sizes[n].get("E", Eg)) + 65536))
+        # X: how many block edges a multi-GPU step EXCHANGES per block (update lists are sent capacity-sized; B's margin
+        # is for memory that costs nothing, X's for bytes that cross xGMI every step); a longer list is flagged
+        x = int(min(b, int(1.5 * max_sizes[n]["B"]) + 2048))
+        caps.append(dict(S=s, C=V, K=k, B=b, E=e, X=x))
+        s = k
+    return caps
+
+
+def _parse_counts(counts_host, L):
+    """The L LayerCounts records of a pinned counts tensor (after a synchronisation) and the OR of their error words."""
+    raw = counts_host.numpy().tobytes()
+    cnts = [_lib.LayerCounts.from_buffer_copy(raw[40 * n: 40 * n + 40]) for n in range(L)]
+    bad = 0
+    for c in cnts:
+        bad |= c.err
+    return cnts, bad
 
 
 class _LayerWs:
@@ -72,7 +212,9 @@ class LayerEngine:
     """Per-graph sampling state.  Not re-entrant and not shareable between DataLoader workers --
     the same ownership rule as the reference sampler's mutable state (bandit_sampler.py:43)."""
 
-    def __init__(self, g: Graph):
+    def __init__(self, g: Graph, kind="stream"):
+        if kind not in KINDS:
+            raise ValueError("kind must be one of %s, not %r" % (", ".join(KINDS), kind))
         if g.device.type != "cuda":
             raise RuntimeError("bliss_gnn_amd samples on the GPU only; move the graph with g.to('cuda') "
                                "(the reference's --data-cpu/--use-uva modes are out of scope)")
@@ -110,14 +252,11 @@ class LayerEngine:
         self.mt_back = torch.empty(626, dtype=torch.int32).pin_memory()        # state handed back
         self._static = {}
         self._static_draw = {}
-        self.exact_k = False                # device-drawn multinomial layers keep at most fanout + S nodes: K capacities are that bound
-        self.exact_b = False                # neighbor layers keep at most fanout edges per seed: B capacities are that bound
-        self.nb_replace = False             # neighbor layers drawn WITH replacement hold exactly fanout edges per non-empty column: B <= S * fanout, not |E|
+        self.kind = kind                    # a key of KINDS; the sampler that binds the engine fixes it
         self._nr_scr = None                 # csrc/replace_draw.hip's node-wise draw: csrc/neighbor.hip's words
         self._nb_scr = None                 # csrc/neighbor.hip: tickets + node bitmap (zero once, left zero by every call)
         self._wn_scr = None                 # csrc/neighbor_w.hip: the same words + a record per seed and a staged key per CSC position
         self._lb_scr = None                 # csrc/labor.hip: the same words + one kept count per seed column; (cap_s, tensor)
-        self.labor_is = False               # LABOR layers run csrc/labor_is.hip also with 0 iterations (fit.ImportanceLaborSampler)
         self._li_scr = None                 # csrc/labor_is.hip: + two |V|-word importance buffers, scales, p_e; (cap_s, cap_b, tensor)
         self._wl_scr = None                 # csrc/labor_w.hip: + three records per seed column and p_e; (cap_s, cap_b, tensor)
         self._wl_p = {}                     # its p_ij outputs: per static slot (slot, layer, cap_b) -> bf16 [cap_b]
@@ -141,22 +280,26 @@ class LayerEngine:
         return self._sets[i]
 
     # ------------------------------------------------------------------ capacities
-    def _init_caps(self, S0, fanouts_sampling_order):
-        caps, s = [], int(S0)
-        for f in fanouts_sampling_order:
-            k = min(self.V, int(1.25 * (f + s)) + 64)
-            caps.append(dict(S=s, C=self.V, K=k, B=int(min(self.Eg, max(1 << 16, 48 * k)))))
-            s = k
-        return caps
+    # What the kind implies (read-only).  exact_k: device-drawn multinomial layers keep at most fanout + S nodes, K capacities are
+    # that bound.  exact_b: neighbor layers keep at most fanout edges per seed, B capacities are that bound; nb_replace: drawn WITH
+    # replacement, B <= S * fanout but not <= |E|.  labor_is: LABOR layers run csrc/labor_is.hip also with 0 iterations.
+    exact_k = property(lambda self: KINDS[self.kind].k_slack == 0)
+    exact_b = property(lambda self: KINDS[self.kind].b_limit is not None)
+    nb_replace = property(lambda self: bool(KINDS[self.kind].b_limit))
+    labor_is = property(lambda self: self.kind == "labor_is")
+
+    def _use(self, kind):
+        """The kind of the exact-shape call at hand; capacities fixed with / without replacement do not carry over."""
+        if bool(KINDS[kind].b_limit) != self.nb_replace:
+            self.caps, self.ws = None, None
+        self.kind = kind
+        return KINDS[kind]
 
     def _ensure(self, S0, fan):
-        if self.caps is None or len(self.caps) != len(fan):
-            self.caps = self._init_caps(S0, fan)
+        caps = layer_caps(self.kind, self.V, self.Eg, S0, fan, self.caps)
+        if self.caps is None or [c["S"] for c in caps] != [c["S"] for c in self.caps]:
             self.ws = None
-        elif self.caps[0]["S"] < S0:
-            fresh = self._init_caps(S0, fan)
-            self.caps = [{k: max(a[k], b[k]) for k in a} for a, b in zip(self.caps, fresh)]
-            self.ws = None
+        self.caps = caps
         if self.ws is None:
             dev = self.g.device
             self.ws = [_LayerWs(dev, c["S"], c["C"]) for c in self.caps]
@@ -222,7 +365,46 @@ class LayerEngine:
         left[0], nxt[0] = int(h[624]), int(h[625])
         torch.set_rng_state(snapshot)
 
-    # ------------------------------------------------------------------ one sample_blocks call
+    # ------------------------------------------------------------------ the exact-shape call
+    def _raise_fatal(self, bad):
+        """End the call on error bits that larger buffers do not cure (the kind's rule); the other bits of _CAP_ERRS regrow."""
+        rule = KINDS[self.kind]
+        fatal = rule.fatal | (0 if self.n_bins else rule.fatal_no_bins)
+        if bad & ~_CAP_ERRS or (bad & fatal and not rule.own_messages):
+            raise RuntimeError(f"sampler kernel error 0x{bad:x}: {_lib.err_string(bad)}")
+        if bad & fatal & 1:
+            raise RuntimeError("frontier longer than the graph has edges (repeated seeds?) or >= 2^31 positions")
+        if bad & fatal & 2:
+            raise RuntimeError("candidate capacity exceeded / seed id out of range")
+
+    def _run(self, kind, w_rows, seeds, fanouts, mode, eta, eps, draw, uniforms=None):
+        """All layers enqueued, one copy of the counts, ONE sync; repeated with larger buffers -- from the same generator
+        snapshot, on the same draw step -- while a capacity was exceeded.  Returns the blocks in sampling order."""
+        rule = self._use(kind)
+        if rule.keyed and draw.state is None:
+            raise ValueError("draw='device' needs a draw_state")
+        seeds = seeds.to(torch.int32).contiguous()
+        L, S0 = len(fanouts), int(seeds.numel())
+        self._ensure(S0, fanouts)
+        snapshot = torch.get_rng_state() if rule.torch_rng and uniforms is None else None
+        while True:
+            counts, layers = self._enqueue(w_rows, seeds, fanouts, mode, eta, eps, uniforms, snapshot, draw)
+            self.counts_host.copy_(counts, non_blocking=True)
+            if snapshot is not None:
+                self.mt_back.copy_(self.mt_dev, non_blocking=True)
+            torch.cuda.current_stream().synchronize()                 # the ONE sync of the step's sampling
+            cnts, bad = _parse_counts(self.counts_host, L)
+            self._raise_fatal(bad)
+            if bad == 0:
+                break
+            if rule.keyed:
+                draw.state.step_dev.sub_(1)                            # the repeated call is the same draw step
+            self._grow([c.err for c in cnts])
+            self._ensure(S0, fanouts)
+        if snapshot is not None:
+            self._commit_rng(snapshot)
+        return [self._block(n, lay, c) for n, (lay, c) in enumerate(zip(layers, cnts))]
+
     def sample_blocks(self, w_rows, seeds, fanouts, mode, eta, eps=0.9999, uniforms=None, draw_state=None, layer_dependency=False):
         """The ``for block_id in reversed(range(L))`` loop of bandit_sampler.py:350-366 /
         ladies_sampler.py:112-122.  ``w_rows[n]`` / ``fanouts[n]`` are in SAMPLING order (last block
@@ -237,39 +419,8 @@ class LayerEngine:
             raise ValueError("uniforms= replaces the stream draw; the keyed draw (draw_state=) has no uniforms to replace")
         if layer_dependency and draw_state is None:
             raise ValueError("layer_dependency belongs to the keyed draw (draw_state=)")
-        seeds = seeds.to(torch.int32).contiguous()
-        L = len(fanouts)
-        self._ensure(int(seeds.numel()), fanouts)
-        snapshot = torch.get_rng_state() if uniforms is None and draw_state is None else None
-        while True:
-            out = self._enqueue(w_rows, seeds, fanouts, mode, eta, eps, uniforms, snapshot, draw_state=draw_state,
-                                poisson=draw_state is not None, layer_dependency=layer_dependency)
-            counts_dev = out[0]
-            self.counts_host.copy_(counts_dev, non_blocking=True)
-            if snapshot is not None:
-                self.mt_back.copy_(self.mt_dev, non_blocking=True)
-            torch.cuda.current_stream().synchronize()                 # the ONE sync of the step's sampling
-            raw = self.counts_host.numpy().tobytes()
-            cnts = [_lib.LayerCounts.from_buffer_copy(raw[40 * n: 40 * n + 40]) for n in range(L)]
-            errs = [c.err for c in cnts]
-            bad = 0
-            for e in errs:
-                bad |= e
-            if bad & ~_CAP_ERRS:
-                raise RuntimeError(f"sampler kernel error 0x{bad:x}: {_lib.err_string(bad)}")
-            if bad & 1:
-                raise RuntimeError("frontier longer than the graph has edges (repeated seeds?) or >= 2^31 positions")
-            if bad & 2 and not self.n_bins:
-                raise RuntimeError("candidate capacity exceeded / seed id out of range")
-            if bad == 0:
-                break
-            if draw_state is not None:
-                draw_state.step_dev.sub_(1)                            # the repeated call is the same draw step
-            self._grow(errs)
-            self._ensure(int(seeds.numel()), fanouts)
-        if snapshot is not None:
-            self._commit_rng(snapshot)
-        return self._finish(out, cnts)
+        return self._run("stream" if draw_state is None else "poisson_keyed", w_rows, seeds, fanouts, mode, eta, eps,
+                         _Draw(draw_state, None, layer_dependency), uniforms)
 
     # ------------------------------------------------------------------ non-Poisson samplers (multinomial draw)
     def sample_blocks_multinomial(self, w_rows, seeds, fanouts, mode, eta, replace=False, fp32_importance=False, draw="host",
@@ -284,26 +435,19 @@ class LayerEngine:
         multinomial_draw, multinomial_select_marked and build_block of all L layers are only enqueued and the call synchronises
         once, at the end, like sample_blocks; torch's CPU generator is not touched."""
         if draw == "device":                   # (``replace``: the keyed draw WITH replacement of csrc/replace_draw.hip, section 24)
-            return self._sample_blocks_mn_device(w_rows, seeds, fanouts, mode, eta, draw_state, replace=bool(replace))
+            return self._run("multinomial_replace" if replace else "multinomial", w_rows, seeds, fanouts, mode, eta, 0.0,
+                             _Draw(draw_state))
         if draw != "host":
             raise ValueError("draw must be 'host' or 'device', not %r" % (draw,))
+        self._use("multinomial_host")
         seeds = seeds.to(torch.int32).contiguous()
-        L = len(fanouts)
-        self._ensure(int(seeds.numel()), fanouts)
-        # a multinomial draw keeps min(num, C) nodes plus the seeds: make room
-        for n in range(L):
-            need = min(self.V, fanouts[n] + self.caps[n]["S"] + 64)
-            if self.caps[n]["K"] < need:
-                self.caps[n]["K"] = need
-            if n + 1 < L and self.caps[n + 1]["S"] < self.caps[n]["K"]:
-                self.caps[n + 1]["S"] = self.caps[n]["K"]
-                self.ws = None
-        self._ensure(int(seeds.numel()), fanouts)
+        L, S0 = len(fanouts), int(seeds.numel())
+        self._ensure(S0, fanouts)
         while True:
             dev, st = self.g.device, _stream()
             counts = torch.empty(L * 10, dtype=torch.int32, device=dev)
             eta_f, ome_f = float(np.float32(eta)), float(np.float32(1.0 - eta))
-            layers, state = [], (seeds, int(seeds.numel()), 0)
+            layers, state = [], (seeds, S0, 0)
             for n in range(L):
                 cur_seeds, n_seeds, n_seeds_dev = state
                 c_ws, c_out, lay, cnt_ptr, kept_nid = self._layer_buffers(n, counts)
@@ -328,129 +472,22 @@ class LayerEngine:
                 state = (kept_nid, -1, cnt_ptr + 12)
             self.counts_host.copy_(counts, non_blocking=True)
             torch.cuda.current_stream().synchronize()
-            raw = self.counts_host.numpy().tobytes()
-            cnts = [_lib.LayerCounts.from_buffer_copy(raw[40 * n: 40 * n + 40]) for n in range(L)]
-            bad = 0
-            for c in cnts:
-                bad |= c.err
-            if bad & ~_CAP_ERRS or bad & 2:
-                raise RuntimeError(f"sampler kernel error 0x{bad:x}: {_lib.err_string(bad)}")
+            cnts, bad = _parse_counts(self.counts_host, L)
+            self._raise_fatal(bad)
             if bad == 0:
-                return self._finish((counts, layers), cnts)
+                return [self._block(n, lay, c) for n, (lay, c) in enumerate(zip(layers, cnts))]
             self._grow([c.err for c in cnts])
-            self._ensure(int(seeds.numel()), fanouts)
+            self._ensure(S0, fanouts)
 
-    def _mn_exact_caps(self, fanouts):
-        """A device-drawn layer keeps union(drawn, seeds): at most fanout + S nodes, so that is its K capacity."""
-        for n in range(len(fanouts)):
-            need = min(self.V, int(fanouts[n]) + self.caps[n]["S"])
-            if self.caps[n]["K"] < need:
-                self.caps[n]["K"] = need
-            if n + 1 < len(fanouts) and self.caps[n + 1]["S"] < self.caps[n]["K"]:
-                self.caps[n + 1]["S"] = self.caps[n]["K"]
-                self.ws = None
-
-    def _sample_blocks_mn_device(self, w_rows, seeds, fanouts, mode, eta, draw_state, replace=False):
-        if draw_state is None:
-            raise ValueError("draw='device' needs a draw_state")
-        seeds = seeds.to(torch.int32).contiguous()
-        L = len(fanouts)
-        self._ensure(int(seeds.numel()), fanouts)
-        self._mn_exact_caps(fanouts)
-        self._ensure(int(seeds.numel()), fanouts)
-        while True:
-            out = self._enqueue(w_rows, seeds, fanouts, mode, eta, 0.0, None, None, draw_state=draw_state, replace=replace)
-            self.counts_host.copy_(out[0], non_blocking=True)
-            torch.cuda.current_stream().synchronize()                 # the one sync of the call
-            raw = self.counts_host.numpy().tobytes()
-            cnts = [_lib.LayerCounts.from_buffer_copy(raw[40 * n: 40 * n + 40]) for n in range(L)]
-            bad = 0
-            for c in cnts:
-                bad |= c.err
-            if bad & ~_CAP_ERRS or bad & 1 or (bad & 2 and not self.n_bins):
-                raise RuntimeError(f"sampler kernel error 0x{bad:x}: {_lib.err_string(bad)}")
-            if bad == 0:
-                return self._finish(out, cnts, keys=not replace)
-            draw_state.step_dev.sub_(1)                                # the repeated call is the same draw step
-            self._grow([c.err for c in cnts])
-            self._ensure(int(seeds.numel()), fanouts)
-            self._mn_exact_caps(fanouts)
-            self._ensure(int(seeds.numel()), fanouts)
-
-    # ------------------------------------------------------------------ neighbor sampler (keyed per-column draw)
-    def _nb_caps(self, S0, fanouts):
-        """Capacities of neighbor layers from their bounds: a layer keeps at most ``fanout`` edges per seed (B exactly bounded
-        when fanout >= 0) and, besides its seeds, at most one new source per kept edge."""
-        caps, s = [], int(S0)
-        for f in fanouts:
-            f = int(f)
-            b = int(min(self.Eg, s * f)) if f >= 0 else int(min(self.Eg, max(1 << 16, 48 * s)))
-            if self.nb_replace and f >= 0:      # (a column of fewer than f edges holds f block edges: |E| is no bound)
-                b = int(min(2 ** 31 - 1, s * f))
-            k = int(min(self.V, s + min(b, self.Eg))) if f >= 0 else self.V
-            caps.append(dict(S=s, C=self.V, K=k, B=b))
-            s = k
-        return caps
-
-    def _ensure_neighbor(self, S0, fan):
-        if self.caps is None or len(self.caps) != len(fan) or self.caps[0]["S"] < S0:
-            fresh = self._nb_caps(S0, fan)
-            if self.caps is not None and len(self.caps) == len(fan):
-                fresh = [{k: max(a.get(k, 0), b[k]) for k in b} for a, b in zip(self.caps, fresh)]
-            self.caps, self.ws = fresh, None
-        self._ensure(S0, fan)
-
+    # ------------------------------------------------------------------ node-wise samplers (keyed per-column / per-source draws)
     def sample_blocks_neighbor(self, seeds, fanouts, draw_state, nb_prob=None, replace=False):
         """fit.NeighborSampler with ``draw="device"`` (csrc/neighbor.hip): the L layers (``fanouts`` in
         SAMPLING order) are only enqueued and the call synchronises once, at the end; torch's generators are not touched.
         ``nb_prob``: the weighted draw of csrc/neighbor_w.hip -- ``neighbor_prob(...)``'s record.
         ``replace``: the draw WITH replacement of csrc/replace_draw.hip, uniform or over a raw-mode
         ``nb_prob``."""
-        if draw_state is None:
-            raise ValueError("draw='device' needs a draw_state")
-        seeds = seeds.to(torch.int32).contiguous()
-        L = len(fanouts)
-        if bool(replace) != self.nb_replace:
-            self.nb_replace, self.caps, self.ws = bool(replace), None, None
-        self._ensure_neighbor(int(seeds.numel()), fanouts)
-        while True:
-            out = self._enqueue(None, seeds, fanouts, 0, 0.0, 0.0, None, None, draw_state=draw_state, neighbor=True, nb_prob=nb_prob,
-                                nb_replace=bool(replace))
-            self.counts_host.copy_(out[0], non_blocking=True)
-            torch.cuda.current_stream().synchronize()                 # the one sync of the call
-            raw = self.counts_host.numpy().tobytes()
-            cnts = [_lib.LayerCounts.from_buffer_copy(raw[40 * n: 40 * n + 40]) for n in range(L)]
-            bad = 0
-            for c in cnts:
-                bad |= c.err
-            if bad & ~_CAP_ERRS or bad & 3:
-                raise RuntimeError(f"sampler kernel error 0x{bad:x}: {_lib.err_string(bad)}")
-            if bad == 0:
-                return self._finish(out, cnts)
-            draw_state.step_dev.sub_(1)                                # the repeated call is the same draw step
-            self._grow([c.err for c in cnts])
-            self._ensure_neighbor(int(seeds.numel()), fanouts)
-
-    # ------------------------------------------------------------------ LABOR-0 sampler (keyed per-source draw)
-    def _lb_caps(self, S0, fanouts):
-        """Starting capacities of LABOR layers.  A column keeps ``fanout`` edges in expectation, not at most: B is NOT exactly
-        bounded, so it starts at twice the expectation (the neighbor rule for fanout < 0) and the regrow loop covers the rest."""
-        caps, s = [], int(S0)
-        for f in fanouts:
-            f = int(f)
-            b = int(min(self.Eg, 2 * s * f + 4096)) if f >= 0 else int(min(self.Eg, max(1 << 16, 48 * s)))
-            k = int(min(self.V, s + b)) if f >= 0 else self.V
-            caps.append(dict(S=s, C=self.V, K=k, B=b))
-            s = k
-        return caps
-
-    def _ensure_labor(self, S0, fan):
-        if self.caps is None or len(self.caps) != len(fan) or self.caps[0]["S"] < S0:
-            fresh = self._lb_caps(S0, fan)
-            if self.caps is not None and len(self.caps) == len(fan):
-                fresh = [{k: max(a.get(k, 0), b[k]) for k in b} for a, b in zip(self.caps, fresh)]
-            self.caps, self.ws = fresh, None
-        self._ensure(S0, fan)
+        kind = "neighbor_replace" if replace else "neighbor" if nb_prob is None else "wneighbor"
+        return self._run(kind, None, seeds, fanouts, 0, 0.0, 0.0, _Draw(draw_state, nb_prob))
 
     def sample_blocks_labor(self, seeds, fanouts, draw_state, layer_dependency=False, iterations=0, lb_prob=None):
         """fit.LaborSampler (csrc/labor.hip): the L layers (``fanouts`` in SAMPLING order) are only enqueued
@@ -458,58 +495,35 @@ class LayerEngine:
         vertex for all layers of a step.  ``iterations`` > 0: LABOR-i layers (fit.ImportanceLaborSampler, csrc/labor_is.hip,
         DESIGN.md section 16).  ``lb_prob``: LABOR layers with edge probabilities (csrc/labor_w.hip) --
         ``neighbor_prob(...)``'s record; the blocks then carry ``_p``, the inclusion probabilities."""
-        if draw_state is None:
-            raise ValueError("the LABOR sampler needs a draw_state")
-        seeds = seeds.to(torch.int32).contiguous()
-        L = len(fanouts)
-        self._ensure_labor(int(seeds.numel()), fanouts)
-        while True:
-            out = self._enqueue(None, seeds, fanouts, 0, 0.0, 0.0, None, None, draw_state=draw_state, labor=True,
-                                layer_dependency=layer_dependency, labor_iterations=iterations, lb_prob=lb_prob)
-            self.counts_host.copy_(out[0], non_blocking=True)
-            torch.cuda.current_stream().synchronize()                 # the one sync of the call
-            raw = self.counts_host.numpy().tobytes()
-            cnts = [_lib.LayerCounts.from_buffer_copy(raw[40 * n: 40 * n + 40]) for n in range(L)]
-            bad = 0
-            for c in cnts:
-                bad |= c.err
-            if bad & ~_CAP_ERRS or bad & 3:
-                raise RuntimeError(f"sampler kernel error 0x{bad:x}: {_lib.err_string(bad)}")
-            if bad == 0:
-                blocks = self._finish(out, cnts)
-                for blk, c, p in zip(blocks, cnts, self._wl_out if lb_prob is not None else ()):
-                    blk._p = p[:c.B]
-                return blocks
-            draw_state.step_dev.sub_(1)                                # the repeated call is the same draw step
-            self._grow([c.err for c in cnts])
-            self._ensure_labor(int(seeds.numel()), fanouts)
+        kind = "labor_is" if iterations > 0 or self.labor_is else "labor"
+        if lb_prob is not None:
+            if kind == "labor_is":
+                raise NotImplementedError("LABOR-i with edge probabilities is out of scope")
+            kind = "wlabor"
+        return self._run(kind, None, seeds, fanouts, 0, 0.0, 0.0, _Draw(draw_state, lb_prob, layer_dependency, iterations))
 
-    def _labor_scratch(self, cap_s):
-        if self._lb_scr is None or self._lb_scr[0] < cap_s:           # (sized once for any seed capacity up to |V|)
-            rows = max(self.V, int(cap_s))
-            nbytes = int(_lib.lib.bliss_labor_scratch_bytes(self.V, rows))
-            self._lb_scr = (rows, torch.zeros(nbytes // 4, dtype=torch.int32, device=self.g.device))
-        return self._lb_scr[1]
+    # ------------------------------------------------------------------ node-wise layers: scratch (zero once, left zero by every call)
+    def _zeros(self, what, *dims):
+        nbytes = int(getattr(_lib.lib, what)(self.V, *dims))
+        if nbytes < 0:
+            raise RuntimeError(what + " failed")
+        return torch.zeros(nbytes // 4, dtype=torch.int32, device=self.g.device)
 
-    def _labor_is_scratch(self, cap_s, cap_b):
-        """Sized once for any seed capacity up to |V| and the largest edge capacity of the layers; regrows with B."""
-        if self._li_scr is None or self._li_scr[0] < cap_s or self._li_scr[1] < cap_b:
-            rows, edges = max(self.V, int(cap_s)), max(int(cap_b), max(c["B"] for c in self.caps))
-            nbytes = int(_lib.lib.bliss_labor_is_scratch_bytes(self.V, rows, edges))
-            if nbytes < 0:
-                raise RuntimeError("bliss_labor_is_scratch_bytes failed")
-            self._li_scr = (rows, edges, torch.zeros(nbytes // 4, dtype=torch.int32, device=self.g.device))
-        return self._li_scr[2]
+    def _scratch_once(self, attr, what, *dims):
+        """Scratch sized once, for any seed capacity up to |V|: ``attr`` holds the tensor."""
+        if getattr(self, attr) is None:
+            setattr(self, attr, self._zeros(what, *dims))
+        return getattr(self, attr)
 
-    def _wlabor_scratch(self, cap_s, cap_b):
-        """Sized once for any seed capacity up to |V| and the largest edge capacity of the layers; regrows with B."""
-        if self._wl_scr is None or self._wl_scr[0] < cap_s or self._wl_scr[1] < cap_b:
-            rows, edges = max(self.V, int(cap_s)), max(int(cap_b), max(c["B"] for c in self.caps))
-            nbytes = int(_lib.lib.bliss_wlabor_scratch_bytes(self.V, rows, edges))
-            if nbytes < 0:
-                raise RuntimeError("bliss_wlabor_scratch_bytes failed")
-            self._wl_scr = (rows, edges, torch.zeros(nbytes // 4, dtype=torch.int32, device=self.g.device))
-        return self._wl_scr[2]
+    def _scratch_grown(self, attr, what, cap_s, cap_b=None):
+        """Scratch sized for any seed capacity up to |V| and (``cap_b``) the largest edge capacity of the layers, regrown with
+        either: ``attr`` holds (rows, tensor) or (rows, edges, tensor)."""
+        scr, need = getattr(self, attr), (cap_s,) if cap_b is None else (cap_s, cap_b)
+        if scr is None or any(have < n for have, n in zip(scr, need)):
+            dims = (max(self.V, int(cap_s)),) + (() if cap_b is None else (max(int(cap_b), max(c["B"] for c in self.caps)),))
+            scr = dims + (self._zeros(what, *dims),)
+            setattr(self, attr, scr)
+        return scr[-1]
 
     def _wlabor_p(self, n, slot, cap_b):
         """The p_ij output of weighted LABOR layer n: persistent per static slot, fresh memory per call otherwise."""
@@ -532,71 +546,25 @@ class LayerEngine:
             return dict(mode=_lib.WN_RAW, rows=rows, eta_f=0.0, ome_f=0.0)
         return dict(mode=_lib.WN_EXP3, rows=rows, eta_f=float(np.float32(eta)), ome_f=float(np.float32(1.0 - eta)))
 
-    def _wneighbor_scratch(self):
-        if self._wn_scr is None:                                      # (sized once for any seed capacity up to |V|)
-            nbytes = int(_lib.lib.bliss_wneighbor_scratch_bytes(self.V, self.V, self.Eg))
-            if nbytes < 0:
-                raise RuntimeError("bliss_wneighbor_scratch_bytes failed")
-            self._wn_scr = torch.zeros(nbytes // 4, dtype=torch.int32, device=self.g.device)
-        return self._wn_scr
-
-    def _enqueue_neighbor_layer(self, n, fanout, cur_seeds, n_seeds, n_seeds_dev, draw_state, last, c_ws, c_out, lay, cnt_ptr, st,
-                                labor=False, layer_dependency=False, labor_iterations=0, nb_prob=None, lb_prob=None, p_out=None,
-                                nb_replace=False):
-        """One bliss_neighbor_layer (``labor``: one bliss_labor_layer, or one bliss_labor_is_layer when ``labor_iterations`` > 0, or
-        one bliss_wlabor_layer with ``lb_prob``, its p_ij into ``p_out``; ``nb_prob``: one bliss_wneighbor_layer) + the by-source
-        index of its block (bliss_block_transpose on the device-resident B).  ``nb_replace``: one bliss_neighbor_replace_layer,
-        uniform or over the raw-mode ``nb_prob``."""
-        cap, ws = self.caps[n], self.ws[n]
-        if nb_replace:
-            if labor or (nb_prob is not None and nb_prob["mode"] != _lib.WN_RAW):
+    def _enqueue_node_layer(self, n, fanout, cur_seeds, n_seeds, n_seeds_dev, draw, last, c_ws, c_out, lay, cnt_ptr, st, p_out=None):
+        """The one ``*_layer`` call of a node-wise kind (KINDS: entry point, scratch, its own arguments; p_ij into ``p_out``) + the
+        by-source index of its block (bliss_block_transpose on the device-resident B)."""
+        rule, cap, ws = KINDS[self.kind], self.caps[n], self.ws[n]
+        f, prob = int(fanout), draw.prob
+        if self.kind == "neighbor_replace":
+            if prob is not None and prob["mode"] != _lib.WN_RAW:
                 raise NotImplementedError("the draw with replacement is the neighbor layers', uniform or over raw probabilities")
-            f = int(fanout)
             if f == 0 or f > _lib.NR_MAX_FANOUT:
                 raise ValueError("the draw with replacement takes fanouts of 1 .. %d (or negative: whole columns), not %d"
                                  % (_lib.NR_MAX_FANOUT, f))
-            if self._nr_scr is None:
-                nbytes = int(_lib.lib.bliss_neighbor_replace_scratch_bytes(self.V, 1))
-                self._nr_scr = torch.zeros(nbytes // 4, dtype=torch.int32, device=self.g.device)
-            row = None if nb_prob is None else nb_prob["rows"][n if len(nb_prob["rows"]) > 1 else 0]
-            _lib.check(_lib.lib.bliss_neighbor_replace_layer(C.byref(self.c_graph), cur_seeds.data_ptr(), n_seeds, n_seeds_dev, cap["S"],
-                                                             f, 0, draw_state.seed, draw_state.step_dev.data_ptr(), n, int(last),
-                                                             _ptr(row), 0, C.byref(c_ws), C.byref(c_out), self._nr_scr.data_ptr(), st),
-                       "bliss_neighbor_replace_layer")
-        elif labor and lb_prob is not None:
-            row = lb_prob["rows"][n if len(lb_prob["rows"]) > 1 else 0]
-            _lib.check(_lib.lib.bliss_wlabor_layer(C.byref(self.c_graph), cur_seeds.data_ptr(), n_seeds, n_seeds_dev, cap["S"],
-                                                   int(fanout), 0, draw_state.seed, draw_state.step_dev.data_ptr(), n, int(last),
-                                                   int(bool(layer_dependency)), lb_prob["mode"], row.data_ptr(), lb_prob["eta_f"],
-                                                   lb_prob["ome_f"], C.byref(c_ws), C.byref(c_out), p_out.data_ptr(),
-                                                   self._wlabor_scratch(cap["S"], c_out.cap_b).data_ptr(), st), "bliss_wlabor_layer")
-        elif nb_prob is not None:
-            row = nb_prob["rows"][n if len(nb_prob["rows"]) > 1 else 0]
-            _lib.check(_lib.lib.bliss_wneighbor_layer(C.byref(self.c_graph), cur_seeds.data_ptr(), n_seeds, n_seeds_dev, cap["S"],
-                                                      int(fanout), 0, draw_state.seed, draw_state.step_dev.data_ptr(), n, int(last),
-                                                      nb_prob["mode"], row.data_ptr(), nb_prob["eta_f"], nb_prob["ome_f"], 0,
-                                                      C.byref(c_ws), C.byref(c_out), self._wneighbor_scratch().data_ptr(), st),
-                       "bliss_wneighbor_layer")
-        elif labor and (labor_iterations > 0 or self.labor_is):
-            _lib.check(_lib.lib.bliss_labor_is_layer(C.byref(self.c_graph), cur_seeds.data_ptr(), n_seeds, n_seeds_dev, cap["S"],
-                                                     int(fanout), 0, draw_state.seed, draw_state.step_dev.data_ptr(), n, int(last),
-                                                     int(bool(layer_dependency)), int(labor_iterations), C.byref(c_ws), C.byref(c_out),
-                                                     self._labor_is_scratch(cap["S"], c_out.cap_b).data_ptr(), st),
-                       "bliss_labor_is_layer")
-        elif labor:
-            _lib.check(_lib.lib.bliss_labor_layer(C.byref(self.c_graph), cur_seeds.data_ptr(), n_seeds, n_seeds_dev, cap["S"], int(fanout),
-                                                  0, draw_state.seed, draw_state.step_dev.data_ptr(), n, int(last),
-                                                  int(bool(layer_dependency)), C.byref(c_ws), C.byref(c_out),
-                                                  self._labor_scratch(cap["S"]).data_ptr(), st), "bliss_labor_layer")
-        else:
-            if self._nb_scr is None:
-                nbytes = int(_lib.lib.bliss_neighbor_scratch_bytes(self.V, 1))
-                self._nb_scr = torch.zeros(nbytes // 4, dtype=torch.int32, device=self.g.device)
-            _lib.check(_lib.lib.bliss_neighbor_layer(C.byref(self.c_graph), cur_seeds.data_ptr(), n_seeds, n_seeds_dev, cap["S"], int(fanout),
-                                                     0, draw_state.seed, draw_state.step_dev.data_ptr(), n, int(last), C.byref(c_ws),
-                                                     C.byref(c_out), self._nb_scr.data_ptr(), st), "bliss_neighbor_layer")
-        b_src, t_indptr, t_edge = lay[1], lay[10], lay[11]
-        if t_indptr is None:
+        row = None if prob is None else prob["rows"][n if len(prob["rows"]) > 1 else 0]
+        scr = rule.scratch(self, cap["S"], c_out.cap_b)
+        args = (C.byref(self.c_graph), cur_seeds.data_ptr(), n_seeds, n_seeds_dev, cap["S"], f, 0, draw.state.seed,
+                draw.state.step_dev.data_ptr(), n, int(last)) + tuple(rule.tail(draw, row)) + (C.byref(c_ws), C.byref(c_out))
+        if rule.p_out:
+            args += (p_out.data_ptr(),)
+        _lib.check(getattr(_lib.lib, rule.entry)(*args, scr.data_ptr(), st), rule.entry)
+        if lay.t_indptr is None:
             return                                                     # (Block.transposed builds it on demand)
         ck, cb = cap["K"], cap["B"]
         if ws.tr_temp is None or ws.tr_temp[0] != (cb, ck):
@@ -605,8 +573,8 @@ class LayerEngine:
                 raise RuntimeError("bliss_block_transpose_temp_bytes failed")
             ws.tr_temp = ((cb, ck), nbytes, torch.empty(max(nbytes, 1), dtype=torch.uint8, device=self.g.device))
         _, nbytes, temp = ws.tr_temp
-        _lib.check(_lib.lib.bliss_block_transpose(b_src.data_ptr(), cnt_ptr + 16, cb, cb, ck, t_indptr.data_ptr(), t_edge.data_ptr(),
-                                                  temp.data_ptr(), nbytes, st), "bliss_block_transpose")
+        _lib.check(_lib.lib.bliss_block_transpose(lay.src.data_ptr(), cnt_ptr + 16, cb, cb, ck, lay.t_indptr.data_ptr(),
+                                                  lay.t_edge.data_ptr(), temp.data_ptr(), nbytes, st), "bliss_block_transpose")
 
     def _layer_buffers(self, n, counts, slot=None):
         """Caller-owned outputs of layer n (one int32 and one bf16 allocation, sliced) + the C descriptors.
@@ -665,7 +633,7 @@ class LayerEngine:
             c_ws.touched_key, c_ws.touched_sum = b["tkey"].data_ptr(), b["tsum"].data_ptr()
         c_out = _lib.BlockOut(b_indptr.data_ptr(), b_src.data_ptr(), b_dst.data_ptr(), b_pos.data_ptr(), b_eid.data_ptr(),
                               b_w.data_ptr(), b_q.data_ptr(), _ptr(t_indptr), _ptr(t_edge), _ptr(t_scr), cb)
-        lay = (b_indptr, b_src, b_dst, b_pos, b_eid, b_w, b_q, kept_nid, node_prob, counts[10 * n:10 * n + 10], t_indptr, t_edge)
+        lay = _LayerOut(b_indptr, b_src, b_dst, b_pos, b_eid, b_w, b_q, kept_nid, node_prob, counts[10 * n:10 * n + 10], t_indptr, t_edge)
         return c_ws, c_out, lay, cnt_ptr, kept_nid
 
     # ------------------------------------------------------------------ static-shape (graph-capturable) variant
@@ -673,23 +641,7 @@ class LayerEngine:
         """Fix the capacities from sizes observed in exact mode (``max_sizes[n] = dict(K=, B=)`` in sampling
         order).  Static shapes mean no host round trip inside a step and a step that can be captured in a HIP graph;
         the price is that a step whose true sizes exceed these capacities is detected only afterwards."""
-        caps, s = [], int(S0)
-        for n, f in enumerate(fanouts):
-            k = min(self.V, int(k_margin * max_sizes[n]["K"]) + 256)
-            if self.exact_k:                # (device-drawn multinomial layer: the exact bound, such a step cannot overflow K)
-                k = min(self.V, int(f) + s)
-            b = int(min(self.Eg, int(b_margin * max_sizes[n]["B"]) + 4096))
-            if self.exact_b and int(f) >= 0:    # (neighbor layer: the exact bound, such a step cannot overflow B)
-                b = int(min(2 ** 31 - 1, s * int(f))) if self.nb_replace else int(min(self.Eg, s * int(f)))
-            # E only sizes launch grids (every kernel strides over the true count): a tight bound lets the hardware balance
-            # the workgroups instead of a capped grid looping unevenly
-            e = int(min(self.Eg, int(1.5 * max_sizes[n].get("E", self.Eg)) + 65536))
-            # X: how many block edges a multi-GPU step EXCHANGES per block (update lists are sent capacity-sized; B's margin
-            # is for memory that costs nothing, X's for bytes that cross xGMI every step); a longer list is flagged
-            x = int(min(b, int(1.5 * max_sizes[n]["B"]) + 2048))
-            caps.append(dict(S=s, C=self.V, K=k, B=b, E=e, X=x))
-            s = k
-        self.caps, self.ws = caps, None
+        self.caps, self.ws = static_caps(self.kind, self.V, self.Eg, S0, fanouts, max_sizes, k_margin, b_margin), None
         self._ensure(S0, fanouts)
 
     def stage_rng_from_torch(self):
@@ -739,11 +691,10 @@ class LayerEngine:
         _lib.check(_lib.lib.bliss_rng_stream_ready(_stream()), "bliss_rng_stream_ready")
 
     def enqueue_static(self, w_rows, seeds, fanouts, mode, eta, eps=0.9999, slot=0, chain_rng=False, external_rng=False, part=None,
-                       last_block=True, ready_flag=0, draw_state=None, neighbor=False, labor=False, layer_dependency=False,
-                       labor_iterations=0, nb_prob=None, lb_prob=None, n_live_dev=None, poisson=False, replace=False,
-                       nb_replace=False):
+                       last_block=True, ready_flag=0, n_live_dev=None, draw=_Draw()):
         """Enqueue one sample_blocks on the current stream with capacity-padded outputs and NO sync.  Returns the
-        blocks (sampling order); sizes, errors and the generator state are read back by finish().
+        blocks (sampling order); sizes, errors and the generator state are read back by finish().  The layers are of the
+        engine's ``kind`` (KINDS); the node-wise kinds ignore ``w_rows`` / ``mode`` / ``eta`` / ``eps``.
 
         ``slot``: which persistent set of output buffers to fill.  ``chain_rng``: continue from the generator state the
         previous enqueue left on the device instead of the host-staged one (several batches sampled per host round trip).
@@ -754,96 +705,53 @@ class LayerEngine:
         ``last_block=False`` with "main": the last-sampled layer's block is left out as well and ``flags[L]`` is raised at the end
         (its draw is done); part "last_block" = only that block, behind a bliss_flag_wait on ``flags[L]``; ``ready_flag``
         (address of a device flag) is raised as soon as the block's forward arrays are final, before its by-source index.
-        ``draw_state`` (a DrawState): the layers draw with the device-side multinomial draw instead of the Poisson chain
-        (whole calls only; no generator is involved); with ``poisson``: the Poisson chain itself with the keyed draw of
-        bliss_poisson_select_keyed (whole calls only, no generator, no staging; ``layer_dependency``: one
-        variate per node for all layers).  ``neighbor``: the layers are neighbor layers (csrc/neighbor.hip; needs
-        ``draw_state``, whole calls only; ``w_rows`` / ``mode`` / ``eta`` / ``eps`` are ignored).  ``labor``: the layers are LABOR-0
-        layers (csrc/labor.hip; the same conditions), with one variate per vertex for all layers when ``layer_dependency``; ``labor_iterations`` > 0:
-        LABOR-i layers (csrc/labor_is.hip).  ``nb_prob`` (with ``neighbor``): the weighted draw of csrc/neighbor_w.hip, from
-        ``neighbor_prob(...)``.  ``lb_prob`` (with ``labor``, ``labor_iterations`` = 0): LABOR layers with edge probabilities
-        (csrc/labor_w.hip), from the same record; the blocks then carry ``_p``, the inclusion probabilities.
+        Only the "stream" kind has a generator to chain or run externally and a split enqueue; every other kind is enqueued
+        as a whole call.
+        ``draw`` (a _Draw): the DrawState of the keyed kinds, the ``neighbor_prob(...)`` record of the weighted ones (the
+        blocks of weighted LABOR layers then carry ``_p``, the inclusion probabilities), ``layer_dependency`` (keyed Poisson,
+        LABOR: one variate per node for all layers) and LABOR-i's ``iterations``.
         ``n_live_dev`` (an int32 word on the device): ``seeds`` is a buffer of CAPACITY length -- the
         capacity the static shapes were fixed for -- of which only the first ``n_live_dev[0]`` slots are this batch's seeds.
         The first-sampled layer is then launched like every later one, with its seed count read on the device, so a captured
         call serves every batch size up to the capacity; the output block's counts record holds the live S.  Slots past the
-        live count are read for no result (they hold valid node ids: zero, or an earlier batch's).  Whole calls only.
-        ``replace`` (with ``draw_state``, the multinomial layers) / ``nb_replace`` (with ``neighbor``): the draws WITH replacement of
-        csrc/replace_draw.hip in place of bliss_multinomial_draw / bliss_neighbor_layer."""
-        if replace and (draw_state is None or poisson or neighbor or labor):
-            raise ValueError("replace=True selects the multinomial layers' keyed draw with replacement: it needs a draw_state")
-        if nb_replace and not neighbor:
-            raise ValueError("nb_replace belongs to the neighbor layers")
-        if neighbor and bool(nb_replace) != self.nb_replace:
-            raise ValueError("the capacities of this engine were fixed %s replacement (LayerEngine.nb_replace)"
-                             % ("with" if self.nb_replace else "without"))
+        live count are read for no result (they hold valid node ids: zero, or an earlier batch's).  Whole calls only."""
+        rule = KINDS[self.kind]
+        whole = part is None and not external_rng and not chain_rng
+        if self.kind == "multinomial_host":
+            raise NotImplementedError("torch.multinomial on the host syncs per layer: no static-shape enqueue")
+        if rule.keyed and draw.state is None:
+            raise ValueError("the %s layers need a draw_state" % self.kind)
+        if not whole and (n_live_dev is not None or not rule.split):
+            raise NotImplementedError("a live seed count and the %s layers have no split / external-generator enqueue (the "
+                                      "pipelined two-stream loop is out of scope)" % self.kind)
         if n_live_dev is not None:
-            if part is not None or external_rng or chain_rng:
-                raise NotImplementedError("a live seed count has no split / external-generator enqueue (the pipelined two-stream "
-                                          "loop is out of scope)")
             if not (torch.is_tensor(n_live_dev) and n_live_dev.dtype == torch.int32 and n_live_dev.numel() == 1
                     and n_live_dev.device == self.g.device):
                 raise ValueError("n_live_dev: one int32 word on the graph's device")
             if self.caps is None or int(seeds.numel()) != self.caps[0]["S"] or seeds.dtype != torch.int32 or not seeds.is_contiguous():
                 raise ValueError("a live seed count needs a contiguous int32 seed buffer of exactly the static seed capacity (%s), "
                                  "got %d slots" % (None if self.caps is None else self.caps[0]["S"], int(seeds.numel())))
-        if nb_prob is not None and not neighbor:
-            raise ValueError("nb_prob belongs to the neighbor layers")
-        if lb_prob is not None and not labor:
-            raise ValueError("lb_prob belongs to the LABOR layers")
-        if labor and (neighbor or draw_state is None or part is not None or external_rng or chain_rng):
-            raise NotImplementedError("the LABOR sampler needs a draw_state and has no split / external-generator enqueue "
-                                      "(the pipelined two-stream loop is out of scope)")
-        if neighbor and (draw_state is None or part is not None or external_rng or chain_rng):
-            raise NotImplementedError("the device-side neighbor sampler needs a draw_state and has no split / external-generator "
-                                      "enqueue (the pipelined two-stream loop is out of scope)")
-        if poisson and (neighbor or labor or draw_state is None):
-            raise ValueError("poisson=True selects the keyed Poisson draw of the layer-wise samplers: it needs a draw_state")
-        if draw_state is not None and (part is not None or external_rng or chain_rng):
-            raise NotImplementedError("the device-side draws (multinomial, keyed Poisson) have no split / external-generator "
-                                      "enqueue (the pipelined two-stream loop is out of scope)")
         if part is not None and (self.scratch_sets < len(fanouts) or not external_rng):
             raise ValueError("split enqueue needs one scratch set per layer and an external generator")
         L = len(fanouts)
-        out = self._enqueue(w_rows, seeds, fanouts, mode, eta, eps, None, True, slot=slot, chain_rng=chain_rng,
-                            external_rng=external_rng, part=part, last_block=last_block, ready_flag=ready_flag, draw_state=draw_state,
-                            neighbor=neighbor, labor=labor, layer_dependency=layer_dependency, labor_iterations=labor_iterations,
-                            nb_prob=nb_prob, lb_prob=lb_prob, n_live_dev=n_live_dev, poisson=poisson, replace=replace,
-                            nb_replace=nb_replace)
-        self._static_draw[slot] = draw_state is not None
-        counts_dev, layers = out
+        counts_dev, layers = self._enqueue(w_rows, seeds, fanouts, mode, eta, eps, None, True, draw, slot=slot, chain_rng=chain_rng,
+                                           external_rng=external_rng, part=part, last_block=last_block, ready_flag=ready_flag,
+                                           n_live_dev=n_live_dev)
+        self._static_draw[slot] = rule.keyed
         if slot not in self._slot_counts_host:
             self._slot_counts_host[slot] = torch.empty(L * 10, dtype=torch.int32).pin_memory()
         if not external_rng:                     # (external: static_rng_end copies both, off the consumer's critical path)
             self._slot_counts_host[slot].copy_(counts_dev, non_blocking=True)
-            if draw_state is None:
+            if not rule.keyed:
                 self.mt_back.copy_(self.mt_dev, non_blocking=True)
-        blocks = []
-        for n, lay in enumerate(layers):
-            b_indptr, b_src, b_dst, b_pos, b_eid, b_w, b_q, kept_nid, node_prob, cdev, t_indptr, t_edge = lay
-            cap = self.caps[n]
-            blk = Block(self.g, cap["K"], cap["S"], b_indptr, b_src, b_dst, b_pos, b_eid, kept_nid)
-            blk._edge_weights, blk._q, blk._node_prob = b_w, b_q, node_prob
-            if lb_prob is not None:
-                blk._p = self._wl_out[n][:cap["B"]]
-            blk._counts, blk._counts_dev = None, cdev
-            blk._nnz_ptr = counts_dev.data_ptr() + 40 * n + 16
-            blk._xcap = int(cap.get("X", cap["B"]))
-            if t_indptr is not None:
-                blk._transposed = (t_indptr, t_edge)
-            blk._trace = {}
-            blocks.append(blk)
+        blocks = [self._block(n, lay, None, counts_dev) for n, lay in enumerate(layers)]
         self._static[slot] = (blocks, L)    # kept: a captured graph replays this enqueue without re-running it
         return blocks
 
     def finish(self, slot=0, commit=True):
         """After the stream has been synchronised: true sizes, error check, generator hand-back."""
         blocks, L = self._static[slot]
-        raw = self._slot_counts_host[slot].numpy().tobytes()
-        cnts = [_lib.LayerCounts.from_buffer_copy(raw[40 * n: 40 * n + 40]) for n in range(L)]
-        bad = 0
-        for c in cnts:
-            bad |= c.err
+        cnts, bad = _parse_counts(self._slot_counts_host[slot], L)
         for b, c in zip(blocks, cnts):
             b._counts = c
         if commit and not self._static_draw.get(slot):       # (the device draw consumed nothing from torch's generator)
@@ -853,14 +761,16 @@ class LayerEngine:
                                f"({_lib.err_string(bad)}); the step's results are invalid -- raise the margins")
         return cnts
 
-    def _enqueue(self, w_rows, seeds, fanouts, mode, eta, eps, uniforms, snapshot, slot=None, chain_rng=False, external_rng=False,
-                 part=None, last_block=True, ready_flag=0, draw_state=None, neighbor=False, labor=False, layer_dependency=False,
-                 labor_iterations=0, nb_prob=None, lb_prob=None, n_live_dev=None, poisson=False, replace=False, nb_replace=False):
-        if lb_prob is not None and (labor_iterations > 0 or self.labor_is):
-            raise NotImplementedError("LABOR-i with edge probabilities is out of scope")
+    def _enqueue(self, w_rows, seeds, fanouts, mode, eta, eps, uniforms, snapshot, draw, slot=None, chain_rng=False, external_rng=False,
+                 part=None, last_block=True, ready_flag=0, n_live_dev=None):
+        """The launches of one call of the engine's kind, on the current stream; returns (counts on the device, [_LayerOut])."""
+        kind, rule, draw_state = self.kind, KINDS[self.kind], draw.state
+        poisson = kind in ("stream", "poisson_keyed")
+        if (draw.prob is None) if rule.prob == "any" else (draw.prob is not None and rule.prob is None):
+            raise ValueError("the %s layers %s" % (kind, "need neighbor_prob(...)'s record" if rule.prob else "take no probabilities"))
         dev, st = self.g.device, _stream()
         L = len(fanouts)
-        if draw_state is None and snapshot is not None and not chain_rng and not external_rng:
+        if not rule.keyed and snapshot is not None and not chain_rng and not external_rng:
             if snapshot is not True:
                 self._stage_rng(snapshot)
             self.mt_dev.copy_(self.mt_host, non_blocking=True)
@@ -870,7 +780,7 @@ class LayerEngine:
             if slot not in self._slot_counts or self._slot_counts[slot].numel() != L * 10:
                 self._slot_counts[slot] = torch.empty(L * 10, dtype=torch.int32, device=dev)
             counts = self._slot_counts[slot]
-        use_rng = uniforms is None and draw_state is None
+        use_rng = uniforms is None and not rule.keyed
         if use_rng and not external_rng:      # fork the generator: it runs beside everything below
             _lib.check(_lib.lib.bliss_rng_stream_begin(self.mt_dev.data_ptr(), self.rng_ctl.data_ptr(), self.rng_out.data_ptr(),
                                                        self.rng_raw.data_ptr(), self.rng_cap, st), "bliss_rng_stream_begin")
@@ -886,41 +796,20 @@ class LayerEngine:
             cs, ws = cap["S"], self.ws[n]
             c_ws, c_out, lay, cnt_ptr, kept_nid = self._layer_buffers(n, counts, slot)
             last = n == L - 1
-            if neighbor or labor:               # neighbor / LABOR layer: 6 / 7 launches and the by-source index, nothing else
+            if rule.family == "node":           # neighbor / LABOR layer: 6 / 7 launches and the by-source index, nothing else
                 p_out = None
-                if labor and lb_prob is not None:
+                if rule.p_out:
                     p_out = self._wlabor_p(n, slot, cap["B"])
                     self._wl_out.append(p_out)
-                self._enqueue_neighbor_layer(n, fanouts[n], cur_seeds, n_seeds, n_seeds_dev, draw_state, last, c_ws, c_out, lay,
-                                             cnt_ptr, st, labor=labor, layer_dependency=layer_dependency,
-                                             labor_iterations=labor_iterations, nb_prob=nb_prob if neighbor else None,
-                                             lb_prob=lb_prob if labor else None, p_out=p_out, nb_replace=nb_replace and neighbor)
+                self._enqueue_node_layer(n, fanouts[n], cur_seeds, n_seeds, n_seeds_dev, draw, last, c_ws, c_out, lay, cnt_ptr, st, p_out)
                 layers.append(lay)
                 cur_seeds, n_seeds, n_seeds_dev = kept_nid, -1, cnt_ptr + 12
                 continue
             w_pos = w_rows[n]
             if part == "main":                  # layer n raises flag n when it starts (= everything before it has completed)
                 c_ws.entry_flag = self.flags.data_ptr() + 4 * n
-            if draw_state is not None and not poisson:   # multinomial samplers, keyed draw: 1 + 5 + 4 launches, then the block
-                _lib.check(_lib.lib.bliss_frontier_prob(C.byref(self.c_graph), C.byref(self._set(n)["c_maps"]), w_pos.data_ptr(),
-                                                        cur_seeds.data_ptr(), n_seeds, n_seeds_dev, cs, mode, eta_f, ome_f,
-                                                        cap.get("E", self.Eg), C.byref(c_ws), st), "bliss_frontier_prob")
-                if replace:                     # the keyed categorical draw with replacement: 3 launches, the same mark format
-                    if ws.rdraw_scr is None:
-                        nbytes = int(_lib.lib.bliss_multinomial_draw_replace_scratch_bytes(cap["C"]))
-                        ws.rdraw_scr = torch.zeros(nbytes // 8, dtype=torch.int64, device=dev)
-                    _lib.check(_lib.lib.bliss_multinomial_draw_replace(ws.p.data_ptr(), cnt_ptr, cap["C"], int(fanouts[n]), 0,
-                                                                       draw_state.seed, draw_state.step_dev.data_ptr(), n, int(last),
-                                                                       ws.rdraw_scr.data_ptr(), ws.new_id.data_ptr(), 0, st),
-                               "bliss_multinomial_draw_replace")
-                else:
-                    _lib.check(_lib.lib.bliss_multinomial_draw(ws.cand_nid.data_ptr(), ws.p.data_ptr(), cnt_ptr, cap["C"], int(fanouts[n]), 0,
-                                                               draw_state.seed, draw_state.step_dev.data_ptr(), n, int(last),
-                                                               ws.draw_scr.data_ptr(), ws.keys.data_ptr(), ws.new_id.data_ptr(), st),
-                               "bliss_multinomial_draw")
-                _lib.check(_lib.lib.bliss_multinomial_select_marked(C.byref(c_ws), st), "bliss_multinomial_select_marked")
-            elif part in (None, "main"):        # candidates, probabilities, draw: all the next layer needs (its seeds = kept_nid)
-                if self.n_bins and self.fuse_scale:
+            if part in (None, "main"):          # candidates, probabilities, draw: all the next layer needs (its seeds = kept_nid)
+                if poisson and self.n_bins and self.fuse_scale:
                     # the Poisson scale rides in the last workgroup of the candidate numbering (one launch less per layer)
                     c_ws.fs_ticket = self.fs_ticket.data_ptr()
                     c_ws.fs_fanout, c_ws.fs_eps = int(fanouts[n]), float(eps)
@@ -930,9 +819,22 @@ class LayerEngine:
                 _lib.check(_lib.lib.bliss_frontier_prob(C.byref(self.c_graph), C.byref(self._set(n)["c_maps"]), w_pos.data_ptr(),
                                                         cur_seeds.data_ptr(), n_seeds, n_seeds_dev, cs, mode, eta_f, ome_f,
                                                         cap.get("E", self.Eg), C.byref(c_ws), st), "bliss_frontier_prob")
-                if poisson:                     # keyed Poisson draw: no generator, no uniforms buffer; the last select bumps the step
+                if kind == "multinomial_replace":   # the keyed categorical draw with replacement: 3 launches, the same mark format
+                    if ws.rdraw_scr is None:
+                        nbytes = int(_lib.lib.bliss_multinomial_draw_replace_scratch_bytes(cap["C"]))
+                        ws.rdraw_scr = torch.zeros(nbytes // 8, dtype=torch.int64, device=dev)
+                    _lib.check(_lib.lib.bliss_multinomial_draw_replace(ws.p.data_ptr(), cnt_ptr, cap["C"], int(fanouts[n]), 0,
+                                                                       draw_state.seed, draw_state.step_dev.data_ptr(), n, int(last),
+                                                                       ws.rdraw_scr.data_ptr(), ws.new_id.data_ptr(), 0, st),
+                               "bliss_multinomial_draw_replace")
+                elif kind == "multinomial":     # the keyed race: 5 launches
+                    _lib.check(_lib.lib.bliss_multinomial_draw(ws.cand_nid.data_ptr(), ws.p.data_ptr(), cnt_ptr, cap["C"], int(fanouts[n]), 0,
+                                                               draw_state.seed, draw_state.step_dev.data_ptr(), n, int(last),
+                                                               ws.draw_scr.data_ptr(), ws.keys.data_ptr(), ws.new_id.data_ptr(), st),
+                               "bliss_multinomial_draw")
+                elif kind == "poisson_keyed":   # keyed Poisson draw: no generator, no uniforms buffer; the last select bumps the step
                     _lib.check(_lib.lib.bliss_poisson_select_keyed(C.byref(c_ws), int(fanouts[n]), float(eps), draw_state.seed,
-                                                                   draw_state.step_dev.data_ptr(), 0 if layer_dependency else n,
+                                                                   draw_state.step_dev.data_ptr(), 0 if draw.layer_dependency else n,
                                                                    int(last), cap["C"], st), "bliss_poisson_select_keyed")
                 elif use_rng:
                     off_ptr = self.rng_ctl.data_ptr() + 4 * (8 + n)
@@ -945,6 +847,8 @@ class LayerEngine:
                     ws.uniforms[:m].copy_(u[:m])
                     _lib.check(_lib.lib.bliss_poisson_select(C.byref(c_ws), int(fanouts[n]), float(eps), ws.uniforms.data_ptr(),
                                                              0, 0, 0, 0, cap["C"], st), "bliss_poisson_select")
+                if not poisson:                 # (both multinomial draws leave marks: 4 launches)
+                    _lib.check(_lib.lib.bliss_multinomial_select_marked(C.byref(c_ws), st), "bliss_multinomial_select_marked")
             # the block of this layer: nothing the next layer's candidate pipeline reads or writes (own scratch set)
             if part is None or (part == "main" and last and last_block) or (part == "early_blocks" and not last) or \
                     (part == "last_block" and last):
@@ -965,20 +869,28 @@ class LayerEngine:
                                                      self.rng_cap, counts.data_ptr() + 20, _stream()), "bliss_rng_stream_end")
         return counts, layers
 
-    def _finish(self, out, cnts, keys=False):
-        _, layers = out
-        blocks = []
-        for n, (lay, c) in enumerate(zip(layers, cnts)):
-            b_indptr, b_src, b_dst, b_pos, b_eid, b_w, b_q, kept_nid, node_prob, cdev, t_indptr, t_edge = lay
-            S, K, B = c.S, c.K, c.B
-            blk = Block(self.g, K, S, b_indptr[:S + 1], b_src[:B], b_dst[:B], b_pos[:B], b_eid[:B], kept_nid[:K])
-            blk._edge_weights, blk._q, blk._node_prob = b_w[:B], b_q[:B], node_prob[:K]
-            blk._counts, blk._counts_dev = c, cdev
-            if t_indptr is not None:
-                blk._transposed = (t_indptr[:K + 1], t_edge[:max(B, 1)])
-            ws = self.ws[n]
-            blk._trace = dict(p=ws.p[:c.C], P=ws.P[:c.C], cand_nid=ws.cand_nid[:c.C], new_id=ws.new_id[:c.C])
-            if keys:
-                blk._trace["keys"] = ws.keys[:c.C]
-            blocks.append(blk)
-        return blocks
+    def _block(self, n, lay, c, counts_dev=None):
+        """The Block of layer n from its outputs.  ``c`` (its LayerCounts): sliced to the true sizes, with the candidate pipeline's
+        _trace.  None: the static path's capacity-sized block -- true sizes stay on the device (``_nnz_ptr`` into
+        ``counts_dev``) and ``_counts`` is filled in by finish()."""
+        cap, rule = self.caps[n], KINDS[self.kind]
+        S, K, B = (cap["S"], cap["K"], cap["B"]) if c is None else (c.S, c.K, c.B)
+        cut = (lambda t, m: t) if c is None else (lambda t, m: t[:m])      # (capacity-sized: the buffers as they are)
+        blk = Block(self.g, K, S, cut(lay.indptr, S + 1), cut(lay.src, B), cut(lay.dst, B), cut(lay.pos, B), cut(lay.eid, B),
+                    cut(lay.kept_nid, K))
+        blk._edge_weights, blk._q, blk._node_prob = cut(lay.w, B), cut(lay.q, B), cut(lay.node_prob, K)
+        if rule.p_out:
+            blk._p = self._wl_out[n][:B]
+        blk._counts, blk._counts_dev = c, lay.counts
+        if lay.t_indptr is not None:
+            blk._transposed = (cut(lay.t_indptr, K + 1), cut(lay.t_edge, max(B, 1)))
+        if c is None:
+            blk._nnz_ptr = counts_dev.data_ptr() + 40 * n + 16
+            blk._xcap = int(cap.get("X", cap["B"]))
+            blk._trace = {}
+            return blk
+        ws = self.ws[n]
+        blk._trace = dict(p=ws.p[:c.C], P=ws.P[:c.C], cand_nid=ws.cand_nid[:c.C], new_id=ws.new_id[:c.C])
+        if rule.keys:
+            blk._trace["keys"] = ws.keys[:c.C]
+        return blk

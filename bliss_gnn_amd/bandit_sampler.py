@@ -14,8 +14,8 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._engine import DrawState, LayerEngine, _stream
-from .graph import EID, NID, Graph, as_graph
+from ._engine import DrawState, LayerEngine, _Draw, _stream
+from .graph import EID, NID, Graph, _publish, as_graph
 
 
 def find_indices_in(a, b):
@@ -105,6 +105,28 @@ class DeviceDraw:
             self._draw_state = DrawState(torch.initial_seed() if seed is None else seed, step, device)
         return self._draw_state
 
+    # -- the engine: one per graph, of the kind of layer this sampler's constructor arguments fix (_engine.KINDS) -------------
+    def _kind(self):
+        if self._poisson:
+            return "poisson_keyed" if self.draw == "device" else "stream"
+        if self.draw != "device":
+            return "multinomial_host"
+        return "multinomial_replace" if self.replace else "multinomial"
+
+    def _graph(self, g):
+        """The bliss Graph behind ``g`` (a DGLGraph-like object is converted once and cached, graph.as_graph)."""
+        return as_graph(g, self.__dict__.setdefault("_graphs", {}))
+
+    def _bind(self, g):
+        g = self._graph(g)
+        if self._engine is None or self._engine.g is not g:
+            self._engine = LayerEngine(g, self._kind())
+        return self._engine
+
+    def _draw_on(self, device, prob=None, iterations=0):
+        """The engine's per-call record."""
+        return _Draw(self._draw_state_on(device), prob, self.layer_dependency, iterations)
+
 
 class BanditLadiesSampler(DeviceDraw, BlockSampler):
     """bandit_sampler.py:29-367.  ``select_neighbors`` (:84-99) is ``torch.multinomial`` on the device-computed
@@ -138,18 +160,8 @@ class BanditLadiesSampler(DeviceDraw, BlockSampler):
         return _lib.MODE_BANDIT | (0 if self.importance_sampling else _lib.MODE_UNIFORM_NODES)
 
     # -- state ------------------------------------------------------------------------------
-    def _graph(self, g):
-        """The bliss Graph behind ``g`` (a DGLGraph-like object is converted once and cached, graph.as_graph)."""
-        if not hasattr(self, "_graphs"):
-            self._graphs = {}
-        return as_graph(g, self._graphs)
-
-    def _bind(self, g):
-        g = self._graph(g)
-        if self._engine is None or self._engine.g is not g:
-            self._engine = LayerEngine(g)
-            self._engine.exact_k = self.draw == "device" and not self._poisson     # (a Poisson layer's K is not bounded by its fanout)
-        return self._engine
+    def _fields(self):
+        return [("edata", self.output_weight, "_edge_weights"), ("edata", "q_ij", "_q"), ("srcdata", self.node_prob, "_node_prob")]
 
     def _ensure_weights(self, g):
         if self._w_pos is None:                                         # bandit_sampler.py:342-343
@@ -201,13 +213,7 @@ class BanditLadiesSampler(DeviceDraw, BlockSampler):
         else:                                                             # select_neighbors :84-99 (torch.multinomial)
             blks = eng.sample_blocks_multinomial(rows, seed_nodes, fan, self._mode(), self.eta, self.replace, draw=self.draw,
                                                  draw_state=self._draw_state_on(g.device))
-        blocks = []
-        for blk in blks:
-            blk.edata[self.output_weight] = blk._edge_weights           # :324
-            blk.edata["q_ij"] = blk._q                                  # :326
-            blk.srcdata[self.node_prob] = blk._node_prob                # :328
-            blocks.insert(0, blk)                                       # :366
-        return blocks[0].srcdata[NID], output_nodes, blocks             # :364,:367
+        return _publish(blks, output_nodes, self._fields())                 # :324-328, :364-367
 
     def sample_blocks_static(self, g, seed_nodes, slot=0, chain_rng=False, external_rng=False, part=None, last_block=True, ready_flag=0,
                              n_live_dev=None):
@@ -224,16 +230,8 @@ class BanditLadiesSampler(DeviceDraw, BlockSampler):
         order = list(reversed(range(len(self.nodes_per_layer))))
         blks = eng.enqueue_static([self._w_pos[b] for b in order], seed_nodes, [self.nodes_per_layer[b] for b in order],
                                   self._mode(), self.eta, self.eps, slot=slot, chain_rng=chain_rng, external_rng=external_rng, part=part,
-                                  last_block=last_block, ready_flag=ready_flag, draw_state=self._draw_state_on(g.device), n_live_dev=n_live_dev,
-                                  poisson=self._poisson and self.draw == "device", layer_dependency=self.layer_dependency,
-                                  replace=self.replace and self.draw == "device")
-        blocks = []
-        for blk in blks:
-            blk.edata[self.output_weight] = blk._edge_weights
-            blk.edata["q_ij"] = blk._q
-            blk.srcdata[self.node_prob] = blk._node_prob
-            blocks.insert(0, blk)
-        return blocks[0].srcdata[NID], seed_nodes, blocks
+                                  last_block=last_block, ready_flag=ready_flag, n_live_dev=n_live_dev, draw=self._draw_on(g.device))
+        return _publish(blks, seed_nodes, self._fields())
 
     def finish_static(self, slot=0, commit=True):
         return self._engine.finish(slot, commit)

@@ -27,9 +27,8 @@ import os
 import torch
 
 from . import _lib
-from ._engine import LayerEngine
 from .bandit_sampler import BanditLadiesSampler, BlockSampler, DeviceDraw
-from .graph import NID, Block, as_graph
+from .graph import NID, Block, _publish, as_graph
 from .ladies_sampler import PoissonLadiesSampler
 from .train import BatchLoader, GraphedEvalStep, GraphedTrainStep, TrainStep, _inputs, _keep_static_caps, _rng_kept
 
@@ -106,13 +105,8 @@ class NeighborSampler(DeviceDraw, BlockSampler):
         self._engine = None
 
     # -- draw="device" ----------------------------------------------------------------------------------------------
-    def _bind(self, g):
-        g = as_graph(g, self.__dict__.setdefault("_graphs", {}))
-        if self._engine is None or self._engine.g is not g:
-            self._engine = LayerEngine(g)
-            self._engine.exact_b = True
-            self._engine.nb_replace = self.replace
-        return self._engine
+    def _kind(self):
+        return "neighbor_replace" if self.replace else "neighbor" if self.prob is None else "wneighbor"
 
     def _nb_prob(self, eng):
         """The engine's probability record of the weighted draw (None without ``prob``); bf16 by position, once per graph."""
@@ -126,14 +120,11 @@ class NeighborSampler(DeviceDraw, BlockSampler):
             self._prob_pos = (g, g.by_position(p.to(g.device).to(torch.bfloat16)).contiguous())
         return eng.neighbor_prob(self._prob_pos[1])
 
+    def _fields(self):
+        return [("edata", "edge_weights", "_edge_weights")] + ([("edata", "q_ij", "_q")] if self.prob is not None else [])
+
     def _blocks(self, blks, seed_nodes):
-        blocks = []
-        for blk in blks:                                   # sampling order -> input-most first
-            blk.edata["edge_weights"] = blk._edge_weights
-            if self.prob is not None:
-                blk.edata["q_ij"] = blk._q
-            blocks.insert(0, blk)
-        return blocks[0].srcdata[NID], seed_nodes, blocks
+        return _publish(blks, seed_nodes, self._fields())
 
     def sample_blocks_static(self, g, seed_nodes, slot=0, **split):
         """sample_blocks with capacity-padded blocks, only ENQUEUED (the contract of the LADIES samplers' method of this name);
@@ -142,8 +133,8 @@ class NeighborSampler(DeviceDraw, BlockSampler):
             raise NotImplementedError("the host draw reads sizes back per layer: no static-shape variant (use draw='device')")
         eng = self._bind(g)
         fan = list(reversed(self.fanouts))
-        return self._blocks(eng.enqueue_static(None, seed_nodes, fan, 0, 0.0, slot=slot, draw_state=self._draw_state_on(eng.g.device),
-                                               neighbor=True, nb_prob=self._nb_prob(eng), nb_replace=self.replace, **split), seed_nodes)
+        return self._blocks(eng.enqueue_static(None, seed_nodes, fan, 0, 0.0, slot=slot,
+                                               draw=self._draw_on(eng.g.device, self._nb_prob(eng)), **split), seed_nodes)
 
     def finish_static(self, slot=0, commit=True):
         return self._engine.finish(slot, commit)
@@ -193,7 +184,34 @@ class NeighborSampler(DeviceDraw, BlockSampler):
         return blocks[0].srcdata[NID], seed_nodes, blocks
 
 
-class BanditNeighborSampler(BanditLadiesSampler):
+class _BanditNodeWise(BanditLadiesSampler):
+    """What the two node-wise bandit samplers share: a weighted node-wise draw over the EXP3 edge probabilities, layer ``b``'s row
+    of the EXP3 weights for block ``b``."""
+
+    def _fields(self):
+        return super()._fields() + ([("edata", "p_ij", "_p")] if self._kind() == "wlabor" else [])
+
+    def _sample(self, g, seed_nodes, static, **kw):
+        g = self._graph(g)
+        eng = self._bind(g)
+        self._ensure_weights(g)
+        order = list(reversed(range(len(self.fanouts))))   # sampling order: the last block first
+        fan = [self.fanouts[b] for b in order]
+        prob = eng.neighbor_prob([self._w_pos[b] for b in order], eta=self.eta)
+        ds = self._draw_state_on(g.device)
+        if static:
+            blks = eng.enqueue_static(None, seed_nodes, fan, 0, 0.0, draw=self._draw_on(g.device, prob), **kw)
+        elif self._kind() == "wlabor":
+            blks = eng.sample_blocks_labor(seed_nodes, fan, ds, self.layer_dependency, lb_prob=prob)
+        else:
+            blks = eng.sample_blocks_neighbor(seed_nodes, fan, ds, nb_prob=prob)
+        return _publish(blks, seed_nodes, self._fields())
+
+    def sample_blocks(self, g, seed_nodes, exclude_eids=None):
+        return self._sample(g, seed_nodes, False)
+
+
+class BanditNeighborSampler(_BanditNodeWise):
     """The node-wise bandit sampler (Liu et al., "Bandit Samplers for Training GNNs", GCN-BS; BLISS is its layer-wise extension): up
     to ``fanout`` in-neighbours per destination, drawn without replacement with the EXP3 edge probabilities q_ij = eta / n_i +
     (1 - eta) * w_ij / sum_j w_ij -- the weighted draw of csrc/neighbor_w.hip in EXP3 mode, layer ``b``'s row
@@ -215,35 +233,8 @@ class BanditNeighborSampler(BanditLadiesSampler):
         self.fanouts = list(fanouts)
         self._draw_init = (seed, 0)
 
-    def _bind(self, g):
-        g = self._graph(g)
-        if self._engine is None or self._engine.g is not g:
-            self._engine = LayerEngine(g)
-            self._engine.exact_b = True                     # (a column keeps at most fanout edges, as the uniform draw)
-        return self._engine
-
-    def _sample(self, g, seed_nodes, static, **kw):
-        g = self._graph(g)
-        eng = self._bind(g)
-        self._ensure_weights(g)
-        order = list(reversed(range(len(self.fanouts))))   # sampling order: the last block first
-        fan = [self.fanouts[b] for b in order]
-        prob = eng.neighbor_prob([self._w_pos[b] for b in order], eta=self.eta)
-        ds = self._draw_state_on(g.device)
-        if static:
-            blks = eng.enqueue_static(None, seed_nodes, fan, 0, 0.0, draw_state=ds, neighbor=True, nb_prob=prob, **kw)
-        else:
-            blks = eng.sample_blocks_neighbor(seed_nodes, fan, ds, nb_prob=prob)
-        blocks = []
-        for blk in blks:
-            blk.edata[self.output_weight] = blk._edge_weights
-            blk.edata["q_ij"] = blk._q
-            blk.srcdata[self.node_prob] = blk._node_prob
-            blocks.insert(0, blk)
-        return blocks[0].srcdata[NID], seed_nodes, blocks
-
-    def sample_blocks(self, g, seed_nodes, exclude_eids=None):
-        return self._sample(g, seed_nodes, False)
+    def _kind(self):
+        return "wneighbor"                                  # (B exactly bounded: a column keeps at most fanout edges, as the uniform draw)
 
     def sample_blocks_static(self, g, seed_nodes, slot=0, **split):
         """sample_blocks with capacity-padded blocks, only ENQUEUED; whole calls only: any split / external-generator keyword
@@ -268,9 +259,6 @@ class LaborSampler(NeighborSampler):
 
     _iterations = 0                                         # (ImportanceLaborSampler: LABOR-i layers, csrc/labor_is.hip)
 
-    def _lb_prob(self, eng):
-        return None                                         # (WeightedLaborSampler: the engine's probability record)
-
     def __init__(self, fanouts, edge_dir="in", prob=None, importance_sampling=0, layer_dependency=False, batch_dependency=1, seed=0,
                  **_ignored):
         if importance_sampling != 0:
@@ -285,26 +273,22 @@ class LaborSampler(NeighborSampler):
         super().__init__(fanouts, seed=seed, draw="device")
         self.layer_dependency = bool(layer_dependency)
 
-    def _bind(self, g):
-        g = as_graph(g, self.__dict__.setdefault("_graphs", {}))
-        if self._engine is None or self._engine.g is not g:
-            self._engine = LayerEngine(g)                   # (exact_b stays False: a column's kept count is data dependent)
-        return self._engine
+    def _kind(self):
+        return "labor"                                      # (B not exactly bounded: a column's kept count is data dependent)
 
     def sample_blocks_static(self, g, seed_nodes, slot=0, **split):
         """sample_blocks with capacity-padded blocks, only ENQUEUED; whole calls only: any split / external-generator keyword
         raises.  A step over its calibrated capacities is reported by ``finish_static``."""
         eng = self._bind(g)
         fan = list(reversed(self.fanouts))
-        return self._blocks(eng.enqueue_static(None, seed_nodes, fan, 0, 0.0, slot=slot, draw_state=self._draw_state_on(eng.g.device),
-                                               labor=True, layer_dependency=self.layer_dependency,
-                                               labor_iterations=self._iterations, lb_prob=self._lb_prob(eng), **split), seed_nodes)
+        return self._blocks(eng.enqueue_static(None, seed_nodes, fan, 0, 0.0, slot=slot,
+                                               draw=self._draw_on(eng.g.device, self._nb_prob(eng), self._iterations), **split), seed_nodes)
 
     def sample_blocks(self, g, seed_nodes, exclude_eids=None):
         g = as_graph(g, self.__dict__.setdefault("_graphs", {}))
         eng = self._bind(g)
         blks = eng.sample_blocks_labor(seed_nodes, list(reversed(self.fanouts)), self._draw_state_on(g.device),
-                                       self.layer_dependency, iterations=self._iterations, lb_prob=self._lb_prob(eng))
+                                       self.layer_dependency, iterations=self._iterations, lb_prob=self._nb_prob(eng))
         return self._blocks(blks, seed_nodes)
 
 
@@ -330,10 +314,8 @@ class ImportanceLaborSampler(LaborSampler):
         super().__init__(fanouts, layer_dependency=layer_dependency, seed=seed)
         self.iterations = self._iterations = int(iterations)
 
-    def _bind(self, g):
-        eng = super()._bind(g)
-        eng.labor_is = True                                 # (also iterations = 0 runs csrc/labor_is.hip, not csrc/labor.hip)
-        return eng
+    def _kind(self):
+        return "labor_is"                                   # (also iterations = 0 runs csrc/labor_is.hip, not csrc/labor.hip)
 
 
 class WeightedLaborSampler(LaborSampler):
@@ -358,16 +340,14 @@ class WeightedLaborSampler(LaborSampler):
         super().__init__(fanouts, layer_dependency=layer_dependency, seed=seed)
         self.prob = prob
 
-    def _lb_prob(self, eng):
-        return self._nb_prob(eng)
+    def _kind(self):
+        return "wlabor"
 
-    def _blocks(self, blks, seed_nodes):
-        for blk in blks:
-            blk.edata["p_ij"] = blk._p
-        return super()._blocks(blks, seed_nodes)
+    def _fields(self):
+        return [("edata", "p_ij", "_p")] + super()._fields()
 
 
-class BanditLaborSampler(BanditLadiesSampler):
+class BanditLaborSampler(_BanditNodeWise):
     """LABOR with learned edge probabilities: ``WeightedLaborSampler``'s draw over the EXP3 edge probabilities q_ij = eta / n_i +
     (1 - eta) * w_ij / sum_j w_ij -- csrc/labor_w.hip in EXP3 mode, layer ``b``'s row of the EXP3 weights for
     block ``b``.  Unlike ``BanditNeighborSampler``'s blocks, these shrink as the probabilities concentrate: one variate per source
@@ -389,36 +369,8 @@ class BanditLaborSampler(BanditLadiesSampler):
         self.layer_dependency = bool(layer_dependency)
         self._draw_init = (seed, 0)
 
-    def _bind(self, g):
-        g = self._graph(g)
-        if self._engine is None or self._engine.g is not g:
-            self._engine = LayerEngine(g)                   # (exact_b stays False: a column's kept count is data dependent)
-        return self._engine
-
-    def _sample(self, g, seed_nodes, static, **kw):
-        g = self._graph(g)
-        eng = self._bind(g)
-        self._ensure_weights(g)
-        order = list(reversed(range(len(self.fanouts))))   # sampling order: the last block first
-        fan = [self.fanouts[b] for b in order]
-        prob = eng.neighbor_prob([self._w_pos[b] for b in order], eta=self.eta)
-        ds = self._draw_state_on(g.device)
-        if static:
-            blks = eng.enqueue_static(None, seed_nodes, fan, 0, 0.0, draw_state=ds, labor=True,
-                                      layer_dependency=self.layer_dependency, lb_prob=prob, **kw)
-        else:
-            blks = eng.sample_blocks_labor(seed_nodes, fan, ds, self.layer_dependency, lb_prob=prob)
-        blocks = []
-        for blk in blks:
-            blk.edata[self.output_weight] = blk._edge_weights
-            blk.edata["q_ij"] = blk._q
-            blk.edata["p_ij"] = blk._p
-            blk.srcdata[self.node_prob] = blk._node_prob
-            blocks.insert(0, blk)
-        return blocks[0].srcdata[NID], seed_nodes, blocks
-
-    def sample_blocks(self, g, seed_nodes, exclude_eids=None):
-        return self._sample(g, seed_nodes, False)
+    def _kind(self):
+        return "wlabor"                                     # (B not exactly bounded: a column's kept count is data dependent)
 
     def sample_blocks_static(self, g, seed_nodes, slot=0, **split):
         """sample_blocks with capacity-padded blocks, only ENQUEUED; whole calls only: any split / external-generator keyword

@@ -331,3 +331,14 @@ def full_neighbor_block(g, b0, b1):
     pos = torch.arange(e0, e1, device=col.device, dtype=torch.int32) if e1 < 2 ** 31 else None
     eid = g.eid[e0:e1] if g.eid is not None else pos
     return Block(g, src_nid.numel(), S, indptr, src, dst, pos, eid, src_nid)
+
+
+def _publish(blks, seed_nodes, fields):
+    """What every sampler returns, from the engine's blocks (sampling order): each ``(target dict, key, block attribute)`` of
+    ``fields`` published, e.g. ``blk.edata[key] = blk._q``, and the order reversed to input-most first."""
+    blocks = []
+    for blk in blks:
+        for target, key, attr in fields:
+            getattr(blk, target)[key] = getattr(blk, attr)
+        blocks.insert(0, blk)
+    return blocks[0].srcdata[NID], seed_nodes, blocks

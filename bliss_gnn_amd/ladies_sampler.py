@@ -5,9 +5,8 @@ weights ``g.edata['w']`` instead of the EXP3 state.  Kernels: include/bliss_gnn.
 import torch
 
 from . import _lib
-from ._engine import LayerEngine
 from .bandit_sampler import BlockSampler, DeviceDraw, find_indices_in, normalized_edata, union  # noqa: F401  (same helpers, ladies_sampler.py:6-22)
-from .graph import NID
+from .graph import _publish
 
 
 class LadiesSampler(DeviceDraw, BlockSampler):
@@ -48,28 +47,10 @@ class LadiesSampler(DeviceDraw, BlockSampler):
             blks = self._engine.sample_blocks_multinomial([w_pos] * len(order), seed_nodes, fan, self._mode(), 0.0, self.replace,
                                                           fp32_importance=not self.importance_sampling, draw=self.draw,
                                                           draw_state=self._draw_state_on(g.device))
-        blocks = []
-        for blk in blks:
-            blk.edata[self.output_weight] = blk._edge_weights            # :100
-            blocks.insert(0, blk)
-        return blocks[0].srcdata[NID], output_nodes, blocks              # :121,:123
-
+        return _publish(blks, output_nodes, [("edata", self.output_weight, "_edge_weights")])      # :100, :121, :123
 
     # -- static-shape variant (graph-capturable; Poisson, or the multinomial samplers' device draw): same contract as
     # PoissonBanditLadiesSampler's --------------------------------------------------------------------------------------
-    def _graph(self, g):
-        from .graph import as_graph
-        if not hasattr(self, "_graphs"):
-            self._graphs = {}
-        return as_graph(g, self._graphs)
-
-    def _bind(self, g):
-        g = self._graph(g)
-        if self._engine is None or self._engine.g is not g:
-            self._engine = LayerEngine(g)
-            self._engine.exact_k = self.draw == "device" and not self._poisson     # (a Poisson layer's K is not bounded by its fanout)
-        return self._engine
-
     def sample_blocks_static(self, g, seed_nodes, slot=0, chain_rng=False, external_rng=False, part=None, last_block=True, ready_flag=0,
                              n_live_dev=None):
         if not self._poisson and self.draw != "device":
@@ -80,14 +61,8 @@ class LadiesSampler(DeviceDraw, BlockSampler):
         order = list(reversed(range(len(self.nodes_per_layer))))
         blks = eng.enqueue_static([w_pos] * len(order), seed_nodes, [self.nodes_per_layer[b] for b in order], self._mode(), 0.0,
                                   self.eps, slot=slot, chain_rng=chain_rng, external_rng=external_rng, part=part, last_block=last_block, ready_flag=ready_flag,
-                                  draw_state=self._draw_state_on(g.device), n_live_dev=n_live_dev,
-                                  poisson=self._poisson and self.draw == "device", layer_dependency=self.layer_dependency,
-                                  replace=self.replace and self.draw == "device")
-        blocks = []
-        for blk in blks:
-            blk.edata[self.output_weight] = blk._edge_weights
-            blocks.insert(0, blk)
-        return blocks[0].srcdata[NID], seed_nodes, blocks
+                                  n_live_dev=n_live_dev, draw=self._draw_on(g.device))
+        return _publish(blks, seed_nodes, [("edata", self.output_weight, "_edge_weights")])
 
     def finish_static(self, slot=0, commit=True):
         return self._engine.finish(slot, commit)

@@ -282,7 +282,8 @@ class _HipShardOps:
         """generate_block (bandit_sampler.py:269-339) for this rank's seeds over the global kept list."""
         eng, dev, st = self.eng, self.g.device, self._layer[n]
         seeds, S, K = st["seeds"], int(st["seeds"].numel()), int(kept_nid_g.numel())
-        b_indptr, b_src, b_dst, b_pos, b_eid, b_w, b_q, kept_nid, node_prob, cdev, t_indptr, t_edge = st["lay"]
+        lay = st["lay"]
+        kept_nid, node_prob, cdev = lay.kept_nid, lay.node_prob, lay.counts
         if S == 0:
             z = torch.zeros(0, dtype=torch.int32, device=dev)
             blk = ShardBlock(self.g, K, 0, torch.zeros(1, dtype=torch.int32, device=dev), z, z, z, z, kept_nid_g, seed_pos)
@@ -306,11 +307,11 @@ class _HipShardOps:
         B, err = int(raw[4]), int(raw[5])
         if err:
             raise RuntimeError(f"sharded block build error 0x{err:x}: {_lib.err_string(err)}")
-        blk = ShardBlock(self.g, K, S, b_indptr[:S + 1], b_src[:B], b_dst[:B], b_pos[:B], b_eid[:B], kept_nid[:K].clone(), seed_pos)
-        blk._edge_weights, blk._q, blk._node_prob = b_w[:B], b_q[:B], node_prob[:K].clone()
+        blk = ShardBlock(self.g, K, S, lay.indptr[:S + 1], lay.src[:B], lay.dst[:B], lay.pos[:B], lay.eid[:B], kept_nid[:K].clone(), seed_pos)
+        blk._edge_weights, blk._q, blk._node_prob = lay.w[:B], lay.q[:B], node_prob[:K].clone()
         blk._counts_dev, blk._layer = cdev, st["layer"]
-        if t_indptr is not None:
-            blk._transposed = (t_indptr[:K + 1], t_edge[:max(B, 1)])
+        if lay.t_indptr is not None:
+            blk._transposed = (lay.t_indptr[:K + 1], lay.t_edge[:max(B, 1)])
         return blk
 
     def exp3_update(self, blk, embed_norm, delta_f):

@@ -236,22 +236,21 @@ class DenseShardedSampler:
                 chk(lib.bliss_build_block(C.byref(eng.c_graph), C.byref(eng._set(n)["c_maps"]), w_pos.data_ptr(), seeds_l.data_ptr(), cs, ops.mode,
                                           eta_f, ome_f, eng.Eg, C.byref(c_ws), C.byref(c_out), st), "bliss_build_block")
                 c_ws.block_ready_flag = keep_flag
-            b_indptr, b_src, b_dst, b_pos, b_eid, b_w, b_q, kept, node_prob, cdev, t_indptr, t_edge = lay
             if not select:                                         # (the block objects exist: made by the call that deferred them)
-                cur, n_seeds, n_seeds_dev = kept, -1, cnt_ptr + 12
+                cur, n_seeds, n_seeds_dev = kept_nid, -1, cnt_ptr + 12
                 continue
             # (the destinations' ids = this rank's seeds: bliss_shard_local_seeds wrote them, padded with the list's first entry, into
             # a persistent per-slot buffer -- block objects of one slot are interchangeable between graphs)
-            blk = ShardBlock(g, cap["K"], cs, b_indptr, b_src, b_dst, b_pos, b_eid, kept, seed_pos, dst_nid=seeds_l)
-            blk._edge_weights, blk._q, blk._node_prob = b_w, b_q, node_prob
-            blk._counts, blk._counts_dev, blk._layer = None, cdev, layer
+            blk = ShardBlock(g, cap["K"], cs, lay.indptr, lay.src, lay.dst, lay.pos, lay.eid, kept_nid, seed_pos, dst_nid=seeds_l)
+            blk._edge_weights, blk._q, blk._node_prob = lay.w, lay.q, lay.node_prob
+            blk._counts, blk._counts_dev, blk._layer = None, lay.counts, layer
             blk._nnz_ptr = sb["counts"].data_ptr() + 40 * n + 16
             blk._xcap = int(cap["B"])
-            if t_indptr is not None:
-                blk._transposed = (t_indptr, t_edge)
-            blk.edata["edge_weights"], blk.edata["q_ij"], blk.srcdata["node_prob"] = b_w, b_q, node_prob
+            if lay.t_indptr is not None:
+                blk._transposed = (lay.t_indptr, lay.t_edge)
+            blk.edata["edge_weights"], blk.edata["q_ij"], blk.srcdata["node_prob"] = lay.w, lay.q, lay.node_prob
             blocks.insert(0, blk)
-            cur, n_seeds, n_seeds_dev = kept, -1, cnt_ptr + 12
+            cur, n_seeds, n_seeds_dev = kept_nid, -1, cnt_ptr + 12
         if not select:
             return None
         self._static_blocks = blocks                             # (the step number went up by one in the last layer's select_kept)
