@@ -131,6 +131,15 @@ class GatGlue(C.Structure):                            # bliss_gat_glue_t
                 ("dout", C.c_void_p), ("dout_stride", C.c_int64), ("din", C.c_void_p), ("din_stride", C.c_int64)]
 
 
+class GcnEpilogue(C.Structure):                        # bliss_gcn_epilogue_t
+    _fields_ = [("a", C.c_void_p), ("a_stride", C.c_int64), ("bias", C.c_void_p),
+                ("n_rows", C.c_int32), ("rows_dev", C.c_void_p), ("width", C.c_int32), ("relu", C.c_int32),
+                ("drop_p", C.c_float), ("drop_seed", C.c_uint32), ("drop_ctr", C.c_void_p), ("drop_ctr_used", C.c_void_p),
+                ("out", C.c_void_p), ("out_stride", C.c_int64), ("norm_out", C.c_void_p),
+                ("dout", C.c_void_p), ("dout_stride", C.c_int64), ("din", C.c_void_p), ("din_stride", C.c_int64),
+                ("db", C.c_void_p), ("db_partials", C.c_void_p)]
+
+
 ADAM_MAX_TENSORS = 32
 F1_MAX_WORKGROUPS, F1_ROWS_PER_WORKGROUP, F1_PAIRS_PER_WORKGROUP = 1024, 4, 256    # BLISS_F1_MAX_WORKGROUPS; csrc/metrics.hip
 
@@ -279,6 +288,12 @@ SIGNATURES = {
     "bliss_gat_glue_fwd": [C.POINTER(GatGlue), _P],
     "bliss_gat_glue_bwd": [C.POINTER(GatGlue), _P],
     "bliss_gat_head_mean": [_P, _I32, _I32, _P, _P, _P],
+    "bliss_gcn_norms": [_P, _I32, _P, _I32, _P, _P, _P],
+    "bliss_gcn_spmm_fwd": [_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _P, _I32, _I32, _P, _I64, _P, _P],
+    "bliss_gcn_spmm_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _P, _I32, _I32, _P, _I64, _P, _P],
+    "bliss_gcn_db_chunk_rows": [],
+    "bliss_gcn_epilogue_fwd": [C.POINTER(GcnEpilogue), _P],
+    "bliss_gcn_epilogue_bwd": [C.POINTER(GcnEpilogue), _P],
     "bliss_shard_local_seeds": [_P, _I32, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P],
     "bliss_shard_scatter_partials": [_P, _P, _P, _P, _P, _P, _P, _I32, _P, _P],
     "bliss_shard_zero_dense": [_P, _I32, _P],

@@ -221,22 +221,58 @@ class GCN(nn.Module):
     weights.  (Unreachable from the reference's CLI -- ``--model gcn`` trains SAGE, train_lightning.py:597-607 -- kept
     for API completeness.)"""
 
-    def __init__(self, in_feats, n_hidden, n_classes, n_layers, activation, dropout):
+    def __init__(self, in_feats, n_hidden, n_classes, n_layers, activation, dropout, transforms="library"):
         super().__init__()
-        from .nn import GraphConv
+        from .nn import GCN_TRANSFORMS, GraphConv
+        if transforms not in GCN_TRANSFORMS:
+            raise ValueError("transforms must be one of %r, not %r" % (GCN_TRANSFORMS, transforms))
+        # "tile" (DESIGN.md section 26): the layers on the bounded kernels of csrc/gcn.hip and the MFMA entry points, the model's
+        # dropout inside each layer's epilogue launch -- the path that runs under a batch capacity; "library": the launches and
+        # bits of before
+        self.transforms = transforms
         self.n_layers, self.n_hidden, self.n_classes = n_layers, n_hidden, n_classes
+        mk = lambda i, o, act: GraphConv(i, o, activation=act, allow_zero_in_degree=True, transforms=transforms)
         self.layers = nn.ModuleList()
         if n_layers > 1:
-            self.layers.append(GraphConv(in_feats, n_hidden, activation=activation, allow_zero_in_degree=True))
+            self.layers.append(mk(in_feats, n_hidden, activation))
             for _ in range(1, n_layers - 1):
-                self.layers.append(GraphConv(n_hidden, n_hidden, activation=activation, allow_zero_in_degree=True))
-            self.layers.append(GraphConv(n_hidden, n_classes, allow_zero_in_degree=True))
+                self.layers.append(mk(n_hidden, n_hidden, activation))
+            self.layers.append(mk(n_hidden, n_classes, None))
         else:
-            self.layers.append(GraphConv(in_feats, n_classes, allow_zero_in_degree=True))
+            self.layers.append(mk(in_feats, n_classes, None))
+        for l, layer in enumerate(self.layers):                    # the dropout stream of layer l (nn.GraphConv._drop_state)
+            layer._drop_salt = l + 1
         self.dropout = nn.Dropout(dropout)
         self.activation = activation
 
+    def tile_refusal(self):
+        """Why this model cannot take the tile path (a layer outside its limits), or None."""
+        for l, layer in enumerate(self.layers):
+            why = layer.tile_refusal("GCN layer %d" % l)
+            if why is not None:
+                return why
+        return None
+
+    def _forward_tile(self, blocks, x):
+        """``forward`` on the bounded kernels: per layer the norms, the degree-normalised SpMM, one MFMA product and ONE epilogue
+        launch that carries the bias, the layer's ReLU, the model's dropout (:437-438) and the next block's embed_norm."""
+        if len(blocks) != len(self.layers):
+            raise ValueError("%d blocks for %d layers" % (len(blocks), len(self.layers)))
+        n = len(self.layers)
+        h, norm = x, _gathered_norm(blocks, x)
+        for l, (layer, block) in enumerate(zip(self.layers, blocks)):
+            last = l == n - 1
+            if norm is None:
+                norm = embed_norm(h)
+            block.srcdata["embed_norm"] = norm                                                    # model.py:425-427
+            p = float(self.dropout.p) if (self.training and not last) else 0.0
+            h, norm = layer.tile_forward(block, h, block.edata["edge_weights"] if "edge_weights" in block.edata else None, p=p,
+                                         want_norm=not last, what="GCN layer %d" % l)
+        return h
+
     def forward(self, blocks, x):
+        if self.transforms == "tile":
+            return self._forward_tile(blocks, x)
         h, norm = x, _gathered_norm(blocks, x)
         for l, (layer, block) in enumerate(zip(self.layers, blocks)):
             block.srcdata["embed_norm"] = embed_norm(h) if (l > 0 or norm is None) else norm      # model.py:425-427

@@ -755,24 +755,206 @@ class SAGEConv(nn.Module):
         return rst
 
 
+# transforms="tile" (DESIGN.md section 26): GraphConv(norm='both') on bounded kernels -- the degree-normalised SpMM of csrc/gcn.hip,
+# the dense products on the MFMA entry points with the operand roles swapped (weight stays [in, out]) and one row-wise epilogue
+# launch per direction; every loop that crosses rows or edges is bounded by the block's device-side counts.
+GCN_TRANSFORMS = ("library", "tile")
+
+
+def _is_relu(act):
+    return act in (torch.relu, torch.nn.functional.relu) or isinstance(act, nn.ReLU)
+
+
+def _gcn_spmm(backward, idx, w, ns, nd, h, n_rows, nnz_dev):
+    """bliss_gcn_spmm_fwd (out [n_dst, dim] from h [n_src, dim]) or _bwd (gh [n_src, dim] from gout [n_dst, dim]) over
+    ``idx`` = (indptr, src, dst, t_indptr, t_edge)."""
+    indptr, src, dst, t_indptr, t_edge = idx
+    B, D = int(src.numel()), h.shape[1]
+    out = torch.empty(n_rows, D, dtype=torch.bfloat16, device=h.device)
+    ec = _lib.lib.bliss_spmm_chunk_edges(B)
+    part = torch.empty(max(2 * ((B + ec - 1) // ec) * D, 4), dtype=torch.float32, device=h.device)
+    wp = 0 if w is None else w.data_ptr()
+    if backward:
+        _lib.check(_lib.lib.bliss_gcn_spmm_bwd(t_indptr.data_ptr(), t_edge.data_ptr(), src.data_ptr(), dst.data_ptr(), wp, ns.data_ptr(),
+                                               nd.data_ptr(), h.data_ptr(), h.stride(0), n_rows, nnz_dev, B, D, out.data_ptr(), out.stride(0),
+                                               part.data_ptr(), _stream()), "bliss_gcn_spmm_bwd")
+    else:
+        _lib.check(_lib.lib.bliss_gcn_spmm_fwd(indptr.data_ptr(), src.data_ptr(), dst.data_ptr(), wp, ns.data_ptr(), nd.data_ptr(),
+                                               h.data_ptr(), h.stride(0), n_rows, nnz_dev, B, D, out.data_ptr(), out.stride(0),
+                                               part.data_ptr(), _stream()), "bliss_gcn_spmm_fwd")
+    return out
+
+
+def _gcn_xwt(d, w, m_bound, m_dev):
+    """d[m, out] . W^T -> [m, in] for W = [in, out]: bliss_tile_gemm reads W as an nn.Linear weight [n = in, k = out]; output-column
+    blocks of at most 256, two per launch; zero rows at or past the count."""
+    out = torch.empty(m_bound, w.shape[0], dtype=torch.bfloat16, device=d.device)
+    sets = [_tg_args(d, w[c0:c1], out[:, c0:c1], m_bound, m_dev=m_dev) for c0, c1 in _col_blocks(w.shape[0])]
+    for i in range(0, len(sets), 2):
+        _tile_gemm(sets[i], sets[i + 1] if i + 1 < len(sets) else None)
+    return out
+
+
+def _gcn_epilogue_args(n_rows, rows_dev, width, relu, p, state, ctr_used):
+    t = _lib.GcnEpilogue()
+    t.n_rows, t.rows_dev, t.width, t.relu = int(n_rows), int(rows_dev), int(width), int(bool(relu))
+    if p > 0:
+        t.drop_p, t.drop_seed, t.drop_ctr, t.drop_ctr_used = float(p), int(state["seed"]) & 0xFFFFFFFF, state["ctr"].data_ptr(), ctr_used.data_ptr()
+    return t
+
+
+class _GcnLayer(torch.autograd.Function):
+    """One GraphConv(norm='both') layer on the bounded kernels: the norms (bliss_gcn_norms), the product with ``weight`` [in, out]
+    before (in > out) or behind the degree-normalised SpMM (bliss_gat_dgrad: A[m, k] . W[k, n]) and the epilogue (bias, ReLU,
+    keyed dropout, the row norms of the stored rows).  Backward: the epilogue's mirror with the bias gradient, the transposed
+    SpMM, dX on bliss_tile_gemm, dW = X^T dY on bliss_sage_wgrad -- all bound by the block's device-side counts."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, idx, ew, n_src, n_dst, words, relu, p, state, want_norm):
+        import ctypes as C
+        ctx.set_materialize_grads(False)
+        x, w = _bf16c(x), _bf16c(weight)
+        dev = x.device
+        dst_dev, src_dev, nnz_dev = words
+        indptr, t_indptr = idx[0], idx[3]
+        ns = torch.empty(n_src, dtype=torch.float32, device=dev)
+        nd = torch.empty(n_dst, dtype=torch.float32, device=dev)
+        _lib.check(_lib.lib.bliss_gcn_norms(indptr.data_ptr(), n_dst, t_indptr.data_ptr(), n_src, nd.data_ptr(), ns.data_ptr(), _stream()),
+                   "bliss_gcn_norms")
+        w_first = w.shape[0] > w.shape[1]
+        if w_first:
+            kept = x
+            a = _gcn_spmm(False, idx, ew, ns, nd, gat_dgrad(x, w, n_src, src_dev), n_dst, nnz_dev)
+        else:
+            kept = _gcn_spmm(False, idx, ew, ns, nd, x, n_dst, nnz_dev)
+            a = gat_dgrad(kept, w, n_dst, dst_dev)
+        width = w.shape[1]
+        out = torch.empty(n_dst, width, dtype=torch.bfloat16, device=dev)
+        norm = torch.empty(n_dst, dtype=torch.bfloat16, device=dev) if want_norm else None
+        ctr_used = torch.empty(1, dtype=torch.int32, device=dev) if p > 0 else None
+        t = _gcn_epilogue_args(n_dst, dst_dev, width, relu, p, state, ctr_used)
+        t.a, t.a_stride, t.bias = a.data_ptr(), a.stride(0), 0 if bias is None else bias.data_ptr()
+        t.out, t.out_stride, t.norm_out = out.data_ptr(), out.stride(0), 0 if norm is None else norm.data_ptr()
+        _lib.check(_lib.lib.bliss_gcn_epilogue_fwd(C.byref(t), _stream()), "bliss_gcn_epilogue_fwd")
+        ctx.save_for_backward(kept, w, out if relu else None, ew, ns, nd, ctr_used, *idx)
+        ctx.cfg = (w_first, n_src, n_dst, words, bool(relu), float(p), state, bias is not None, x.shape[0])
+        if norm is not None:
+            ctx.mark_non_differentiable(norm)
+        return out, norm
+
+    @staticmethod
+    def backward(ctx, dout, _dnorm):
+        import ctypes as C
+        kept, w, out, ew, ns, nd, ctr_used = ctx.saved_tensors[:7]
+        idx = tuple(ctx.saved_tensors[7:])
+        w_first, n_src, n_dst, words, relu, p, state, has_bias, x_rows = ctx.cfg
+        if dout is None:
+            return (None,) * 12
+        dst_dev, src_dev, nnz_dev = words
+        dout = _bf16c(dout)
+        dev, width = dout.device, w.shape[1]
+        g = torch.empty(n_dst, width, dtype=torch.bfloat16, device=dev)
+        db = torch.empty(width, dtype=torch.bfloat16, device=dev) if has_bias else None
+        t = _gcn_epilogue_args(n_dst, dst_dev, width, relu, p, state, ctr_used)
+        t.dout, t.dout_stride, t.din, t.din_stride = dout.data_ptr(), dout.stride(0), g.data_ptr(), g.stride(0)
+        if relu:
+            t.out, t.out_stride = out.data_ptr(), out.stride(0)
+        if has_bias:
+            rows = int(_lib.lib.bliss_gcn_db_chunk_rows())
+            part = torch.empty(max(((n_dst + rows - 1) // rows) * width, 4), dtype=torch.float32, device=dev)
+            t.db, t.db_partials = db.data_ptr(), part.data_ptr()
+        _lib.check(_lib.lib.bliss_gcn_epilogue_bwd(C.byref(t), _stream()), "bliss_gcn_epilogue_bwd")
+        dx = None
+        if w_first:
+            dz = _gcn_spmm(True, idx, ew, ns, nd, g, n_src, nnz_dev)                       # [n_src, out]
+            dw = _wgrad_blocks([(kept, dz, n_src, src_dev, False)])[0][0]
+            if ctx.needs_input_grad[0]:
+                dx = _gcn_xwt(dz, w, n_src, src_dev)
+        else:
+            dw = _wgrad_blocks([(kept, g, n_dst, dst_dev, False)])[0][0]
+            if ctx.needs_input_grad[0]:
+                dx = _gcn_spmm(True, idx, ew, ns, nd, _gcn_xwt(g, w, n_dst, dst_dev), n_src, nnz_dev)
+        if dx is not None and x_rows > n_src:
+            dx = torch.cat([dx, _zero_rows(x_rows - n_src, dx)])
+        return (dx, dw, db) + (None,) * 9
+
+
 class GraphConv(nn.Module):
     """dglnn.GraphConv(in, out, norm='both', weight=True, bias=True) as built at model.py:397-417.
 
     [DGL-recalled] forward(graph, feat, edge_weight): feat_src * out_deg^-1/2 (degrees clamped to >= 1); weight first
     iff in > out; aggregate = update_all(u_mul_e('h','_edge_weight'), sum); then weight; * in_deg^-1/2; + bias;
-    activation.  Degrees are the block's structural degrees (edge weights do not enter the normalisation)."""
+    activation.  Degrees are the block's structural degrees (edge weights do not enter the normalisation).
 
-    def __init__(self, in_feats, out_feats, norm="both", weight=True, bias=True, activation=None, allow_zero_in_degree=False):
+    ``transforms="tile"`` runs the layer on the bounded kernels of csrc/gcn.hip and the MFMA entry
+    points -- the path that runs under a batch capacity; ``"library"`` (the default) is the torch-op path with the launches and
+    bits of before."""
+
+    def __init__(self, in_feats, out_feats, norm="both", weight=True, bias=True, activation=None, allow_zero_in_degree=False,
+                 transforms="library"):
         super().__init__()
         if norm != "both" or not weight:
             raise NotImplementedError("the reference only builds GraphConv(norm='both', weight=True)")
+        if transforms not in GCN_TRANSFORMS:
+            raise ValueError("transforms must be one of %r, not %r" % (GCN_TRANSFORMS, transforms))
+        self.transforms = transforms
         self._in_feats, self._out_feats, self._activation = in_feats, out_feats, activation
         self._allow_zero_in_degree = allow_zero_in_degree
         self.weight = nn.Parameter(torch.empty(in_feats, out_feats))
         self.bias = nn.Parameter(torch.zeros(out_feats)) if bias else None
         nn.init.xavier_uniform_(self.weight)
 
+    # -- transforms="tile" (DESIGN.md section 26) -------------------------------------------------------------------------
+    def _drop_state(self, device):
+        st = getattr(self, "_dstate", None)
+        if st is None or st["ctr"].device != device:
+            st = self._dstate = gat_drop_state(getattr(self, "_drop_salt", 0), device)
+        return st
+
+    def tile_refusal(self, what="GraphConv"):
+        """Why this layer cannot take the tile path, or None: the limits that do not depend on the input tensor."""
+        for name, n in (("in_feats", self._in_feats), ("out_feats", self._out_feats)):
+            if n > TILE_GEMM_MAX_K:
+                return ('%s: transforms="tile" takes %s <= %d (the MFMA kernels keep a row tile\'s k columns in LDS), this layer has '
+                        '%d; build it with transforms="library"' % (what, name, TILE_GEMM_MAX_K, n))
+        if not (self._activation is None or _is_relu(self._activation)):
+            return '%s: transforms="tile" covers the activations ReLU and None, not %r' % (what, self._activation)
+        if not _mfma_bwd_on():
+            return "%s: transforms=\"tile\" needs the MFMA backward (BLISS_SAGE_MFMA_BWD=0 is set)" % what
+        ps = [self.weight] + ([self.bias] if self.bias is not None else [])
+        if not all(q.is_cuda and q.dtype == torch.bfloat16 for q in ps):
+            return '%s: transforms="tile" takes bf16 parameters on the GPU' % what
+        return None
+
+    def tile_forward(self, graph, feat, edge_weight=None, p=0.0, want_norm=False, what="GraphConv"):
+        """The layer on the bounded kernels -> (out [n_dst, out_feats], its bf16 row norms or None).  ``p`` > 0: the keyed dropout
+        of the model behind the layer's activation (the stream of this layer, ``_drop_state``).  Rows at or past the block's
+        live destination count come out as zeros."""
+        why = self.tile_refusal(what)
+        if why is None and not (torch.is_tensor(feat) and feat.is_cuda and feat.dtype == torch.bfloat16 and feat.dim() == 2):
+            why = '%s: transforms="tile" takes bf16 features [rows, in_feats] on the GPU' % what
+        if why is not None:
+            raise NotImplementedError(why)
+        K, S = graph.num_src_nodes(), graph.num_dst_nodes()
+        if feat.shape[0] < K or feat.shape[1] != self._in_feats:
+            raise ValueError("%s: %d x %d input rows for a block of %d sources and in_feats %d" % (what, feat.shape[0], feat.shape[1], K, self._in_feats))
+        _wait_block(graph)
+        ew = None
+        if edge_weight is not None:
+            ew = _bf16c(edge_weight.detach().reshape(-1))
+            if ew.numel() != graph.num_edges():
+                raise ValueError("%s: %d edge weights for %d edges" % (what, ew.numel(), graph.num_edges()))
+        t_indptr, t_edge = graph.transposed()                   # the norms need the by-source index, also in evaluation
+        p = float(p)
+        return _GcnLayer.apply(feat, self.weight, self.bias, (graph.indptr, graph.src, graph.dst, t_indptr, t_edge), ew, K, S,
+                               _block_words(graph), self._activation is not None, p, self._drop_state(feat.device) if p > 0 else None,
+                               bool(want_norm))
+
     def forward(self, graph, feat, weight=None, edge_weight=None):
+        if self.transforms == "tile":
+            if weight is not None:
+                raise NotImplementedError('GraphConv: transforms="tile" multiplies by the layer\'s own weight')
+            return self.tile_forward(graph, feat, edge_weight)[0]
         n_dst = graph.num_dst_nodes()
         src, ones = graph.src, None
         if getattr(graph, "_nnz_ptr", 0) and getattr(graph, "_counts_dev", None) is not None:

@@ -128,8 +128,13 @@ def _live_refusal(model):
     """Why ``model`` cannot run on a capacity-padded OUTPUT block, or None if it can.  Rows past the live
     count hold whatever the buffers held: only a path whose every row loop is bounded by the block's device-side counts keeps
     them out of the weight gradients (0 * NaN is NaN)."""
-    from .model import GATv2, SAGE
+    from .model import GATv2, GCN, SAGE
     from .nn import _mfma_bwd_on
+    if isinstance(model, GCN):
+        if model.transforms != "tile":
+            return ('GCN runs live on its bounded kernels only: with transforms="library" its layers run over all capacity rows of '
+                    'the output block; build it with GCN(..., transforms="tile") (DESIGN.md section 26)')
+        return model.tile_refusal()
     if isinstance(model, GATv2):
         if model.transforms != "tile":
             return ('GATv2 runs live on its bounded kernels only: with transforms="library" its layers run over all capacity rows of '
@@ -139,8 +144,8 @@ def _live_refusal(model):
             return 'GATv2(transforms="tile") takes bf16 parameters on the GPU'
         return model.tile_refusal()
     if not isinstance(model, SAGE):
-        return ("%s has no live path: its layers run over all capacity rows of the output block (only SAGE on its MFMA path and "
-                'GATv2(transforms="tile") bound every row loop by the block\'s device-side counts)' % type(model).__name__)
+        return ("%s has no live path: its layers run over all capacity rows of the output block (only SAGE on its MFMA path, "
+                'GATv2(transforms="tile") and GCN(transforms="tile") bound every row loop by the block\'s device-side counts)' % type(model).__name__)
     ps = list(model.parameters())
     if not ps or not model._mfma_ok(ps[0]) or not _mfma_bwd_on():
         return ("SAGE runs live on its MFMA path only (bf16 on the GPU, ReLU, layers within the tile kernel's limits, "

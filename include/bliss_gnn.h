@@ -1043,6 +1043,51 @@ int bliss_gat_glue_fwd(const bliss_gat_glue_t* args, void* stream);
 int bliss_gat_glue_bwd(const bliss_gat_glue_t* args, void* stream);
 int bliss_gat_head_mean(const void* x, int32_t heads, int32_t n_edges, const int32_t* n_edges_dev, void* out, void* stream);
 
+/* dglnn.GraphConv(norm='both') message passing with sampler edge weights on bounded kernels (csrc/gcn.hip, DESIGN.md section 26;
+ * model.py:386-439):
+ *   ns[j] = 1 / sqrt(max(outdeg_j, 1)),  outdeg_j = t_indptr[j+1] - t_indptr[j]  (the block's by-source index)
+ *   nd[i] = 1 / sqrt(max(indeg_i, 1)),   indeg_i  = indptr[i+1] - indptr[i]
+ *   fwd:  out[i, :] = bf16( nd[i] * sum_{e in row i}    (float(w_e) * ns[src_e]) * h[src_e, :] )
+ *   bwd:  gh[j, :]  = bf16( ns[j] * sum_{e : src_e = j} (float(w_e) * nd[dst_e]) * gout[dst_e, :] )
+ * ns, nd fp32 (IEEE sqrt, one division); the coefficient is one fp32 product; fp32 accumulation in edge order inside a work
+ * chunk, chunk partials added in chunk order; one rounding to bf16 at the store.  w bf16 [nnz] or NULL (= 1).
+ * bliss_gcn_norms: one launch, ns[n_src] and nd[n_dst]; rows past the live counts are empty in both index arrays (norm 1).
+ * bliss_gcn_spmm_fwd / _bwd: arguments as bliss_spmm_fwd / bliss_spmm_bwd plus the two norm vectors; nnz_dev (optional): the
+ * live edge count, nothing at or past it is read; partials: fp32 scratch [2 * ceil(nnz / EC) * dim], EC =
+ * bliss_spmm_chunk_edges(nnz).  Rows without edges (capacity padding included) are written as zeros. */
+int bliss_gcn_norms(const int32_t* indptr, int32_t n_dst, const int32_t* t_indptr, int32_t n_src, float* nd, float* ns, void* stream);
+int bliss_gcn_spmm_fwd(const int32_t* indptr, const int32_t* src, const int32_t* dst, const void* w, const float* ns, const float* nd,
+                       const void* h, int64_t h_stride, int32_t n_dst, const int32_t* nnz_dev, int32_t nnz, int32_t dim, void* out,
+                       int64_t out_stride, float* partials, void* stream);
+int bliss_gcn_spmm_bwd(const int32_t* t_indptr, const int32_t* t_edge, const int32_t* src, const int32_t* dst, const void* w,
+                       const float* ns, const float* nd, const void* gout, int64_t gout_stride, int32_t n_src, const int32_t* nnz_dev,
+                       int32_t nnz, int32_t dim, void* gh, int64_t gh_stride, float* partials, void* stream);
+
+/* The row-wise tail of a GraphConv layer, bounded by a device-side row count.  For r < min(n_rows, *rows_dev) (rows_dev NULL:
+ * n_rows):  x = bf16(a[r, c] + bias[c]) (bias NULL: a[r, c]);  relu != 0: max(x, 0);  drop_p > 0:  keep ? bf16(x / (1 - p)) : 0
+ * with keep from the keyed hash of (drop_seed, launch counter, r * width + c) -- the stream of bliss_gat_glue_fwd: drop_ctr is a
+ * device uint64[2], zero-initialised once and bumped behind every launch with drop_p > 0; drop_ctr_used (device uint32) receives
+ * the counter the launch used.  norm_out (optional, bf16 [n_rows]): the row norms of the stored rows in bliss_embed_norm's
+ * summation order.  Rows at or past the count are written as zeros (norm 0) and nothing of their inputs is read.
+ * _bwd: din[r, c] = dout[r, c] masked and scaled as the forward did, then zero where the stored out[r, c] <= 0 (relu != 0);
+ * zero rows at or past the count;  db (optional, bf16 [width]) = sum_{r < live} din[r, c]: fp32 sums over chunks of
+ * bliss_gcn_db_chunk_rows() rows (a size that does not depend on n_rows) in db_partials (fp32 [ceil(n_rows / chunk) * width]),
+ * added in chunk order and rounded once. */
+typedef struct {
+  const void* a; int64_t a_stride;
+  const void* bias;
+  int32_t n_rows; const int32_t* rows_dev; int32_t width; int32_t relu;
+  float drop_p; uint32_t drop_seed; uint64_t* drop_ctr; uint32_t* drop_ctr_used;
+  void* out; int64_t out_stride;
+  void* norm_out;
+  const void* dout; int64_t dout_stride;
+  void* din; int64_t din_stride;
+  void* db; float* db_partials;
+} bliss_gcn_epilogue_t;
+int bliss_gcn_db_chunk_rows(void);
+int bliss_gcn_epilogue_fwd(const bliss_gcn_epilogue_t* args, void* stream);
+int bliss_gcn_epilogue_bwd(const bliss_gcn_epilogue_t* args, void* stream);
+
 /* Per-kernel timing with HIP events recorded on the launching stream (bench.py's roofline object).
  * bliss_prof_enable(id): -2 off (default), -1 every kernel, >= 0 one kernel id; names via
  * bliss_prof_kernel_name(id), id < bliss_prof_kernel_count().  bliss_prof_read synchronises on the
