@@ -281,16 +281,108 @@ class GCN(nn.Module):
                 h = self.dropout(h)                                           # model.py:437-438
         return h
 
+    INFERENCE_PATHS = ("auto", "blocks", "csc")
+    # "csc": a destination range closes at the first batch boundary at or after a multiple of this many edges.  The by-source sort
+    # of a range costs about 24 bytes of scratch per edge (t_edge, three key / value arrays, rocPRIM's pair of buffers): 200 MB at 2^23
+    csc_max_edges = 1 << 23
+    # the SpMM keeps no scratch, and a launch lasts at least as long as its longest row: one launch takes consecutive ranges as long
+    # as they hold at most this many edges together (32-bit offsets inside a launch)
+    csc_spmm_edges = 2 ** 31 - 1
+    last_inference_path = None      # the path the last ``inference`` call took
+
+    def csc_refusal(self, g, h, batch_size=128):
+        """Why ``inference(path="csc")`` cannot run on this graph, these features and this batch size, or None."""
+        if int(batch_size) < 1:
+            return "GCN.inference: the CSC path takes batch_size >= 1, not %d" % int(batch_size)
+        if not (g.device.type == "cuda" and h.is_cuda):
+            return "GCN.inference: the CSC path runs on the GPU (graph on %s, features on %s)" % (g.device, h.device)
+        for l, layer in enumerate(self.layers):
+            why = layer.infer_refusal(h, "GCN layer %d" % l)
+            if why is not None:
+                return why
+        return None
+
+    def _csc_ranges(self, g, batch_size):
+        """Destination ranges of the CSC path: [(row0, row1, edge0, edges)], contiguous, whole batches, at least one batch each.
+        Cut k is the first batch boundary whose edge offset is at or past k * csc_max_edges, so a range holds fewer than
+        csc_max_edges edges plus one batch's -- cut on the device, read by the host ONCE per call."""
+        V, E, bs = g.num_nodes(), g.num_edges(), int(batch_size)
+        bounds = torch.cat([torch.arange(0, V, bs, device=g.device, dtype=torch.int64), torch.tensor([V], device=g.device, dtype=torch.int64)])
+        off = g.indptr[bounds]                                                                    # E0_b of every batch, then E
+        cuts = [bounds[:1], bounds[-1:]]
+        if E > self.csc_max_edges:
+            targets = off[0] + torch.arange(1, E // int(self.csc_max_edges) + 1, device=g.device, dtype=torch.int64) * int(self.csc_max_edges)
+            cuts.append(bounds[torch.searchsorted(off, targets).clamp_(max=bounds.numel() - 1)])  # the first boundary at or past a target
+        cuts = torch.unique(torch.cat(cuts))                                                      # (sorted)
+        both = torch.stack([cuts, g.indptr[cuts]]).tolist()                                       # the call's one host read
+        ranges = [(r0, r1, e0, e1 - e0) for r0, r1, e0, e1 in zip(both[0][:-1], both[0][1:], both[1][:-1], both[1][1:])]
+        if any(r[3] >= 2 ** 31 for r in ranges):
+            raise NotImplementedError("GCN.inference: a range of 2^31 or more edges is beyond the CSC path (lower batch_size)")
+        return ranges
+
+    def _csc_groups(self, ranges):
+        """The SpMM's launches: consecutive ranges joined while they hold at most csc_spmm_edges edges together."""
+        groups = []
+        for r0, r1, e0, edges in ranges:
+            if groups and groups[-1][3] + edges <= int(self.csc_spmm_edges):
+                p0, _, pe0, pedges = groups[-1]
+                groups[-1] = (p0, r1, pe0, pedges + edges)
+            else:
+                groups.append((r0, r1, e0, edges))
+        return groups
+
+    def _inference_csc(self, g, h, batch_size):
+        """The per-edge source norms of the batch structure ONCE per call (they do not depend on the layer; [E] fp32 kept for the
+        call; one by-source sort per destination range), then per layer: a weight-first product once over all rows, one SpMM
+        launch per group of ranges off the graph's own indptr / indices, an aggregate-first product and the epilogue once over
+        all rows."""
+        from .nn import gcn_infer_src_norms, gcn_infer_state
+        ranges = self._csc_ranges(g, batch_size)
+        V, state = g.num_nodes(), gcn_infer_state()
+        ns = torch.empty(max(g.num_edges(), 1), dtype=torch.float32, device=h.device)
+        for r0, r1, e0, edges in ranges:
+            gcn_infer_src_norms(g.indptr, g.indices, batch_size, r0, r1, e0, edges, ns[e0:e0 + edges], state)
+        del state
+        groups = self._csc_groups(ranges)
+        for layer in self.layers:
+            table = layer.infer_transform(h)
+            agg = torch.empty(V, table.shape[1], dtype=torch.bfloat16, device=h.device)
+            for r0, r1, e0, edges in groups:
+                layer.infer_rows(g, batch_size, r0, r1, e0, edges, ns[e0:e0 + edges], table, agg[r0:r1])
+            del table
+            h = layer.infer_finish(agg)
+            g.ndata["h"] = h
+        return h
+
     @torch.no_grad()
-    def inference(self, g, device=None, batch_size=128, use_uva=False, num_workers=0):
+    def inference(self, g, device=None, batch_size=128, use_uva=False, num_workers=0, path="auto"):
         """model.py:441-488.  GraphConv(norm='both') normalises by the BLOCK's out-degrees, so the result depends on how
-        the nodes are batched: ``batch_size`` is honoured exactly (contiguous batches, unshuffled, last one short)."""
+        the nodes are batched: ``batch_size`` is honoured exactly (contiguous batches, unshuffled, last one short).
+
+        ``path="blocks"``: the full-neighbour block of every batch through the layers' ``forward``.
+        ``path="csc"``: straight off the graph's CSC -- the same batches, the same bits for a
+        ``transforms="tile"`` model, no block built.  Raises NotImplementedError naming the reason when it cannot run.
+        ``path="auto"``: "csc" when nothing refuses it (a ``transforms="tile"`` model with bf16 features on the GPU), "blocks"
+        otherwise.  The path taken is left in ``last_inference_path``."""
+        if path not in self.INFERENCE_PATHS:
+            raise ValueError("path must be one of %r, not %r" % (self.INFERENCE_PATHS, path))
+        h = g.ndata["features"]
+        if path != "blocks":
+            why = self.csc_refusal(g, h, batch_size)
+            if path == "csc" and why is not None:
+                raise NotImplementedError(why)
+            path = "csc" if why is None else "blocks"
         was_training = self.training
         self.eval()
-        n = len(self.layers)
-        h = _blockwise_inference(self.layers, g, g.ndata["features"], int(batch_size),
-                                 lambda l, out: self.dropout(out) if l < n - 1 else out)
-        self.train(was_training)
+        try:
+            if path == "csc":
+                h = self._inference_csc(g, h, int(batch_size))
+            else:
+                n = len(self.layers)
+                h = _blockwise_inference(self.layers, g, h, int(batch_size), lambda l, out: self.dropout(out) if l < n - 1 else out)
+        finally:
+            self.train(was_training)
+        self.last_inference_path = path
         return h
 
 

@@ -879,6 +879,74 @@ class _GcnLayer(torch.autograd.Function):
         return (dx, dw, db) + (None,) * 9
 
 
+# Full-neighbour inference of GraphConv(norm='both') straight off the graph's CSC (csrc/gcn_infer.hip): the
+# batch-by-batch walk of GCN.inference without a block -- per-edge source norms of the batch structure, then a wave per row.
+def _gcn_infer_args(indptr, indices, batch_size, row0, row1, edge0, n_edges, ns, what):
+    V = indptr.numel() - 1
+    if indptr.dtype != torch.int64 or indices.dtype != torch.int32 or not (indptr.is_contiguous() and indices.is_contiguous()):
+        raise ValueError("%s: the graph's CSC is int64 indptr / int32 indices, contiguous" % what)
+    if not (indptr.is_cuda and indices.is_cuda):
+        raise NotImplementedError("%s: the CSC inference path runs on the GPU" % what)
+    if not (0 <= row0 <= row1 <= V) or batch_size < 1:
+        raise ValueError("%s: rows %d .. %d of %d nodes, batch_size %d" % (what, row0, row1, V, batch_size))
+    if n_edges >= 2 ** 31:
+        raise NotImplementedError("%s: a range of 2^31 or more edges is beyond the CSC path" % what)
+    if ns.dtype != torch.float32 or ns.numel() < n_edges or not ns.is_contiguous() or ns.device != indptr.device:
+        raise ValueError("%s: ns is fp32 [%d] on %s" % (what, n_edges, indptr.device))
+    t = _lib.GcnInfer()
+    t.indptr, t.indices, t.n_nodes, t.batch_size = indptr.data_ptr(), indices.data_ptr(), V, int(batch_size)
+    t.row0, t.n_rows, t.edge0, t.n_edges, t.ns = int(row0), int(row1) - int(row0), int(edge0), int(n_edges), ns.data_ptr()
+    return t
+
+
+def gcn_infer_state():
+    """Scratch of ``gcn_infer_src_norms`` (the by-source sort of a range's edges); it grows with the largest range seen."""
+    return dict(t_indptr=None, t_edge=None, temp=None)
+
+
+def gcn_infer_src_norms(indptr, indices, batch_size, row0, row1, edge0, n_edges, ns, state=None):
+    """``ns[e - edge0] = 1 / sqrt(max(cnt, 1))`` for the CSC positions of the destination rows ``row0 .. row1 - 1`` (whole
+    batches of ``batch_size`` rows), ``cnt`` = the positions of e's batch that share e's source: the source norm GraphConv takes
+    from the batch's full-neighbour block (bliss_gcn_infer_src_norms).  ``edge0`` / ``n_edges`` = indptr[row0] and the range's
+    edge count as the host read them; ``ns`` fp32 [n_edges].  No host read."""
+    import ctypes as C
+    t = _gcn_infer_args(indptr, indices, batch_size, row0, row1, edge0, n_edges, ns, "gcn_infer_src_norms")
+    if t.n_rows == 0 or t.n_edges == 0:
+        return ns
+    st = gcn_infer_state() if state is None else state
+    dev, V = indptr.device, t.n_nodes
+    nbytes = int(_lib.lib.bliss_block_transpose_temp_bytes(t.n_edges, V))
+    if nbytes < 0:
+        raise RuntimeError("bliss_block_transpose_temp_bytes failed")
+    if st["t_indptr"] is None or st["t_indptr"].numel() < V + 1:
+        st["t_indptr"] = torch.empty(V + 1, dtype=torch.int32, device=dev)
+    if st["t_edge"] is None or st["t_edge"].numel() < t.n_edges:
+        st["t_edge"] = torch.empty(t.n_edges, dtype=torch.int32, device=dev)
+    if st["temp"] is None or st["temp"].numel() < nbytes:
+        st["temp"] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    t.t_indptr, t.t_edge, t.temp, t.temp_bytes = st["t_indptr"].data_ptr(), st["t_edge"].data_ptr(), st["temp"].data_ptr(), st["temp"].numel()
+    _lib.check(_lib.lib.bliss_gcn_infer_src_norms(C.byref(t), _stream()), "bliss_gcn_infer_src_norms")
+    return ns
+
+
+def gcn_infer_spmm(indptr, indices, batch_size, row0, row1, edge0, n_edges, ns, h, out):
+    """``out[r - row0] = bf16(nd_r * sum_e ns_e * h[indices[e]])`` for the rows ``row0 .. row1 - 1`` with the bits
+    bliss_gcn_spmm_fwd gives on the full-neighbour block of every batch (bliss_gcn_infer_spmm).  ``h`` bf16 [V, dim] of ALL
+    nodes; ``out`` bf16 [row1 - row0, dim] (a view of the layer's rows); ``ns`` from ``gcn_infer_src_norms`` on the same range."""
+    import ctypes as C
+    t = _gcn_infer_args(indptr, indices, batch_size, row0, row1, edge0, n_edges, ns, "gcn_infer_spmm")
+    dev, dim = indptr.device, h.shape[1]
+    if h.dtype != torch.bfloat16 or h.dim() != 2 or h.shape[0] < t.n_nodes or h.stride(1) != 1 or h.device != dev:
+        raise ValueError("gcn_infer_spmm: h is bf16 [%d, dim] on %s" % (t.n_nodes, dev))
+    if out.dtype != torch.bfloat16 or out.shape != (t.n_rows, dim) or (dim > 1 and out.stride(1) != 1) or out.device != dev:
+        raise ValueError("gcn_infer_spmm: out is bf16 [%d, %d] on %s" % (t.n_rows, dim, dev))
+    if t.n_rows == 0:
+        return out
+    t.h, t.h_stride, t.dim, t.out, t.out_stride = h.data_ptr(), h.stride(0), dim, out.data_ptr(), out.stride(0)
+    _lib.check(_lib.lib.bliss_gcn_infer_spmm(C.byref(t), _stream()), "bliss_gcn_infer_spmm")
+    return out
+
+
 class GraphConv(nn.Module):
     """dglnn.GraphConv(in, out, norm='both', weight=True, bias=True) as built at model.py:397-417.
 
@@ -949,6 +1017,40 @@ class GraphConv(nn.Module):
         return _GcnLayer.apply(feat, self.weight, self.bias, (graph.indptr, graph.src, graph.dst, t_indptr, t_edge), ew, K, S,
                                _block_words(graph), self._activation is not None, p, self._drop_state(feat.device) if p > 0 else None,
                                bool(want_norm))
+
+    # -- full-neighbour inference off the graph's CSC -------------------------------------------------
+    def infer_refusal(self, h_all, what="GraphConv"):
+        """Why ``infer_transform`` / ``infer_rows`` / ``infer_finish`` cannot run on these input rows, or None."""
+        if not (torch.is_tensor(h_all) and h_all.is_cuda and h_all.dtype == torch.bfloat16 and h_all.dim() == 2):
+            return "%s: the CSC inference path takes bf16 rows on the GPU, not %s on %s" % (what, h_all.dtype, h_all.device)
+        if self.transforms != "tile":
+            return ('%s: the CSC inference path has the bits of the bounded kernels; build the layer with transforms="tile" '
+                    "(this one is %r)" % (what, self.transforms))
+        return self.tile_refusal(what)
+
+    def infer_transform(self, h_all):
+        """The [V, dim] table the range SpMM gathers from: ``h W`` over ALL rows in one launch for a weight-first layer
+        (bliss_gat_dgrad: a row's bits do not depend on how many rows the launch has), the input itself otherwise."""
+        if self._in_feats > self._out_feats:
+            return gat_dgrad(_bf16c(h_all), _bf16c(self.weight.detach()), h_all.shape[0])
+        return _bf16c(h_all)
+
+    def infer_rows(self, g, batch_size, row0, row1, edge0, n_edges, ns, table, out):
+        """The degree-normalised sums of the rows ``row0 .. row1 - 1`` (whole batches) into ``out`` (see ``gcn_infer_spmm``)."""
+        return gcn_infer_spmm(g.indptr, g.indices, batch_size, row0, row1, edge0, n_edges, ns, table, out)
+
+    def infer_finish(self, agg):
+        """The finished rows of the layer in evaluation mode from the aggregated rows: the product with the weight for an
+        aggregate-first layer, then the epilogue (bias, ReLU; no dropout, no row norms)."""
+        import ctypes as C
+        w = _bf16c(self.weight.detach())
+        a = agg if self._in_feats > self._out_feats else gat_dgrad(agg, w, agg.shape[0])
+        out = torch.empty(a.shape[0], w.shape[1], dtype=torch.bfloat16, device=a.device)
+        t = _gcn_epilogue_args(a.shape[0], 0, w.shape[1], self._activation is not None, 0.0, None, None)
+        t.a, t.a_stride, t.bias = a.data_ptr(), a.stride(0), 0 if self.bias is None else self.bias.data_ptr()
+        t.out, t.out_stride = out.data_ptr(), out.stride(0)
+        _lib.check(_lib.lib.bliss_gcn_epilogue_fwd(C.byref(t), _stream()), "bliss_gcn_epilogue_fwd")
+        return out
 
     def forward(self, graph, feat, weight=None, edge_weight=None):
         if self.transforms == "tile":

@@ -1088,6 +1088,46 @@ int bliss_gcn_db_chunk_rows(void);
 int bliss_gcn_epilogue_fwd(const bliss_gcn_epilogue_t* args, void* stream);
 int bliss_gcn_epilogue_bwd(const bliss_gcn_epilogue_t* args, void* stream);
 
+/* GraphConv(norm='both') full-neighbour inference straight off the graph's CSC (csrc/gcn_infer.hip, DESIGN.md section 27;
+ * model.py:441-488): the message passing of GCN.inference's batch-by-batch walk without a block.  Batch b is the rows
+ * [b * batch_size, min(n_nodes, (b + 1) * batch_size)), its first edge E0_b = indptr[b * batch_size], its n_b edges the CSC
+ * positions up to the next batch's first.  For the CSC position e of batch b with source j = indices[e]:
+ *   cnt   = positions of batch b whose source is j (parallel edges count once each: the block's out-degree of j)
+ *   ns[e] = 1 / sqrt(max(cnt, 1)),   nd[i] = 1 / sqrt(max(indeg_i, 1))          (bliss_gcn_norms' expressions, fp32)
+ *   out[i, :] = bf16( nd[i] * sum_{e in row i} ns[e] * h[indices[e], :] )
+ * and the fp32 sum is the one bliss_gcn_spmm_fwd produces on the batch's full-neighbour block: the batch's positions are cut
+ * into chunks of EC_b = bliss_spmm_chunk_edges(n_b) counted from E0_b, a row's terms inside a chunk are added in edge order
+ * starting from zero, a row's chunk partials are added in chunk order starting from the first; one product with nd[i], one
+ * rounding.  Rows without edges are zeros.  Bitwise reproducible: no float atomics, no tickets, no spin waits.
+ * Both calls work on a destination range of whole batches: row0 % batch_size == 0 and row0 + n_rows a multiple of batch_size
+ * or n_nodes.  edge0 = indptr[row0] and n_edges = indptr[row0 + n_rows] - edge0 as the HOST knows them; n_edges < 2^31
+ * (offsets inside a range are 32-bit, everything added to a pointer is 64-bit).  indices[] < n_nodes is the caller's.
+ *   indptr int64 [n_nodes + 1], 8-byte aligned; indices int32, 4-byte aligned; ns fp32 [n_edges]: ns[e - edge0].
+ * bliss_gcn_infer_src_norms writes ns for the range: bliss_block_transpose on indices[edge0 .. edge0 + n_edges) with n_nodes
+ *   source slots, then one launch with a thread per edge (its row by bisection of indptr, cnt as two lower bounds in its
+ *   source's ascending position list).  Scratch: t_indptr int32 [n_nodes + 1], t_edge int32 [n_edges], temp of temp_bytes >=
+ *   bliss_block_transpose_temp_bytes(n_edges, n_nodes).  h / dim / out are not looked at.  Nothing to do (returns 0, scratch may be
+ *   NULL) when n_rows or n_edges is 0.
+ * bliss_gcn_infer_spmm reads ns and gathers rows of h (bf16 [n_nodes, dim], row stride h_stride >= dim) into out (bf16
+ *   [n_rows, dim]: row r of the RANGE, stride out_stride >= dim); one launch, a wave per row.  8-byte accesses when dim % 4 == 0,
+ *   both strides % 4 == 0 and h, out 8-byte aligned; one feature per lane otherwise (same bits).  A row whose batch does not lie
+ *   inside [edge0, edge0 + n_edges) is left untouched.  The scratch fields are not looked at.  n_rows == 0 returns 0.
+ * bliss_gcn_infer_chunk_edges(n_b): the EC_b the kernel uses (= bliss_spmm_chunk_edges).
+ * BLISS_EINVAL before any launch: args, indptr or indices NULL; n_nodes <= 0; batch_size < 1; row0 or n_rows negative or past
+ * n_nodes; a range that cuts a batch; edge0 or n_edges negative, n_edges >= 2^31; ns NULL with n_edges > 0; a misaligned
+ * pointer; src_norms: missing or misaligned scratch, temp_bytes too small; spmm: h or out NULL, dim <= 0, a stride below dim. */
+typedef struct {
+  const int64_t* indptr; const int32_t* indices; int32_t n_nodes; int32_t batch_size;
+  int32_t row0; int32_t n_rows; int64_t edge0; int64_t n_edges;
+  float* ns;
+  int32_t* t_indptr; int32_t* t_edge; void* temp; int64_t temp_bytes;
+  const void* h; int64_t h_stride; int32_t dim;
+  void* out; int64_t out_stride;
+} bliss_gcn_infer_t;
+int bliss_gcn_infer_chunk_edges(int32_t n_batch_edges);
+int bliss_gcn_infer_src_norms(const bliss_gcn_infer_t* args, void* stream);
+int bliss_gcn_infer_spmm(const bliss_gcn_infer_t* args, void* stream);
+
 /* Per-kernel timing with HIP events recorded on the launching stream (bench.py's roofline object).
  * bliss_prof_enable(id): -2 off (default), -1 every kernel, >= 0 one kernel id; names via
  * bliss_prof_kernel_name(id), id < bliss_prof_kernel_count().  bliss_prof_read synchronises on the
