@@ -36,6 +36,16 @@ def _up8(n):
     return (int(n) + 7) & ~7
 
 
+def spmm_partials(B, D, device, floor=None):
+    """The fp32 head / tail partials of the balanced SpMM walk (csrc/spmm_walk.cuh): two rows of D per chunk of B edges.
+    ``floor`` = the least number of floats to allocate; None = no buffer at all for a block without edges."""
+    ec = _lib.lib.bliss_spmm_chunk_edges(B)
+    n = 2 * ((B + ec - 1) // ec) * D
+    if floor is None:
+        return torch.empty(n, dtype=torch.float32, device=device) if B > 0 else None
+    return torch.empty(max(n, floor), dtype=torch.float32, device=device)
+
+
 # ---------------------------------------------------------------------- the kinds of layer an engine runs
 class _Kind(NamedTuple):
     """What the host driver knows about one kind of layer; an engine runs one kind (``LayerEngine.kind``)."""

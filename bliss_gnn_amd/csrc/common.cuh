@@ -180,6 +180,17 @@ __device__ __forceinline__ long long bf_fixed_plain(bf16_t b, int frac) {
   return (long long)((uint64_t)m << (shift & 63));
 }
 
+// The keyed dropout hash of every layer epilogue (SAGE, the tile GEMM's fused tail, GCN, the GAT glue and the fused GAT
+// aggregation): a counter-based hash of (seed, launch counter, element index); an element is kept when the hash is >= the
+// threshold.  Forward and backward of a layer must draw the same mask, so this is the only copy.
+__device__ __forceinline__ uint32_t drop_hash(uint32_t seed, uint32_t ctr, uint32_t idx) {
+  uint32_t x = idx * 0x9e3779b1u + seed;
+  x ^= ctr * 0x85ebca77u + 0x165667b1u;
+  x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;    // lowbias32 finaliser
+  x += ctr; x ^= x >> 15; x *= 0x2c1b3c6du; x ^= x >> 12;
+  return x;
+}
+
 __device__ __forceinline__ int lane_id() { return threadIdx.x & (BLISS_WAVE - 1); }
 
 __device__ __forceinline__ int64_t shfl_up_i64(int64_t v, int d) {

@@ -15,10 +15,13 @@
 // fp32 products with one rounding.  F32 variants (no intermediate rounding, float outputs) exist for the north star's
 // 1e-4 check against fp32 math on the same bf16 operands.  The backward kernels differentiate the fp32 formulas.
 #include "common.cuh"
+#include "spmm_walk.cuh"
 #include "bliss_gnn.h"
 #include "prof.h"
 
 namespace {
+
+using namespace spmm_walk;       // f4, load4, bcast_i
 
 #define GAT_TPB 256
 #define GAT_EC 16          // edges per wave in the per-edge dot kernels
@@ -29,16 +32,6 @@ __device__ __forceinline__ float lrelu(float x, float s) { return x > 0.f ? x : 
 // per-edge, per-head dot product of two gathered rows.
 //   MODE 0 (logits):  e[e,h]  = sum_d attn[h,d] * lrelu(feat[src_e,h,d] + feat[dst_e,h,d])
 //   MODE 1 (d_a):     out[e,h] = sum_d g[dst_e,h,d] * feat[src_e,h,d]
-struct g4 { float x, y, z, w; };
-__device__ __forceinline__ g4 gload4(const bf16_t* p) {
-  const uint2 v = *reinterpret_cast<const uint2*>(p);
-  g4 r;
-  r.x = __uint_as_float(v.x << 16); r.y = __uint_as_float(v.x & 0xffff0000u);
-  r.z = __uint_as_float(v.y << 16); r.w = __uint_as_float(v.y & 0xffff0000u);
-  return r;
-}
-__device__ __forceinline__ int gb_i(int v, int j) { return __builtin_amdgcn_readlane(v, j); }    // wave-uniform lane index
-
 template <int MODE, bool VEC4, bool F32>
 __global__ void __launch_bounds__(GAT_TPB) k_gat_edge_dot(const int* __restrict__ src, const int* __restrict__ dst,
                                                          const int* __restrict__ nnz_dev, int nnz_host,
@@ -63,17 +56,17 @@ __global__ void __launch_bounds__(GAT_TPB) k_gat_edge_dot(const int* __restrict_
   int my_s = 0, my_d = 0;
   if (e0 + lane < e1) { my_s = src[e0 + lane]; my_d = dst[e0 + lane]; }
   for (int e = e0; e < e1; ++e) {
-    const bf16_t* a = feat + (int64_t)gb_i(my_s, e - e0) * feat_stride;
-    const bf16_t* b = (MODE == 0 ? feat + (int64_t)gb_i(my_d, e - e0) * feat_stride : g + (int64_t)gb_i(my_d, e - e0) * g_stride);
+    const bf16_t* a = feat + (int64_t)bcast_i(my_s, e - e0) * feat_stride;
+    const bf16_t* b = (MODE == 0 ? feat + (int64_t)bcast_i(my_d, e - e0) * feat_stride : g + (int64_t)bcast_i(my_d, e - e0) * g_stride);
     float part[GAT_MAXH];
 #pragma unroll
     for (int h = 0; h < GAT_MAXH; ++h) part[h] = 0.f;
     for (int idx = lane * W; idx < HD; idx += 64 * W) {
       float v;
       if (VEC4) {                                       // D % 4 == 0: the four columns belong to one head
-        const g4 x = gload4(a + idx), y = gload4(b + idx);
+        const f4 x = load4(a + idx), y = load4(b + idx);
         if (MODE == 0) {
-          const g4 t = gload4(attn + idx);
+          const f4 t = load4(attn + idx);
           v = term(t.x, x.x, y.x) + term(t.y, x.y, y.y) + term(t.z, x.z, y.z) + term(t.w, x.w, y.w);
         } else v = x.x * y.x + x.y * y.y + x.z * y.z + x.w * y.w;
       } else {
@@ -201,7 +194,7 @@ __global__ void __launch_bounds__(GAT_TPB) k_gat_rows(const int* __restrict__ ro
       float at[W], acc[W], attn_acc[W];
 #pragma unroll
       for (int i = 0; i < W; ++i) { at[i] = (LBWD && act) ? bf2f(attn[col + i]) : 0.f; acc[i] = 0.f; attn_acc[i] = 0.f; }
-      int cur = gb_i(my_row, 0);
+      int cur = bcast_i(my_row, 0);
       auto flush = [&](int r) {
         if (act) {
           const int rb = row_ptr[r], re = row_ptr[r + 1];
@@ -227,21 +220,21 @@ __global__ void __launch_bounds__(GAT_TPB) k_gat_rows(const int* __restrict__ ro
         for (int i = 0; i < W; ++i) acc[i] = 0.f;
       };
       for (int j = 0; j < cnt; ++j) {
-        const int r = gb_i(my_row, j), e = gb_i(my_e, j), s_ = gb_i(my_s, j), d_ = gb_i(my_d, j);
+        const int r = bcast_i(my_row, j), e = bcast_i(my_e, j), s_ = bcast_i(my_s, j), d_ = bcast_i(my_d, j);
         if (r != cur) { flush(cur); cur = r; }
         if (act) {
           const float cf = F32 ? reinterpret_cast<const float*>(coef)[(int64_t)e * H + hd] : bf2f(coef[(int64_t)e * H + hd]);
           if (LBWD && BY_SRC && g2) {
             const float cf2 = bf2f(coef2[(int64_t)e * H + hd]);
             if (VEC4) {
-              const g4 f = gload4(g2 + (int64_t)d_ * g2_stride + col);
+              const f4 f = load4(g2 + (int64_t)d_ * g2_stride + col);
               acc[0] += cf2 * f.x; acc[1 % W] += cf2 * f.y; acc[2 % W] += cf2 * f.z; acc[3 % W] += cf2 * f.w;
             } else acc[0] += cf2 * bf2f(g2[(int64_t)d_ * g2_stride + col]);
           }
           if (LBWD) {
             float xs[W], xd[W];
             if (VEC4) {
-              const g4 a = gload4(feat + (int64_t)s_ * feat_stride + col), b = gload4(feat + (int64_t)d_ * feat_stride + col);
+              const f4 a = load4(feat + (int64_t)s_ * feat_stride + col), b = load4(feat + (int64_t)d_ * feat_stride + col);
               xs[0] = a.x; xs[1 % W] = a.y; xs[2 % W] = a.z; xs[3 % W] = a.w;
               xd[0] = b.x; xd[1 % W] = b.y; xd[2 % W] = b.z; xd[3 % W] = b.w;
             } else { xs[0] = bf2f(feat[(int64_t)s_ * feat_stride + col]); xd[0] = bf2f(feat[(int64_t)d_ * feat_stride + col]); }
@@ -254,7 +247,7 @@ __global__ void __launch_bounds__(GAT_TPB) k_gat_rows(const int* __restrict__ ro
           } else {
             const int nb = BY_SRC ? d_ : s_;
             if (VEC4) {
-              const g4 f = gload4(feat + (int64_t)nb * feat_stride + col);
+              const f4 f = load4(feat + (int64_t)nb * feat_stride + col);
               acc[0] += cf * f.x; acc[1 % W] += cf * f.y; acc[2 % W] += cf * f.z; acc[3 % W] += cf * f.w;
             } else acc[0] += cf * bf2f(feat[(int64_t)nb * feat_stride + col]);
           }

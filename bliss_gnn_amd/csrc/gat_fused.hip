@@ -67,14 +67,6 @@ __device__ __forceinline__ g4f ldrow(const bf16_t* p) {            // W consecut
   return r;
 }
 
-__device__ __forceinline__ uint32_t gf_drop_hash(uint32_t seed, uint32_t ctr, uint32_t idx) {      // = drop_hash of spmm.hip / sage.hip
-  uint32_t x = idx * 0x9e3779b1u + seed;
-  x ^= ctr * 0x85ebca77u + 0x165667b1u;
-  x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-  x += ctr; x ^= x >> 15; x *= 0x2c1b3c6du; x ^= x >> 12;
-  return x;
-}
-
 // phase stamps for scratch/gatbench.py (bliss_gat_fused_stamps): 8 x s_memrealtime (100 MHz) per virtual workgroup of the forward
 __device__ long long* g_gf_stamps = nullptr;
 __device__ long long* g_gf_stamps_bwd = nullptr;
@@ -560,7 +552,7 @@ __global__ void __launch_bounds__(GF_TPB, 4) k_gat_fwd(GatFused p) {
     if (!INFER) p.a[o] = av;
     bf16_t cv = av;
     if (p.drop_thresh) {                               // nn.Dropout on a bf16 tensor: a * mask / (1 - p), one rounding
-      const bool keep = gf_drop_hash(p.seed, ctr, (uint32_t)o) >= p.drop_thresh;
+      const bool keep = drop_hash(p.seed, ctr, (uint32_t)o) >= p.drop_thresh;
       cv = keep ? f2bf(bf2f(av) * p.drop_scale) : (bf16_t)0;
       p.ad[o] = cv;
     }

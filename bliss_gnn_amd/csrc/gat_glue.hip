@@ -23,14 +23,6 @@ namespace {
 #define GG_TPB 256
 #define GG_MAX_WGS 2048
 
-__device__ __forceinline__ uint32_t gg_drop_hash(uint32_t seed, uint32_t ctr, uint32_t idx) {   // = drop_hash of spmm.hip
-  uint32_t x = idx * 0x9e3779b1u + seed;
-  x ^= ctr * 0x85ebca77u + 0x165667b1u;
-  x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-  x += ctr; x ^= x >> 15; x *= 0x2c1b3c6du; x ^= x >> 12;
-  return x;
-}
-
 struct Glue {
   const bf16_t* rst; long long rst_stride;
   const bf16_t* res; long long res_stride;
@@ -142,7 +134,7 @@ __global__ void __launch_bounds__(GG_TPB) k_gat_glue_fwd(Glue p) {
     if (p.drop_thresh) {
       const uint32_t base = (uint32_t)(row * width + c0);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) z[j] = gg_drop_hash(p.seed, ctr, base + j) >= p.drop_thresh ? rbf(z[j] * p.drop_scale) : 0.f;
+      for (int j = 0; j < 8; ++j) z[j] = drop_hash(p.seed, ctr, base + j) >= p.drop_thresh ? rbf(z[j] * p.drop_scale) : 0.f;
     }
     gg_store8(o, valid, p.vec, z);
   }
@@ -168,7 +160,7 @@ __global__ void __launch_bounds__(GG_TPB) k_gat_glue_bwd(Glue p) {
     if (p.drop_thresh) {
       const uint32_t base = (uint32_t)(row * width + c0);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) g[j] = gg_drop_hash(p.seed, ctr, base + j) >= p.drop_thresh ? rbf(g[j] * p.drop_scale) : 0.f;
+      for (int j = 0; j < 8; ++j) g[j] = drop_hash(p.seed, ctr, base + j) >= p.drop_thresh ? rbf(g[j] * p.drop_scale) : 0.f;
     }
     if (p.head_mean) {
 #pragma unroll

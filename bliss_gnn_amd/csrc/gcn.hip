@@ -12,52 +12,25 @@
 // the edge weights do not enter them.
 //
 // k_gcn_norms writes both norm vectors in one coalesced launch (computed once per block: looking the degrees up per edge would
-// put two more dependent loads into every edge's chain).  k_gcn_spmm is the balanced traversal of spmm.hip (a wave owns EC
-// consecutive edges, a lane 4 consecutive bf16 features, neighbour index and coefficient fetched coalesced and broadcast by
-// v_readlane, four neighbour rows in flight, head / tail partials for rows cut by chunk boundaries) with the coefficient
-// gathered beside the weight; k_gcn_fixup adds the partials of cut rows in chunk order and clears rows without edges.  No float
-// atomics, no tickets, no spin waits; nothing at or past the live edge count is read.
+// put two more dependent loads into every edge's chain).  k_gcn_spmm is the balanced traversal of spmm_walk.cuh (the one SAGEConv
+// runs in spmm.hip) with the coefficient gathered beside the weight (GcnPolicy); k_gcn_fixup is its fix-up: it adds the partials
+// of cut rows in chunk order and clears rows without edges.  No float atomics, no tickets, no spin waits; nothing at or past the
+// live edge count is read.
 //
 // k_gcn_epilogue_fwd / _bwd are the row-wise tail of a layer, bounded by the block's live row count: bias add, ReLU, the keyed
 // dropout mask of gat_glue.hip (drop_hash(seed, launch counter, r * width + c): no row's mask depends on the capacity), the
 // next block's row norms in k_embed_norm's summation order; the backward also reduces the bias gradient over fixed chunks of
 // GE_DB_ROWS rows (fp32 partials, summed in chunk order, one rounding).
 #include "common.cuh"
+#include "spmm_walk.cuh"
 #include "bliss_gnn.h"
-
-extern "C" int bliss_spmm_chunk_edges(int32_t nnz_bound);
 
 namespace {
 
+using namespace spmm_walk;
+
 #define GC_TPB 256
 #define GE_DB_ROWS 32
-
-struct f4 { float x, y, z, w; };
-
-__device__ __forceinline__ int bcast_i(int v, int j) { return __builtin_amdgcn_readlane(v, j); }
-__device__ __forceinline__ float bcast_f(float v, int j) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), j)); }
-
-__device__ __forceinline__ f4 load4(const bf16_t* p) {
-  uint2 v = *reinterpret_cast<const uint2*>(p);
-  f4 r;
-  r.x = __uint_as_float(v.x << 16); r.y = __uint_as_float(v.x & 0xffff0000u);
-  r.z = __uint_as_float(v.y << 16); r.w = __uint_as_float(v.y & 0xffff0000u);
-  return r;
-}
-
-__device__ __forceinline__ void store4(bf16_t* p, f4 a) {
-  uint2 v;
-  v.x = (uint32_t)f2bf(a.x) | ((uint32_t)f2bf(a.y) << 16);
-  v.y = (uint32_t)f2bf(a.z) | ((uint32_t)f2bf(a.w) << 16);
-  *reinterpret_cast<uint2*>(p) = v;
-}
-
-template <bool VEC4>
-__device__ __forceinline__ void store_row(bf16_t* out, int64_t off, f4 a, float scale) {
-  a.x *= scale; a.y *= scale; a.z *= scale; a.w *= scale;
-  if (VEC4) store4(out + off, a);
-  else out[off] = f2bf(a.x);
-}
 
 // ns[j] (j < n_src) and nd[i] (i < n_dst) in one launch; rows past the live counts are empty in both index arrays: norm 1
 __global__ void __launch_bounds__(GC_TPB) k_gcn_norms(const int* __restrict__ indptr, int n_dst, const int* __restrict__ t_indptr, int n_src,
@@ -73,8 +46,17 @@ __global__ void __launch_bounds__(GC_TPB) k_gcn_norms(const int* __restrict__ in
   }
 }
 
-// FWD: row = destination (CSR row), neighbour = src[e], coefficient = w[e] * ns[src[e]], store scale nd[row]
-// BWD: row = source (t_edge groups the edges by source), neighbour = dst[e], coefficient = w[e] * nd[dst[e]], store scale ns[row]
+// GraphConv's coefficients on the shared walk (spmm_walk.cuh); k_gcn_spmm hands n_nbr / n_row over by direction:
+// FWD: coefficient = w[e] * ns[src[e]], store scale nd[row]
+// BWD: coefficient = w[e] * nd[dst[e]], store scale ns[row]
+template <bool BWD>
+struct GcnPolicy {
+  const float* n_nbr;
+  const float* n_row;
+  __device__ __forceinline__ float coef(float c, int s, int d) const { return c * n_nbr[BWD ? d : s]; }
+  __device__ __forceinline__ float scale(int r, int rb, int re) const { return n_row[r]; }
+};
+
 template <bool VEC4, bool BWD>
 __global__ void __launch_bounds__(GC_TPB) k_gcn_spmm(const int* __restrict__ row_ptr, const int* __restrict__ t_edge,
                                                     const int* __restrict__ src, const int* __restrict__ dst,
@@ -84,120 +66,34 @@ __global__ void __launch_bounds__(GC_TPB) k_gcn_spmm(const int* __restrict__ row
                                                     int64_t out_stride, float* __restrict__ part, int EC) {
   int nnz = nnz_host;
   if (nnz_dev) { const int t = *nnz_dev; nnz = t < nnz ? t : nnz; }
-  if (nnz < 0) nnz = 0;
-  const int lane = lane_id();
-  const int chunk = blockIdx.x * (GC_TPB / 64) + (threadIdx.x >> 6);
+  if (nnz < 0) nnz = 0;                                     // a negative device count is no edges
+  const int ci = blockIdx.x * (GC_TPB / 64) + (threadIdx.x >> 6);
   const int nchunks = (nnz + EC - 1) / EC;
-  if (chunk >= nchunks) return;
-  const int c0 = chunk * EC, c1 = min(nnz, c0 + EC), cnt = c1 - c0;
-  int my_row = -1, my_n = 0;
-  float my_c = 0.f;
-  if (lane < cnt) {
-    const int e = BWD ? t_edge[c0 + lane] : c0 + lane;
-    const int s = src[e], d = dst[e];
-    my_row = BWD ? s : d;
-    my_n = BWD ? d : s;
-    my_c = (w ? bf2f(w[e]) : 1.0f) * n_nbr[my_n];
-  }
-  constexpr int W = VEC4 ? 4 : 1;
-  const f4 zero = {0.f, 0.f, 0.f, 0.f};
-  for (int col0 = 0; col0 < dim; col0 += 64 * W) {
-    const int col = col0 + lane * W;
-    const bool act = col < dim;
-    auto flush = [&](int r, f4 acc) {
-      const int rb = row_ptr[r], re = row_ptr[r + 1];
-      const bool starts = rb >= c0, ends = re <= c1;
-      if (!act) return;
-      if (starts && ends) {
-        store_row<VEC4>(out, r * out_stride + col, acc, n_row[r]);
-      } else {
-        float* q = part + ((int64_t)chunk * 2 + (starts ? 1 : 0)) * dim + col;
-        q[0] = acc.x;
-        if (VEC4) { q[1] = acc.y; q[2] = acc.z; q[3] = acc.w; }
-      }
-    };
-    int cur = bcast_i(my_row, 0);
-    f4 acc = zero;
-    for (int j = 0; j < cnt;) {
-      const int r = bcast_i(my_row, j);
-      if (r != cur) { flush(cur, acc); acc = zero; cur = r; }
-      const int run = __popcll(__ballot(my_row == r && lane >= j));
-      const int end = j + run;
-      for (; j + 4 <= end; j += 4) {
-        int n0 = bcast_i(my_n, j), n1 = bcast_i(my_n, j + 1), n2 = bcast_i(my_n, j + 2), n3 = bcast_i(my_n, j + 3);
-        float k0 = bcast_f(my_c, j), k1 = bcast_f(my_c, j + 1), k2 = bcast_f(my_c, j + 2), k3 = bcast_f(my_c, j + 3);
-        if (act) {
-          if (VEC4) {
-            f4 a0 = load4(h + n0 * h_stride + col), a1 = load4(h + n1 * h_stride + col);
-            f4 a2 = load4(h + n2 * h_stride + col), a3 = load4(h + n3 * h_stride + col);
-            acc.x += k0 * a0.x; acc.y += k0 * a0.y; acc.z += k0 * a0.z; acc.w += k0 * a0.w;
-            acc.x += k1 * a1.x; acc.y += k1 * a1.y; acc.z += k1 * a1.z; acc.w += k1 * a1.w;
-            acc.x += k2 * a2.x; acc.y += k2 * a2.y; acc.z += k2 * a2.z; acc.w += k2 * a2.w;
-            acc.x += k3 * a3.x; acc.y += k3 * a3.y; acc.z += k3 * a3.z; acc.w += k3 * a3.w;
-          } else {
-            float a0 = bf2f(h[n0 * h_stride + col]), a1 = bf2f(h[n1 * h_stride + col]);
-            float a2 = bf2f(h[n2 * h_stride + col]), a3 = bf2f(h[n3 * h_stride + col]);
-            acc.x += k0 * a0; acc.x += k1 * a1; acc.x += k2 * a2; acc.x += k3 * a3;
-          }
-        }
-      }
-      for (; j < end; ++j) {
-        int n0 = bcast_i(my_n, j);
-        float k0 = bcast_f(my_c, j);
-        if (act) {
-          if (VEC4) {
-            f4 a0 = load4(h + n0 * h_stride + col);
-            acc.x += k0 * a0.x; acc.y += k0 * a0.y; acc.z += k0 * a0.z; acc.w += k0 * a0.w;
-          } else acc.x += k0 * bf2f(h[n0 * h_stride + col]);
-        }
-      }
-    }
-    flush(cur, acc);
-  }
+  if (ci >= nchunks) return;
+  chunk<VEC4, false, BWD>(GcnPolicy<BWD>{n_nbr, n_row}, ci, nnz, EC, row_ptr, t_edge, src, dst, w, h, h_stride, dim, out, out_stride,
+                          part);
 }
 
-// rows cut by chunk boundaries: the tail partial of the chunk they start in + the head partials of the following chunks, in
-// chunk order; rows without edges (isolated or capacity padding) are cleared.  One wave per row.
 template <bool VEC4>
 __global__ void __launch_bounds__(GC_TPB) k_gcn_fixup(const int* __restrict__ row_ptr, int n_rows, int dim, const float* __restrict__ n_row,
                                                      const float* __restrict__ part, bf16_t* __restrict__ out, int64_t out_stride, int EC) {
-  const int lane = lane_id();
   const int r = blockIdx.x * (GC_TPB / 64) + (threadIdx.x >> 6);
   if (r >= n_rows) return;
-  const int rb = row_ptr[r], re = row_ptr[r + 1];
-  constexpr int W = VEC4 ? 4 : 1;
-  const f4 zero = {0.f, 0.f, 0.f, 0.f};
-  if (re <= rb) {
-    for (int col = lane * W; col < dim; col += 64 * W) store_row<VEC4>(out, r * out_stride + col, zero, 1.0f);
-    return;
-  }
-  const int c = rb / EC, c_end = (re - 1) / EC;
-  if (c_end == c) return;                                   // finished by its chunk
-  const float scale = n_row[r];
-  for (int col = lane * W; col < dim; col += 64 * W) {
-    f4 sum = zero;
-    if (VEC4) {
-      const float4 v = *reinterpret_cast<const float4*>(part + ((int64_t)c * 2 + 1) * dim + col);
-      sum.x = v.x; sum.y = v.y; sum.z = v.z; sum.w = v.w;
-#pragma unroll 4
-      for (int cc = c + 1; cc <= c_end; ++cc) {
-        const float4 u = *reinterpret_cast<const float4*>(part + ((int64_t)cc * 2) * dim + col);
-        sum.x += u.x; sum.y += u.y; sum.z += u.z; sum.w += u.w;
-      }
-    } else {
-      sum.x = part[((int64_t)c * 2 + 1) * dim + col];
-      for (int cc = c + 1; cc <= c_end; ++cc) sum.x += part[((int64_t)cc * 2) * dim + col];
-    }
-    store_row<VEC4>(out, r * out_stride + col, sum, scale);
-  }
+  fixup<VEC4, false>(GcnPolicy<false>{nullptr, n_row}, r, row_ptr, dim, part, out, out_stride, EC);     // the fix-up asks scale() only
 }
 
+// What this launcher does differently from spmm.hip's launch_spmm, on purpose:
+//   * nnz == 0 launches no main kernel, only the fix-up that clears the rows (SAGE launches one idle chunk);
+//   * k_gcn_spmm clamps a negative device-side count to 0 (SAGE takes the count as it is);
+//   * the entry points require `partials` whenever nnz > 0 (SAGE: only when nnz > EC);
+//   * ONE vec4 decision for both kernels, with the alignment of `part` folded in (SAGE decides the fix-up's separately);
+//   * only n_rows == 0 returns early; dim <= 0 is refused by the entry points.
 template <bool BWD>
 int launch_gcn_spmm(const int* row_ptr, const int* t_edge, const int* src, const int* dst, const void* w, const float* n_nbr,
                     const float* n_row, const void* h, int64_t h_stride, int n_rows, const int* nnz_dev, int nnz, int dim, void* out,
                     int64_t out_stride, float* part, hipStream_t st) {
   if (n_rows == 0) return 0;
-  const int EC = bliss_spmm_chunk_edges(nnz);
+  const int EC = spmm_chunk_edges(nnz);
   const bool vec4 = (dim % 4 == 0) && (h_stride % 4 == 0) && (out_stride % 4 == 0) && (((uintptr_t)h) % 8 == 0) &&
                     (((uintptr_t)out) % 8 == 0) && (((uintptr_t)part) % 16 == 0);
   const int nchunks = (nnz + EC - 1) / EC;
@@ -215,14 +111,6 @@ int launch_gcn_spmm(const int* row_ptr, const int* t_edge, const int* src, const
 }
 
 // ------------------------------------------------------------------------------------------------------------ epilogue
-__device__ __forceinline__ uint32_t ge_drop_hash(uint32_t seed, uint32_t ctr, uint32_t idx) {   // = drop_hash of spmm.hip
-  uint32_t x = idx * 0x9e3779b1u + seed;
-  x ^= ctr * 0x85ebca77u + 0x165667b1u;
-  x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-  x += ctr; x ^= x >> 15; x *= 0x2c1b3c6du; x ^= x >> 12;
-  return x;
-}
-
 struct Epi {
   const bf16_t* a; long long a_stride;
   const bf16_t* bias;
@@ -273,13 +161,13 @@ __global__ void __launch_bounds__(GC_TPB) k_gcn_epilogue_fwd(Epi p) {
       if (p.bias) t = rbf(t + bf2f(p.bias[col + i]));
       if (p.relu) t = t > 0.f ? t : 0.f;
       if (p.drop_thresh) {
-        const bool keep = ge_drop_hash(p.seed, ctr, (uint32_t)row * (uint32_t)dim + (uint32_t)(col + i)) >= p.drop_thresh;
+        const bool keep = drop_hash(p.seed, ctr, (uint32_t)row * (uint32_t)dim + (uint32_t)(col + i)) >= p.drop_thresh;
         t = keep ? rbf(t * p.drop_scale) : 0.f;
       }
       v[i] = t;
       s += t * t;
     }
-    if (p.vec) { f4 o = {v[0], v[1], v[2], v[3]}; store4(po + col, o); }
+    if (p.vec) { f4 o = {v[0], v[1], v[2], v[3]}; store4<false>(po, col, o); }
     else for (int i = 0; i < W; ++i) po[col + i] = f2bf(v[i]);
   }
   for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d);
@@ -300,7 +188,7 @@ __global__ void __launch_bounds__(GC_TPB) k_gcn_epilogue_bwd(Epi p) {
       bf16_t* pd = p.din + r * p.din_stride + c;
       if (r >= n) { *pd = 0; continue; }
       float g = bf2f(p.dout[r * p.dout_stride + c]);
-      if (p.drop_thresh) g = ge_drop_hash(p.seed, ctr, (uint32_t)r * (uint32_t)p.width + (uint32_t)c) >= p.drop_thresh ? rbf(g * p.drop_scale) : 0.f;
+      if (p.drop_thresh) g = drop_hash(p.seed, ctr, (uint32_t)r * (uint32_t)p.width + (uint32_t)c) >= p.drop_thresh ? rbf(g * p.drop_scale) : 0.f;
       if (p.relu) g = bf2f(p.out[r * p.out_stride + c]) > 0.f ? g : 0.f;
       *pd = f2bf(g);
       sum += g;

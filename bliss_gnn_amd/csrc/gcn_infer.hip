@@ -8,7 +8,7 @@
 //     ns_e        = 1 / sqrt(max(cnt(b, indices[e]), 1))       nd_i = 1 / sqrt(max(indeg_i, 1))      (k_gcn_norms' expressions)
 //     out[i, :]   = bf16( nd_i * sum_e ns_e * h[indices[e], :] )
 // with the fp32 sum in the order k_gcn_spmm + k_gcn_fixup produce on the batch's block: the batch's edges are cut into chunks of
-// EC_b = bliss_spmm_chunk_edges(n_b) positions counted from E0_b; a row's terms inside a chunk are added one by one in edge
+// EC_b = spmm_chunk_edges(n_b) positions counted from E0_b; a row's terms inside a chunk are added one by one in edge
 // order starting from zero, the per-chunk partials of a row are added in chunk order starting from the first partial; one
 // product with nd_i and one rounding at the store.
 //
@@ -22,39 +22,14 @@
 // above comes out of registers: no partial rows in memory, no fix-up launch, no float atomics, no tickets, no spin waits.
 // A row is one wave's work: a launch lasts at least as long as its longest row (DESIGN.md section 27 has the figures).
 #include "common.cuh"
+#include "spmm_walk.cuh"
 #include "bliss_gnn.h"
 
 namespace {
 
 #define GI_TPB 256
 
-struct f4 { float x, y, z, w; };
-
-__device__ __forceinline__ int bcast_i(int v, int j) { return __builtin_amdgcn_readlane(v, j); }
-__device__ __forceinline__ float bcast_f(float v, int j) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), j)); }
-
-__device__ __forceinline__ f4 load4(const bf16_t* p) {
-  uint2 v = *reinterpret_cast<const uint2*>(p);
-  f4 r;
-  r.x = __uint_as_float(v.x << 16); r.y = __uint_as_float(v.x & 0xffff0000u);
-  r.z = __uint_as_float(v.y << 16); r.w = __uint_as_float(v.y & 0xffff0000u);
-  return r;
-}
-
-template <bool VEC4>
-__device__ __forceinline__ void store_row(bf16_t* p, f4 a, float scale) {
-  a.x *= scale; a.y *= scale; a.z *= scale; a.w *= scale;
-  if (VEC4) {
-    uint2 v;
-    v.x = (uint32_t)f2bf(a.x) | ((uint32_t)f2bf(a.y) << 16);
-    v.y = (uint32_t)f2bf(a.z) | ((uint32_t)f2bf(a.w) << 16);
-    *reinterpret_cast<uint2*>(p) = v;
-  } else *p = f2bf(a.x);
-}
-
-// = bliss_spmm_chunk_edges (spmm.hip), which the block path asks with the batch's edge count (tests/test_gcn_infer_abi.py
-// holds the two together through bliss_gcn_infer_chunk_edges)
-__host__ __device__ __forceinline__ int gi_chunk_edges(int nnz) { return nnz >= 200000 ? 64 : (nnz >= 50000 ? 32 : 16); }
+using namespace spmm_walk;       // the row primitives, and the chunk rule the block path cuts a batch's edges by
 
 struct Range {
   const long long* indptr; const int* indices; int V, bs, row0, n_rows;
@@ -144,14 +119,14 @@ __global__ void __launch_bounds__(GI_TPB) k_gi_spmm(Range g, const float* __rest
   constexpr int W = VEC4 ? 4 : 1;
   const f4 zero = {0.f, 0.f, 0.f, 0.f};
   if (re_abs <= rs_abs) {                                     // a row without edges
-    for (int col = lane * W; col < dim; col += 64 * W) store_row<VEC4>(po + col, zero, 1.0f);
+    for (int col = lane * W; col < dim; col += 64 * W) store_row<VEC4, false>(po, col, zero, 1.0f);
     return;
   }
   const long long b0 = (long long)(r / g.bs) * g.bs;
   const long long b1 = b0 + g.bs < g.V ? b0 + g.bs : g.V;
   const long long E0 = g.indptr[b0], E1 = g.indptr[b1];
   if (E0 < g.edge0 || E1 > g.edge0 + g.n_edges || rs_abs < E0 || re_abs > E1) return;     // not the range the caller stated
-  const int EC = gi_chunk_edges((int)(E1 - E0));
+  const int EC = spmm_chunk_edges((int)(E1 - E0));
   const int rs = (int)(rs_abs - E0), re = (int)(re_abs - E0);                              // relative to the batch's first edge
   const int deg = re - rs;
   const float nd = 1.0f / sqrtf((float)(deg > 1 ? deg : 1));
@@ -173,7 +148,7 @@ __global__ void __launch_bounds__(GI_TPB) k_gi_spmm(Range g, const float* __rest
       for (; j < n; ++j) gi_group<VEC4, 1>(h, h_stride, col, act, my_n, my_c, j, t0 + j, rs, EC - 1, acc, sum, first);
     }
     gi_close(acc, sum, first);                                // the row ends: its last partial
-    if (act) store_row<VEC4>(po + col, sum, nd);
+    if (act) store_row<VEC4, false>(po, col, sum, nd);
   }
 }
 
@@ -197,7 +172,7 @@ inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 extern "C" {
 
-int bliss_gcn_infer_chunk_edges(int32_t n_batch_edges) { return gi_chunk_edges(n_batch_edges); }
+int bliss_gcn_infer_chunk_edges(int32_t n_batch_edges) { return spmm_chunk_edges(n_batch_edges); }
 
 int bliss_gcn_infer_src_norms(const bliss_gcn_infer_t* args, void* stream) {
   Range g;

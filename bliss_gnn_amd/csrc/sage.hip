@@ -54,14 +54,6 @@ __device__ __host__ __forceinline__ int lds_stride(int k) {
   return ((k + 15) & ~15) + 8;
 }
 
-__device__ __forceinline__ uint32_t tg_drop_hash(uint32_t seed, uint32_t ctr, uint32_t idx) {   // = drop_hash of spmm.hip
-  uint32_t x = idx * 0x9e3779b1u + seed;
-  x ^= ctr * 0x85ebca77u + 0x165667b1u;
-  x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-  x += ctr; x ^= x >> 15; x *= 0x2c1b3c6du; x ^= x >> 12;
-  return x;
-}
-
 // sum of squares of one LDS row in k_embed_norm's order (spmm.hip): vec4 = the 4-columns-per-lane walk, else 1 per lane
 __device__ __forceinline__ float row_sumsq(const bf16_t* sh, int dim, int vec4, int lane) {
   float s = 0.f;
@@ -340,7 +332,7 @@ __device__ __forceinline__ void tile_gemm_body(const TileGemm& p, bf16_t* lds, i
         float t = rbf(acc[m][i] + bv);                       // fp32 accumulator + bias, ONE rounding to bf16
         if (p.relu) t = t > 0.f ? t : 0.f;
         if (p.drop_thresh) {
-          const bool keep = tg_drop_hash(p.seed, ctr, (uint32_t)((row0 + lr) * N + col)) >= p.drop_thresh;
+          const bool keep = drop_hash(p.seed, ctr, (uint32_t)((row0 + lr) * N + col)) >= p.drop_thresh;
           t = keep ? rbf(t * p.drop_scale) : 0.f;
         }
         ot[(size_t)lr * so + col] = (row0 + lr < M && col < N) ? f2bf(t) : (bf16_t)0;

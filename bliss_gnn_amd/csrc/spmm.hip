@@ -4,62 +4,34 @@
 // (dglnn.SAGEConv.forward, called from model.py:321-329) and its autograd backward, plus
 // th.norm(h, dim=1) of model.py:318-320.
 //
-// HBM-bound gather kernels: a 64-lane wave owns 64 consecutive edges; a lane owns 4 consecutive bf16
-// features (8-byte loads, 512 B per wave-instruction for a 256-wide row); the (neighbour, coefficient)
-// pairs are fetched coalesced and broadcast by lane; 4 neighbour rows are kept in flight.  fp32
-// accumulation, one rounding to bf16 at the store.  The backward is a gather too (through the by-source
-// transposed index), so it is deterministic and needs no float atomics.
+// k_spmm / k_spmm_fixup are the balanced traversal of spmm_walk.cuh with SAGEConv's coefficients (SagePolicy).  The backward
+// is a gather too (through the by-source transposed index), so it is deterministic and needs no float atomics.
 #include "common.cuh"
+#include "spmm_walk.cuh"
 #include "bliss_gnn.h"
 #include "prof.h"
 
-extern "C" int bliss_spmm_chunk_edges(int32_t nnz_bound);
-
 namespace {
+
+using namespace spmm_walk;
 
 #define SP_TPB 256
 
-struct f4 { float x, y, z, w; };
-
-// broadcast from a lane whose index is wave-uniform: v_readlane (scalar result, no LDS round trip like __shfl's ds_bpermute)
-__device__ __forceinline__ int bcast_i(int v, int j) { return __builtin_amdgcn_readlane(v, j); }
-__device__ __forceinline__ float bcast_f(float v, int j) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), j)); }
-
-__device__ __forceinline__ f4 load4(const bf16_t* p) {
-  uint2 v = *reinterpret_cast<const uint2*>(p);
-  f4 r;
-  r.x = __uint_as_float(v.x << 16); r.y = __uint_as_float(v.x & 0xffff0000u);
-  r.z = __uint_as_float(v.y << 16); r.w = __uint_as_float(v.y & 0xffff0000u);
-  return r;
-}
-
-template <bool OUT_F32>
-__device__ __forceinline__ void store4(void* out, int64_t off, f4 a) {
-  if (OUT_F32) {
-    *reinterpret_cast<float4*>((float*)out + off) = make_float4(a.x, a.y, a.z, a.w);
-  } else {
-    uint2 v;
-    v.x = (uint32_t)f2bf(a.x) | ((uint32_t)f2bf(a.y) << 16);
-    v.y = (uint32_t)f2bf(a.z) | ((uint32_t)f2bf(a.w) << 16);
-    *reinterpret_cast<uint2*>((bf16_t*)out + off) = v;
+// SAGEConv's coefficients on the shared walk (spmm_walk.cuh):
+// FWD: coefficient = w[e]            (x 1/deg at the store)
+// BWD: coefficient = w[e]/deg(dst[e])
+template <bool BWD>
+struct SagePolicy {
+  const int* blk_indptr;                                    // the block's CSR by destination (BWD with mean only)
+  int mean;
+  __device__ __forceinline__ float coef(float c, int s, int d) const {
+    if (BWD && mean) c = c / (float)max(blk_indptr[d + 1] - blk_indptr[d], 1);
+    return c;
   }
-}
-
-// Balanced ("merge-style") traversal: a wave owns EC consecutive entries of the edge list (bliss_spmm_chunk_edges), whatever
-// rows they belong to, so a 30 000-edge hub row and a 3-edge row cost the same per wave.  Rows that lie
-// inside one chunk are finished and stored by that wave; a row cut by chunk boundaries leaves fp32
-// partials (one "head" and one "tail" slot per chunk) that k_spmm_fixup adds IN CHUNK ORDER -- the sum
-// order is fixed, so results are bitwise reproducible without float atomics.
-// FWD: row = destination (CSR row), neighbour = src[e], coefficient = w[e]            (x 1/deg at the store)
-// BWD: row = source (t_edge groups the edges by source), neighbour = dst[e], coefficient = w[e]/deg(dst[e])
-
-template <bool VEC4, bool OUT_F32>
-__device__ __forceinline__ void store_row(void* out, int64_t off, f4 a, float scale) {
-  a.x *= scale; a.y *= scale; a.z *= scale; a.w *= scale;
-  if (VEC4) store4<OUT_F32>(out, off, a);
-  else if (OUT_F32) ((float*)out)[off] = a.x;
-  else ((bf16_t*)out)[off] = f2bf(a.x);
-}
+  __device__ __forceinline__ float scale(int r, int rb, int re) const {
+    return (!BWD && mean) ? 1.0f / (float)max(re - rb, 1) : 1.0f;
+  }
+};
 
 template <bool VEC4, bool OUT_F32, bool BWD>
 __global__ void __launch_bounds__(SP_TPB) k_spmm(const int* __restrict__ row_ptr, const int* __restrict__ t_edge,
@@ -69,115 +41,19 @@ __global__ void __launch_bounds__(SP_TPB) k_spmm(const int* __restrict__ row_ptr
                                                 const int* __restrict__ nnz_dev, int nnz_host, int dim,
                                                 int mean, void* out, int64_t out_stride, float* __restrict__ part, int EC) {
   const int nnz = nnz_dev ? min(*nnz_dev, nnz_host) : nnz_host;
-  const int lane = lane_id();
-  const int chunk = blockIdx.x * (SP_TPB / 64) + (threadIdx.x >> 6);
-  const int nchunks = nnz > 0 ? (nnz + EC - 1) / EC : 1;
-  if (chunk >= nchunks) return;
-  const int c0 = chunk * EC, c1 = min(nnz, c0 + EC), cnt = c1 - c0;
-  int my_row = -1, my_n = 0;
-  float my_c = 0.f;
-  if (lane < cnt) {
-    const int e = BWD ? t_edge[c0 + lane] : c0 + lane;
-    my_row = BWD ? src[e] : dst[e];
-    my_n = BWD ? dst[e] : src[e];
-    float c = w ? bf2f(w[e]) : 1.0f;
-    if (BWD && mean) { const int d = dst[e]; c = c / (float)max(blk_indptr[d + 1] - blk_indptr[d], 1); }
-    my_c = c;
-  }
-  constexpr int W = VEC4 ? 4 : 1;
-  const f4 zero = {0.f, 0.f, 0.f, 0.f};
-  for (int col0 = 0; col0 < dim; col0 += 64 * W) {
-    const int col = col0 + lane * W;
-    const bool act = col < dim;
-    // finish row r with the accumulated value: store, or leave a partial for the fix-up pass
-    auto flush = [&](int r, f4 acc) {
-      const int rb = row_ptr[r], re = row_ptr[r + 1];
-      const bool starts = rb >= c0, ends = re <= c1;
-      if (!act) return;
-      if (starts && ends) {
-        const float scale = (!BWD && mean) ? 1.0f / (float)max(re - rb, 1) : 1.0f;
-        store_row<VEC4, OUT_F32>(out, r * out_stride + col, acc, scale);
-      } else {
-        float* q = part + ((int64_t)chunk * 2 + (starts ? 1 : 0)) * dim + col;
-        q[0] = acc.x;
-        if (VEC4) { q[1] = acc.y; q[2] = acc.z; q[3] = acc.w; }
-      }
-    };
-    if (cnt == 0) continue;                                 // rows without edges are cleared by k_spmm_fixup
-    int cur = bcast_i(my_row, 0);
-    f4 acc = zero;
-    for (int j = 0; j < cnt;) {
-      const int r = bcast_i(my_row, j);
-      if (r != cur) { flush(cur, acc); acc = zero; cur = r; }
-      const int run = __popcll(__ballot(my_row == r && lane >= j));
-      const int end = j + run;
-      for (; j + 4 <= end; j += 4) {
-        int n0 = bcast_i(my_n, j), n1 = bcast_i(my_n, j + 1), n2 = bcast_i(my_n, j + 2), n3 = bcast_i(my_n, j + 3);
-        float k0 = bcast_f(my_c, j), k1 = bcast_f(my_c, j + 1), k2 = bcast_f(my_c, j + 2), k3 = bcast_f(my_c, j + 3);
-        if (act) {
-          if (VEC4) {
-            f4 a0 = load4(h + n0 * h_stride + col), a1 = load4(h + n1 * h_stride + col);
-            f4 a2 = load4(h + n2 * h_stride + col), a3 = load4(h + n3 * h_stride + col);
-            acc.x += k0 * a0.x; acc.y += k0 * a0.y; acc.z += k0 * a0.z; acc.w += k0 * a0.w;
-            acc.x += k1 * a1.x; acc.y += k1 * a1.y; acc.z += k1 * a1.z; acc.w += k1 * a1.w;
-            acc.x += k2 * a2.x; acc.y += k2 * a2.y; acc.z += k2 * a2.z; acc.w += k2 * a2.w;
-            acc.x += k3 * a3.x; acc.y += k3 * a3.y; acc.z += k3 * a3.z; acc.w += k3 * a3.w;
-          } else {
-            float a0 = bf2f(h[n0 * h_stride + col]), a1 = bf2f(h[n1 * h_stride + col]);
-            float a2 = bf2f(h[n2 * h_stride + col]), a3 = bf2f(h[n3 * h_stride + col]);
-            acc.x += k0 * a0; acc.x += k1 * a1; acc.x += k2 * a2; acc.x += k3 * a3;
-          }
-        }
-      }
-      for (; j < end; ++j) {
-        int n0 = bcast_i(my_n, j);
-        float k0 = bcast_f(my_c, j);
-        if (act) {
-          if (VEC4) {
-            f4 a0 = load4(h + n0 * h_stride + col);
-            acc.x += k0 * a0.x; acc.y += k0 * a0.y; acc.z += k0 * a0.z; acc.w += k0 * a0.w;
-          } else acc.x += k0 * bf2f(h[n0 * h_stride + col]);
-        }
-      }
-    }
-    flush(cur, acc);
-  }
+  const int ci = blockIdx.x * (SP_TPB / 64) + (threadIdx.x >> 6);
+  const int nchunks = nnz > 0 ? (nnz + EC - 1) / EC : 1;    // no edges: one idle chunk (launch_spmm)
+  if (ci >= nchunks) return;
+  chunk<VEC4, OUT_F32, BWD>(SagePolicy<BWD>{blk_indptr, mean}, ci, nnz, EC, row_ptr, t_edge, src, dst, w, h, h_stride, dim, out,
+                            out_stride, part);
 }
 
-// rows cut by chunk boundaries: tail partial of the chunk they start in + head partials of the following chunks;
-// rows without edges (isolated or capacity-padded) are cleared here, one wave per row
 template <bool OUT_F32, bool BWD, bool VEC4>
 __global__ void __launch_bounds__(SP_TPB) k_spmm_fixup(const int* __restrict__ row_ptr, int n_rows, int dim, int mean,
                                                       const float* __restrict__ part, void* out, int64_t out_stride, int EC) {
-  const int lane = lane_id();
   const int r = blockIdx.x * (SP_TPB / 64) + (threadIdx.x >> 6);
   if (r >= n_rows) return;
-  const int rb = row_ptr[r], re = row_ptr[r + 1];
-  constexpr int W = VEC4 ? 4 : 1;
-  const f4 zero = {0.f, 0.f, 0.f, 0.f};
-  if (re <= rb) {                                           // no edges (incl. capacity-padded rows): the output row is zero
-    for (int col = lane * W; col < dim; col += 64 * W) store_row<VEC4, OUT_F32>(out, r * out_stride + col, zero, 1.0f);
-    return;
-  }
-  const int c = rb / EC, c_end = (re - 1) / EC;
-  if (c_end == c) return;                                   // finished by its chunk
-  const float scale = (!BWD && mean) ? 1.0f / (float)(re - rb) : 1.0f;
-  for (int col = lane * W; col < dim; col += 64 * W) {
-    f4 sum = zero;
-    if (VEC4) {
-      const float4 v = *reinterpret_cast<const float4*>(part + ((int64_t)c * 2 + 1) * dim + col);
-      sum.x = v.x; sum.y = v.y; sum.z = v.z; sum.w = v.w;
-#pragma unroll 4
-      for (int cc = c + 1; cc <= c_end; ++cc) {
-        const float4 u = *reinterpret_cast<const float4*>(part + ((int64_t)cc * 2) * dim + col);
-        sum.x += u.x; sum.y += u.y; sum.z += u.z; sum.w += u.w;
-      }
-    } else {
-      sum.x = part[((int64_t)c * 2 + 1) * dim + col];
-      for (int cc = c + 1; cc <= c_end; ++cc) sum.x += part[((int64_t)cc * 2) * dim + col];
-    }
-    store_row<VEC4, OUT_F32>(out, r * out_stride + col, sum, scale);
-  }
+  fixup<VEC4, OUT_F32>(SagePolicy<BWD>{nullptr, mean}, r, row_ptr, dim, part, out, out_stride, EC);
 }
 
 // ||h_j||_2 per row  (model.py:318-320)
@@ -247,15 +123,7 @@ __global__ void __launch_bounds__(SP_TPB) k_gather_rows_norm(const bf16_t* __res
 // (the same accumulation order as k_embed_norm).  The dropout bits come from a counter-based hash of (seed, launch
 // counter, element index): the same Bernoulli(1-p) law as torch's fused_dropout, a different (device-resident,
 // graph-replayable) random stream.  ctr[0] = launch counter, ctr[1] (and ctr[2..65]) = tickets: the last workgroup to finish bumps the
-// counter, so every workgroup of a launch has read the same value.
-__device__ __forceinline__ uint32_t drop_hash(uint32_t seed, uint32_t ctr, uint32_t idx) {
-  uint32_t x = idx * 0x9e3779b1u + seed;
-  x ^= ctr * 0x85ebca77u + 0x165667b1u;
-  x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;    // lowbias32 finaliser
-  x += ctr; x ^= x >> 15; x *= 0x2c1b3c6du; x ^= x >> 12;
-  return x;
-}
-
+// counter, so every workgroup of a launch has read the same value.  drop_hash: common.cuh.
 template <bool VEC4>
 __global__ void __launch_bounds__(SP_TPB) k_sage_epilogue(const bf16_t* __restrict__ a, int64_t a_stride, const bf16_t* __restrict__ b,
                                                          int64_t b_stride, int n_rows, int dim, uint32_t drop_thresh, float scale,
@@ -337,13 +205,20 @@ __global__ void __launch_bounds__(SP_TPB) k_sage_epilogue_bwd(const bf16_t* __re
   }
 }
 
+// What this launcher does differently from gcn.hip's launch_gcn_spmm, on purpose:
+//   * nnz == 0 launches ONE idle chunk of k_spmm (GCN launches no main kernel);
+//   * a device-side count is taken as it is, the caller keeps it >= 0 (GCN clamps a negative one to 0);
+//   * `part` is required only when nnz > EC (GCN: whenever nnz > 0);
+//   * the fix-up takes its VEC4 from vec4 AND the alignment of `part` (fv), the walk from vec4 alone (GCN folds the alignment
+//     of `part` into the one vec4 of both kernels);
+//   * n_rows <= 0 or dim <= 0 returns before anything is looked at.
 template <bool BWD>
 int launch_spmm(const int* row_ptr, const int* t_edge, const int* src, const int* dst, const int* blk_indptr, const void* w,
                 const void* h, int64_t h_stride, int n_rows, const int* nnz_dev, int nnz, int dim, int mean, void* out,
                 int64_t out_stride, int out_fp32, float* part, hipStream_t st) {
   if (n_rows <= 0 || dim <= 0) return 0;
-  const int EC = bliss_spmm_chunk_edges(nnz);
-  if (nnz > EC && !part) return BLISS_EINVAL;
+  const int EC = spmm_chunk_edges(nnz);
+  if (nnz > EC && !part) return BLISS_EINVAL;               // partials only when a row can be cut: more than one chunk
   const bool vec4 = (dim % 4 == 0) && (h_stride % 4 == 0) && (out_stride % 4 == 0) &&
                     (((uintptr_t)h) % 8 == 0) && (((uintptr_t)out) % (out_fp32 ? 16 : 8) == 0);
   const int nchunks = nnz > 0 ? (nnz + EC - 1) / EC : 1;
@@ -366,10 +241,7 @@ int launch_spmm(const int* row_ptr, const int* t_edge, const int* src, const int
 
 extern "C" {
 
-// A wave walks its chunk edge by edge (a dependent chain of broadcasts and row loads), so the chunk length trades
-// parallelism against per-chunk overhead: the sampled blocks of this path hold 2 K - 500 K edges, far too few for
-// 64-edge chunks to fill the chip: 64 edges per wave from 200 K edges up, 32 from 50 K, 16 below.
-int bliss_spmm_chunk_edges(int32_t nnz_bound) { return nnz_bound >= 200000 ? 64 : (nnz_bound >= 50000 ? 32 : 16); }
+int bliss_spmm_chunk_edges(int32_t nnz_bound) { return spmm_chunk_edges(nnz_bound); }
 
 int bliss_spmm_fwd(const int32_t* indptr, const int32_t* src, const int32_t* dst, const void* w, const void* h,
                    int64_t h_stride, int32_t n_dst, const int32_t* nnz_dev, int32_t nnz, int32_t dim, int mean, void* out,

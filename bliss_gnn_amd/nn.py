@@ -10,7 +10,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._engine import _stream
+from ._engine import _stream, spmm_partials
 
 
 def embed_norm(h):
@@ -771,8 +771,7 @@ def _gcn_spmm(backward, idx, w, ns, nd, h, n_rows, nnz_dev):
     indptr, src, dst, t_indptr, t_edge = idx
     B, D = int(src.numel()), h.shape[1]
     out = torch.empty(n_rows, D, dtype=torch.bfloat16, device=h.device)
-    ec = _lib.lib.bliss_spmm_chunk_edges(B)
-    part = torch.empty(max(2 * ((B + ec - 1) // ec) * D, 4), dtype=torch.float32, device=h.device)
+    part = spmm_partials(B, D, h.device, floor=4)
     wp = 0 if w is None else w.data_ptr()
     if backward:
         _lib.check(_lib.lib.bliss_gcn_spmm_bwd(t_indptr.data_ptr(), t_edge.data_ptr(), src.data_ptr(), dst.data_ptr(), wp, ns.data_ptr(),
@@ -1088,6 +1087,13 @@ def _nnz(block):
     return block._nnz_ptr, int(block.src.numel())
 
 
+def _gat_partials(B, HD, device, floor):
+    """The fp32 head / tail partials of the GAT kernels' balanced walk: two rows of HD per chunk of B edges, at least ``floor``
+    floats (4 where a kernel reads the buffer in 16-byte pieces)."""
+    n = 2 * (-(-B // _lib.lib.bliss_gat_chunk_edges())) * HD
+    return torch.empty(max(n, floor), dtype=torch.float32, device=device)
+
+
 class _GatLogits(torch.autograd.Function):
     """e[e,h] = attn[h,:] . leaky_relu(feat[src_e,h,:] + feat[dst_e,h,:])   (model.py:82-86)."""
 
@@ -1109,7 +1115,7 @@ class _GatLogits(torch.autograd.Function):
         de = de.contiguous().bfloat16()
         nnz_ptr, B = _nnz(block)
         K, S, HD = feat.shape[0], block.num_dst_nodes(), H * D
-        part = torch.empty(max(2 * (-(-B // _lib.lib.bliss_gat_chunk_edges())) * HD, 1), dtype=torch.float32, device=feat.device)
+        part = _gat_partials(B, HD, feat.device, 1)
         d_attn = torch.zeros(HD, dtype=torch.float32, device=feat.device)
         d_el = torch.empty(K, HD, dtype=torch.bfloat16, device=feat.device)
         d_er = torch.empty(S, HD, dtype=torch.bfloat16, device=feat.device)
@@ -1156,7 +1162,7 @@ class _GatAggregate(torch.autograd.Function):
         nnz_ptr, B = _nnz(block)
         S, HD = block.num_dst_nodes(), H * D
         out = torch.empty(S, HD, dtype=torch.bfloat16, device=feat.device)
-        part = torch.empty(max(2 * (-(-B // _lib.lib.bliss_gat_chunk_edges())) * HD, 1), dtype=torch.float32, device=feat.device)
+        part = _gat_partials(B, HD, feat.device, 1)
         _lib.check(_lib.lib.bliss_gat_rows(0, block.indptr.data_ptr(), S, 0, block.src.data_ptr(), block.dst.data_ptr(), nnz_ptr, B,
                                            a.data_ptr(), feat.data_ptr(), feat.stride(0), 0, H, D, 0.0, out.data_ptr(),
                                            out.stride(0), part.data_ptr(), 0, _stream()), "bliss_gat_rows")
@@ -1176,7 +1182,7 @@ class _GatAggregate(torch.autograd.Function):
                                                dout.data_ptr(), dout.stride(0), H, D, da.data_ptr(), _stream()), "bliss_gat_edge_dot")
         t_indptr, t_edge = block.transposed()
         d_feat = torch.empty(K, HD, dtype=torch.bfloat16, device=feat.device)
-        part = torch.empty(max(2 * (-(-B // _lib.lib.bliss_gat_chunk_edges())) * HD, 1), dtype=torch.float32, device=feat.device)
+        part = _gat_partials(B, HD, feat.device, 1)
         _lib.check(_lib.lib.bliss_gat_rows(1, t_indptr.data_ptr(), K, t_edge.data_ptr(), block.src.data_ptr(), block.dst.data_ptr(),
                                            nnz_ptr, B, a.data_ptr(), dout.data_ptr(), dout.stride(0), 0, H, D, 0.0,
                                            d_feat.data_ptr(), d_feat.stride(0), part.data_ptr(), 0, _stream()), "bliss_gat_rows")
@@ -1271,7 +1277,7 @@ class _GatFusedMP(torch.autograd.Function):
                    "bliss_gat_fused_bwd_dst")
         t_indptr, t_edge = block.transposed()
         d_feat = torch.empty(K, HD, dtype=torch.bfloat16, device=dev)
-        part = torch.empty(max(2 * (-(-B // _lib.lib.bliss_gat_chunk_edges())) * HD, 4), dtype=torch.float32, device=dev)
+        part = _gat_partials(B, HD, dev, 4)
         _lib.check(_lib.lib.bliss_gat_rows_src_fused(t_indptr.data_ptr(), K, t_edge.data_ptr(), block.src.data_ptr(), block.dst.data_ptr(), nnz_ptr, B,
                                                      de.data_ptr(), ad.data_ptr(), feat.data_ptr(), feat.stride(0), g.data_ptr(), g.stride(0),
                                                      attn_f.data_ptr(), H, D, ctx.slope, d_feat.data_ptr(), d_feat.stride(0), part.data_ptr(),
@@ -1593,7 +1599,7 @@ def gat_forward_f32(graph, feat, attn, H, D, slope):
     e = torch.empty(B, H, dtype=torch.float32, device=dev)
     a = torch.empty(B, H, dtype=torch.float32, device=dev)
     out = torch.empty(S, HD, dtype=torch.float32, device=dev)
-    part = torch.empty(max(2 * (-(-B // _lib.lib.bliss_gat_chunk_edges())) * HD, 1), dtype=torch.float32, device=dev)
+    part = _gat_partials(B, HD, dev, 1)
     _lib.check(_lib.lib.bliss_gat_logits_f32(graph.src.data_ptr(), graph.dst.data_ptr(), nnz_ptr, B, feat.data_ptr(), feat.stride(0),
                                              attn.data_ptr(), H, D, float(slope), e.data_ptr(), _stream()), "bliss_gat_logits_f32")
     _lib.check(_lib.lib.bliss_gat_edge_softmax(graph.indptr.data_ptr(), S, e.data_ptr(), 0, H, 2, a.data_ptr(), _stream()),

@@ -12,7 +12,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._engine import _stream
+from ._engine import _stream, spmm_partials
 
 
 def _p(t):
@@ -30,8 +30,7 @@ def spmm(indptr: Tensor, src: Tensor, dst: Tensor, w: Optional[Tensor], h: Tenso
     assert h.is_cuda and h.dtype == torch.bfloat16 and h.stride(1) == 1, "bf16 features on the GPU (load_graph.py:7)"
     B, D = int(src.numel()), h.shape[1]
     out = torch.empty(n_dst, D, dtype=torch.float32 if out_fp32 else torch.bfloat16, device=h.device)
-    ec = _lib.lib.bliss_spmm_chunk_edges(B)
-    part = torch.empty(2 * ((B + ec - 1) // ec) * D, dtype=torch.float32, device=h.device) if B > 0 else None
+    part = spmm_partials(B, D, h.device)
     _lib.check(_lib.lib.bliss_spmm_fwd(indptr.data_ptr(), src.data_ptr(), dst.data_ptr(), _p(w), h.data_ptr(), h.stride(0), n_dst,
                                        _nnz_ptr(counts), B, D, int(mean), out.data_ptr(), out.stride(0), int(out_fp32), _p(part),
                                        _stream()), "bliss_spmm_fwd")
@@ -49,8 +48,7 @@ def spmm_t(t_indptr: Tensor, t_edge: Tensor, src: Tensor, dst: Tensor, indptr: T
     """The transposed product: gh[j] = sum_{e : src_e = j} (w_e / deg_{dst_e} if mean) gout[dst_e]  (by-source index t_*)."""
     B, D = int(src.numel()), gout.shape[1]
     gh = torch.empty(n_src, D, dtype=torch.bfloat16, device=gout.device)
-    ec = _lib.lib.bliss_spmm_chunk_edges(B)
-    part = torch.empty(2 * ((B + ec - 1) // ec) * D, dtype=torch.float32, device=gout.device) if B > 0 else None
+    part = spmm_partials(B, D, gout.device)
     _lib.check(_lib.lib.bliss_spmm_bwd(t_indptr.data_ptr(), t_edge.data_ptr(), src.data_ptr(), dst.data_ptr(), indptr.data_ptr(), _p(w),
                                        gout.data_ptr(), gout.stride(0), n_src, _nnz_ptr(counts), B, D, int(mean), gh.data_ptr(),
                                        gh.stride(0), 0, _p(part), _stream()), "bliss_spmm_bwd")
