@@ -187,7 +187,13 @@ class BanditLadiesSampler(DeviceDraw, BlockSampler):
             self._w_pos = None
             return
         g = self._engine.g
-        self._w_pos = g.by_position(value.to(torch.bfloat16)).contiguous().clone()
+        value = value.to(torch.bfloat16)
+        # bliss_row_sum has no error word: what the exact row sum cannot hold (exp3.hip, row_digits) is refused here, where
+        # outside weights enter the state (a set-up path: the sync is fine)
+        v = value.float()
+        if not bool((torch.isfinite(v) & (v >= 0) & (v < 2.0 ** 24)).all()):
+            raise ValueError("exp3_weights must be finite, non-negative and below 2**24")
+        self._w_pos = g.by_position(value).contiguous().clone()
         L = self._w_pos.shape[0]
         self._row_sum = torch.zeros(L, 96, dtype=torch.int64, device=g.device)
         self._scratch = torch.zeros(L, 98, dtype=torch.int64, device=g.device)
