@@ -11,6 +11,7 @@ LIB_PATH = os.path.join(_HERE, "libbliss_gnn.so")
 
 EINVAL = -1
 MODE_BANDIT, MODE_LADIES, MODE_UNIFORM_NODES, MODE_PARTIALS = 0, 1, 4, 8
+WIDE_MAX_K = 16384                     # BLISS_WIDE_MAX_K: bliss_tile_gemm_wide / bliss_dgrad_wide walk K in panels up to here
 NR_MAX_FANOUT = 1024                   # BLISS_NR_MAX_FANOUT: bliss_neighbor_replace_layer orders a column's draws in LDS
 WN_RAW, WN_EXP3 = 0, 1                 # bliss_wneighbor_layer / bliss_wlabor_layer: probabilities as given / EXP3 weights
 
@@ -254,6 +255,7 @@ SIGNATURES = {
     "bliss_wlabor_layer": [C.POINTER(Graph), _P, _I32, _P, _I32, _I32, _P, C.c_uint64, _P, _I32, C.c_int, C.c_int, _I32, _P, _F, _F,
                            C.POINTER(LayerWs), C.POINTER(BlockOut), _P, _P, _P],
     "bliss_tile_gemm": [C.POINTER(TileGemm), C.POINTER(TileGemm), _P],
+    "bliss_tile_gemm_wide": [C.POINTER(TileGemm), C.POINTER(TileGemm), _P],
     "bliss_cross_entropy": [_P, _I64, _P, _I32, _I32, _P, _P, _I64, _P, _P, _P, _P],
     "bliss_cross_entropy_sum": [_P, _I64, _P, _I64, _P, _P, _I32, _I32, _P, _P, _I64, _P, _P, _P, _P],
     "bliss_cross_entropy_masked": [_P, _I64, _P, _I64, _P, _I32, _P, _I32, _I32, _P, _F, _I32, _P, _P, _I64, _P, _P, _P, _P],
@@ -294,6 +296,7 @@ SIGNATURES = {
     "bliss_sage_dgrad": [C.POINTER(DGrad), _P],
     "bliss_sage_wgrad": [C.POINTER(WGrad), _I32, _P, _I64, _P],
     "bliss_gat_dgrad": [C.POINTER(DGrad), _P],
+    "bliss_dgrad_wide": [C.POINTER(DGrad), _P],
     "bliss_gat_glue_fwd": [C.POINTER(GatGlue), _P],
     "bliss_gat_glue_bwd": [C.POINTER(GatGlue), _P],
     "bliss_gat_head_mean": [_P, _I32, _I32, _P, _P, _P],

@@ -70,7 +70,37 @@ __device__ __forceinline__ float row_sumsq(const bf16_t* sh, int dim, int vec4, 
 }
 
 // bf16 norms of this wave's rows of an LDS tile, each in k_embed_norm's summation order (row_sumsq), the rows side by side:
-// independent accumulators, so the LDS reads and the butterfly shuffles of the 8 rows overlap instead of queueing
+// independent accumulators, so the LDS reads and the butterfly shuffles of the 8 rows overlap instead of queueing.
+// rows_sumsq_add: the per-lane partial sums over `dim` staged columns (vec4: the 4-columns-per-lane walk); rows_norm_store: the
+// butterfly and the store.  A lane's columns are lane * 4 + 256 j (or lane + 64 j), so partial sums carried over column
+// panels whose width is a multiple of 256 add up in exactly the order of one walk over the whole row (k_tile_gemm_wide).
+#define TG_RPW (TG_M / TG_WAVES)
+__device__ __forceinline__ void rows_sumsq_add(float s[TG_RPW], const bf16_t* tile, int stride, int dim, bool vec4, int wave, int lane) {
+  if (vec4) {
+    for (int c = lane * 4; c < dim; c += 256)
+#pragma unroll
+      for (int q = 0; q < TG_RPW; ++q) {
+        const bf16_t* sh = tile + (size_t)(q * TG_WAVES + wave) * stride + c;
+        const float a = bf2f(sh[0]), b = bf2f(sh[1]), cc = bf2f(sh[2]), d = bf2f(sh[3]);
+        s[q] += a * a; s[q] += b * b; s[q] += cc * cc; s[q] += d * d;
+      }
+  } else {
+    for (int c = lane; c < dim; c += 64)
+#pragma unroll
+      for (int q = 0; q < TG_RPW; ++q) { const float a = bf2f(tile[(size_t)(q * TG_WAVES + wave) * stride + c]); s[q] += a * a; }
+  }
+}
+__device__ __forceinline__ void rows_norm_store(float s[TG_RPW], int row0, int M, int m_bound, bf16_t* __restrict__ out, int wave, int lane) {
+  for (int d = 32; d >= 1; d >>= 1)
+#pragma unroll
+    for (int q = 0; q < TG_RPW; ++q) s[q] += __shfl_xor(s[q], d);
+#pragma unroll
+  for (int q = 0; q < TG_RPW; ++q) {
+    const int r = row0 + q * TG_WAVES + wave;
+    if (lane == 0 && r < m_bound) out[r] = r < M ? f2bf(sqrtf(s[q])) : (bf16_t)0;
+  }
+}
+// (the narrow kernel's walk in one piece, kept as it was written so that k_tile_gemm compiles to the code it always had)
 __device__ __forceinline__ void rows_norm(const bf16_t* tile, int stride, int dim, int row0, int M, int m_bound, bf16_t* __restrict__ out,
                                           int wave, int lane) {
   constexpr int RPW = TG_M / TG_WAVES;
@@ -260,6 +290,12 @@ __device__ __forceinline__ void mma_product(WRegs& ga, WRegs& gb, const bf16_t* 
   }
 }
 
+// WIDE (k_tile_gemm_wide): K is walked in panels of TG_PANEL columns, ONE operand panel in LDS at a time (66 KB at any K); the
+// accumulators and the norm's partial sums stay in registers across the panels and across both products.  The k order is the
+// narrow kernel's (ascending 16-steps, operand 1 first), a panel boundary is a slab boundary, and one panel IS the narrow walk:
+// at K <= TG_PANEL both kernels give the same bits.
+#define TG_PANEL 1024
+template <bool WIDE>
 __device__ __forceinline__ void tile_gemm_body(const TileGemm& p, bf16_t* lds, int* row_id, int dbg) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   int M = p.m_bound;
@@ -279,44 +315,82 @@ __device__ __forceinline__ void tile_gemm_body(const TileGemm& p, bf16_t* lds, i
     }
     return;
   }
-  const int s1 = lds_stride(p.k1), s2 = p.k2 ? lds_stride(p.k2) : 0;
-  bf16_t* t1 = lds;
-  bf16_t* t2 = lds + (size_t)TG_M * s1;
   const int n0 = wave * 32 * TG_NB;
-  bf16_t* wl = lds + (size_t)TG_M * (s1 + s2);              // the W slab behind the staged rows
   float bias_v[TG_NB];
 #pragma unroll
   for (int nb = 0; nb < TG_NB; ++nb) bias_v[nb] = 0.f;
 #pragma unroll
   for (int nb = 0; nb < TG_NB; ++nb) { const int col = n0 + 32 * nb + (lane & 31); if (p.bias && col < N) bias_v[nb] = bf2f(p.bias[col]); }
-  // the first two W slabs depend on nothing: requested now, they arrive while the rows are gathered
   WRegs ga, gb;
-  {
-    const int nf = w_full_slabs(p.w1, p.w1_stride, p.k1);
-    if (nf > 0) w_slab_load_full(ga, p.w1, p.w1_stride, N, 0, tid);
-    if (nf > 1) w_slab_load_full(gb, p.w1, p.w1_stride, N, 1, tid);
-  }
-  if (tid < TG_M) {
-    const int r = row0 + tid;
-    row_id[tid] = r < M ? (p.ids ? p.ids[r] : r) : -1;
-    row_id[TG_M + tid] = r < M ? r : -1;
-  }
-  __syncthreads();
-  if (!(dbg & 1)) stage_rows(p.a1, p.a1_stride, row_id, p.k1, row0, p.m_bound, t1, s1, p.a_copy, p.copy_stride, wave, lane);
-  if (p.k2) stage_rows(p.a2, p.a2_stride, row_id + TG_M, p.k2, row0, p.m_bound, t2, s2, nullptr, 0, wave, lane);
-  __syncthreads();
-  if (p.in_norm && !(dbg & 4)) rows_norm(t1, s1, p.k1, row0, M, p.m_bound, p.in_norm, wave, lane);   // model.py:318-320 of THIS layer
   f32x16_t acc[TG_NB];
+  if constexpr (WIDE) {
+    const int kmax = p.k1 > p.k2 ? p.k1 : p.k2;
+    bf16_t* wl = lds + (size_t)TG_M * lds_stride(kmax < TG_PANEL ? kmax : TG_PANEL);     // the W slab behind the one staged panel
+    if (tid < TG_M) {
+      const int r = row0 + tid;
+      row_id[tid] = r < M ? (p.ids ? p.ids[r] : r) : -1;
+      row_id[TG_M + tid] = r < M ? r : -1;
+    }
 #pragma unroll
-  for (int m = 0; m < TG_NB; ++m)
+    for (int m = 0; m < TG_NB; ++m)
 #pragma unroll
-    for (int i = 0; i < 16; ++i) acc[m][i] = 0.f;
-  if (!(dbg & 2)) mma_product(ga, gb, t1, s1, p.k1, p.w1, p.w1_stride, n0, N, wl, tid, lane, acc);
-  if (p.k2) {
-    const int nf = w_full_slabs(p.w2, p.w2_stride, p.k2);
-    if (nf > 0) w_slab_load_full(ga, p.w2, p.w2_stride, N, 0, tid);
-    if (nf > 1) w_slab_load_full(gb, p.w2, p.w2_stride, N, 1, tid);
-    mma_product(ga, gb, t2, s2, p.k2, p.w2, p.w2_stride, n0, N, wl, tid, lane, acc);
+      for (int i = 0; i < 16; ++i) acc[m][i] = 0.f;
+    float ss[TG_RPW];
+#pragma unroll
+    for (int q = 0; q < TG_RPW; ++q) ss[q] = 0.f;
+    const bool vec4 = p.k1 % 4 == 0;                        // (on the full row length, as k_embed_norm chooses)
+    for (int op = 0; op < (p.k2 ? 2 : 1); ++op) {
+      const bf16_t* a = op ? p.a2 : p.a1;
+      const bf16_t* w = op ? p.w2 : p.w1;
+      const long long a_stride = op ? p.a2_stride : p.a1_stride, w_stride = op ? p.w2_stride : p.w1_stride;
+      const int K = op ? p.k2 : p.k1;
+      for (int c0 = 0; c0 < K; c0 += TG_PANEL) {
+        // every fast-path predicate below is taken on the panel's own base pointer and width
+        const int pw = K - c0 < TG_PANEL ? K - c0 : TG_PANEL, st = lds_stride(pw);
+        const int nf = w_full_slabs(w + c0, w_stride, pw);
+        if (nf > 0) w_slab_load_full(ga, w + c0, w_stride, N, 0, tid);
+        if (nf > 1) w_slab_load_full(gb, w + c0, w_stride, N, 1, tid);
+        __syncthreads();                                    // every wave has multiplied the previous panel (first panel: row_id is set)
+        stage_rows(a + c0, a_stride, row_id + op * TG_M, pw, row0, p.m_bound, lds, st, (op == 0 && p.a_copy) ? p.a_copy + c0 : nullptr,
+                   p.copy_stride, wave, lane);
+        __syncthreads();
+        if (op == 0 && p.in_norm) rows_sumsq_add(ss, lds, st, pw, vec4, wave, lane);
+        mma_product(ga, gb, lds, st, pw, w + c0, w_stride, n0, N, wl, tid, lane, acc);
+      }
+      if (op == 0 && p.in_norm) rows_norm_store(ss, row0, M, p.m_bound, p.in_norm, wave, lane);   // model.py:318-320 of THIS layer
+    }
+  } else {
+    const int s1 = lds_stride(p.k1), s2 = p.k2 ? lds_stride(p.k2) : 0;
+    bf16_t* t1 = lds;
+    bf16_t* t2 = lds + (size_t)TG_M * s1;
+    bf16_t* wl = lds + (size_t)TG_M * (s1 + s2);              // the W slab behind the staged rows
+    // the first two W slabs depend on nothing: requested now, they arrive while the rows are gathered
+    {
+      const int nf = w_full_slabs(p.w1, p.w1_stride, p.k1);
+      if (nf > 0) w_slab_load_full(ga, p.w1, p.w1_stride, N, 0, tid);
+      if (nf > 1) w_slab_load_full(gb, p.w1, p.w1_stride, N, 1, tid);
+    }
+    if (tid < TG_M) {
+      const int r = row0 + tid;
+      row_id[tid] = r < M ? (p.ids ? p.ids[r] : r) : -1;
+      row_id[TG_M + tid] = r < M ? r : -1;
+    }
+    __syncthreads();
+    if (!(dbg & 1)) stage_rows(p.a1, p.a1_stride, row_id, p.k1, row0, p.m_bound, t1, s1, p.a_copy, p.copy_stride, wave, lane);
+    if (p.k2) stage_rows(p.a2, p.a2_stride, row_id + TG_M, p.k2, row0, p.m_bound, t2, s2, nullptr, 0, wave, lane);
+    __syncthreads();
+    if (p.in_norm && !(dbg & 4)) rows_norm(t1, s1, p.k1, row0, M, p.m_bound, p.in_norm, wave, lane);   // model.py:318-320 of THIS layer
+#pragma unroll
+    for (int m = 0; m < TG_NB; ++m)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) acc[m][i] = 0.f;
+    if (!(dbg & 2)) mma_product(ga, gb, t1, s1, p.k1, p.w1, p.w1_stride, n0, N, wl, tid, lane, acc);
+    if (p.k2) {
+      const int nf = w_full_slabs(p.w2, p.w2_stride, p.k2);
+      if (nf > 0) w_slab_load_full(ga, p.w2, p.w2_stride, N, 0, tid);
+      if (nf > 1) w_slab_load_full(gb, p.w2, p.w2_stride, N, 1, tid);
+      mma_product(ga, gb, t2, s2, p.k2, p.w2, p.w2_stride, n0, N, wl, tid, lane, acc);
+    }
   }
   __syncthreads();                                          // every wave is done reading the staged rows: reuse the LDS for the output tile
   const int so = ((N + 63) & ~63) + 8;
@@ -352,12 +426,8 @@ __device__ __forceinline__ void tile_gemm_body(const TileGemm& p, bf16_t* lds, i
   if (p.out_norm) rows_norm(ot, so, N, row0, M, p.m_bound, p.out_norm, wave, lane);
 }
 
-__global__ void __launch_bounds__(TG_TPB) k_tile_gemm(TileGemm p0, TileGemm p1, int n_sets, int dbg) {
-  extern __shared__ __attribute__((aligned(16))) bf16_t tg_lds[];
-  __shared__ int row_id[2 * TG_M];
-  if (dbg & 8) return;
-  tile_gemm_body(blockIdx.y == 0 ? p0 : p1, tg_lds, row_id, dbg);
-  // dropout stream: the last workgroup of the launch bumps the device-resident launch counter (everybody has read it)
+// dropout stream: the last workgroup of the launch bumps the device-resident launch counter (everybody has read it)
+__device__ __forceinline__ void bump_drop_counter(const TileGemm& p0, const TileGemm& p1, int n_sets) {
   unsigned long long* ctr = p0.drop_thresh ? p0.ctr : (n_sets > 1 && p1.drop_thresh ? p1.ctr : nullptr);
   if (ctr) {
     __syncthreads();
@@ -371,9 +441,38 @@ __global__ void __launch_bounds__(TG_TPB) k_tile_gemm(TileGemm p0, TileGemm p1, 
   }
 }
 
-bool convert(const bliss_tile_gemm_t* a, TileGemm* p, size_t* lds_bytes, int* tiles) {
-  if (!a->a1 || !a->w1 || !a->out || a->k1 <= 0 || a->k1 > 1024 || a->n <= 0 || a->n > 256 || a->m_bound <= 0) return false;
-  if (a->k2 < 0 || a->k2 > 1024 || (a->k2 > 0 && (!a->a2 || !a->w2))) return false;
+__global__ void __launch_bounds__(TG_TPB) k_tile_gemm(TileGemm p0, TileGemm p1, int n_sets, int dbg) {
+  extern __shared__ __attribute__((aligned(16))) bf16_t tg_lds[];
+  __shared__ int row_id[2 * TG_M];
+  if (dbg & 8) return;
+  tile_gemm_body<false>(blockIdx.y == 0 ? p0 : p1, tg_lds, row_id, dbg);
+  bump_drop_counter(p0, p1, n_sets);
+}
+
+// (the wide body reads its arguments inside the panel loops: a set chosen field by field stays in scalar registers, where a
+// reference chosen by blockIdx.y put both sets into scratch memory)
+__device__ __forceinline__ TileGemm pick_set(const TileGemm& a, const TileGemm& b, bool first) {
+  TileGemm p;
+#define TG_PICK(f) p.f = first ? a.f : b.f
+  TG_PICK(a1); TG_PICK(a1_stride); TG_PICK(ids); TG_PICK(w1); TG_PICK(w1_stride); TG_PICK(k1);
+  TG_PICK(a2); TG_PICK(a2_stride); TG_PICK(w2); TG_PICK(w2_stride); TG_PICK(k2); TG_PICK(bias);
+  TG_PICK(m_bound); TG_PICK(m_dev); TG_PICK(n); TG_PICK(out); TG_PICK(out_stride); TG_PICK(a_copy); TG_PICK(copy_stride);
+  TG_PICK(in_norm); TG_PICK(out_norm); TG_PICK(relu); TG_PICK(drop_thresh); TG_PICK(drop_scale); TG_PICK(seed); TG_PICK(ctr);
+#undef TG_PICK
+  return p;
+}
+
+__global__ void __launch_bounds__(TG_TPB) k_tile_gemm_wide(TileGemm p0, TileGemm p1, int n_sets) {
+  extern __shared__ __attribute__((aligned(16))) bf16_t tg_lds[];
+  __shared__ int row_id[2 * TG_M];
+  tile_gemm_body<true>(pick_set(p0, p1, blockIdx.y == 0), tg_lds, row_id, 0);
+  bump_drop_counter(p0, p1, n_sets);
+}
+
+bool convert(const bliss_tile_gemm_t* a, TileGemm* p, size_t* lds_bytes, int* tiles, bool wide) {
+  const int k_max = wide ? BLISS_WIDE_MAX_K : 1024;
+  if (!a->a1 || !a->w1 || !a->out || a->k1 <= 0 || a->k1 > k_max || a->n <= 0 || a->n > 256 || a->m_bound <= 0) return false;
+  if (a->k2 < 0 || a->k2 > k_max || (a->k2 > 0 && (!a->a2 || !a->w2))) return false;
   if (a->drop_p < 0.f || a->drop_p >= 1.f || (a->drop_p > 0.f && !a->drop_ctr)) return false;
   p->a1 = (const bf16_t*)a->a1; p->a1_stride = a->a1_stride; p->ids = a->ids;
   p->w1 = (const bf16_t*)a->w1; p->w1_stride = a->w1_stride; p->k1 = a->k1;
@@ -384,32 +483,45 @@ bool convert(const bliss_tile_gemm_t* a, TileGemm* p, size_t* lds_bytes, int* ti
   p->drop_thresh = a->drop_p > 0.f ? (unsigned)((double)a->drop_p * 4294967296.0) : 0u;
   p->drop_scale = a->drop_p > 0.f ? 1.0f / (1.0f - a->drop_p) : 1.0f;
   p->seed = a->drop_seed; p->ctr = (unsigned long long*)a->drop_ctr;
-  const size_t stage = ((size_t)TG_M * (lds_stride(a->k1) + (a->k2 ? lds_stride(a->k2) : 0)) + (size_t)TG_WROWS * TG_WSTRIDE) * sizeof(bf16_t);
+  const int k_wide = a->k1 > a->k2 ? a->k1 : a->k2;       // wide: one panel of the wider operand at a time
+  const size_t rows = wide ? (size_t)lds_stride(k_wide < TG_PANEL ? k_wide : TG_PANEL) : (size_t)lds_stride(a->k1) + (a->k2 ? lds_stride(a->k2) : 0);
+  const size_t stage = ((size_t)TG_M * rows + (size_t)TG_WROWS * TG_WSTRIDE) * sizeof(bf16_t);
   const size_t outt = (size_t)TG_M * (((a->n + 63) & ~63) + 8) * sizeof(bf16_t);
   *lds_bytes = stage > outt ? stage : outt;
   *tiles = (a->m_bound + TG_M - 1) / TG_M;
   return true;
 }
 
-}  // namespace
-
-extern "C" int bliss_tile_gemm(const bliss_tile_gemm_t* first, const bliss_tile_gemm_t* second, void* stream) {
+template <typename Kernel, typename... Dbg>
+int tile_gemm_launch(Kernel kernel, size_t* lds_set, bool wide, const bliss_tile_gemm_t* first, const bliss_tile_gemm_t* second, void* stream, Dbg... dbg) {
   if (!first) return BLISS_EINVAL;
   TileGemm p0, p1;
   size_t l0 = 0, l1 = 0;
   int t0 = 0, t1 = 0;
-  if (!convert(first, &p0, &l0, &t0)) return BLISS_EINVAL;
+  if (!convert(first, &p0, &l0, &t0, wide)) return BLISS_EINVAL;
   p1 = p0;
-  if (second && !convert(second, &p1, &l1, &t1)) return BLISS_EINVAL;
+  if (second && !convert(second, &p1, &l1, &t1, wide)) return BLISS_EINVAL;
   const size_t lds = l0 > l1 ? l0 : l1;
   if (lds > 160 * 1024) return BLISS_EINVAL;
-  static size_t lds_set = 0;
-  if (lds > lds_set) {
-    if (hipFuncSetAttribute((const void*)k_tile_gemm, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return BLISS_EINVAL;
-    lds_set = lds;
+  if (lds > *lds_set) {
+    if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return BLISS_EINVAL;
+    *lds_set = lds;
   }
   const dim3 grid(t0 > t1 ? t0 : t1, second ? 2 : 1);
-  static const int dbg = []() { const char* e = getenv("BLISS_TG_DEBUG"); return e ? atoi(e) : 0; }();
-  k_tile_gemm<<<grid, TG_TPB, lds, (hipStream_t)stream>>>(p0, p1, second ? 2 : 1, dbg);
+  kernel<<<grid, TG_TPB, lds, (hipStream_t)stream>>>(p0, p1, second ? 2 : 1, dbg...);
   return (int)hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" int bliss_tile_gemm(const bliss_tile_gemm_t* first, const bliss_tile_gemm_t* second, void* stream) {
+  static size_t lds_set = 0;
+  static const int dbg = []() { const char* e = getenv("BLISS_TG_DEBUG"); return e ? atoi(e) : 0; }();
+  return tile_gemm_launch(k_tile_gemm, &lds_set, false, first, second, stream, dbg);
+}
+
+// The same walk with K in panels (tile_gemm_body<true>): k1, k2 <= BLISS_WIDE_MAX_K, one panel in LDS at any K.
+extern "C" int bliss_tile_gemm_wide(const bliss_tile_gemm_t* first, const bliss_tile_gemm_t* second, void* stream) {
+  static size_t lds_set = 0;
+  return tile_gemm_launch(k_tile_gemm_wide, &lds_set, true, first, second, stream);
 }

@@ -115,8 +115,12 @@ __device__ __forceinline__ void dg_product(const bf16_t* tile, int k, const bf16
   }
 }
 
-__global__ void __launch_bounds__(DG_TPB) k_dgrad(DGrad p) {
-  extern __shared__ __attribute__((aligned(16))) bf16_t dg_lds[];
+// WIDE (k_dgrad_wide): k is walked in panels of DG_PANEL columns of A (= rows of W, which is [k][n] here), ONE operand panel in
+// LDS at a time; the accumulator stays in registers across the panels and across both products.  The k order is the narrow
+// kernel's (ascending 16-steps, operand 1 first) and a panel boundary is a slab boundary: at k <= DG_PANEL the bits are equal.
+#define DG_PANEL 1024
+template <bool WIDE>
+__device__ __forceinline__ void dgrad_body(const DGrad& p, bf16_t* dg_lds) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   int M = p.m_bound;
   if (p.m_dev) { const int t = *p.m_dev; M = t < M ? t : M; }
@@ -133,18 +137,38 @@ __global__ void __launch_bounds__(DG_TPB) k_dgrad(DGrad p) {
     }
     return;
   }
-  const int s1 = dg_astride(p.k1), s2 = p.k2 ? dg_astride(p.k2) : 0;
-  bf16_t* t1 = dg_lds;
-  bf16_t* t2 = t1 + (size_t)DG_M * s1;
-  bf16_t* wl = t2 + (size_t)DG_M * s2;
-  dg_stage_a(p.a1, p.a1_stride, p.k1, row0, M, t1, tid);
   const bool second = p.k2 && row0 < M2;               // (workgroup-uniform)
-  if (second) dg_stage_a(p.a2, p.a2_stride, p.k2, row0, M2, t2, tid);
   f32x16_t acc;
+  if constexpr (WIDE) {
+    const int kmax = p.k1 > p.k2 ? p.k1 : p.k2;
+    bf16_t* wl = dg_lds + (size_t)DG_M * dg_astride(kmax < DG_PANEL ? kmax : DG_PANEL);   // the W slab behind the one staged panel
 #pragma unroll
-  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-  dg_product(t1, p.k1, p.w1, p.w1_stride, N, n0, wl, tid, lane, wave, acc);
-  if (second) dg_product(t2, p.k2, p.w2, p.w2_stride, N, n0, wl, tid, lane, wave, acc);
+    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+    for (int op = 0; op < (second ? 2 : 1); ++op) {
+      const bf16_t* a = op ? p.a2 : p.a1;
+      const bf16_t* w = op ? p.w2 : p.w1;
+      const long long a_stride = op ? p.a2_stride : p.a1_stride, w_stride = op ? p.w2_stride : p.w1_stride;
+      const int K = op ? p.k2 : p.k1, Mop = op ? M2 : M;
+      for (int c0 = 0; c0 < K; c0 += DG_PANEL) {
+        // the alignment predicates of dg_stage_a / dg_stage_w are taken on the panel's own base pointers
+        const int pw = K - c0 < DG_PANEL ? K - c0 : DG_PANEL;
+        if (op || c0) __syncthreads();                 // every wave has multiplied the previous panel: its tile may be overwritten
+        dg_stage_a(a + c0, a_stride, pw, row0, Mop, dg_lds, tid);
+        dg_product(dg_lds, pw, w + (long long)c0 * w_stride, w_stride, N, n0, wl, tid, lane, wave, acc);
+      }
+    }
+  } else {
+    const int s1 = dg_astride(p.k1), s2 = p.k2 ? dg_astride(p.k2) : 0;
+    bf16_t* t1 = dg_lds;
+    bf16_t* t2 = t1 + (size_t)DG_M * s1;
+    bf16_t* wl = t2 + (size_t)DG_M * s2;
+    dg_stage_a(p.a1, p.a1_stride, p.k1, row0, M, t1, tid);
+    if (second) dg_stage_a(p.a2, p.a2_stride, p.k2, row0, M2, t2, tid);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+    dg_product(t1, p.k1, p.w1, p.w1_stride, N, n0, wl, tid, lane, wave, acc);
+    if (second) dg_product(t2, p.k2, p.w2, p.w2_stride, N, n0, wl, tid, lane, wave, acc);
+  }
   __syncthreads();                                     // every wave is done with the staged rows: reuse the LDS for the output tile
   const int so = 256 + 8;
   bf16_t* ot = dg_lds;
@@ -166,6 +190,16 @@ __global__ void __launch_bounds__(DG_TPB) k_dgrad(DGrad p) {
     if (pair_ok && (n0 % 2 == 0)) { for (int c = lane * 2; c < nn; c += 128) *reinterpret_cast<uint32_t*>(o + c) = *reinterpret_cast<const uint32_t*>(sh + c); }
     else for (int c = lane; c < nn; c += 64) o[c] = sh[c];
   }
+}
+
+__global__ void __launch_bounds__(DG_TPB) k_dgrad(DGrad p) {
+  extern __shared__ __attribute__((aligned(16))) bf16_t dg_lds[];
+  dgrad_body<false>(p, dg_lds);
+}
+
+__global__ void __launch_bounds__(DG_TPB) k_dgrad_wide(DGrad p) {
+  extern __shared__ __attribute__((aligned(16))) bf16_t dg_lds[];
+  dgrad_body<true>(p, dg_lds);
 }
 
 // ------------------------------------------------------------------------------------------------------------------ wgrad
@@ -356,7 +390,8 @@ bool wgrad_plan(const bliss_wgrad_t* a, int n_probs, WGradLaunch* L, long long* 
   return true;
 }
 
-int dgrad_launch(const bliss_dgrad_t* a, int k_max, void* stream) {
+template <typename Kernel>
+int dgrad_launch(Kernel kernel, size_t* lds_set, bool wide, const bliss_dgrad_t* a, int k_max, void* stream) {
   if (!a || !a->a1 || !a->w1 || !a->out || a->k1 <= 0 || a->k1 > k_max || a->n <= 0 || a->m_bound <= 0) return BLISS_EINVAL;
   if (a->k2 < 0 || a->k2 > k_max || (a->k2 > 0 && (!a->a2 || !a->w2 || a->m2_bound <= 0))) return BLISS_EINVAL;
   DGrad p;
@@ -365,30 +400,40 @@ int dgrad_launch(const bliss_dgrad_t* a, int k_max, void* stream) {
   p.m2_bound = a->m2_bound; p.m2_dev = a->m2_dev;
   p.m_bound = a->m_bound; p.m_dev = a->m_dev; p.n = a->n;
   p.out = (bf16_t*)a->out; p.out_stride = a->out_stride;
-  const size_t stage = ((size_t)DG_M * (dg_astride(a->k1) + (a->k2 ? dg_astride(a->k2) : 0)) + (size_t)DG_SLAB * DG_WSTRIDE) * sizeof(bf16_t);
+  const int k_wide = a->k1 > a->k2 ? a->k1 : a->k2;       // wide: one panel of the wider operand at a time
+  const size_t rows = wide ? (size_t)dg_astride(k_wide < DG_PANEL ? k_wide : DG_PANEL) : (size_t)dg_astride(a->k1) + (a->k2 ? dg_astride(a->k2) : 0);
+  const size_t stage = ((size_t)DG_M * rows + (size_t)DG_SLAB * DG_WSTRIDE) * sizeof(bf16_t);
   const size_t outt = (size_t)DG_M * (256 + 8) * sizeof(bf16_t);
   const size_t lds = stage > outt ? stage : outt;
   if (lds > 160 * 1024) return BLISS_EINVAL;
-  static size_t lds_set = 0;
-  if (lds > lds_set) {
-    if (hipFuncSetAttribute((const void*)k_dgrad, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return BLISS_EINVAL;
-    lds_set = lds;
+  if (lds > *lds_set) {
+    if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return BLISS_EINVAL;
+    *lds_set = lds;
   }
   const dim3 grid((a->m_bound + DG_M - 1) / DG_M, (a->n + 255) / 256);
-  k_dgrad<<<grid, DG_TPB, lds, (hipStream_t)stream>>>(p);
+  kernel<<<grid, DG_TPB, lds, (hipStream_t)stream>>>(p);
   return (int)hipGetLastError();
 }
+
+size_t g_dgrad_lds_set = 0;                              // bliss_sage_dgrad and bliss_gat_dgrad share k_dgrad and so its LDS attribute
 
 }  // namespace
 
 extern "C" {
 
-int bliss_sage_dgrad(const bliss_dgrad_t* a, void* stream) { return dgrad_launch(a, 256, stream); }
+int bliss_sage_dgrad(const bliss_dgrad_t* a, void* stream) { return dgrad_launch(k_dgrad, &g_dgrad_lds_set, false, a, 256, stream); }
 
 // The same kernel with its k-loop run further: k1, k2 <= 1024 (a GATv2 layer's H*D gradient columns).  k_dgrad
 // walks k in 64-row slabs of W and keeps all of a row tile's k columns in LDS, so the limit is the LDS a workgroup may hold:
 // BLISS_EINVAL when the two staged operands and a W slab pass 160 KiB (k1 + k2 above ~1900: the caller then launches twice).
-int bliss_gat_dgrad(const bliss_dgrad_t* a, void* stream) { return dgrad_launch(a, 1024, stream); }
+int bliss_gat_dgrad(const bliss_dgrad_t* a, void* stream) { return dgrad_launch(k_dgrad, &g_dgrad_lds_set, false, a, 1024, stream); }
+
+// The same walk with k in panels (dgrad_body<true>): k1, k2 <= BLISS_WIDE_MAX_K, one operand panel in LDS at any k, so the 160 KiB
+// check never refuses and wide k1 + k2 need no second launch.
+int bliss_dgrad_wide(const bliss_dgrad_t* a, void* stream) {
+  static size_t lds_set = 0;
+  return dgrad_launch(k_dgrad_wide, &lds_set, true, a, BLISS_WIDE_MAX_K, stream);
+}
 
 int64_t bliss_sage_wgrad_workspace(const bliss_wgrad_t* probs, int32_t n_probs) {
   WGradLaunch L;

@@ -7,7 +7,7 @@ runs the SAGEConv layers with the sampler's edge weights (model.py:321-329).
 import torch
 import torch.nn as nn
 
-from .nn import SAGEConv, embed_norm, sage_epilogue
+from .nn import TILE_KINDS, SAGEConv, embed_norm, sage_epilogue
 
 
 def _gathered_norm(blocks, x):
@@ -20,8 +20,16 @@ def _gathered_norm(blocks, x):
 class SAGE(nn.Module):
     """model.py:292-383."""
 
-    def __init__(self, in_feats, n_hidden, n_classes, n_layers, activation, dropout):
+    # "auto": the fused MFMA path when every layer is within the tile kernel's limits (in <= 1024, out <= 256), else -- silently --
+    # library GEMMs.  "wide" (DESIGN.md section 29): in_feats up to nn.TILE_WIDE_MAX_K on the K-panelled tile kernel, and
+    # NotImplementedError naming the reason where the MFMA path cannot be taken: no silent fall-back.
+    SAGE_TRANSFORMS = ("auto", "wide")
+
+    def __init__(self, in_feats, n_hidden, n_classes, n_layers, activation, dropout, transforms="auto"):
         super().__init__()
+        if transforms not in self.SAGE_TRANSFORMS:
+            raise ValueError("transforms must be one of %r, not %r" % (self.SAGE_TRANSFORMS, transforms))
+        self.transforms = transforms
         self.n_layers, self.n_hidden, self.n_classes = n_layers, n_hidden, n_classes
         self.layers = nn.ModuleList()
         if n_layers > 1:
@@ -62,9 +70,39 @@ class SAGE(nn.Module):
             return False
         act = self.activation
         relu = act in (torch.relu, torch.nn.functional.relu) or isinstance(act, nn.ReLU)
-        dims = all(tile_gemm_ok(l._in_src_feats, l._out_feats) and l.fc_self.bias is not None and l.norm is None and l.activation is None
+        wide = self.transforms == "wide"
+        dims = all(tile_gemm_ok(l._in_src_feats, l._out_feats, wide) and l.fc_self.bias is not None and l.norm is None and l.activation is None
                    and l.feat_drop.p == 0 for l in self.layers)
+        if wide and not all(q.is_cuda and q.dtype == torch.bfloat16 for q in self.parameters()):
+            return False                                   # ("auto" rounds other parameters to bf16 per launch, as it always has)
         return relu and dims and x.is_cuda and x.dtype == torch.bfloat16 and isinstance(self.dropout, nn.Dropout)
+
+    def mfma_refusal(self, x):
+        """Why the MFMA path cannot take ``x`` (a tensor or LazyRows of the input rows, or a parameter), or None."""
+        import os
+        from .nn import TILE_GEMM_MAX_N, TILE_WIDE_MAX_K, tile_gemm_ok
+        if self._mfma_ok(x):
+            return None
+        what = 'SAGE: transforms="%s"' % self.transforms
+        if os.environ.get("BLISS_SAGE_MFMA", "1") == "0":
+            return "%s runs on the MFMA kernels (BLISS_SAGE_MFMA=0 is set)" % what
+        bad = [q for q in [x] + list(self.parameters()) if not (q.is_cuda and q.dtype == torch.bfloat16)]
+        if bad:
+            return "%s takes bf16 features and parameters on the GPU, not %s on %s" % (what, bad[0].dtype, bad[0].device)
+        wide = self.transforms == "wide"
+        for l, layer in enumerate(self.layers):
+            if not tile_gemm_ok(layer._in_src_feats, layer._out_feats, wide):
+                return ("SAGE layer %d: transforms=\"%s\" takes in_feats <= %d and out_feats <= %d, this layer has %d -> %d"
+                        % (l, self.transforms, TILE_WIDE_MAX_K if wide else 1024, TILE_GEMM_MAX_N, layer._in_src_feats, layer._out_feats))
+        return "%s covers ReLU, nn.Dropout and plain SAGEConv layers with a bias (no norm, activation or feat_drop of their own)" % what
+
+    def _mfma_path(self, x):
+        """Does this forward run on the MFMA kernels?  Under "wide" the answer is yes or an error, never the library path."""
+        if self._mfma_ok(x):
+            return True
+        if self.transforms == "wide":
+            raise NotImplementedError(self.mfma_refusal(x))
+        return False
 
     def _layers_mfma(self, blocks, h, norm, lo, hi, parts=False):
         """model.py:312-333, layers lo..hi-1, with the Linear layers on hand-written MFMA tiles: per W-first layer ONE launch
@@ -85,7 +123,8 @@ class SAGE(nn.Module):
             fc_n, fc_s = layer.fc_neigh, layer.fc_self
             if layer._in_src_feats > layer._out_feats:                           # fc_neigh before the aggregation
                 table, ids = (h.table, h.ids) if isinstance(h, LazyRows) else (h, None)
-                z, y, _rows, in_norm = _SageLinearPair.apply(table, ids, fc_n.weight, fc_s.weight, fc_s.bias, K_b, S_b, src_dev, dst_dev)
+                z, y, _rows, in_norm = _SageLinearPair.apply(table, ids, fc_n.weight, fc_s.weight, fc_s.bias, K_b, S_b, src_dev, dst_dev,
+                                                             self.transforms == "wide")
                 block.srcdata["embed_norm"] = in_norm if norm is None else norm  # model.py:318-320 (same bits either way)
                 agg = weighted_aggregate(block, z, ew, mean=True)
                 if last:
@@ -135,7 +174,7 @@ class SAGE(nn.Module):
         return self._layers_plain(blocks, x, norm, lo, hi)
 
     def forward(self, blocks, x):
-        return self._layers(blocks, x, None, 0, len(self.layers), self._mfma_ok(x))[0]
+        return self._layers(blocks, x, None, 0, len(self.layers), self._mfma_path(x))[0]
 
     # The bandit update (sampler.exp3) reads every block's INPUT row norms (model.py:318-320) and nothing the output layer
     # computes, so a training loop may run forward_hidden -> exp3 -> next batch's sampler and leave forward_last + loss +
@@ -145,7 +184,7 @@ class SAGE(nn.Module):
         n = len(self.layers)
         if n < 2:
             raise ValueError("forward_hidden needs at least one hidden layer")
-        mfma = self._mfma_ok(x)
+        mfma = self._mfma_path(x)
         h, norm = self._layers(blocks, x, None, 0, n - 1, mfma)
         if norm is None:
             norm = embed_norm(h)
@@ -228,7 +267,7 @@ class GCN(nn.Module):
             raise ValueError("transforms must be one of %r, not %r" % (GCN_TRANSFORMS, transforms))
         # "tile" (DESIGN.md section 26): the layers on the bounded kernels of csrc/gcn.hip and the MFMA entry points, the model's
         # dropout inside each layer's epilogue launch -- the path that runs under a batch capacity; "library": the launches and
-        # bits of before
+        # bits of before; "wide" (section 29): "tile" with in_feats up to nn.TILE_WIDE_MAX_K
         self.transforms = transforms
         self.n_layers, self.n_hidden, self.n_classes = n_layers, n_hidden, n_classes
         mk = lambda i, o, act: GraphConv(i, o, activation=act, allow_zero_in_degree=True, transforms=transforms)
@@ -271,7 +310,7 @@ class GCN(nn.Module):
         return h
 
     def forward(self, blocks, x):
-        if self.transforms == "tile":
+        if self.transforms in TILE_KINDS:
             return self._forward_tile(blocks, x)
         h, norm = x, _gathered_norm(blocks, x)
         for l, (layer, block) in enumerate(zip(self.layers, blocks)):
@@ -416,7 +455,8 @@ class GATv2(nn.Module):
         if transforms not in GAT_TRANSFORMS:
             raise ValueError("transforms must be one of %r, not %r" % (GAT_TRANSFORMS, transforms))
         # "tile" (DESIGN.md section 22): the dense transforms on the MFMA tile kernels and the glue between the layers in one
-        # bounded launch per direction -- the path that runs under a batch capacity; "library": the launches and bits of before
+        # bounded launch per direction -- the path that runs under a batch capacity; "library": the launches and bits of before;
+        # "wide" (section 29): "tile" with in_dim up to nn.TILE_WIDE_MAX_K
         self.transforms = transforms
         self.num_layers, self.activation = num_layers, activation
         self.num_hidden, self.num_classes, self.heads = num_hidden, num_classes, heads
@@ -449,7 +489,7 @@ class GATv2(nn.Module):
             raise ValueError("%d blocks for %d layers" % (len(blocks), len(self.gatv2_layers)))
         why = self.tile_refusal()
         if why is None and not (inputs.is_cuda and inputs.dtype == torch.bfloat16):
-            why = 'GATv2: transforms="tile" takes bf16 features on the GPU'
+            why = 'GATv2: transforms="%s" takes bf16 features on the GPU' % self.transforms
         if why is not None:
             raise NotImplementedError(why)
         n = len(blocks)
@@ -470,7 +510,7 @@ class GATv2(nn.Module):
         return h_drop
 
     def forward(self, blocks, inputs):
-        if self.transforms == "tile":
+        if self.transforms in TILE_KINDS:
             return self._forward_tile(blocks, inputs)
         h = inputs.bfloat16()
         norm = _gathered_norm(blocks, h)
@@ -559,7 +599,7 @@ class GATv2(nn.Module):
             why = self.csc_refusal(g, h)
             if path == "csc" and why is not None:
                 raise NotImplementedError(why)
-            path = "csc" if (why is None and (path == "csc" or self.transforms == "tile")) else "blocks"
+            path = "csc" if (why is None and (path == "csc" or self.transforms in TILE_KINDS)) else "blocks"
         was_training = self.training
         self.eval()                                                                                            # :265
         try:

@@ -360,6 +360,9 @@ class BCEWithLogitsLoss(nn.Module):
 
 # ------------------------------------------------------------------------------------------------ MFMA tile GEMM (csrc/sage.hip)
 TILE_GEMM_MAX_K, TILE_GEMM_MAX_N = 1024, 256
+# transforms="wide" (DESIGN.md section 29): a product whose reduction passes TILE_GEMM_MAX_K walks it in panels of that many
+# columns (bliss_tile_gemm_wide, bliss_dgrad_wide); a product within it keeps the entry point, launches and bits it always had
+TILE_WIDE_MAX_K = _lib.WIDE_MAX_K
 
 
 class LazyRows:
@@ -398,8 +401,14 @@ def _tg_args(a1, w1, out, m_bound, ids=None, a2=None, w2=None, bias=None, m_dev=
     return t
 
 
-def _tile_gemm(first, second=None):
+def _tile_gemm(first, second=None, wide=False):
+    """One launch for one or two argument sets.  ``wide``: a launch with a reduction past TILE_GEMM_MAX_K goes to the K-panelled
+    entry point; every other launch is bliss_tile_gemm's, wide or not."""
     import ctypes as C
+    sets = [first] + ([] if second is None else [second])
+    if wide and any(max(t.k1, t.k2) > TILE_GEMM_MAX_K for t in sets):
+        _lib.check(_lib.lib.bliss_tile_gemm_wide(C.byref(first), None if second is None else C.byref(second), _stream()), "bliss_tile_gemm_wide")
+        return
     _lib.check(_lib.lib.bliss_tile_gemm(C.byref(first), None if second is None else C.byref(second), _stream()), "bliss_tile_gemm")
 
 
@@ -467,7 +476,7 @@ class _SageLinearPair(torch.autograd.Function):
     the fly.  Returns (Z [K, out], Y [S, out], the input rows [K, in], their bf16 norms [K])."""
 
     @staticmethod
-    def forward(ctx, x, ids, w_neigh, w_self, b_self, n_src, n_dst, src_dev, dst_dev):
+    def forward(ctx, x, ids, w_neigh, w_self, b_self, n_src, n_dst, src_dev, dst_dev, wide=False):
         ctx.set_materialize_grads(False)          # (else autograd zero-fills a gradient for `rows`: 13 MB on the input layer)
         x, wn, ws = _bf16c(x), _bf16c(w_neigh), _bf16c(w_self)
         dev, n_out = x.device, wn.shape[0]
@@ -476,7 +485,7 @@ class _SageLinearPair(torch.autograd.Function):
         norm = torch.empty(n_src, dtype=torch.bfloat16, device=dev)
         rows = torch.empty(n_src, x.shape[1], dtype=torch.bfloat16, device=dev) if ids is not None else x
         _tile_gemm(_tg_args(x, wn, z, n_src, ids=ids, m_dev=src_dev, a_copy=rows if ids is not None else None, in_norm=norm),
-                   _tg_args(x, ws, y, n_dst, ids=ids, bias=b_self, m_dev=dst_dev))
+                   _tg_args(x, ws, y, n_dst, ids=ids, bias=b_self, m_dev=dst_dev), wide=wide)
         ctx.save_for_backward(rows, wn, ws)
         ctx.gathered, ctx.n_dst, ctx.has_bias = ids is not None, n_dst, b_self is not None
         ctx.n_src, ctx.src_dev, ctx.dst_dev = n_src, src_dev, dst_dev
@@ -498,7 +507,7 @@ class _SageLinearPair(torch.autograd.Function):
                 dx = sage_dgrad(dz, wn, ctx.n_src, ctx.src_dev, a2=dy, w2=ws, m2_bound=ctx.n_dst, m2_dev=ctx.dst_dev)
                 if _drows is not None:
                     dx = dx + _drows
-            return dx, None, d_wn, d_ws, d_b, None, None, None, None
+            return dx, None, d_wn, d_ws, d_b, None, None, None, None, None
         if dz is not None:
             dz = _bf16c(dz)
             d_wn = _weight_grad(dz, rows)
@@ -514,7 +523,7 @@ class _SageLinearPair(torch.autograd.Function):
                 dx[: ctx.n_dst].addmm_(dy, ws)                                   # (the GEMM accumulates: no separate add)
         if _drows is not None and want_dx:
             dx = _drows if dx is None else dx + _drows
-        return dx, None, d_wn, d_ws, d_b, None, None, None, None
+        return dx, None, d_wn, d_ws, d_b, None, None, None, None, None
 
 
 class _SageLinearSplit(torch.autograd.Function):
@@ -709,8 +718,8 @@ def sage_agg_dual(block, h, edge_weight, w_neigh, w_self, bias, relu, p, ctr, se
                               bias, relu, p, ctr, seed, rows_dev)
 
 
-def tile_gemm_ok(in_feats, out_feats):
-    return in_feats <= TILE_GEMM_MAX_K and out_feats <= TILE_GEMM_MAX_N
+def tile_gemm_ok(in_feats, out_feats, wide=False):
+    return in_feats <= (TILE_WIDE_MAX_K if wide else TILE_GEMM_MAX_K) and out_feats <= TILE_GEMM_MAX_N
 
 
 class SAGEConv(nn.Module):
@@ -758,7 +767,10 @@ class SAGEConv(nn.Module):
 # transforms="tile" (DESIGN.md section 26): GraphConv(norm='both') on bounded kernels -- the degree-normalised SpMM of csrc/gcn.hip,
 # the dense products on the MFMA entry points with the operand roles swapped (weight stays [in, out]) and one row-wise epilogue
 # launch per direction; every loop that crosses rows or edges is bounded by the block's device-side counts.
-GCN_TRANSFORMS = ("library", "tile")
+# transforms="wide" (DESIGN.md section 29): everything "tile" is, with in_feats up to TILE_WIDE_MAX_K -- the one product whose
+# reduction is in_feats walks it in panels when it passes TILE_GEMM_MAX_K; a layer within 1024 has the launches and bits of "tile".
+GCN_TRANSFORMS = ("library", "tile", "wide")
+TILE_KINDS = ("tile", "wide")            # the values of ``transforms`` that take the bounded-kernel branch
 
 
 def _is_relu(act):
@@ -809,7 +821,7 @@ class _GcnLayer(torch.autograd.Function):
     SpMM, dX on bliss_tile_gemm, dW = X^T dY on bliss_sage_wgrad -- all bound by the block's device-side counts."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, idx, ew, n_src, n_dst, words, relu, p, state, want_norm):
+    def forward(ctx, x, weight, bias, idx, ew, n_src, n_dst, words, relu, p, state, want_norm, wide=False):
         import ctypes as C
         ctx.set_materialize_grads(False)
         x, w = _bf16c(x), _bf16c(weight)
@@ -823,7 +835,7 @@ class _GcnLayer(torch.autograd.Function):
         w_first = w.shape[0] > w.shape[1]
         if w_first:
             kept = x
-            a = _gcn_spmm(False, idx, ew, ns, nd, gat_dgrad(x, w, n_src, src_dev), n_dst, nnz_dev)
+            a = _gcn_spmm(False, idx, ew, ns, nd, gat_dgrad(x, w, n_src, src_dev, wide=wide), n_dst, nnz_dev)    # (k = in_feats)
         else:
             kept = _gcn_spmm(False, idx, ew, ns, nd, x, n_dst, nnz_dev)
             a = gat_dgrad(kept, w, n_dst, dst_dev)
@@ -848,7 +860,7 @@ class _GcnLayer(torch.autograd.Function):
         idx = tuple(ctx.saved_tensors[7:])
         w_first, n_src, n_dst, words, relu, p, state, has_bias, x_rows = ctx.cfg
         if dout is None:
-            return (None,) * 12
+            return (None,) * 13
         dst_dev, src_dev, nnz_dev = words
         dout = _bf16c(dout)
         dev, width = dout.device, w.shape[1]
@@ -875,7 +887,7 @@ class _GcnLayer(torch.autograd.Function):
                 dx = _gcn_spmm(True, idx, ew, ns, nd, _gcn_xwt(g, w, n_dst, dst_dev), n_src, nnz_dev)
         if dx is not None and x_rows > n_src:
             dx = torch.cat([dx, _zero_rows(x_rows - n_src, dx)])
-        return (dx, dw, db) + (None,) * 9
+        return (dx, dw, db) + (None,) * 10
 
 
 # Full-neighbour inference of GraphConv(norm='both') straight off the graph's CSC (csrc/gcn_infer.hip): the
@@ -980,17 +992,22 @@ class GraphConv(nn.Module):
 
     def tile_refusal(self, what="GraphConv"):
         """Why this layer cannot take the tile path, or None: the limits that do not depend on the input tensor."""
+        wide = self.transforms == "wide"
         for name, n in (("in_feats", self._in_feats), ("out_feats", self._out_feats)):
-            if n > TILE_GEMM_MAX_K:
-                return ('%s: transforms="tile" takes %s <= %d (the MFMA kernels keep a row tile\'s k columns in LDS), this layer has '
-                        '%d; build it with transforms="library"' % (what, name, TILE_GEMM_MAX_K, n))
+            if wide and name == "in_feats":                # (out_feats is the k of _gcn_xwt and of the aggregate-first product)
+                if n > TILE_WIDE_MAX_K:
+                    return ('%s: transforms="wide" takes in_feats <= %d (the K-panelled MFMA kernels), this layer has %d; build it '
+                            'with transforms="library"' % (what, TILE_WIDE_MAX_K, n))
+            elif n > TILE_GEMM_MAX_K:
+                return ('%s: transforms="%s" takes %s <= %d (the MFMA kernels keep a row tile\'s k columns in LDS), this layer has '
+                        '%d; build it with transforms="library"' % (what, self.transforms, name, TILE_GEMM_MAX_K, n))
         if not (self._activation is None or _is_relu(self._activation)):
-            return '%s: transforms="tile" covers the activations ReLU and None, not %r' % (what, self._activation)
+            return '%s: transforms="%s" covers the activations ReLU and None, not %r' % (what, self.transforms, self._activation)
         if not _mfma_bwd_on():
-            return "%s: transforms=\"tile\" needs the MFMA backward (BLISS_SAGE_MFMA_BWD=0 is set)" % what
+            return "%s: transforms=\"%s\" needs the MFMA backward (BLISS_SAGE_MFMA_BWD=0 is set)" % (what, self.transforms)
         ps = [self.weight] + ([self.bias] if self.bias is not None else [])
         if not all(q.is_cuda and q.dtype == torch.bfloat16 for q in ps):
-            return '%s: transforms="tile" takes bf16 parameters on the GPU' % what
+            return '%s: transforms="%s" takes bf16 parameters on the GPU' % (what, self.transforms)
         return None
 
     def tile_forward(self, graph, feat, edge_weight=None, p=0.0, want_norm=False, what="GraphConv"):
@@ -999,7 +1016,7 @@ class GraphConv(nn.Module):
         live destination count come out as zeros."""
         why = self.tile_refusal(what)
         if why is None and not (torch.is_tensor(feat) and feat.is_cuda and feat.dtype == torch.bfloat16 and feat.dim() == 2):
-            why = '%s: transforms="tile" takes bf16 features [rows, in_feats] on the GPU' % what
+            why = '%s: transforms="%s" takes bf16 features [rows, in_feats] on the GPU' % (what, self.transforms)
         if why is not None:
             raise NotImplementedError(why)
         K, S = graph.num_src_nodes(), graph.num_dst_nodes()
@@ -1015,14 +1032,14 @@ class GraphConv(nn.Module):
         p = float(p)
         return _GcnLayer.apply(feat, self.weight, self.bias, (graph.indptr, graph.src, graph.dst, t_indptr, t_edge), ew, K, S,
                                _block_words(graph), self._activation is not None, p, self._drop_state(feat.device) if p > 0 else None,
-                               bool(want_norm))
+                               bool(want_norm), self.transforms == "wide")
 
     # -- full-neighbour inference off the graph's CSC -------------------------------------------------
     def infer_refusal(self, h_all, what="GraphConv"):
         """Why ``infer_transform`` / ``infer_rows`` / ``infer_finish`` cannot run on these input rows, or None."""
         if not (torch.is_tensor(h_all) and h_all.is_cuda and h_all.dtype == torch.bfloat16 and h_all.dim() == 2):
             return "%s: the CSC inference path takes bf16 rows on the GPU, not %s on %s" % (what, h_all.dtype, h_all.device)
-        if self.transforms != "tile":
+        if self.transforms not in TILE_KINDS:
             return ('%s: the CSC inference path has the bits of the bounded kernels; build the layer with transforms="tile" '
                     "(this one is %r)" % (what, self.transforms))
         return self.tile_refusal(what)
@@ -1031,7 +1048,7 @@ class GraphConv(nn.Module):
         """The [V, dim] table the range SpMM gathers from: ``h W`` over ALL rows in one launch for a weight-first layer
         (bliss_gat_dgrad: a row's bits do not depend on how many rows the launch has), the input itself otherwise."""
         if self._in_feats > self._out_feats:
-            return gat_dgrad(_bf16c(h_all), _bf16c(self.weight.detach()), h_all.shape[0])
+            return gat_dgrad(_bf16c(h_all), _bf16c(self.weight.detach()), h_all.shape[0], wide=self.transforms == "wide")
         return _bf16c(h_all)
 
     def infer_rows(self, g, batch_size, row0, row1, edge0, n_edges, ns, table, out):
@@ -1052,9 +1069,9 @@ class GraphConv(nn.Module):
         return out
 
     def forward(self, graph, feat, weight=None, edge_weight=None):
-        if self.transforms == "tile":
+        if self.transforms in TILE_KINDS:
             if weight is not None:
-                raise NotImplementedError('GraphConv: transforms="tile" multiplies by the layer\'s own weight')
+                raise NotImplementedError('GraphConv: transforms="%s" multiplies by the layer\'s own weight' % self.transforms)
             return self.tile_forward(graph, feat, edge_weight)[0]
         n_dst = graph.num_dst_nodes()
         src, ones = graph.src, None
@@ -1350,7 +1367,9 @@ def gat_infer_layer(indptr, indices, row0, row1, n_edges, feat, attn, H, D, slop
 # transforms="tile" (DESIGN.md section 22): fc_src / res_fc on the MFMA tile kernels, the glue around the message passing in one
 # launch per direction (csrc/gat_glue.hip) -- every loop that crosses rows is bounded by the block's device-side counts, so the
 # layers run on a capacity-padded output block (train.GraphedTrainStep(batch_capacity=...)).
-GAT_TRANSFORMS = ("library", "tile")
+# transforms="wide" (DESIGN.md section 29): "tile" with in_feats up to TILE_WIDE_MAX_K (fc_src / res_fc of a wide input layer on
+# bliss_tile_gemm_wide); a layer within 1024 has the launches and bits of "tile".
+GAT_TRANSFORMS = ("library", "tile", "wide")
 
 
 def _block_words(block):
@@ -1371,9 +1390,10 @@ def _dgrad_fits(k1, k2):
     return 2 * (32 * (st(k1) + st(k2)) + 64 * (256 + 32)) <= 160 * 1024
 
 
-def gat_dgrad(a1, w1, m_bound, m_dev=0, a2=None, w2=None, m2_bound=0, m2_dev=0):
+def gat_dgrad(a1, w1, m_bound, m_dev=0, a2=None, w2=None, m2_bound=0, m2_dev=0, wide=False):
     """sage_dgrad for gradient rows of up to 1024 columns (bliss_gat_dgrad): out[r] = a1[r] @ w1 (+ a2[r] @ w2 for r < m2), fp32
-    accumulation over all of it, one rounding; zero rows at or past the counts."""
+    accumulation over all of it, one rounding; zero rows at or past the counts.  ``wide``: rows of more than 1024 columns (up
+    to TILE_WIDE_MAX_K) go to bliss_dgrad_wide; a product within 1024 stays on bliss_gat_dgrad, wide or not."""
     import ctypes as C
     out = torch.empty(m_bound, w1.shape[1], dtype=torch.bfloat16, device=a1.device)
     t = _lib.DGrad()
@@ -1383,6 +1403,9 @@ def gat_dgrad(a1, w1, m_bound, m_dev=0, a2=None, w2=None, m2_bound=0, m2_dev=0):
         t.m2_bound, t.m2_dev = int(m2_bound), int(m2_dev)
     t.m_bound, t.m_dev, t.n = int(m_bound), int(m_dev), w1.shape[1]
     t.out, t.out_stride = out.data_ptr(), out.stride(0)
+    if wide and max(t.k1, t.k2) > TILE_GEMM_MAX_K:
+        _lib.check(_lib.lib.bliss_dgrad_wide(C.byref(t), _stream()), "bliss_dgrad_wide")
+        return out
     _lib.check(_lib.lib.bliss_gat_dgrad(C.byref(t), _stream()), "bliss_gat_dgrad")
     return out
 
@@ -1428,19 +1451,20 @@ class _GatLinear(torch.autograd.Function):
     fp32 accumulator when they fit)."""
 
     @staticmethod
-    def forward(ctx, x, w1, b1, n1, dev1, w2, b2, n2, dev2):
+    def forward(ctx, x, w1, b1, n1, dev1, w2, b2, n2, dev2, wide=False):
         ctx.set_materialize_grads(False)
         x, w1 = _bf16c(x), _bf16c(w1)
         w2 = None if w2 is None else _bf16c(w2)
-        if x.shape[1] > TILE_GEMM_MAX_K or x.shape[0] < n1 or (w2 is not None and n2 > n1):
-            raise ValueError("_GatLinear: in_feats <= %d, n2 <= n1 <= rows" % TILE_GEMM_MAX_K)
+        k_max = TILE_WIDE_MAX_K if wide else TILE_GEMM_MAX_K
+        if x.shape[1] > k_max or x.shape[0] < n1 or (w2 is not None and n2 > n1):
+            raise ValueError("_GatLinear: in_feats <= %d, n2 <= n1 <= rows" % k_max)
         y1 = torch.empty(n1, w1.shape[0], dtype=torch.bfloat16, device=x.device)
         y2 = None if w2 is None else torch.empty(n2, w2.shape[0], dtype=torch.bfloat16, device=x.device)
         sets = [_tg_args(x, w1[c0:c1], y1[:, c0:c1], n1, bias=None if b1 is None else b1[c0:c1], m_dev=dev1) for c0, c1 in _col_blocks(w1.shape[0])]
         if w2 is not None:
             sets += [_tg_args(x, w2[c0:c1], y2[:, c0:c1], n2, bias=None if b2 is None else b2[c0:c1], m_dev=dev2) for c0, c1 in _col_blocks(w2.shape[0])]
         for i in range(0, len(sets), 2):
-            _tile_gemm(sets[i], sets[i + 1] if i + 1 < len(sets) else None)
+            _tile_gemm(sets[i], sets[i + 1] if i + 1 < len(sets) else None, wide=wide)
         ctx.save_for_backward(x, w1, w2)
         ctx.n1, ctx.dev1, ctx.n2, ctx.dev2, ctx.has_b1, ctx.has_b2 = n1, dev1, n2, dev2, b1 is not None, b2 is not None
         return y1, y2
@@ -1472,12 +1496,12 @@ class _GatLinear(torch.autograd.Function):
                         dx[: ctx.n2] += dx2
             if x.shape[0] > ctx.n1:
                 dx = torch.cat([dx, _zero_rows(x.shape[0] - ctx.n1, dx)])
-        return dx, dw1, db1, None, None, dw2, db2, None, None
+        return dx, dw1, db1, None, None, dw2, db2, None, None, None
 
 
-def gat_linear(x, w, b, n_rows, rows_dev=0, w2=None, b2=None, n2_rows=0, rows2_dev=0):
-    """``_GatLinear``: (x[:n_rows] @ w^T + b, x[:n2_rows] @ w2^T + b2 or None)."""
-    return _GatLinear.apply(x, w, b, int(n_rows), int(rows_dev), w2, b2, int(n2_rows), int(rows2_dev))
+def gat_linear(x, w, b, n_rows, rows_dev=0, w2=None, b2=None, n2_rows=0, rows2_dev=0, wide=False):
+    """``_GatLinear``: (x[:n_rows] @ w^T + b, x[:n2_rows] @ w2^T + b2 or None).  ``wide``: in_feats up to TILE_WIDE_MAX_K."""
+    return _GatLinear.apply(x, w, b, int(n_rows), int(rows_dev), w2, b2, int(n2_rows), int(rows2_dev), bool(wide))
 
 
 def gat_drop_state(salt, device):
@@ -1674,15 +1698,19 @@ class GATv2Conv(nn.Module):
 
     def tile_refusal(self, what="GATv2Conv"):
         """Why this layer cannot take the tile path, or None: the limits that do not depend on the input tensor."""
-        H, D = self._num_heads, self._out_feats
-        if self._in > TILE_GEMM_MAX_K:
+        H, D, kind = self._num_heads, self._out_feats, self.transforms
+        if kind == "wide":
+            if self._in > TILE_WIDE_MAX_K:
+                return ('%s: transforms="wide" takes in_feats <= %d (the K-panelled tile kernel), this layer has %d; build it with '
+                        'transforms="library"' % (what, TILE_WIDE_MAX_K, self._in))
+        elif self._in > TILE_GEMM_MAX_K:
             return ('%s: transforms="tile" takes in_feats <= %d (the tile kernel keeps a row tile\'s K columns in LDS), this layer '
                     'has %d; build it with transforms="library"' % (what, TILE_GEMM_MAX_K, self._in))
         if not _gat_fused_on(H, D):
-            return ('%s: transforms="tile" runs on the fused message-passing kernels (bliss_gat_fused_supported(%d, %d) is false or '
-                    'BLISS_GAT_FUSED=0)' % (what, H, D))
+            return ('%s: transforms="%s" runs on the fused message-passing kernels (bliss_gat_fused_supported(%d, %d) is false or '
+                    'BLISS_GAT_FUSED=0)' % (what, kind, H, D))
         if not _mfma_bwd_on():
-            return "%s: transforms=\"tile\" needs the MFMA backward (BLISS_SAGE_MFMA_BWD=0 is set)" % what
+            return "%s: transforms=\"%s\" needs the MFMA backward (BLISS_SAGE_MFMA_BWD=0 is set)" % (what, kind)
         try:
             _glue_act(self.activation, what)
         except NotImplementedError as e:
@@ -1692,7 +1720,7 @@ class GATv2Conv(nn.Module):
     def _tile_check(self, feat, what):
         why = self.tile_refusal(what)
         if why is None and not (feat.is_cuda and feat.dtype == torch.bfloat16 and self.fc_src.weight.dtype == torch.bfloat16):
-            why = '%s: transforms="tile" takes bf16 features and parameters on the GPU' % what
+            why = '%s: transforms="%s" takes bf16 features and parameters on the GPU' % (what, self.transforms)
         if why is not None:
             raise NotImplementedError(why)
 
@@ -1716,7 +1744,8 @@ class GATv2Conv(nn.Module):
         dst_dev, src_dev, _ = _block_words(graph)
         lin = isinstance(self.res_fc, nn.Linear)
         feat_src, res = gat_linear(h_src, self.fc_src.weight, self.fc_src.bias, K, src_dev,
-                                   self.res_fc.weight if lin else None, self.res_fc.bias if lin else None, S if lin else 0, dst_dev if lin else 0)
+                                   self.res_fc.weight if lin else None, self.res_fc.bias if lin else None, S if lin else 0, dst_dev if lin else 0,
+                                   wide=self.transforms == "wide")
         if self.res_fc is not None and not lin:
             res = h_src[:S]                                                      # nn.Identity (in_feats == H * D)
         p_drop = float(self.attn_drop.p) if self.training else 0.0
@@ -1729,8 +1758,8 @@ class GATv2Conv(nn.Module):
         why = _gat_infer_refusal(h_all, self._num_heads, self._out_feats, what)
         if why is None and self.fc_src.weight.dtype != torch.bfloat16:
             why = "%s: the CSC inference path takes bf16 parameters" % what
-        if why is None and self.transforms == "tile" and self._in > TILE_GEMM_MAX_K:
-            why = self.tile_refusal(what)
+        if why is None and self.transforms in TILE_KINDS and self._in > TILE_GEMM_MAX_K:
+            why = self.tile_refusal(what)                  # ("wide": None up to TILE_WIDE_MAX_K)
         if why is None:
             try:
                 _glue_act(self.activation, what)
@@ -1743,10 +1772,10 @@ class GATv2Conv(nn.Module):
         ``transforms="tile"`` layer (a row's bits do not depend on how many rows the launch has), on nn.Linear otherwise.
         An identity residual is the input itself."""
         lin = isinstance(self.res_fc, nn.Linear)
-        if self.transforms == "tile":
+        if self.transforms in TILE_KINDS:
             V = h_all.shape[0]
             feat_src, res = gat_linear(h_all, self.fc_src.weight, self.fc_src.bias, V, 0, self.res_fc.weight if lin else None,
-                                       self.res_fc.bias if lin else None, V if lin else 0, 0)
+                                       self.res_fc.bias if lin else None, V if lin else 0, 0, wide=self.transforms == "wide")
         else:
             feat_src, res = self.fc_src(h_all), (self.res_fc(h_all) if lin else None)
         if self.res_fc is not None and not lin:
@@ -1769,7 +1798,7 @@ class GATv2Conv(nn.Module):
 
     def forward(self, graph, feat, edge_weight=None, get_attention=False):
         H, D, S = self._num_heads, self._out_feats, graph.num_dst_nodes()
-        if self.transforms == "tile":
+        if self.transforms in TILE_KINDS:
             return self._forward_tile(graph, feat, get_attention)
         if not self._allow_zero_in_degree and bool((graph.in_degrees() == 0).any()):
             raise RuntimeError("There are 0-in-degree nodes in the graph (model.py:49-61); build the layer with "

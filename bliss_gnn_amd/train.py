@@ -129,19 +129,19 @@ def _live_refusal(model):
     count hold whatever the buffers held: only a path whose every row loop is bounded by the block's device-side counts keeps
     them out of the weight gradients (0 * NaN is NaN)."""
     from .model import GATv2, GCN, SAGE
-    from .nn import _mfma_bwd_on
+    from .nn import TILE_KINDS, _mfma_bwd_on
     if isinstance(model, GCN):
-        if model.transforms != "tile":
+        if model.transforms not in TILE_KINDS:
             return ('GCN runs live on its bounded kernels only: with transforms="library" its layers run over all capacity rows of '
                     'the output block; build it with GCN(..., transforms="tile") (DESIGN.md section 26)')
         return model.tile_refusal()
     if isinstance(model, GATv2):
-        if model.transforms != "tile":
+        if model.transforms not in TILE_KINDS:
             return ('GATv2 runs live on its bounded kernels only: with transforms="library" its layers run over all capacity rows of '
                     'the output block; build it with GATv2(..., transforms="tile") (DESIGN.md section 22)')
         ps = list(model.parameters())
         if not ps or not all(p.is_cuda and p.dtype == torch.bfloat16 for p in ps):
-            return 'GATv2(transforms="tile") takes bf16 parameters on the GPU'
+            return 'GATv2(transforms="%s") takes bf16 parameters on the GPU' % model.transforms
         return model.tile_refusal()
     if not isinstance(model, SAGE):
         return ("%s has no live path: its layers run over all capacity rows of the output block (only SAGE on its MFMA path, "

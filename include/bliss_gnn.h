@@ -552,6 +552,17 @@ typedef struct {
   int32_t relu; float drop_p; uint32_t drop_seed; void* drop_ctr;
 } bliss_tile_gemm_t;
 int bliss_tile_gemm(const bliss_tile_gemm_t* first, const bliss_tile_gemm_t* second_or_null, void* stream);
+/* bliss_tile_gemm with 1 <= k1 <= BLISS_WIDE_MAX_K and 0 <= k2 <= BLISS_WIDE_MAX_K (a Cora-like input layer: 1433 columns); every other
+ * limit and argument check is bliss_tile_gemm's (n <= 256, BLISS_EINVAL before any launch).  A workgroup walks K in panels of 1024
+ * columns, the last one shorter, ONE operand panel in LDS at a time (66 KB plus the W slab at any K); the fp32 accumulators stay in
+ * registers across the panels and across both products, one rounding to bf16 at the end.  The k order is bliss_tile_gemm's with
+ * unbounded LDS: ascending 16-steps, operand 1 before operand 2.  At k1, k2 <= 1024 it runs one panel per operand and returns the
+ * BITS of bliss_tile_gemm on the same arguments (out, in_norm, out_norm, a_copy, zero rows, dropout from an equal counter) -- also
+ * where bliss_tile_gemm refuses k1 + k2 for its LDS.  in_norm is bit-equal to bliss_embed_norm of the rows at every K (per-lane
+ * partial sums carried over the panels, one butterfly), a_copy receives every panel.  The alignment fast paths are chosen per
+ * panel on the panel's base pointer and width: a misaligned or odd-length operand changes no bit (it is staged element-wise). */
+#define BLISS_WIDE_MAX_K 16384
+int bliss_tile_gemm_wide(const bliss_tile_gemm_t* first, const bliss_tile_gemm_t* second_or_null, void* stream);
 
 /* The BACKWARD products of those Linear layers on the matrix cores (csrc/sage_bwd.hip) -- what autograd derives for
  * fc_neigh / fc_self of dglnn.SAGEConv (model.py:303-308, 321-329); W = [out, in] as nn.Linear stores it.
@@ -574,6 +585,11 @@ int bliss_sage_dgrad(const bliss_dgrad_t* args, void* stream);
  * heads * head_dim columns (csrc/sage_bwd.hip: the same kernel, its k-loop run further; the existing entry point and its bits are
  * untouched).  BLISS_EINVAL when both staged operands and a W slab do not fit a workgroup's 160 KiB of LDS. */
 int bliss_gat_dgrad(const bliss_dgrad_t* args, void* stream);
+/* The same kernel with its k walked in panels of 1024 (rows of W, which is [k, n] here): 1 <= k1 <= BLISS_WIDE_MAX_K,
+ * 0 <= k2 <= BLISS_WIDE_MAX_K, one operand panel in LDS at a time, so no k1 + k2 is refused for LDS.  The weight-first forward product
+ * of a wide input layer (A = the feature rows, k = in_feats) and any out = A . W with a long reduction.  Same argument checks, same k
+ * order; at k1, k2 <= 1024 the bits of bliss_gat_dgrad. */
+int bliss_dgrad_wide(const bliss_dgrad_t* args, void* stream);
 typedef struct {
   const void* d; int64_t d_stride; int32_t n_out;
   const void* x; int64_t x_stride; int32_t k_in;
