@@ -395,7 +395,7 @@ void plan_shape(int cap_total, RngPlan* p) {
   const char* serial = getenv("BLISS_RNG_SERIAL");
   if ((serial && serial[0] == '1') || need <= p->b0 + 16) { p->n_stretch = 0; p->J = 0; p->total_blocks = need; return; }
   const int rest = need - p->b0;
-  int n = (rest + 7) / 8;                                // >= 8 blocks per stretch; at most 32 stretches
+  int n = (rest + 7) / 8;                                // 6 .. 8 blocks per stretch (rest >= 17), until 32 stretches: then longer ones
   if (n > 32) n = 32;
   p->n_stretch = n;
   p->J = (rest + n - 1) / n;

@@ -7,19 +7,7 @@ import pytest
 import torch
 
 from bliss_gnn_amd import _lib
-
-N, M = 624, 397
-
-
-def _next_block(od):
-    """at::mt19937::next_state (ATen/core/MT19937RNGEngine.h), out of place."""
-    nw = np.zeros(N, dtype=np.uint32)
-    for k in range(N):
-        u, v = int(od[k]), int(od[k + 1]) if k < N - 1 else int(nw[0])
-        m = int(od[k + M]) if k < N - M else int(nw[k - (N - M)])
-        y = (u & 0x80000000) | (v & 0x7FFFFFFF)
-        nw[k] = m ^ (y >> 1) ^ (0x9908B0DF if v & 1 else 0)
-    return nw
+from mt_ref import M, N, _next_block
 
 
 @pytest.mark.parametrize("blocks_ahead", [33, 41, 120])
