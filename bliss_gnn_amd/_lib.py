@@ -279,6 +279,8 @@ SIGNATURES = {
     "bliss_embed_norm": [_P, _I32, _I32, _I64, _P, _P],
     "bliss_spmm_fwd": [_P, _P, _P, _P, _P, _I64, _I32, _P, _I32, _I32, C.c_int, _P, _I64, C.c_int, _P, _P],
     "bliss_spmm_bwd": [_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _P, _I32, _I32, C.c_int, _P, _I64, C.c_int, _P, _P],
+    "bliss_spmm_max_fwd": [_P, _P, _P, _P, _P, _I64, _I32, _P, _I32, _I32, _P, _I64, _P, _I64, _P, _P],
+    "bliss_spmm_max_bwd": [_P, _P, _P, _P, _P, _P, _I64, _P, _I64, _I32, _P, _I32, _I32, _P, _I64, _P, _P],
     "bliss_block_transpose": [_P, _P, _I32, _I32, _I32, _P, _P, _P, _I64, _P],
     "bliss_spmm_chunk_edges": [_I32],
     "bliss_sage_epilogue_fwd": [_P, _I64, _P, _I64, _I32, _I32, _F, C.c_uint32, _P, _P, _I64, _P, _P],
@@ -341,7 +343,8 @@ SPECIAL_SIGNATURES = ("bliss_prof_kernel_name", "bliss_block_transpose_temp_byte
                       "bliss_graph_prepare_temp_bytes", "bliss_rng_stream_handle", "bliss_sage_wgrad_workspace",
                       "bliss_multinomial_draw_scratch_bytes", "bliss_neighbor_scratch_bytes", "bliss_wneighbor_scratch_bytes",
                       "bliss_labor_scratch_bytes", "bliss_labor_is_scratch_bytes", "bliss_wlabor_scratch_bytes",
-                      "bliss_neighbor_replace_scratch_bytes", "bliss_multinomial_draw_replace_scratch_bytes")   # non-int return types, set in _load()
+                      "bliss_neighbor_replace_scratch_bytes", "bliss_multinomial_draw_replace_scratch_bytes",
+                      "bliss_spmm_max_partial_bytes")   # non-int return types, set in _load()
 
 
 def _load():
@@ -377,6 +380,8 @@ def _load():
     lib.bliss_neighbor_replace_scratch_bytes.restype = C.c_int64
     lib.bliss_multinomial_draw_replace_scratch_bytes.argtypes = [_I32]
     lib.bliss_multinomial_draw_replace_scratch_bytes.restype = C.c_int64
+    lib.bliss_spmm_max_partial_bytes.argtypes = [_I32, _I32]
+    lib.bliss_spmm_max_partial_bytes.restype = C.c_int64
     lib.bliss_rng_stream_handle.argtypes = []
     lib.bliss_rng_stream_handle.restype = C.c_int64
     lib.bliss_prof_kernel_name.argtypes = [C.c_int]

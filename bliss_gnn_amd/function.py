@@ -33,3 +33,8 @@ def sum(msg, out):       # noqa: A001  (dgl.function.sum)
 
 def mean(msg, out):
     return _Reduce("mean", msg, out)
+
+
+def max(msg, out):       # noqa: A001  (dgl.function.max)
+    """dst[out] = element-wise max of the messages, 0 for a node without in-edges (SAGEConv 'pool'; the lowest edge wins a tie)."""
+    return _Reduce("max", msg, out)

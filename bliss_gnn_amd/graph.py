@@ -276,8 +276,9 @@ class Block:
         kernels (csrc/spmm.hip, csrc/gat.hip); the result lands in ``dstdata[out]`` (model.py:98-99)."""
         from . import nn as bnn
         kind, red = getattr(message_func, "kind", None), getattr(reduce_func, "kind", None)
-        if kind not in ("u_mul_e", "copy_u") or red not in ("sum", "mean") or reduce_func.msg != message_func.out:
-            raise NotImplementedError("update_all: (u_mul_e | copy_u) with (sum | mean), as the reference's layers use them")
+        if kind not in ("u_mul_e", "copy_u") or red not in ("sum", "mean", "max") or reduce_func.msg != message_func.out:
+            raise NotImplementedError("update_all: (u_mul_e | copy_u) with (sum | mean), as the reference's layers use them, or "
+                                      "with max (SAGEConv 'pool')")
         h = self.srcdata[message_func.lhs]
         w = self.edata[message_func.rhs] if kind == "u_mul_e" else None
         S = self.num_dst_nodes()
@@ -288,7 +289,8 @@ class Block:
             out = bnn._GatAggregate.apply(w.reshape(-1, H), h.reshape(K, H * D), self, H, D).view(S, H, D)
         else:
             h2 = h.reshape(h.shape[0], -1)
-            out = bnn.weighted_aggregate(self, h2, None if w is None else w.reshape(-1), mean=(red == "mean"))
+            w1 = None if w is None else w.reshape(-1)
+            out = bnn.max_aggregate(self, h2, w1) if red == "max" else bnn.weighted_aggregate(self, h2, w1, mean=(red == "mean"))
             out = out.view((S,) + tuple(h.shape[1:]))
         self.dstdata[reduce_func.out] = out
 

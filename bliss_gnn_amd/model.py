@@ -24,21 +24,29 @@ class SAGE(nn.Module):
     # library GEMMs.  "wide" (DESIGN.md section 29): in_feats up to nn.TILE_WIDE_MAX_K on the K-panelled tile kernel, and
     # NotImplementedError naming the reason where the MFMA path cannot be taken: no silent fall-back.
     SAGE_TRANSFORMS = ("auto", "wide")
+    # "pool" (DESIGN.md section 30): SAGEConv(..., "pool") layers on library GEMMs and the max-reduce kernels of csrc/spmm_max.hip;
+    # the MFMA transforms cover "mean" only.
+    SAGE_AGGREGATORS = ("mean", "pool")
 
-    def __init__(self, in_feats, n_hidden, n_classes, n_layers, activation, dropout, transforms="auto"):
+    def __init__(self, in_feats, n_hidden, n_classes, n_layers, activation, dropout, transforms="auto", aggregator_type="mean"):
         super().__init__()
         if transforms not in self.SAGE_TRANSFORMS:
             raise ValueError("transforms must be one of %r, not %r" % (self.SAGE_TRANSFORMS, transforms))
-        self.transforms = transforms
+        if aggregator_type not in self.SAGE_AGGREGATORS:
+            raise NotImplementedError("SAGE: aggregator_type must be one of %r, not %r" % (self.SAGE_AGGREGATORS, aggregator_type))
+        if aggregator_type != "mean" and transforms == "wide":
+            raise NotImplementedError('SAGE: transforms="wide" runs the MFMA tile path, which covers aggregator_type="mean", not %r'
+                                      % (aggregator_type,))
+        self.transforms, self.aggregator_type = transforms, aggregator_type
         self.n_layers, self.n_hidden, self.n_classes = n_layers, n_hidden, n_classes
         self.layers = nn.ModuleList()
         if n_layers > 1:
-            self.layers.append(SAGEConv(in_feats, n_hidden, "mean"))
+            self.layers.append(SAGEConv(in_feats, n_hidden, aggregator_type))
             for _ in range(1, n_layers - 1):
-                self.layers.append(SAGEConv(n_hidden, n_hidden, "mean"))
-            self.layers.append(SAGEConv(n_hidden, n_classes, "mean"))
+                self.layers.append(SAGEConv(n_hidden, n_hidden, aggregator_type))
+            self.layers.append(SAGEConv(n_hidden, n_classes, aggregator_type))
         else:
-            self.layers.append(SAGEConv(in_feats, n_classes, "mean"))
+            self.layers.append(SAGEConv(in_feats, n_classes, aggregator_type))
         self.dropout = nn.Dropout(dropout)
         self.activation = activation
 
@@ -66,7 +74,7 @@ class SAGE(nn.Module):
         # BLISS_SAGE_MFMA=0 falls back to library GEMMs + separate gather / epilogue kernels (the round-1 path).  Device time per
         # launch on the Reddit-like step (scratch/tgbench.py, graph replay): 602 -> 256 pair with the gather 32-37 us (gather +
         # two tuned library GEMMs: 46), 256 + 256 dual with epilogue 20 (23), 256 -> 41 pair 13 (18), and five launches fewer
-        if os.environ.get("BLISS_SAGE_MFMA", "1") == "0":
+        if os.environ.get("BLISS_SAGE_MFMA", "1") == "0" or self.aggregator_type != "mean":
             return False
         act = self.activation
         relu = act in (torch.relu, torch.nn.functional.relu) or isinstance(act, nn.ReLU)
@@ -221,13 +229,17 @@ class SAGE(nn.Module):
         deg = g.indptr[1:] - g.indptr[:-1]
         dst_all = torch.repeat_interleave(torch.arange(V, device=g.device, dtype=torch.int32), deg)
         h = g.ndata["features"]                                              # :346
+        pool = self.aggregator_type == "pool"
         for l, layer in enumerate(self.layers):                              # :366
-            before = layer._in_src_feats > layer._out_feats                  # SAGEConv: fc_neigh before aggregation iff in > out
-            src_feat = layer.fc_neigh(h) if before else h
+            before = not pool and layer._in_src_feats > layer._out_feats     # SAGEConv 'mean': fc_neigh before aggregation iff in > out
+            if pool:                                                         # relu(fc_pool(h)) once over all nodes, fc_neigh after the max
+                src_feat = torch.relu(layer.fc_pool(h))
+            else:
+                src_feat = layer.fc_neigh(h) if before else h
             y = torch.empty(V, layer._out_feats, dtype=h.dtype, device=h.device)
             for b0 in range(0, V, node_chunk):
                 b1 = min(V, b0 + node_chunk)
-                neigh = _full_neighbor_mean(g, src_feat, b0, b1, dst_all)
+                neigh = _full_neighbor(g, src_feat, b0, b1, dst_all, pool)
                 if not before:
                     neigh = layer.fc_neigh(neigh)
                 out = layer.fc_self(h[b0:b1]) + neigh
@@ -240,19 +252,19 @@ class SAGE(nn.Module):
         return h
 
 
-def _full_neighbor_mean(g, h, b0, b1, dst_all):
-    """mean over ALL in-neighbours of nodes b0..b1-1 (a MultiLayerFullNeighborSampler(1) block without edge weights,
-    model.py:347-349, 375-376): the CSC columns of a contiguous node range are one contiguous slice."""
+def _full_neighbor(g, h, b0, b1, dst_all, pool=False):
+    """mean (``pool``: max, no winning edge recorded) over ALL in-neighbours of nodes b0..b1-1 (a MultiLayerFullNeighborSampler(1)
+    block without edge weights, model.py:347-349, 375-376): the CSC columns of a contiguous node range are one contiguous slice."""
     import torch
     from .graph import Block
-    from .nn import weighted_aggregate
+    from .nn import max_aggregate, weighted_aggregate
     e0, e1 = int(g.indptr[b0]), int(g.indptr[b1])
     indptr = (g.indptr[b0:b1 + 1] - e0).to(torch.int32)
     src = g.indices[e0:e1]
     dst = dst_all[e0:e1] - b0
     blk = Block(None, h.shape[0], b1 - b0, indptr, src, dst, src, src, torch.empty(0, dtype=torch.int32, device=h.device))
     blk._transposed = (None, None)
-    return weighted_aggregate(blk, h, None, mean=True)
+    return max_aggregate(blk, h, None) if pool else weighted_aggregate(blk, h, None, mean=True)
 
 
 class GCN(nn.Module):

@@ -33,11 +33,9 @@ def _wait_block(block):
         block._ready = None
 
 
-def weighted_aggregate(block, h, edge_weight=None, mean=True, out_fp32=False):
-    """out[i] = (1/deg_i if mean) * sum_{e -> i} w_e h[src_e] over a Block -- ``torch.ops.bliss.spmm`` (bliss_gnn_amd/ops.py: a
-    torch.library custom op with a fake kernel and the transposed SpMM as its autograd formula); gradient w.r.t. h only
-    (the sampler's edge weights carry no grad, SURVEY.md m6)."""
-    from . import ops
+def _aggregate_operands(block, h, edge_weight):
+    """What weighted_aggregate and max_aggregate hand to their op: h with unit column stride, w bf16 contiguous or None, the
+    device-side counts of a capacity-padded block, and the by-source index when a gradient w.r.t. h is needed (else None, None)."""
     assert h.is_cuda and h.dtype == torch.bfloat16, "bf16 features on the GPU (load_graph.py:7)"
     _wait_block(block)
     if h.stride(1) != 1:
@@ -52,7 +50,28 @@ def weighted_aggregate(block, h, edge_weight=None, mean=True, out_fp32=False):
     counts = getattr(block, "_counts_dev", None) if block._nnz_ptr else None
     need_t = h.requires_grad and torch.is_grad_enabled()
     t_indptr, t_edge = block.transposed() if need_t else (None, None)
+    return h, w, counts, t_indptr, t_edge
+
+
+def weighted_aggregate(block, h, edge_weight=None, mean=True, out_fp32=False):
+    """out[i] = (1/deg_i if mean) * sum_{e -> i} w_e h[src_e] over a Block -- ``torch.ops.bliss.spmm`` (bliss_gnn_amd/ops.py: a
+    torch.library custom op with a fake kernel and the transposed SpMM as its autograd formula); gradient w.r.t. h only
+    (the sampler's edge weights carry no grad, SURVEY.md m6)."""
+    from . import ops
+    h, w, counts, t_indptr, t_edge = _aggregate_operands(block, h, edge_weight)
     return ops.spmm(block.indptr, block.src, block.dst, w, h, block.num_dst_nodes(), counts, bool(mean), bool(out_fp32), t_indptr, t_edge)
+
+
+def max_aggregate(block, h, edge_weight=None, return_arg=False):
+    """out[i, c] = max_{e -> i} bf16(w_e h[src_e, c]) over a Block, 0 for a row without edges -- ``torch.ops.bliss.spmm_max``
+    (csrc/spmm_max.hip, DESIGN.md section 30: DGL's ``update_all(u_mul_e | copy_u, fn.max)``, the lowest edge wins a tie);
+    gradient w.r.t. h only, routed to the recorded edge of every element.  ``return_arg=True`` also returns arg int32 [S, dim]
+    (the winning edge, -1 for a row without edges)."""
+    from . import ops
+    h, w, counts, t_indptr, t_edge = _aggregate_operands(block, h, edge_weight)
+    out, arg = ops.spmm_max(block.indptr, block.src, block.dst, w, h, block.num_dst_nodes(), counts,
+                            bool(return_arg or t_indptr is not None), t_indptr, t_edge)
+    return (out, arg) if return_arg else out
 
 
 class _SageEpilogue(torch.autograd.Function):
@@ -723,22 +742,30 @@ def tile_gemm_ok(in_feats, out_feats, wide=False):
 
 
 class SAGEConv(nn.Module):
-    """dglnn.SAGEConv(in_feats, out_feats, 'mean') as used at model.py:303-308, 321-329."""
+    """dglnn.SAGEConv(in_feats, out_feats, 'mean') as used at model.py:303-308, 321-329, and [DGL-recalled] the 'pool'
+    aggregator: neigh = max over the in-edges of relu(fc_pool(feat_src))[src_e] * w_e, then fc_neigh --
+    never fc_neigh before the aggregation, which DGL has for 'mean' and 'gcn' only."""
 
     def __init__(self, in_feats, out_feats, aggregator_type="mean", feat_drop=0.0, bias=True, norm=None, activation=None):
         super().__init__()
-        if aggregator_type != "mean":
-            raise NotImplementedError("the reference only builds SAGEConv(..., 'mean') (model.py:303-308)")
+        if aggregator_type not in ("mean", "pool"):
+            raise NotImplementedError("SAGEConv: aggregator_type 'mean' (model.py:303-308) and 'pool' are built, not %r "
+                                      "('gcn' and 'lstm' are not: DESIGN.md section 30)" % (aggregator_type,))
+        self._aggre_type = aggregator_type
         self._in_src_feats = self._in_dst_feats = in_feats
         self._out_feats = out_feats
         self.feat_drop = nn.Dropout(feat_drop)
         self.norm, self.activation = norm, activation
+        if aggregator_type == "pool":
+            self.fc_pool = nn.Linear(in_feats, in_feats)
         self.fc_neigh = nn.Linear(in_feats, out_feats, bias=False)
         self.fc_self = nn.Linear(in_feats, out_feats, bias=bias)
         self.reset_parameters()
 
     def reset_parameters(self):
         gain = nn.init.calculate_gain("relu")
+        if self._aggre_type == "pool":
+            nn.init.xavier_uniform_(self.fc_pool.weight, gain=gain)
         nn.init.xavier_uniform_(self.fc_self.weight, gain=gain)
         nn.init.xavier_uniform_(self.fc_neigh.weight, gain=gain)
 
@@ -749,8 +776,9 @@ class SAGEConv(nn.Module):
         else:
             feat_src = self.feat_drop(feat)
             feat_dst = feat_src[: graph.num_dst_nodes()]
-        lin_before_mp = self._in_src_feats > self._out_feats
-        if lin_before_mp:
+        if self._aggre_type == "pool":
+            h_neigh = self.fc_neigh(max_aggregate(graph, torch.relu(self.fc_pool(feat_src)), edge_weight))
+        elif self._in_src_feats > self._out_feats:   # fc_neigh before the aggregation
             h_neigh = weighted_aggregate(graph, self.fc_neigh(feat_src), edge_weight, mean=True)
         else:
             h_neigh = self.fc_neigh(weighted_aggregate(graph, feat_src, edge_weight, mean=True))

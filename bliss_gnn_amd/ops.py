@@ -6,7 +6,7 @@ implementations are the C ABI calls of include/bliss_gnn.h -- there is no other 
 
 ``counts`` (optional int32[10] = a bliss_layer_counts_t on the device) marks capacity-padded blocks: the true edge count is
 read on the device, padded edges are inert (bliss_gnn_amd._engine)."""
-from typing import Optional
+from typing import Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -78,6 +78,78 @@ def _spmm_backward(ctx, gout):
 
 
 spmm.register_autograd(_spmm_backward, setup_context=_spmm_setup)
+
+
+def _max_partials(B, D, device):
+    n = int(_lib.lib.bliss_spmm_max_partial_bytes(B, D))
+    if n < 0:
+        raise RuntimeError("bliss_spmm_max_partial_bytes failed")
+    return torch.empty(n // 4, dtype=torch.float32, device=device) if n else None
+
+
+@torch.library.custom_op("bliss::spmm_max", mutates_args=())
+def spmm_max(indptr: Tensor, src: Tensor, dst: Tensor, w: Optional[Tensor], h: Tensor, n_dst: int, counts: Optional[Tensor],
+             want_arg: bool, t_indptr: Optional[Tensor], t_edge: Optional[Tensor]) -> Tuple[Tensor, Tensor]:
+    """out[i, c] = max_{e -> i} bf16(w_e h[src_e, c]), arg[i, c] = the lowest edge that attains it (-1 and 0 for a row without
+    edges) -- CSR by destination (csrc/spmm_max.hip).  ``want_arg=False`` (inference): arg is empty."""
+    assert h.is_cuda and h.dtype == torch.bfloat16 and h.stride(1) == 1, "bf16 features on the GPU (load_graph.py:7)"
+    B, D = int(src.numel()), h.shape[1]
+    out = torch.empty(n_dst, D, dtype=torch.bfloat16, device=h.device)
+    arg = torch.empty((n_dst, D) if want_arg else (0, D), dtype=torch.int32, device=h.device)
+    part = _max_partials(B, D, h.device)
+    _lib.check(_lib.lib.bliss_spmm_max_fwd(indptr.data_ptr(), src.data_ptr(), dst.data_ptr(), _p(w), h.data_ptr(), h.stride(0), n_dst,
+                                           _nnz_ptr(counts), B, D, out.data_ptr(), out.stride(0), arg.data_ptr() if want_arg else 0,
+                                           D, _p(part), _stream()), "bliss_spmm_max_fwd")
+    return out, arg
+
+
+@spmm_max.register_fake
+def _(indptr, src, dst, w, h, n_dst, counts, want_arg, t_indptr, t_edge):
+    D = h.shape[1]
+    return h.new_empty((n_dst, D), dtype=torch.bfloat16), h.new_empty((n_dst, D) if want_arg else (0, D), dtype=torch.int32)
+
+
+@torch.library.custom_op("bliss::spmm_max_t", mutates_args=())
+def spmm_max_t(t_indptr: Tensor, t_edge: Tensor, src: Tensor, dst: Tensor, w: Optional[Tensor], gout: Tensor, arg: Tensor, n_src: int,
+               counts: Optional[Tensor]) -> Tensor:
+    """The routed backward: gh[j, c] = sum_{e : src_e = j, arg[dst_e, c] == e} w_e gout[dst_e, c]  (by-source index t_*)."""
+    B, D = int(src.numel()), gout.shape[1]
+    gh = torch.empty(n_src, D, dtype=torch.bfloat16, device=gout.device)
+    part = _max_partials(B, D, gout.device)
+    _lib.check(_lib.lib.bliss_spmm_max_bwd(t_indptr.data_ptr(), t_edge.data_ptr(), src.data_ptr(), dst.data_ptr(), _p(w), gout.data_ptr(),
+                                           gout.stride(0), arg.data_ptr(), arg.stride(0), n_src, _nnz_ptr(counts), B, D, gh.data_ptr(),
+                                           gh.stride(0), _p(part), _stream()), "bliss_spmm_max_bwd")
+    return gh
+
+
+@spmm_max_t.register_fake
+def _(t_indptr, t_edge, src, dst, w, gout, arg, n_src, counts):
+    return gout.new_empty((n_src, gout.shape[1]), dtype=torch.bfloat16)
+
+
+def _spmm_max_setup(ctx, inputs, output):
+    indptr, src, dst, w, h, n_dst, counts, want_arg, t_indptr, t_edge = inputs
+    ctx.save_for_backward(src, dst, w, counts, t_indptr, t_edge, output[1])
+    ctx.n_src, ctx.want_arg = h.shape[0], want_arg
+    ctx.mark_non_differentiable(output[1])
+    ctx.set_materialize_grads(False)
+
+
+def _spmm_max_backward(ctx, gout, _garg):
+    src, dst, w, counts, t_indptr, t_edge, arg = ctx.saved_tensors
+    if gout is None:
+        return (None,) * 10
+    if t_indptr is None or t_edge is None or not ctx.want_arg:
+        raise RuntimeError("bliss::spmm_max needs the block's by-source index (Block.transposed()) and want_arg=True to "
+                           "differentiate w.r.t. h")
+    g = gout.contiguous()
+    if g.dtype != torch.bfloat16:
+        g = g.bfloat16()
+    gh = spmm_max_t(t_indptr, t_edge, src, dst, w, g, arg, ctx.n_src, counts)
+    return (None, None, None, None, gh, None, None, None, None, None)             # the sampler's edge weights carry no grad (m6)
+
+
+spmm_max.register_autograd(_spmm_max_backward, setup_context=_spmm_max_setup)
 
 
 @torch.library.custom_op("bliss::embed_norm", mutates_args=())

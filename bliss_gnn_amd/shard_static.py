@@ -583,7 +583,7 @@ class StaticShardedTrainStep:
         return (os.environ.get("BLISS_SHARD_MFMA", "1") != "0" and relu and hasattr(m, "_dropout_state") and isinstance(m.dropout, torch.nn.Dropout)
                 and h.is_cuda and h.dtype == torch.bfloat16 and layer._in_src_feats <= layer._out_feats
                 and tile_gemm_ok(layer._in_src_feats, layer._out_feats) and layer.fc_self.bias is not None and layer.norm is None
-                and layer.activation is None and layer.feat_drop.p == 0)
+                and layer.activation is None and layer.feat_drop.p == 0 and getattr(layer, "_aggre_type", "mean") == "mean")
 
     def _split_layer_ok(self, layer, h):
         """The same for a Linear-first SAGEConv (in > out): nn._SageLinearSplit + the fused epilogue."""
@@ -595,7 +595,7 @@ class StaticShardedTrainStep:
         return (os.environ.get("BLISS_SHARD_MFMA", "1") != "0" and relu and hasattr(m, "_dropout_state") and isinstance(m.dropout, torch.nn.Dropout)
                 and h.is_cuda and h.dtype == torch.bfloat16 and layer._in_src_feats > layer._out_feats
                 and tile_gemm_ok(layer._in_src_feats, layer._out_feats) and layer.fc_self.bias is not None and layer.norm is None
-                and layer.activation is None and layer.feat_drop.p == 0)
+                and layer.activation is None and layer.feat_drop.p == 0 and getattr(layer, "_aggre_type", "mean") == "mean")
 
     def _forward(self, blocks, slot=0, defer_output=False):
         """SAGE.forward (model.py:312-333) over this rank's blocks.  ``defer_output``: stop in front of the output layer's compute

@@ -810,6 +810,28 @@ int bliss_spmm_bwd(const int32_t* t_indptr, const int32_t* t_edge, const int32_t
                    const int32_t* nnz_dev, int32_t nnz, int32_t dim, int mean, void* gh, int64_t gh_stride, int out_fp32,
                    float* partials, void* stream);
 
+/* SAGEConv 'pool' message passing [DGL-recalled: update_all(u_mul_e | copy_u, max)], csrc/spmm_max.hip, DESIGN.md section 30:
+ *   m_e[c]    = bf16(float(w_e) * float(h[src_e, c]))   (w == NULL: m_e = h[src_e])
+ *   arg[i, c] = the lowest edge index e among the in-edges of row i whose m_e[c] is largest (float compare, strict >)
+ *   out[i, c] = m_arg[c];   a row without edges (degree 0, capacity padding, edges at or past *nnz_dev): out = 0, arg = -1
+ * h, out bf16, arg int32 [n_dst, dim] or NULL (forward only: inference), strides in elements; indptr / src / dst / w / nnz_dev /
+ * nnz as for bliss_spmm_fwd.  Inputs are finite (NaN ordering is not defined).
+ * bliss_spmm_max_bwd: gh[j, c] = bf16( sum_{e : src_e = j and arg[dst_e, c] == e} float(w_e) * float(gout[dst_e, c]) ), fp32
+ * sums in by-source order inside a work chunk, chunk partials added in chunk order; gh bf16 [n_src, dim], sources that receive
+ * nothing are zeros; t_indptr / t_edge as for bliss_spmm_bwd.  No float atomics: both calls are bitwise reproducible.
+ * partials (both calls): bliss_spmm_max_partial_bytes(nnz, dim) bytes with the same nnz (bound) as passed to the call
+ * (per chunk of bliss_spmm_chunk_edges(nnz) edges a head and a tail slot of dim fp32 values + dim int32 args); may be NULL
+ * when nnz is at most one chunk.  A negative result of bliss_spmm_max_partial_bytes is BLISS_EINVAL (nnz_bound < 0, dim <= 0).
+ * BLISS_EINVAL before any launch: a NULL required pointer (indptr / t_indptr, h / gout, out / gh, the backward's arg; the edge
+ * arrays when nnz > 0), a negative count, dim <= 0, a stride below dim, partials NULL with more than one chunk. */
+int64_t bliss_spmm_max_partial_bytes(int32_t nnz_bound, int32_t dim);
+int bliss_spmm_max_fwd(const int32_t* indptr, const int32_t* src, const int32_t* dst, const void* w, const void* h,
+                       int64_t h_stride, int32_t n_dst, const int32_t* nnz_dev, int32_t nnz, int32_t dim, void* out,
+                       int64_t out_stride, int32_t* arg, int64_t arg_stride, void* partials, void* stream);
+int bliss_spmm_max_bwd(const int32_t* t_indptr, const int32_t* t_edge, const int32_t* src, const int32_t* dst, const void* w,
+                       const void* gout, int64_t gout_stride, const int32_t* arg, int64_t arg_stride, int32_t n_src,
+                       const int32_t* nnz_dev, int32_t nnz, int32_t dim, void* gh, int64_t gh_stride, void* partials, void* stream);
+
 /* The element-wise tail of a hidden SAGE layer in one pass (model.py:321-333 and :318-320 of the next layer):
  * out = dropout_p(relu(a + b)) row by row, norm_out[row] = ||out[row,:]||_2 (bf16, may be NULL).  a, b, out: bf16
  * [n_rows, dim].  p_drop = 0 (evaluation) makes it deterministic.  ctr: device uint64[66], zero-initialised once: the
