@@ -124,7 +124,11 @@ __global__ void __launch_bounds__(SP_TPB) k_gather_rows_norm(const bf16_t* __res
 // counter, element index): the same Bernoulli(1-p) law as torch's fused_dropout, a different (device-resident,
 // graph-replayable) random stream.  ctr[0] = launch counter, ctr[1] (and ctr[2..65]) = tickets: the last workgroup to finish bumps the
 // counter, so every workgroup of a launch has read the same value.  drop_hash: common.cuh.
-template <bool VEC4>
+// VEC4 is the access width (8-byte loads and stores: a, b and out all allow them); NORM4 is the summation order of the norm,
+// which follows `out` alone, like bliss_embed_norm(out): a lane owns columns 4l .. 4l + 3 (+ 256 j) and adds their squares in
+// turn.  VEC4 implies NORM4.  <false, true> (an `a` or `b` that is only 2-byte aligned beside an aligned `out`) walks the vec4
+// order with 2-byte accesses, as k_gather_rows_norm's norm_vec4 does.
+template <bool VEC4, bool NORM4>
 __global__ void __launch_bounds__(SP_TPB) k_sage_epilogue(const bf16_t* __restrict__ a, int64_t a_stride, const bf16_t* __restrict__ b,
                                                          int64_t b_stride, int n_rows, int dim, uint32_t drop_thresh, float scale,
                                                          uint32_t seed, unsigned long long* ctr, bf16_t* __restrict__ out,
@@ -136,13 +140,17 @@ __global__ void __launch_bounds__(SP_TPB) k_sage_epilogue(const bf16_t* __restri
     const bf16_t *pa = a + row * a_stride, *pb = b + row * b_stride;
     bf16_t* po = out + row * out_stride;
     float s = 0.f;
-    constexpr int W = VEC4 ? 4 : 1;
+    static_assert(NORM4 || !VEC4, "8-byte accesses imply the vec4 order");
+    constexpr int W = NORM4 ? 4 : 1;
     for (int col = lane * W; col < dim; col += 64 * W) {
       float v[W];
       if (VEC4) {
         const f4 x = load4(pa + col), y = load4(pb + col);
         v[0] = x.x + y.x; v[1 % W] = x.y + y.y; v[2 % W] = x.z + y.z; v[3 % W] = x.w + y.w;
-      } else v[0] = bf2f(pa[col]) + bf2f(pb[col]);
+      } else {
+#pragma unroll
+        for (int i = 0; i < W; ++i) v[i] = bf2f(pa[col + i]) + bf2f(pb[col + i]);     // (NORM4: dim % 4 == 0, col + 3 < dim)
+      }
 #pragma unroll
       for (int i = 0; i < W; ++i) {
         float t = rbf(v[i]);                                  // the add's bf16 result
@@ -159,7 +167,10 @@ __global__ void __launch_bounds__(SP_TPB) k_sage_epilogue(const bf16_t* __restri
         o.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1 % W]) << 16);
         o.y = (uint32_t)f2bf(v[2 % W]) | ((uint32_t)f2bf(v[3 % W]) << 16);
         *reinterpret_cast<uint2*>(po + col) = o;
-      } else po[col] = f2bf(v[0]);
+      } else {
+#pragma unroll
+        for (int i = 0; i < W; ++i) po[col + i] = f2bf(v[i]);
+      }
     }
     for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d);
     if (lane == 0 && norm_out) norm_out[row] = f2bf(sqrtf(s));
@@ -262,7 +273,7 @@ int bliss_spmm_bwd(const int32_t* t_indptr, const int32_t* t_edge, const int32_t
 
 int bliss_sage_epilogue_fwd(const void* a, int64_t a_stride, const void* b, int64_t b_stride, int32_t n_rows, int32_t dim,
                             float p_drop, uint32_t seed, uint64_t* ctr, void* out, int64_t out_stride, void* norm_out, void* stream) {
-  if (!a || !b || !out || n_rows < 0 || dim <= 0 || p_drop < 0.f || p_drop >= 1.f || (p_drop > 0.f && !ctr)) return BLISS_EINVAL;
+  if (!a || !b || !out || n_rows < 0 || dim <= 0 || !(p_drop >= 0.f && p_drop < 1.f) || (p_drop > 0.f && !ctr)) return BLISS_EINVAL;   // (NaN too)
   if (n_rows == 0) return 0;
   const bool v4 = dim % 4 == 0 && a_stride % 4 == 0 && b_stride % 4 == 0 && out_stride % 4 == 0 && ((uintptr_t)a) % 8 == 0 &&
                   ((uintptr_t)b) % 8 == 0 && ((uintptr_t)out) % 8 == 0;
@@ -270,16 +281,17 @@ int bliss_sage_epilogue_fwd(const void* a, int64_t a_stride, const void* b, int6
   const float scale = p_drop > 0.f ? 1.0f / (1.0f - p_drop) : 1.0f;
   hipStream_t st = (hipStream_t)stream;
   const int grid = (n_rows + SP_TPB / 64 - 1) / (SP_TPB / 64);
-  if (v4) k_sage_epilogue<true><<<grid, SP_TPB, 0, st>>>((const bf16_t*)a, a_stride, (const bf16_t*)b, b_stride, n_rows, dim, thresh, scale, seed,
-                                                        (unsigned long long*)ctr, (bf16_t*)out, out_stride, (bf16_t*)norm_out);
-  else k_sage_epilogue<false><<<grid, SP_TPB, 0, st>>>((const bf16_t*)a, a_stride, (const bf16_t*)b, b_stride, n_rows, dim, thresh, scale, seed,
-                                                      (unsigned long long*)ctr, (bf16_t*)out, out_stride, (bf16_t*)norm_out);
+  const bool n4 = dim % 4 == 0 && out_stride % 4 == 0 && ((uintptr_t)out) % 8 == 0;                  // = bliss_embed_norm(out)
+#define GO(V, N) k_sage_epilogue<V, N><<<grid, SP_TPB, 0, st>>>((const bf16_t*)a, a_stride, (const bf16_t*)b, b_stride, n_rows, dim, thresh, scale, \
+                                                              seed, (unsigned long long*)ctr, (bf16_t*)out, out_stride, (bf16_t*)norm_out)
+  if (v4) GO(true, true); else if (n4) GO(false, true); else GO(false, false);
+#undef GO
   return (int)hipGetLastError();
 }
 
 int bliss_sage_epilogue_bwd(const void* dout, int64_t dout_stride, const void* out, int64_t out_stride, int32_t n_rows, int32_t dim,
                             float p_drop, void* din, int64_t din_stride, void* stream) {
-  if (!dout || !out || !din || n_rows < 0 || dim <= 0 || p_drop < 0.f || p_drop >= 1.f) return BLISS_EINVAL;
+  if (!dout || !out || !din || n_rows < 0 || dim <= 0 || !(p_drop >= 0.f && p_drop < 1.f)) return BLISS_EINVAL;
   if (n_rows == 0) return 0;
   const bool v4 = dim % 4 == 0 && dout_stride % 4 == 0 && out_stride % 4 == 0 && din_stride % 4 == 0 && ((uintptr_t)dout) % 8 == 0 &&
                   ((uintptr_t)out) % 8 == 0 && ((uintptr_t)din) % 8 == 0;

@@ -627,6 +627,14 @@ def _weight_grad(d, x, split=4):
     return p.sum(0).to(d.dtype)
 
 
+def _dropout_needs_relu(relu, p):
+    """bliss_sage_epilogue_bwd takes the dropout mask AND the ReLU mask from ``out > 0`` (include/bliss_gnn.h): without the ReLU
+    a kept negative element would lose its gradient.  Refused before any launch."""
+    if p > 0 and not relu:
+        raise ValueError("dropout (p = %g) without ReLU: the backward reads its mask from out > 0, which is the dropout mask "
+                         "only behind a ReLU" % p)
+
+
 class _SageDualLinear(torch.autograd.Function):
     """An aggregate-first SAGEConv layer's tail (in <= out): fc_neigh(h_neigh) + fc_self(h_dst) + bias, ReLU, dropout and the
     row norms of the result (model.py:321-333, :318-320 of the next layer) in ONE launch: both products accumulate in the
@@ -635,6 +643,7 @@ class _SageDualLinear(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a_neigh, a_self, w_neigh, w_self, bias, relu, p, ctr, seed, n_rows, rows_dev):
         ctx.set_materialize_grads(False)
+        _dropout_needs_relu(relu, p)
         a1, a2, w1, w2 = _bf16c(a_neigh), _bf16c(a_self), _bf16c(w_neigh), _bf16c(w_self)
         out = torch.empty(n_rows, w1.shape[0], dtype=torch.bfloat16, device=a1.device)
         norm = torch.empty(n_rows, dtype=torch.bfloat16, device=a1.device)
@@ -678,6 +687,7 @@ class _SageAggDual(torch.autograd.Function):
     def forward(ctx, h, indptr, src, dst, w, counts, t_indptr, t_edge, n_dst, w_neigh, w_self, bias, relu, p, ctr, seed, rows_dev):
         from . import ops
         ctx.set_materialize_grads(False)
+        _dropout_needs_relu(relu, p)
         h, w1, w2 = _bf16c(h), _bf16c(w_neigh), _bf16c(w_self)
         agg = ops.spmm(indptr, src, dst, w, h, n_dst, counts, True, False, None, None)
         out = torch.empty(n_dst, w1.shape[0], dtype=torch.bfloat16, device=h.device)

@@ -783,11 +783,17 @@ int bliss_normalized_edata(const bliss_graph_t* g, void* w_pos, void* stream);
  * out[r, :] = feat[ids[r], :] for r < n_rows, bf16 rows of `dim` elements (strides in elements).  norm_out (optional, bf16
  * [n_rows]) receives the row norms of the gathered rows with exactly the bits bliss_embed_norm(out, ...) would produce --
  * the embed_norm model.py:318-320 takes of the same rows right afterwards.  ids must be valid row numbers (padded rows of
- * a static-shape block point at row 0).  BLISS_EINVAL if dim exceeds what one wave stages in LDS (6144 elements). */
+ * a static-shape block point at row 0).  The copy runs 8, 4 or 2 bytes at a time, as feat, out and both strides allow; the
+ * norm's summation order follows dim, out_stride and the address of `out` alone (bliss_embed_norm's rule).  norm_out NULL: the
+ * copy alone.  BLISS_EINVAL before any launch: feat, ids or out NULL; dim <= 0; a stride below dim; dim above what one wave
+ * stages in LDS (6144 elements: exactly 48 KiB a workgroup).  n_rows <= 0 returns 0. */
 int bliss_gather_rows(const void* feat, int64_t feat_stride, const int32_t* ids, int32_t n_rows, int32_t dim, void* out,
                       int64_t out_stride, void* norm_out, void* stream);
 
-/* th.norm(h, dim=1)   model.py:318-320: embed_norm[j] = ||h_j||_2, fp32 accumulation, bf16 out. */
+/* th.norm(h, dim=1)   model.py:318-320: embed_norm[j] = ||h_j||_2, fp32 accumulation, bf16 out.  The summation order (and with
+ * it the bits) follows how the rows are stored: four columns per lane (4 lane + 256 j) when dim % 4 == 0, row_stride % 4 == 0 and
+ * h is 8-byte aligned, else one (lane + 64 j); then the xor butterfly over the 64 lanes.  BLISS_EINVAL:
+ * h or out NULL.  n_rows <= 0 returns 0. */
 int bliss_embed_norm(const void* h, int32_t n_rows, int32_t dim, int64_t row_stride, void* out, void* stream);
 
 /* SAGEConv 'mean' message passing with edge weights [DGL-recalled: update_all(u_mul_e, mean)],
@@ -836,9 +842,17 @@ int bliss_spmm_max_bwd(const int32_t* t_indptr, const int32_t* t_edge, const int
  * out = dropout_p(relu(a + b)) row by row, norm_out[row] = ||out[row,:]||_2 (bf16, may be NULL).  a, b, out: bf16
  * [n_rows, dim].  p_drop = 0 (evaluation) makes it deterministic.  ctr: device uint64[66], zero-initialised once: the
  * dropout stream's launch counter + tickets (bumped by every call with p_drop > 0) -- counter-based bits, not torch's generator.
- * _bwd: din = dout / (1 - p) where out > 0, else 0 (the gradient w.r.t. both a and b). */
+ * norm_out has the bits of bliss_embed_norm(out, n_rows, dim, out_stride): its summation order follows dim, out_stride and the
+ * address of `out` alone, whatever the alignment of a and b lets the loads be.  A sum that is NaN stores +0 (it is not positive).
+ * The ReLU is part of the contract: there is no p_drop > 0 without it, because
+ * _bwd: din = bf16(dout * (1 / (1 - p))) where out > 0, else +0 (the gradient w.r.t. both a and b) takes BOTH masks from the
+ * stored `out`.  That is the gradient only behind a ReLU, where a kept element is positive or has a zero gradient anyway; behind a
+ * dropout WITHOUT ReLU it would zero the gradient of every kept negative element (nn.py refuses that combination).
+ * BLISS_EINVAL before any launch: a, b, out (dout, out, din) NULL; dim <= 0; n_rows < 0; p_drop outside [0, 1); p_drop > 0 with
+ * ctr NULL.  n_rows == 0 returns 0; at p_drop == 0 ctr may be NULL and is not touched. */
 int bliss_sage_epilogue_fwd(const void* a, int64_t a_stride, const void* b, int64_t b_stride, int32_t n_rows, int32_t dim,
                             float p_drop, uint32_t seed, uint64_t* ctr, void* out, int64_t out_stride, void* norm_out, void* stream);
+/* (the mask is `out > 0`: right only where `out` went through the ReLU, see above) */
 int bliss_sage_epilogue_bwd(const void* dout, int64_t dout_stride, const void* out, int64_t out_stride, int32_t n_rows, int32_t dim,
                             float p_drop, void* din, int64_t din_stride, void* stream);
 
