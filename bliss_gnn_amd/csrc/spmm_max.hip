@@ -6,6 +6,8 @@
 //   arg[i, c] = the lowest edge e of row i whose m_e[c] is largest (float compare, the running best moves on strict > only)
 //   out[i, c] = m_arg[c];  a row without edges: out = 0, arg = -1
 //   gh[j, c]  = bf16( sum_{e : src_e = j and arg[dst_e, c] == e} float(w_e) * float(gout[dst_e, c]) )     (fp32 sum)
+// and, for a layer whose maximised rows are act = relu(z), the backward with the ReLU's mask folded in:
+//   gz[j, c]  = act[j, c] > 0 ? gh[j, c] : +0       (the mask behind the one rounding, never on the fp32 chunk partials)
 //
 // Both directions keep the balanced chunk decomposition of spmm_walk.cuh (a wave owns spmm_chunk_edges(nnz) consecutive
 // entries of the edge list, a lane 4 bf16 columns, the (neighbour, weight) pairs fetched coalesced and broadcast by
@@ -210,14 +212,22 @@ __global__ void __launch_bounds__(SM_TPB) k_spmm_max_fixup(const int* __restrict
   }
 }
 
+// the ReLU's mask on four finished sums: a column whose activation is not above zero (either zero, or negative) sends +0
+__device__ __forceinline__ f4 relu_mask4(f4 v, f4 a) {
+  return f4{a.x > 0.f ? v.x : 0.f, a.y > 0.f ? v.y : 0.f, a.z > 0.f ? v.z : 0.f, a.w > 0.f ? v.w : 0.f};
+}
+
 // ---- backward: a gather through the by-source index ---------------------------------------------------------------------------
 // Entry k of the by-source list is edge e = t_edge[k] of source row_ptr-row j; column c of it contributes w_e * gout[dst_e, c]
 // iff arg[dst_e, c] == e.  Per edge the wave reads a gout row (2 B per column) and an arg row (4 B per column).
-template <bool VEC4, bool HAS_W>
+// RELU: a finished source row is stored under the mask act[r] > 0 -- one bf16 row read per source row of the chunk, issued where the
+// row BEGINS (its address needs the row id alone), so it travels with the row's first edge loads and the store does not wait for it.
+template <bool VEC4, bool HAS_W, bool RELU>
 __global__ void __launch_bounds__(SM_TPB) k_spmm_max_bwd(const int* __restrict__ row_ptr, const int* __restrict__ t_edge,
                                                         const int* __restrict__ src, const int* __restrict__ dst,
                                                         const bf16_t* __restrict__ w, const bf16_t* __restrict__ g, int64_t g_stride,
                                                         const int* __restrict__ arg, int64_t arg_stride,
+                                                        const bf16_t* __restrict__ actv, int64_t act_stride,
                                                         const int* __restrict__ nnz_dev, int nnz_host, int dim,
                                                         bf16_t* __restrict__ gh, int64_t gh_stride, float* __restrict__ part, int EC) {
   const int nnz = nnz_dev ? max(0, min(*nnz_dev, nnz_host)) : nnz_host;
@@ -238,11 +248,21 @@ __global__ void __launch_bounds__(SM_TPB) k_spmm_max_bwd(const int* __restrict__
   for (int col0 = 0; col0 < dim; col0 += 64 * W) {
     const int col = col0 + lane * W;
     const bool act = col < dim;
-    auto flush = [&](int r, f4 acc) {
+    // the activations of row r's columns (RELU only; r is a live source of this chunk: in bounds)
+    auto act_of = [&](int r) {
+      f4 a = zero;
+      if (RELU && act) {
+        if (VEC4) a = load4(actv + r * act_stride + col);
+        else a.x = bf2f(actv[r * act_stride + col]);
+      }
+      return a;
+    };
+    auto flush = [&](int r, f4 acc, f4 am) {
       const int rb = row_ptr[r], re = min(row_ptr[r + 1], nnz);
       const bool starts = rb >= c0, ends = re <= c1;
       if (!act) return;
       if (starts && ends) {
+        if (RELU) acc = relu_mask4(acc, am);
         if (VEC4) store4<false>(gh, r * gh_stride + col, acc);
         else gh[r * gh_stride + col] = f2bf(acc.x);
       } else {
@@ -257,10 +277,10 @@ __global__ void __launch_bounds__(SM_TPB) k_spmm_max_bwd(const int* __restrict__
       acc.z += m.z == e ? k * a.z : 0.f; acc.w += m.w == e ? k * a.w : 0.f;
     };
     int cur = bcast_i(my_row, 0);
-    f4 acc = zero;
+    f4 acc = zero, am = act_of(cur);
     for (int j = 0; j < cnt;) {
       const int r = bcast_i(my_row, j);
-      if (r != cur) { flush(cur, acc); acc = zero; cur = r; }
+      if (r != cur) { flush(cur, acc, am); acc = zero; cur = r; am = act_of(r); }
       const int run = __popcll(__ballot(my_row == r && lane >= j));
       const int end = j + run;
       for (; j + 4 <= end; j += 4) {
@@ -293,17 +313,17 @@ __global__ void __launch_bounds__(SM_TPB) k_spmm_max_bwd(const int* __restrict__
         }
       }
     }
-    flush(cur, acc);
+    flush(cur, acc, am);
   }
 }
 
 // Source row r after the backward walk: chunk partials added in chunk order, one rounding; a source that sends nothing (rows
-// past the live count included) is cleared.
-template <bool VEC4>
+// past the live count included) is cleared -- RELU: without reading its act row; a combined row is stored under act[r] > 0.
+template <bool VEC4, bool RELU>
 __global__ void __launch_bounds__(SM_TPB) k_spmm_max_bwd_fixup(const int* __restrict__ row_ptr, int n_rows,
                                                               const int* __restrict__ nnz_dev, int nnz_host, int dim,
-                                                              const float* __restrict__ part, bf16_t* __restrict__ gh,
-                                                              int64_t gh_stride, int EC) {
+                                                              const float* __restrict__ part, const bf16_t* __restrict__ actv,
+                                                              int64_t act_stride, bf16_t* __restrict__ gh, int64_t gh_stride, int EC) {
   const int r = blockIdx.x * (SM_TPB / 64) + (threadIdx.x >> 6);
   if (r >= n_rows) return;
   const int nnz = nnz_dev ? max(0, min(*nnz_dev, nnz_host)) : nnz_host;
@@ -321,21 +341,53 @@ __global__ void __launch_bounds__(SM_TPB) k_spmm_max_bwd_fixup(const int* __rest
   if (c_end == c) return;
   for (int col = lane * W; col < dim; col += 64 * W) {
     if (VEC4) {
+      f4 am = {0.f, 0.f, 0.f, 0.f};
+      if (RELU) am = load4(actv + r * act_stride + col);        // (issued in front of the partials' loads, used behind them)
       f4 sum = load4f(part + ((int64_t)c * 2 + 1) * dim + col);
       for (int cc = c + 1; cc <= c_end; ++cc) {
         const f4 u = load4f(part + ((int64_t)cc * 2) * dim + col);
         sum.x += u.x; sum.y += u.y; sum.z += u.z; sum.w += u.w;
       }
+      if (RELU) sum = relu_mask4(sum, am);
       store4<false>(gh, r * gh_stride + col, sum);
     } else {
+      const float am = RELU ? bf2f(actv[r * act_stride + col]) : 1.f;
       float sum = part[((int64_t)c * 2 + 1) * dim + col];
       for (int cc = c + 1; cc <= c_end; ++cc) sum += part[((int64_t)cc * 2) * dim + col];
+      if (RELU) sum = am > 0.f ? sum : 0.f;
       gh[r * gh_stride + col] = f2bf(sum);
     }
   }
 }
 
 inline bool al(const void* p, uintptr_t a) { return ((uintptr_t)p) % a == 0; }
+
+// Both backward entry points: RELU = false is bliss_spmm_max_bwd (act unused), true bliss_spmm_max_bwd_relu.
+template <bool RELU>
+int max_bwd_launch(const int32_t* t_indptr, const int32_t* t_edge, const int32_t* src, const int32_t* dst, const void* w, const void* gout,
+                   int64_t gout_stride, const int32_t* arg, int64_t arg_stride, const void* act, int64_t act_stride, int32_t n_src,
+                   const int32_t* nnz_dev, int32_t nnz, int32_t dim, void* gh, int64_t gh_stride, void* partials, void* stream) {
+  if (!t_indptr || !gout || !arg || !gh || n_src < 0 || nnz < 0 || dim <= 0 || (nnz > 0 && (!t_edge || !src || !dst))) return BLISS_EINVAL;
+  if (gout_stride < dim || arg_stride < dim || gh_stride < dim) return BLISS_EINVAL;
+  const int EC = spmm_chunk_edges(nnz);
+  if (nnz > EC && !partials) return BLISS_EINVAL;
+  if (n_src == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  const bool vec4 = dim % 4 == 0 && gout_stride % 4 == 0 && arg_stride % 4 == 0 && gh_stride % 4 == 0 && al(gout, 8) && al(arg, 16) &&
+                    al(gh, 8) && al(partials, 16) && (!RELU || (act_stride % 4 == 0 && al(act, 8)));
+  const int nchunks = (nnz + EC - 1) / EC;
+  const dim3 block(SM_TPB), grid((nchunks + SM_TPB / 64 - 1) / (SM_TPB / 64)), gfix((n_src + SM_TPB / 64 - 1) / (SM_TPB / 64));
+#define GO(V, HW) PROF_LAUNCH(RELU ? BK_SPMM_MAX_BWD_RELU : BK_SPMM_MAX_BWD, st, k_spmm_max_bwd<V, HW, RELU><<<grid, block, 0, st>>>(t_indptr, t_edge, src, dst, (const bf16_t*)w, (const bf16_t*)gout, gout_stride, arg, arg_stride, (const bf16_t*)act, act_stride, nnz_dev, nnz, dim, (bf16_t*)gh, gh_stride, (float*)partials, EC))
+  if (nchunks > 0) {
+    if (vec4) { if (w) GO(true, true); else GO(true, false); }
+    else      { if (w) GO(false, true); else GO(false, false); }
+  }
+#undef GO
+#define FIX(V) PROF_LAUNCH(RELU ? BK_SPMM_MAX_BWD_RELU_FIXUP : BK_SPMM_MAX_BWD_FIXUP, st, k_spmm_max_bwd_fixup<V, RELU><<<gfix, block, 0, st>>>(t_indptr, n_src, nnz_dev, nnz, dim, (const float*)partials, (const bf16_t*)act, act_stride, (bf16_t*)gh, gh_stride, EC))
+  if (vec4) FIX(true); else FIX(false);
+#undef FIX
+  return (int)hipGetLastError();
+}
 
 }  // namespace
 
@@ -376,26 +428,17 @@ int bliss_spmm_max_fwd(const int32_t* indptr, const int32_t* src, const int32_t*
 int bliss_spmm_max_bwd(const int32_t* t_indptr, const int32_t* t_edge, const int32_t* src, const int32_t* dst, const void* w,
                        const void* gout, int64_t gout_stride, const int32_t* arg, int64_t arg_stride, int32_t n_src,
                        const int32_t* nnz_dev, int32_t nnz, int32_t dim, void* gh, int64_t gh_stride, void* partials, void* stream) {
-  if (!t_indptr || !gout || !arg || !gh || n_src < 0 || nnz < 0 || dim <= 0 || (nnz > 0 && (!t_edge || !src || !dst))) return BLISS_EINVAL;
-  if (gout_stride < dim || arg_stride < dim || gh_stride < dim) return BLISS_EINVAL;
-  const int EC = spmm_chunk_edges(nnz);
-  if (nnz > EC && !partials) return BLISS_EINVAL;
-  if (n_src == 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
-  const bool vec4 = dim % 4 == 0 && gout_stride % 4 == 0 && arg_stride % 4 == 0 && gh_stride % 4 == 0 && al(gout, 8) && al(arg, 16) &&
-                    al(gh, 8) && al(partials, 16);
-  const int nchunks = (nnz + EC - 1) / EC;
-  const dim3 block(SM_TPB), grid((nchunks + SM_TPB / 64 - 1) / (SM_TPB / 64)), gfix((n_src + SM_TPB / 64 - 1) / (SM_TPB / 64));
-#define GO(V, HW) PROF_LAUNCH(BK_SPMM_MAX_BWD, st, k_spmm_max_bwd<V, HW><<<grid, block, 0, st>>>(t_indptr, t_edge, src, dst, (const bf16_t*)w, (const bf16_t*)gout, gout_stride, arg, arg_stride, nnz_dev, nnz, dim, (bf16_t*)gh, gh_stride, (float*)partials, EC))
-  if (nchunks > 0) {
-    if (vec4) { if (w) GO(true, true); else GO(true, false); }
-    else      { if (w) GO(false, true); else GO(false, false); }
-  }
-#undef GO
-#define FIX(V) PROF_LAUNCH(BK_SPMM_MAX_BWD_FIXUP, st, k_spmm_max_bwd_fixup<V><<<gfix, block, 0, st>>>(t_indptr, n_src, nnz_dev, nnz, dim, (const float*)partials, (bf16_t*)gh, gh_stride, EC))
-  if (vec4) FIX(true); else FIX(false);
-#undef FIX
-  return (int)hipGetLastError();
+  return max_bwd_launch<false>(t_indptr, t_edge, src, dst, w, gout, gout_stride, arg, arg_stride, nullptr, 0, n_src, nnz_dev, nnz, dim, gh,
+                               gh_stride, partials, stream);
+}
+
+int bliss_spmm_max_bwd_relu(const int32_t* t_indptr, const int32_t* t_edge, const int32_t* src, const int32_t* dst, const void* w,
+                            const void* gout, int64_t gout_stride, const int32_t* arg, int64_t arg_stride, const void* act,
+                            int64_t act_stride, int32_t n_src, const int32_t* nnz_dev, int32_t nnz, int32_t dim, void* gh,
+                            int64_t gh_stride, void* partials, void* stream) {
+  if (!act || act_stride < dim) return BLISS_EINVAL;
+  return max_bwd_launch<true>(t_indptr, t_edge, src, dst, w, gout, gout_stride, arg, arg_stride, act, act_stride, n_src, nnz_dev, nnz, dim,
+                              gh, gh_stride, partials, stream);
 }
 
 }  // extern "C"

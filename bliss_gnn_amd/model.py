@@ -22,10 +22,12 @@ class SAGE(nn.Module):
 
     # "auto": the fused MFMA path when every layer is within the tile kernel's limits (in <= 1024, out <= 256), else -- silently --
     # library GEMMs.  "wide" (DESIGN.md section 29): in_feats up to nn.TILE_WIDE_MAX_K on the K-panelled tile kernel, and
-    # NotImplementedError naming the reason where the MFMA path cannot be taken: no silent fall-back.
-    SAGE_TRANSFORMS = ("auto", "wide")
-    # "pool" (DESIGN.md section 30): SAGEConv(..., "pool") layers on library GEMMs and the max-reduce kernels of csrc/spmm_max.hip;
-    # the MFMA transforms cover "mean" only.
+    # NotImplementedError naming the reason where the MFMA path cannot be taken: no silent fall-back.  "tile" (DESIGN.md section
+    # 32): only kernels whose every row and edge loop is bounded by the block's device-side counts, or NotImplementedError --
+    # for "mean" the MFMA path of "auto" (same launches and bits, in_feats <= 1024), for "pool" nn.sage_pool_tile per layer.
+    SAGE_TRANSFORMS = ("auto", "wide", "tile")
+    # "pool" (DESIGN.md section 30): SAGEConv(..., "pool") layers on library GEMMs and the max-reduce kernels of csrc/spmm_max.hip
+    # under "auto"; on the tile kernels under "tile" (section 32).
     SAGE_AGGREGATORS = ("mean", "pool")
 
     def __init__(self, in_feats, n_hidden, n_classes, n_layers, activation, dropout, transforms="auto", aggregator_type="mean"):
@@ -81,7 +83,7 @@ class SAGE(nn.Module):
         wide = self.transforms == "wide"
         dims = all(tile_gemm_ok(l._in_src_feats, l._out_feats, wide) and l.fc_self.bias is not None and l.norm is None and l.activation is None
                    and l.feat_drop.p == 0 for l in self.layers)
-        if wide and not all(q.is_cuda and q.dtype == torch.bfloat16 for q in self.parameters()):
+        if self.transforms != "auto" and not all(q.is_cuda and q.dtype == torch.bfloat16 for q in self.parameters()):
             return False                                   # ("auto" rounds other parameters to bf16 per launch, as it always has)
         return relu and dims and x.is_cuda and x.dtype == torch.bfloat16 and isinstance(self.dropout, nn.Dropout)
 
@@ -104,13 +106,67 @@ class SAGE(nn.Module):
                         % (l, self.transforms, TILE_WIDE_MAX_K if wide else 1024, TILE_GEMM_MAX_N, layer._in_src_feats, layer._out_feats))
         return "%s covers ReLU, nn.Dropout and plain SAGEConv layers with a bias (no norm, activation or feat_drop of their own)" % what
 
+    @property
+    def _pool_tile(self):
+        return self.transforms == "tile" and self.aggregator_type == "pool"
+
+    def tile_refusal(self, x):
+        """Why transforms="tile" cannot take ``x`` (a tensor or LazyRows of the input rows, or a parameter), or None."""
+        import os
+        from .nn import TILE_GEMM_MAX_K, TILE_GEMM_MAX_N, tile_gemm_ok
+        if not self._pool_tile:
+            return self.mfma_refusal(x)
+        what = 'SAGE: transforms="tile"'
+        for env in ("BLISS_SAGE_MFMA", "BLISS_SAGE_MFMA_BWD"):
+            if os.environ.get(env, "1") == "0":
+                return "%s runs on the MFMA kernels, forward and backward (%s=0 is set)" % (what, env)
+        bad = [q for q in [x] + list(self.parameters()) if not (q.is_cuda and q.dtype == torch.bfloat16)]
+        if bad:
+            return "%s takes bf16 features and parameters on the GPU, not %s on %s" % (what, bad[0].dtype, bad[0].device)
+        act = self.activation
+        if not (act in (torch.relu, torch.nn.functional.relu) or isinstance(act, nn.ReLU)):
+            return "%s covers the activation ReLU (the tail's and the backward's mask), not %r" % (what, act)
+        if not isinstance(self.dropout, nn.Dropout):
+            return "%s covers nn.Dropout (the tail's own counter-based stream), not %s" % (what, type(self.dropout).__name__)
+        for l, layer in enumerate(self.layers):
+            if layer.norm is not None or layer.activation is not None or layer.feat_drop.p != 0 or layer.fc_self.bias is None:
+                return ("SAGE layer %d: transforms=\"tile\" covers plain SAGEConv layers with a bias (no norm, activation or feat_drop "
+                        "of their own)" % l)
+            if not tile_gemm_ok(layer._in_src_feats, layer._out_feats):
+                return ("SAGE layer %d: transforms=\"tile\" takes in_feats <= %d and out_feats <= %d, this layer has %d -> %d"
+                        % (l, TILE_GEMM_MAX_K, TILE_GEMM_MAX_N, layer._in_src_feats, layer._out_feats))
+        return None
+
     def _mfma_path(self, x):
-        """Does this forward run on the MFMA kernels?  Under "wide" the answer is yes or an error, never the library path."""
+        """Does this forward run on the MFMA kernels?  Under "wide" and "tile" the answer is yes or an error, never the library
+        path; "pool" for the tile pool model (its own layer chain, _layers_pool_tile)."""
+        if self._pool_tile:
+            why = self.tile_refusal(x)
+            if why is not None:
+                raise NotImplementedError(why)
+            return "pool"
         if self._mfma_ok(x):
             return True
-        if self.transforms == "wide":
+        if self.transforms != "auto":
             raise NotImplementedError(self.mfma_refusal(x))
         return False
+
+    def _layers_pool_tile(self, blocks, h, norm, lo, hi):
+        """model.py:312-333, layers lo..hi-1, for 'pool' on bounded kernels: per layer one autograd node,
+        nn.sage_pool_tile -- fc_pool + ReLU, the max-reduce, and both Linears with the bias, ReLU, dropout and the next layer's
+        norms.  The layer's input norms come out of its first launch."""
+        from .nn import sage_pool_tile
+        n_layers = len(self.layers)
+        for l in range(lo, hi):
+            layer, block = self.layers[l], blocks[l]
+            last = l == n_layers - 1
+            ew = block.edata["edge_weights"] if "edge_weights" in block.edata else None
+            p = self.dropout.p if (self.training and not last) else 0.0
+            ctr, seed = self._dropout_state(l, h.device) if p > 0 else (None, 0)
+            h, out_norm, in_norm = sage_pool_tile(block, h, ew, layer, not last, p, ctr, seed)
+            block.srcdata["embed_norm"] = in_norm if norm is None else norm      # model.py:318-320 (same bits either way)
+            norm = None if last else out_norm
+        return h, norm
 
     def _layers_mfma(self, blocks, h, norm, lo, hi, parts=False):
         """model.py:312-333, layers lo..hi-1, with the Linear layers on hand-written MFMA tiles: per W-first layer ONE launch
@@ -173,6 +229,8 @@ class SAGE(nn.Module):
 
     def _layers(self, blocks, x, norm, lo, hi, mfma):
         from .nn import LazyRows
+        if mfma == "pool":
+            return self._layers_pool_tile(blocks, x, norm, lo, hi)
         if mfma:
             return self._layers_mfma(blocks, x, norm, lo, hi)
         if isinstance(x, LazyRows):
@@ -211,7 +269,7 @@ class SAGE(nn.Module):
         h, norm, mfma = hidden
         n = len(self.layers)
         layer = self.layers[n - 1]
-        if not (mfma and layer._in_src_feats > layer._out_feats):
+        if mfma is not True or layer._in_src_feats <= layer._out_feats:      # (no pool layer runs fc_neigh first)
             return None
         return self._layers_mfma(blocks, h, norm, n - 1, n, parts=True)[0]
 

@@ -1542,6 +1542,136 @@ def gat_linear(x, w, b, n_rows, rows_dev=0, w2=None, b2=None, n2_rows=0, rows2_d
     return _GatLinear.apply(x, w, b, int(n_rows), int(rows_dev), w2, b2, int(n2_rows), int(rows2_dev), bool(wide))
 
 
+# ------------------------------------------------------------------------------------------------ SAGEConv 'pool' on the tile kernels
+# transforms="tile" (DESIGN.md section 32): relu(fc_pool(h)) on bliss_tile_gemm, the max-reduce of csrc/spmm_max.hip, the layer's
+# tail (fc_neigh + fc_self + bias, ReLU, dropout, row norms) in one launch; the backward's ReLU mask of fc_pool inside the routed
+# max backward (bliss_spmm_max_bwd_relu).  Every row and edge loop is bounded by the block's device-side counts.
+def _tile_gemm_fits(k1, k2=0, n=TILE_GEMM_MAX_N):
+    """Does one argument set of bliss_tile_gemm fit a workgroup's 160 KiB of LDS?  The size formula of csrc/sage.hip (convert):
+    32 staged rows of each operand at stride round16(k) + 8, a 256 x 72 slab of W, or the output tile, whichever is larger."""
+    st = lambda k: (((k + 15) & ~15) + 8) if k else 0
+    stage = 2 * (32 * (st(k1) + st(k2)) + 256 * (64 + 8))
+    outt = 2 * 32 * (((n + 63) & ~63) + 8)
+    return max(stage, outt) <= 160 * 1024
+
+
+def _tile_gemm_by_size(first, second=None):
+    """One launch on bliss_tile_gemm, or -- where a set's operands pass its LDS -- on bliss_tile_gemm_wide, which stages one operand
+    panel at a time and returns bliss_tile_gemm's bits at k <= 1024.  Decided from the size formula, never by trying the call."""
+    import ctypes as C
+    sets = [first] + ([] if second is None else [second])
+    wide = not all(_tile_gemm_fits(t.k1, t.k2, t.n) for t in sets)
+    name = "bliss_tile_gemm_wide" if wide else "bliss_tile_gemm"
+    _lib.check(getattr(_lib.lib, name)(C.byref(first), None if second is None else C.byref(second), _stream()), name)
+    return name
+
+
+class _SagePoolTile(torch.autograd.Function):
+    """A SAGEConv('pool') layer with its tail on a block, ONE autograd node:
+
+        pooled = relu(fc_pool(h))                      bliss_tile_gemm, output-column blocks of <= 256, two per launch, rows < K
+        neigh, arg = max_{e -> i} bf16(w_e pooled[src_e])   bliss_spmm_max_fwd, edges < B
+        out = dropout_p(relu(fc_neigh(neigh) + fc_self(h[:S]) + bias))   one launch, rows < S (the last layer: no ReLU, p = 0)
+
+    K, S, B the block's live counts (its device words when it is capacity-padded).  With ``ids`` the rows of ``x`` are gathered by
+    the first launch, which also writes them out for the later launches and the backward.  Returns (out, out_norm, in_norm); the
+    norms have the bits of ops.embed_norm.  Backward: the epilogue's mask, dW_neigh / dW_self / db_self in one launch pair,
+    d_neigh = d W_neigh, d_z = the routed max backward under the mask pooled > 0 (no element-wise torch op), dW_pool / db_pool in
+    column blocks, dh = d_z W_pool + d W_self on the first S rows in one accumulator.  ``dbg``: a dict that receives pooled, neigh,
+    arg, out, the entry point of the tail and (backward) d, d_neigh, d_z -- the stage-by-stage tests read it; None in use."""
+
+    @staticmethod
+    def forward(ctx, x, ids, w_pool, b_pool, w_neigh, w_self, b_self, blk, relu, p, ctr, seed, dbg):
+        from . import ops
+        ctx.set_materialize_grads(False)
+        _dropout_needs_relu(relu, p)
+        indptr, src, dst, w, counts, t_indptr, t_edge, K, S, src_dev, dst_dev = blk
+        x, wp, wn, ws = _bf16c(x), _bf16c(w_pool), _bf16c(w_neigh), _bf16c(w_self)
+        fin, fout, dev = wp.shape[1], wn.shape[0], x.device
+        gathered = ids is not None
+        if x.shape[1] != fin or (not gathered and x.shape[0] < K) or S > K:
+            raise ValueError("_SagePoolTile: x [>= K, in_feats], S <= K")
+        rows = torch.empty(K, fin, dtype=torch.bfloat16, device=dev) if gathered else x
+        pooled = torch.empty(K, fin, dtype=torch.bfloat16, device=dev)
+        in_norm = torch.empty(K, dtype=torch.bfloat16, device=dev)
+        sets = []
+        for i, (c0, c1) in enumerate(_col_blocks(fin)):
+            # the first launch reads the table itself (its second block gathers again: the copy is still being written beside it)
+            a, a_ids = (x, ids) if i < 2 else (rows, None)
+            sets.append(_tg_args(a, wp[c0:c1], pooled[:, c0:c1], K, ids=a_ids, bias=None if b_pool is None else b_pool[c0:c1], m_dev=src_dev,
+                                 a_copy=rows if (gathered and i == 0) else None, in_norm=in_norm if i == 0 else None, relu=True))
+        for i in range(0, len(sets), 2):
+            _tile_gemm(sets[i], sets[i + 1] if i + 1 < len(sets) else None)
+        neigh, arg = ops.spmm_max(indptr, src, dst, w, pooled, S, counts, True, None, None)
+        out = torch.empty(S, fout, dtype=torch.bfloat16, device=dev)
+        out_norm = torch.empty(S, dtype=torch.bfloat16, device=dev)
+        entry = _tile_gemm_by_size(_tg_args(neigh, wn, out, S, a2=rows, w2=ws, bias=b_self, m_dev=dst_dev, out_norm=out_norm, relu=relu, p=p,
+                                            seed=seed, ctr=ctr))
+        ctx.save_for_backward(rows, pooled, neigh, arg, out, wp, wn, ws, indptr, src, dst, w, counts, t_indptr, t_edge)
+        ctx.relu, ctx.p, ctx.has_bp, ctx.has_bs, ctx.gathered, ctx.x_rows = bool(relu), float(p), b_pool is not None, b_self is not None, gathered, x.shape[0]
+        ctx.K, ctx.S, ctx.src_dev, ctx.dst_dev, ctx.dbg = K, S, src_dev, dst_dev, dbg
+        if dbg is not None:
+            dbg.update(pooled=pooled, neigh=neigh, arg=arg, out=out, rows=rows, tail_entry=entry)
+        ctx.mark_non_differentiable(out_norm, in_norm)
+        return out, out_norm, in_norm
+
+    @staticmethod
+    def backward(ctx, dout, _dn1, _dn2):
+        from . import ops
+        rows, pooled, neigh, arg, out, wp, wn, ws, indptr, src, dst, w, counts, t_indptr, t_edge = ctx.saved_tensors
+        if dout is None:
+            return (None,) * 13
+        K, S, src_dev, dst_dev = ctx.K, ctx.S, ctx.src_dev, ctx.dst_dev
+        d = _bf16c(dout)
+        if ctx.relu or ctx.p > 0:
+            din = torch.empty_like(out)
+            _lib.check(_lib.lib.bliss_sage_epilogue_bwd(d.data_ptr(), d.stride(0), out.data_ptr(), out.stride(0), out.shape[0],
+                                                        out.shape[1], ctx.p, din.data_ptr(), din.stride(0), _stream()),
+                       "bliss_sage_epilogue_bwd")
+            d = din
+        (d_wn, _), (d_ws, d_bs) = sage_wgrad([(d, neigh, S, dst_dev, False), (d, rows, S, dst_dev, ctx.has_bs)])
+        want_dx = ctx.needs_input_grad[0] and not ctx.gathered
+        d_wp = d_bp = dx = d_neigh = d_z = None
+        if want_dx or ctx.needs_input_grad[2] or (ctx.has_bp and ctx.needs_input_grad[3]):
+            if t_indptr is None or t_edge is None:
+                raise RuntimeError("the block's by-source index (Block.transposed()) is needed to differentiate through fc_pool")
+            d_neigh = sage_dgrad(d, wn, S, dst_dev)
+            d_z = ops.spmm_max_t_relu(t_indptr, t_edge, src, dst, w, d_neigh, arg, pooled, K, counts)
+            ((d_wp, d_bp),) = _wgrad_blocks([(d_z, rows, K, src_dev, ctx.has_bp)])
+            if want_dx:
+                fin, fout = wp.shape[0], ws.shape[0]
+                if _dgrad_fits(fin, fout):
+                    dx = gat_dgrad(d_z, wp, K, src_dev, a2=d, w2=ws, m2_bound=S, m2_dev=dst_dev)
+                else:
+                    dx = gat_dgrad(d_z, wp, K, src_dev)
+                    dx[:S] += gat_dgrad(d, ws, S, dst_dev)                  # (zero rows at or past the count)
+                if ctx.x_rows > K:
+                    dx = torch.cat([dx, _zero_rows(ctx.x_rows - K, dx)])
+        if ctx.dbg is not None:
+            ctx.dbg.update(d=d, d_neigh=d_neigh, d_z=d_z)
+        return dx, None, d_wp, d_bp, d_wn, d_ws, d_bs, None, None, None, None, None, None
+
+
+def sage_pool_tile(block, h, edge_weight, layer, relu, p, ctr, seed, dbg=None):
+    """``layer`` = SAGEConv(in, out, 'pool') on ``block`` through _SagePoolTile: (out, out_norm, in_norm).  ``h``: the layer's input
+    rows, a bf16 tensor on the GPU or a LazyRows (gathered by the first launch)."""
+    assert h.is_cuda and h.dtype == torch.bfloat16, "bf16 features on the GPU (load_graph.py:7)"
+    _wait_block(block)
+    w = None
+    if edge_weight is not None:
+        w = edge_weight.reshape(-1)
+        w = (w if w.dtype == torch.bfloat16 else w.bfloat16()).contiguous()
+    dst_dev, src_dev, _ = _block_words(block)
+    counts = block._counts_dev if dst_dev else None
+    table, ids = (h.table, h.ids) if isinstance(h, LazyRows) else (h, None)
+    fp = layer.fc_pool
+    need_t = torch.is_grad_enabled() and ((ids is None and h.requires_grad) or fp.weight.requires_grad or fp.bias.requires_grad)
+    t_indptr, t_edge = block.transposed() if need_t else (None, None)
+    blk = (block.indptr, block.src, block.dst, w, counts, t_indptr, t_edge, block.num_src_nodes(), block.num_dst_nodes(), src_dev, dst_dev)
+    return _SagePoolTile.apply(table, ids, fp.weight, fp.bias, layer.fc_neigh.weight, layer.fc_self.weight, layer.fc_self.bias, blk,
+                               bool(relu), float(p), ctr, int(seed), dbg)
+
+
 def gat_drop_state(salt, device):
     """The feat_drop stream of one GATv2 layer: its launch counter (device uint64[2]) and seed -- a function of torch's CUDA seed
     and of the layer's ordinal, like the attention dropout's (GATv2Conv._fused_state)."""

@@ -127,6 +127,27 @@ def _(t_indptr, t_edge, src, dst, w, gout, arg, n_src, counts):
     return gout.new_empty((n_src, gout.shape[1]), dtype=torch.bfloat16)
 
 
+@torch.library.custom_op("bliss::spmm_max_t_relu", mutates_args=())
+def spmm_max_t_relu(t_indptr: Tensor, t_edge: Tensor, src: Tensor, dst: Tensor, w: Optional[Tensor], gout: Tensor, arg: Tensor,
+                    act: Tensor, n_src: int, counts: Optional[Tensor]) -> Tensor:
+    """spmm_max_t under the ReLU mask of the maximised rows ``act`` = relu(z) [n_src, dim]: where(act > 0, spmm_max_t(...), +0) in
+    the same two launches (bliss_spmm_max_bwd_relu); rows without a live entry are cleared unread."""
+    B, D = int(src.numel()), gout.shape[1]
+    assert act.dtype == torch.bfloat16 and act.shape[0] >= n_src and act.shape[1] == D and act.stride(1) == 1
+    gh = torch.empty(n_src, D, dtype=torch.bfloat16, device=gout.device)
+    part = _max_partials(B, D, gout.device)
+    _lib.check(_lib.lib.bliss_spmm_max_bwd_relu(t_indptr.data_ptr(), t_edge.data_ptr(), src.data_ptr(), dst.data_ptr(), _p(w),
+                                                gout.data_ptr(), gout.stride(0), arg.data_ptr(), arg.stride(0), act.data_ptr(),
+                                                act.stride(0), n_src, _nnz_ptr(counts), B, D, gh.data_ptr(), gh.stride(0), _p(part),
+                                                _stream()), "bliss_spmm_max_bwd_relu")
+    return gh
+
+
+@spmm_max_t_relu.register_fake
+def _(t_indptr, t_edge, src, dst, w, gout, arg, act, n_src, counts):
+    return gout.new_empty((n_src, gout.shape[1]), dtype=torch.bfloat16)
+
+
 def _spmm_max_setup(ctx, inputs, output):
     indptr, src, dst, w, h, n_dst, counts, want_arg, t_indptr, t_edge = inputs
     ctx.save_for_backward(src, dst, w, counts, t_indptr, t_edge, output[1])

@@ -147,6 +147,8 @@ def _live_refusal(model):
         return ("%s has no live path: its layers run over all capacity rows of the output block (only SAGE on its MFMA path, "
                 'GATv2(transforms="tile") and GCN(transforms="tile") bound every row loop by the block\'s device-side counts)' % type(model).__name__)
     ps = list(model.parameters())
+    if ps and model._pool_tile:                  # 'pool' on the tile kernels: bounded like the MFMA path
+        return model.tile_refusal(ps[0])
     if not ps or not model._mfma_ok(ps[0]) or not _mfma_bwd_on():
         return ("SAGE runs live on its MFMA path only (bf16 on the GPU, ReLU, layers within the tile kernel's limits, "
                 "BLISS_SAGE_MFMA / BLISS_SAGE_MFMA_BWD not 0): the library-GEMM path multiplies stale capacity rows into the "

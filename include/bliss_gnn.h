@@ -838,6 +838,20 @@ int bliss_spmm_max_bwd(const int32_t* t_indptr, const int32_t* t_edge, const int
                        const void* gout, int64_t gout_stride, const int32_t* arg, int64_t arg_stride, int32_t n_src,
                        const int32_t* nnz_dev, int32_t nnz, int32_t dim, void* gh, int64_t gh_stride, void* partials, void* stream);
 
+/* bliss_spmm_max_bwd with the ReLU mask of the maximised rows folded in (the pool layer on the tile kernels).
+ * act bf16 [n_src, dim], row stride act_stride in elements: the rows the forward maximised over, relu(fc_pool(h)).
+ *   gh[j, c] = act[j, c] > 0 ? bf16( sum_{e : src_e = j and arg[dst_e, c] == e} float(w_e) * float(gout[dst_e, c]) ) : +0
+ * Where the mask passes: the sums, their order and the single rounding of bliss_spmm_max_bwd; the result is bit-equal to
+ * where(act > 0, bliss_spmm_max_bwd's result, +0).  act = +0 and act = -0 both mask.  The mask is applied where a finished row is
+ * rounded and stored, never to the fp32 chunk partials; act is read once per source row of a work chunk, where the row begins.  A source with no entry
+ * below the live edge count (rows past the live source count of a capacity-padded block included) is cleared WITHOUT reading its
+ * act row, which may hold anything.  partials as for bliss_spmm_max_bwd.  BLISS_EINVAL before any launch: every case of
+ * bliss_spmm_max_bwd, act == NULL, act_stride < dim. */
+int bliss_spmm_max_bwd_relu(const int32_t* t_indptr, const int32_t* t_edge, const int32_t* src, const int32_t* dst, const void* w,
+                            const void* gout, int64_t gout_stride, const int32_t* arg, int64_t arg_stride, const void* act,
+                            int64_t act_stride, int32_t n_src, const int32_t* nnz_dev, int32_t nnz, int32_t dim, void* gh,
+                            int64_t gh_stride, void* partials, void* stream);
+
 /* The element-wise tail of a hidden SAGE layer in one pass (model.py:321-333 and :318-320 of the next layer):
  * out = dropout_p(relu(a + b)) row by row, norm_out[row] = ||out[row,:]||_2 (bf16, may be NULL).  a, b, out: bf16
  * [n_rows, dim].  p_drop = 0 (evaluation) makes it deterministic.  ctr: device uint64[66], zero-initialised once: the
