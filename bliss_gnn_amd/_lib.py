@@ -150,6 +150,17 @@ class GcnInfer(C.Structure):                           # bliss_gcn_infer_t
                 ("out", C.c_void_p), ("out_stride", C.c_int64)]
 
 
+SAGE_INFER_MEAN, SAGE_INFER_MAX = 0, 1                # BLISS_SAGE_INFER_MEAN / _MAX
+
+
+class SageInfer(C.Structure):                          # bliss_sage_infer_t
+    _fields_ = [("indptr", C.c_void_p), ("indices", C.c_void_p), ("n_nodes", C.c_int32), ("batch_size", C.c_int32),
+                ("row0", C.c_int32), ("n_rows", C.c_int32), ("edge0", C.c_int64), ("n_edges", C.c_int64),
+                ("reduce", C.c_int32),
+                ("h", C.c_void_p), ("h_stride", C.c_int64), ("dim", C.c_int32),
+                ("out", C.c_void_p), ("out_stride", C.c_int64)]
+
+
 ADAM_MAX_TENSORS = 32
 F1_MAX_WORKGROUPS, F1_ROWS_PER_WORKGROUP, F1_PAIRS_PER_WORKGROUP = 1024, 4, 256    # BLISS_F1_MAX_WORKGROUPS; csrc/metrics.hip
 
@@ -312,6 +323,7 @@ SIGNATURES = {
     "bliss_gcn_infer_chunk_edges": [_I32],
     "bliss_gcn_infer_src_norms": [C.POINTER(GcnInfer), _P],
     "bliss_gcn_infer_spmm": [C.POINTER(GcnInfer), _P],
+    "bliss_sage_infer_spmm": [C.POINTER(SageInfer), _P],
     "bliss_shard_local_seeds": [_P, _I32, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P],
     "bliss_shard_scatter_partials": [_P, _P, _P, _P, _P, _P, _P, _I32, _P, _P],
     "bliss_shard_zero_dense": [_P, _I32, _P],

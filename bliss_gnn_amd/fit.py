@@ -594,7 +594,8 @@ def evaluate(g, sampler, model, ids, batch_size, multilabel=False, loss_fn=None,
 
 def fit(g, sampler, model, train_nid, val_nid, test_nid=None, batch_size=1024, lr=0.002, max_epochs=10, max_steps=None,
         multilabel=False, val_acc_target=1.0, early_stopping_patience=1000, checkpoint_path=None, seed=0, log=None,
-        eval_step="eager", train_metric=False, train_step="eager", vertex_limit=-1, limit_factor=3, batch_capacity=None):
+        eval_step="eager", train_metric=False, train_step="eager", vertex_limit=-1, limit_factor=3, batch_capacity=None,
+        inference_path=None):
     """One run of ``trainer.fit`` + the final evaluation (train_lightning.py:640-705).  Returns a dict of metrics.
     ``eval_step``: "eager" (``evaluate`` as it stands) or "graphed" (one train.GraphedEvalStep serves every epoch's validation;
     the sampler needs a static-shape path).  ``train_metric``: keep train_acc (:143) on the device beside every step and add it,
@@ -609,7 +610,10 @@ def fit(g, sampler, model, train_nid, val_nid, test_nid=None, batch_size=1024, l
     ``batch_size`` (the epoch's), ``batch_size_clamped``, ``input_nodes`` (the controller's ``n``, ``m``, ``s`` at the epoch's end)
     and ``sampled_nodes`` / ``sampled_edges`` in both loops.  The graphed loop runs under ``batch_capacity`` seeds (default twice
     the batch size): one captured step serves every size, nothing is re-captured, and the statistics come with the epoch's one
-    read-back.  ``-1`` (and no ``batch_capacity``): the loops as they were."""
+    read-back.  ``-1`` (and no ``batch_capacity``): the loops as they were.
+
+    ``inference_path``: when not None, passed as ``path=`` to the final ``model.inference(g)`` (SAGE, GCN and GATv2 each name their
+    paths in ``INFERENCE_PATHS``); None: the call as it was."""
     if eval_step not in ("eager", "graphed"):
         raise ValueError("eval_step must be 'eager' or 'graphed', not %r" % (eval_step,))
     if train_step not in ("eager", "graphed"):
@@ -621,7 +625,7 @@ def fit(g, sampler, model, train_nid, val_nid, test_nid=None, batch_size=1024, l
     if train_step == "graphed":
         return _fit_graphed(g, sampler, model, train_nid, val_nid, test_nid, batch_size, lr, max_epochs, max_steps, multilabel,
                             val_acc_target, early_stopping_patience, checkpoint_path, seed, log, eval_step, train_metric, ctl,
-                            batch_capacity)
+                            batch_capacity, inference_path)
     step = TrainStep(g, sampler, model, lr=lr, multilabel=multilabel, train_metric=train_metric)
     ev_cap = batch_capacity
     if ev_cap is None and ctl is not None and eval_step == "graphed":
@@ -667,15 +671,16 @@ def fit(g, sampler, model, train_nid, val_nid, test_nid=None, batch_size=1024, l
     if ev is not None:
         ev.close()
     return dict(history=history, best_val_acc=ckpt.best, steps=n_steps, final=_final_metrics(g, model, ckpt, train_nid, val_nid, test_nid,
-                                                                                             multilabel))
+                                                                                             multilabel, inference_path))
 
 
-def _final_metrics(g, model, ckpt, train_nid, val_nid, test_nid, multilabel):
-    """The best checkpoint reloaded, then the Final Accuracy of the three splits (train_lightning.py:662-705)."""
+def _final_metrics(g, model, ckpt, train_nid, val_nid, test_nid, multilabel, inference_path=None):
+    """The best checkpoint reloaded, then the Final Accuracy of the three splits (train_lightning.py:662-705).  ``inference_path``:
+    the ``path=`` of ``model.inference`` when not None."""
     ckpt.restore(model)                                                          # the best val_acc checkpoint (:662-685)
     final = {}
     if hasattr(model, "inference") and "features" in g.ndata:
-        pred = model.inference(g)                                                # :686-693 layer-wise full-neighbour inference
+        pred = model.inference(g) if inference_path is None else model.inference(g, path=inference_path)     # :686-693 layer-wise full-neighbour inference
         for name, nid in (("Train", train_nid), ("Validation", val_nid), ("Test", test_nid)):
             if nid is not None and nid.numel():
                 final[name] = _split_f1(pred, g.ndata["labels"], nid, multilabel)                            # :694-705
@@ -683,7 +688,8 @@ def _final_metrics(g, model, ckpt, train_nid, val_nid, test_nid, multilabel):
 
 
 def _fit_graphed(g, sampler, model, train_nid, val_nid, test_nid, batch_size, lr, max_epochs, max_steps, multilabel, val_acc_target,
-                 early_stopping_patience, checkpoint_path, seed, log, eval_step, train_metric, ctl=None, batch_capacity=None):
+                 early_stopping_patience, checkpoint_path, seed, log, eval_step, train_metric, ctl=None, batch_capacity=None,
+                 inference_path=None):
     """``fit`` with the epoch's steps replayed from one captured train step (train.GraphedTrainStep with its ledger): the same
     protocol, batches, random streams and bits as the eager loop; the host reads one ledger record per epoch."""
     static = hasattr(sampler, "sample_blocks_static") and (getattr(sampler, "_poisson", False) or getattr(sampler, "draw", "host") == "device")
@@ -760,7 +766,7 @@ def _fit_graphed(g, sampler, model, train_nid, val_nid, test_nid, batch_size, lr
             ev.close()
         step.close()
     return dict(history=history, best_val_acc=ckpt.best, steps=n_steps, final=_final_metrics(g, model, ckpt, train_nid, val_nid, test_nid,
-                                                                                             multilabel))
+                                                                                             multilabel, inference_path))
 
 
 def k_runs(run_fn, k):

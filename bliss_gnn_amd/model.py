@@ -273,20 +273,139 @@ class SAGE(nn.Module):
             return None
         return self._layers_mfma(blocks, h, norm, n - 1, n, parts=True)[0]
 
-    @torch.no_grad()
-    def inference(self, g, device=None, batch_size=128, use_uva=False, num_workers=0, node_chunk=16384):
-        """model.py:335-383: layer-wise full-neighbour inference over ALL nodes (no sampling, plain mean, no edge weights).
+    INFERENCE_PATHS = ("chunks", "blocks", "csc", "auto")
+    # "csc": the rows are cut into ranges of whole batches and grouped into launches as in GCN.inference (_csc_ranges,
+    # _csc_groups); the SpMM keeps no scratch, so the two limits only bound a launch's 32-bit edge offsets
+    csc_max_edges = 1 << 23
+    csc_spmm_edges = 2 ** 31 - 1
+    last_inference_path = None      # the path the last ``inference`` call took
 
-        The reference walks the nodes 128 at a time through a DataLoader; every output row depends only on its own
-        in-neighbours, so the rows are computed here in chunks of ``node_chunk`` contiguous nodes straight from the CSC
-        (``batch_size``, ``use_uva`` and ``num_workers`` are accepted for signature compatibility).  Returns y [V, classes]
-        and leaves it in ``g.ndata['h']`` like the reference (:382)."""
+    def csc_refusal(self, g, h, batch_size=128):
+        """Why ``inference(path="csc")`` cannot run on this graph, these features and this batch size, or None."""
+        if int(batch_size) < 1:
+            return "SAGE.inference: the CSC path takes batch_size >= 1, not %d" % int(batch_size)
+        if self.aggregator_type == "pool":
+            if self.transforms != "tile":
+                return ('SAGE.inference: the CSC path of aggregator_type="pool" has the bits of the tile kernels; build the model '
+                        'with transforms="tile" (this one is %r)' % (self.transforms,))
+            why = self.tile_refusal(h)
+        else:
+            why = self.mfma_refusal(h)                # (the default "auto" model on its MFMA path: the tile path's bits)
+        if why is not None:
+            return why
+        if not (g.device.type == "cuda" and h.is_cuda):
+            return "SAGE.inference: the CSC path runs on the GPU (graph on %s, features on %s)" % (g.device, h.device)
+        return None
+
+    def _inference_blocks(self, g, h, batch_size):
+        """The reference's own loop (model.py:366-382): per layer, per contiguous batch of ``batch_size`` nodes, the
+        full-neighbour block through layer l of the model's own layer chain (MFMA, pool-tile or library, whichever the model is
+        on) in evaluation mode.  The yardstick of the CSC path; slow on purpose."""
+        from .graph import full_neighbor_block
+        if batch_size < 1:
+            raise ValueError("SAGE.inference: batch_size >= 1, not %d" % batch_size)
+        V, mfma = g.num_nodes(), self._mfma_path(h)
+        for l in range(len(self.layers)):
+            y = None
+            for b0 in range(0, V, batch_size):
+                b1 = min(V, b0 + batch_size)
+                blk = full_neighbor_block(g, b0, b1)
+                out = self._layers([None] * l + [blk], h[blk.srcdata["_ID"].long()], None, l, l + 1, mfma)[0]
+                if y is None:
+                    y = torch.empty(V, out.shape[1], dtype=out.dtype, device=out.device)
+                y[b0:b1] = out
+            h = y
+        return h
+
+    def _inference_csc(self, g, h, batch_size):
+        """Per layer over ALL rows at once: the dense transforms once on the tile kernels -- the argument
+        sets of _SageLinearPair / _SageAggDual / _SagePoolTile without ids, norms, dropout -- and one forward-only
+        message-passing launch per group of ranges off the graph's own indptr / indices (nn.sage_infer_spmm).  Evaluation mode:
+        no dropout, no norms.  One host read per call (_csc_ranges); nothing of size E is allocated."""
+        from .nn import _bf16c, _col_blocks, _tg_args, _tile_gemm, _tile_gemm_by_size, sage_infer_spmm
+        groups = _csc_groups(_csc_ranges(g, batch_size, self.csc_max_edges, "SAGE.inference"), self.csc_spmm_edges)
+        V, dev, n_layers = g.num_nodes(), h.device, len(self.layers)
+        pool, wide = self.aggregator_type == "pool", self.transforms == "wide"
+        new = lambda n: torch.empty(V, n, dtype=torch.bfloat16, device=dev)
+
+        def message_passing(table, reduce):
+            agg = new(table.shape[1])
+            for r0, r1, e0, edges in groups:
+                sage_infer_spmm(g.indptr, g.indices, batch_size, r0, r1, e0, edges, table, agg[r0:r1], reduce)
+            return agg
+
+        h = _bf16c(h)
+        for l, layer in enumerate(self.layers):
+            last = l == n_layers - 1
+            wn, ws, b = _bf16c(layer.fc_neigh.weight), _bf16c(layer.fc_self.weight), layer.fc_self.bias
+            fin, fout = layer._in_src_feats, layer._out_feats
+            if pool:
+                wp, bp = _bf16c(layer.fc_pool.weight), layer.fc_pool.bias
+                pooled = new(fin)
+                sets = [_tg_args(h, wp[c0:c1], pooled[:, c0:c1], V, bias=None if bp is None else bp[c0:c1], relu=True)
+                        for c0, c1 in _col_blocks(fin)]
+                for i in range(0, len(sets), 2):
+                    _tile_gemm(sets[i], sets[i + 1] if i + 1 < len(sets) else None)
+                neigh = message_passing(pooled, "max")
+                out = new(fout)
+                _tile_gemm_by_size(_tg_args(neigh, wn, out, V, a2=h, w2=ws, bias=b, relu=not last))
+            elif fin > fout:                                                     # fc_neigh before the aggregation
+                z, y = new(fout), new(fout)
+                _tile_gemm(_tg_args(h, wn, z, V), _tg_args(h, ws, y, V, bias=b), wide=wide)
+                agg = message_passing(z, "mean")
+                out = y + agg if last else sage_epilogue(y, agg, 0.0, None, 0)[0]
+            else:
+                agg = message_passing(h, "mean")
+                out = new(fout)
+                _tile_gemm(_tg_args(agg, wn, out, V, a2=h, w2=ws, bias=b, relu=not last))
+            h = out
+        return h
+
+    @torch.no_grad()
+    def inference(self, g, device=None, batch_size=128, use_uva=False, num_workers=0, node_chunk=16384, path="chunks"):
+        """model.py:335-383: layer-wise full-neighbour inference over ALL nodes (no sampling, plain mean, no edge weights).
+        Returns y [V, classes] and leaves it in ``g.ndata['h']`` like the reference (:382); the path taken is left in
+        ``last_inference_path``.
+
+        ``path="chunks"`` (the default): the reference walks the nodes 128 at a time through a DataLoader; every output row
+        depends only on its own in-neighbours, so the rows are computed in chunks of ``node_chunk`` contiguous nodes straight from
+        the CSC, the Linear layers on library GEMMs (``batch_size``, ``use_uva`` and ``num_workers`` are accepted for signature
+        compatibility).
+        ``path="blocks"``: the reference's own loop honouring ``batch_size`` -- the full-neighbour block of every contiguous batch
+        through the model's own layer chain, i.e. the kernels the model trains on.
+        ``path="csc"``: one pass per layer over all nodes, the dense transforms once on the tile kernels,
+        one forward-only message-passing launch per range of rows straight off the graph's CSC -- the bits of "blocks" at the
+        same ``batch_size``, no block built (``node_chunk`` is ignored).  Raises NotImplementedError naming the reason
+        (``csc_refusal``) when it cannot run.
+        ``path="auto"``: "csc" when nothing refuses it, "chunks" otherwise."""
+        if path not in self.INFERENCE_PATHS:
+            raise ValueError("path must be one of %r, not %r" % (self.INFERENCE_PATHS, path))
+        h = g.ndata["features"]                                              # :346
+        if path in ("csc", "auto"):
+            why = self.csc_refusal(g, h, batch_size)
+            if path == "csc" and why is not None:
+                raise NotImplementedError(why)
+            path = "csc" if why is None else "chunks"
         was_training = self.training
         self.eval()                                                          # :364
+        try:
+            if path == "csc":
+                h = self._inference_csc(g, h, int(batch_size))
+            elif path == "blocks":
+                h = self._inference_blocks(g, h, int(batch_size))
+            else:
+                h = self._inference_chunks(g, h, node_chunk)
+        finally:
+            self.train(was_training)
+        g.ndata["h"] = h
+        self.last_inference_path = path
+        return h
+
+    def _inference_chunks(self, g, h, node_chunk):
+        """``inference(path="chunks")``: library GEMMs over all rows, the block kernels' message passing per chunk of rows."""
         V = g.num_nodes()
         deg = g.indptr[1:] - g.indptr[:-1]
         dst_all = torch.repeat_interleave(torch.arange(V, device=g.device, dtype=torch.int32), deg)
-        h = g.ndata["features"]                                              # :346
         pool = self.aggregator_type == "pool"
         for l, layer in enumerate(self.layers):                              # :366
             before = not pool and layer._in_src_feats > layer._out_feats     # SAGEConv 'mean': fc_neigh before aggregation iff in > out
@@ -305,9 +424,38 @@ class SAGE(nn.Module):
                     out = self.dropout(self.activation(out))                 # :377-379 (dropout is the identity in eval mode)
                 y[b0:b1] = out
             h = y
-        g.ndata["h"] = h
-        self.train(was_training)
         return h
+
+
+def _csc_ranges(g, batch_size, max_edges, what):
+    """Destination ranges of a CSC inference path: [(row0, row1, edge0, edges)], contiguous, whole batches, at least one batch each.
+    Cut k is the first batch boundary whose edge offset is at or past k * max_edges, so a range holds fewer than max_edges edges
+    plus one batch's -- cut on the device, read by the host ONCE per call."""
+    V, E, bs = g.num_nodes(), g.num_edges(), int(batch_size)
+    bounds = torch.cat([torch.arange(0, V, bs, device=g.device, dtype=torch.int64), torch.tensor([V], device=g.device, dtype=torch.int64)])
+    off = g.indptr[bounds]                                                                    # E0_b of every batch, then E
+    cuts = [bounds[:1], bounds[-1:]]
+    if E > max_edges:
+        targets = off[0] + torch.arange(1, E // int(max_edges) + 1, device=g.device, dtype=torch.int64) * int(max_edges)
+        cuts.append(bounds[torch.searchsorted(off, targets).clamp_(max=bounds.numel() - 1)])  # the first boundary at or past a target
+    cuts = torch.unique(torch.cat(cuts))                                                      # (sorted)
+    both = torch.stack([cuts, g.indptr[cuts]]).tolist()                                       # the call's one host read
+    ranges = [(r0, r1, e0, e1 - e0) for r0, r1, e0, e1 in zip(both[0][:-1], both[0][1:], both[1][:-1], both[1][1:])]
+    if any(r[3] >= 2 ** 31 for r in ranges):
+        raise NotImplementedError("%s: a range of 2^31 or more edges is beyond the CSC path (lower batch_size)" % what)
+    return ranges
+
+
+def _csc_groups(ranges, spmm_edges):
+    """The SpMM's launches: consecutive ranges joined while they hold at most spmm_edges edges together."""
+    groups = []
+    for r0, r1, e0, edges in ranges:
+        if groups and groups[-1][3] + edges <= int(spmm_edges):
+            p0, _, pe0, pedges = groups[-1]
+            groups[-1] = (p0, r1, pe0, pedges + edges)
+        else:
+            groups.append((r0, r1, e0, edges))
+    return groups
 
 
 def _full_neighbor(g, h, b0, b1, dst_all, pool=False):
@@ -415,30 +563,11 @@ class GCN(nn.Module):
         """Destination ranges of the CSC path: [(row0, row1, edge0, edges)], contiguous, whole batches, at least one batch each.
         Cut k is the first batch boundary whose edge offset is at or past k * csc_max_edges, so a range holds fewer than
         csc_max_edges edges plus one batch's -- cut on the device, read by the host ONCE per call."""
-        V, E, bs = g.num_nodes(), g.num_edges(), int(batch_size)
-        bounds = torch.cat([torch.arange(0, V, bs, device=g.device, dtype=torch.int64), torch.tensor([V], device=g.device, dtype=torch.int64)])
-        off = g.indptr[bounds]                                                                    # E0_b of every batch, then E
-        cuts = [bounds[:1], bounds[-1:]]
-        if E > self.csc_max_edges:
-            targets = off[0] + torch.arange(1, E // int(self.csc_max_edges) + 1, device=g.device, dtype=torch.int64) * int(self.csc_max_edges)
-            cuts.append(bounds[torch.searchsorted(off, targets).clamp_(max=bounds.numel() - 1)])  # the first boundary at or past a target
-        cuts = torch.unique(torch.cat(cuts))                                                      # (sorted)
-        both = torch.stack([cuts, g.indptr[cuts]]).tolist()                                       # the call's one host read
-        ranges = [(r0, r1, e0, e1 - e0) for r0, r1, e0, e1 in zip(both[0][:-1], both[0][1:], both[1][:-1], both[1][1:])]
-        if any(r[3] >= 2 ** 31 for r in ranges):
-            raise NotImplementedError("GCN.inference: a range of 2^31 or more edges is beyond the CSC path (lower batch_size)")
-        return ranges
+        return _csc_ranges(g, batch_size, self.csc_max_edges, "GCN.inference")
 
     def _csc_groups(self, ranges):
         """The SpMM's launches: consecutive ranges joined while they hold at most csc_spmm_edges edges together."""
-        groups = []
-        for r0, r1, e0, edges in ranges:
-            if groups and groups[-1][3] + edges <= int(self.csc_spmm_edges):
-                p0, _, pe0, pedges = groups[-1]
-                groups[-1] = (p0, r1, pe0, pedges + edges)
-            else:
-                groups.append((r0, r1, e0, edges))
-        return groups
+        return _csc_groups(ranges, self.csc_spmm_edges)
 
     def _inference_csc(self, g, h, batch_size):
         """The per-edge source norms of the batch structure ONCE per call (they do not depend on the layer; [E] fp32 kept for the

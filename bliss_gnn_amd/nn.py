@@ -996,6 +996,45 @@ def gcn_infer_spmm(indptr, indices, batch_size, row0, row1, edge0, n_edges, ns, 
     return out
 
 
+SAGE_INFER_REDUCE = {"mean": _lib.SAGE_INFER_MEAN, "max": _lib.SAGE_INFER_MAX}
+
+
+def sage_infer_spmm(indptr, indices, batch_size, row0, row1, edge0, n_edges, h, out, reduce="mean"):
+    """SAGEConv's full-neighbour message passing for the rows ``row0 .. row1 - 1`` (whole batches of ``batch_size`` rows) straight
+    off the graph's CSC (bliss_sage_infer_spmm, csrc/sage_infer.hip), one launch:
+    ``reduce="mean"``: ``out[r - row0] = bf16(1 / max(deg_r, 1) * sum_e h[indices[e]])`` with the bits ``weighted_aggregate(blk, x,
+    None, mean=True)`` gives on the full-neighbour block of every batch; ``reduce="max"``: the column-wise maximum with the bits of
+    ``max_aggregate(blk, x, None)``.  ``h`` bf16 [V, dim] of ALL nodes; ``out`` bf16 [row1 - row0, dim] (a view of the layer's
+    rows); ``edge0`` / ``n_edges`` = indptr[row0] and the range's edge count as the host read them.  No host read."""
+    import ctypes as C
+    what = "sage_infer_spmm"
+    if reduce not in SAGE_INFER_REDUCE:
+        raise ValueError("%s: reduce must be one of %r, not %r" % (what, tuple(SAGE_INFER_REDUCE), reduce))
+    V = indptr.numel() - 1
+    if indptr.dtype != torch.int64 or indices.dtype != torch.int32 or not (indptr.is_contiguous() and indices.is_contiguous()):
+        raise ValueError("%s: the graph's CSC is int64 indptr / int32 indices, contiguous" % what)
+    if not (indptr.is_cuda and indices.is_cuda):
+        raise NotImplementedError("%s: the CSC inference path runs on the GPU" % what)
+    if not (0 <= row0 <= row1 <= V) or batch_size < 1:
+        raise ValueError("%s: rows %d .. %d of %d nodes, batch_size %d" % (what, row0, row1, V, batch_size))
+    if n_edges >= 2 ** 31:
+        raise NotImplementedError("%s: a range of 2^31 or more edges is beyond the CSC path" % what)
+    dev, n_rows = indptr.device, int(row1) - int(row0)
+    if h.dtype != torch.bfloat16 or h.dim() != 2 or h.shape[0] < V or h.stride(1) != 1 or h.device != dev:
+        raise ValueError("%s: h is bf16 [%d, dim] on %s" % (what, V, dev))
+    dim = h.shape[1]
+    if out.dtype != torch.bfloat16 or out.shape != (n_rows, dim) or (dim > 1 and out.stride(1) != 1) or out.device != dev:
+        raise ValueError("%s: out is bf16 [%d, %d] on %s" % (what, n_rows, dim, dev))
+    if n_rows == 0:
+        return out
+    t = _lib.SageInfer()
+    t.indptr, t.indices, t.n_nodes, t.batch_size = indptr.data_ptr(), indices.data_ptr(), V, int(batch_size)
+    t.row0, t.n_rows, t.edge0, t.n_edges, t.reduce = int(row0), n_rows, int(edge0), int(n_edges), SAGE_INFER_REDUCE[reduce]
+    t.h, t.h_stride, t.dim, t.out, t.out_stride = h.data_ptr(), h.stride(0), dim, out.data_ptr(), out.stride(0)
+    _lib.check(_lib.lib.bliss_sage_infer_spmm(C.byref(t), _stream()), "bliss_sage_infer_spmm")
+    return out
+
+
 class GraphConv(nn.Module):
     """dglnn.GraphConv(in, out, norm='both', weight=True, bias=True) as built at model.py:397-417.
 

@@ -1194,6 +1194,40 @@ int bliss_gcn_infer_chunk_edges(int32_t n_batch_edges);
 int bliss_gcn_infer_src_norms(const bliss_gcn_infer_t* args, void* stream);
 int bliss_gcn_infer_spmm(const bliss_gcn_infer_t* args, void* stream);
 
+/* SAGEConv full-neighbour inference straight off the graph's CSC (csrc/sage_infer.hip; model.py:335-383):
+ * the message passing of SAGE.inference's batch-by-batch walk without a block, forward only.  The batch structure is that of
+ * bliss_gcn_infer_t: batch b is the rows [b * batch_size, min(n_nodes, (b + 1) * batch_size)), its first edge E0_b =
+ * indptr[b * batch_size], it has n_b edges, EC_b = bliss_spmm_chunk_edges(n_b).
+ *   BLISS_SAGE_INFER_MEAN: out[i, :] = bf16( (1.0f / (float)max(deg_i, 1)) * S_i ), S_i the fp32 sum bliss_spmm_fwd(mean = 1,
+ *     w = NULL) produces for row i on the full-neighbour block of i's batch: the batch's CSC positions are cut into chunks of EC_b
+ *     counted from E0_b, a row's terms inside a chunk are added in edge order starting from +0, a row's chunk partials are added
+ *     in chunk order starting from the first; one product with the scale, one rounding.
+ *   BLISS_SAGE_INFER_MAX: out[i, c] = max over the in-edges of h[indices[e], c] by the rule of bliss_spmm_max_fwd(w = NULL,
+ *     arg = NULL): the running best starts at the first edge's value and moves on strict > (float compare) in edge order; the
+ *     batch structure does not enter the value.  Inputs are finite.  No arg is written.
+ *   A row without edges is +0 under both.  Bitwise reproducible: no float atomics, no partial buffer, no fix-up launch.
+ * The range rules are bliss_gcn_infer_spmm's: row0 % batch_size == 0 and row0 + n_rows a multiple of batch_size or n_nodes;
+ * edge0 = indptr[row0] and n_edges = indptr[row0 + n_rows] - edge0 as the HOST knows them; n_edges < 2^31 (offsets inside a range
+ * are 32-bit, everything added to a pointer is 64-bit).  indices[] < n_nodes is the caller's.
+ *   indptr int64 [n_nodes + 1], 8-byte aligned; indices int32, 4-byte aligned; h bf16 [n_nodes, dim], row stride h_stride >= dim;
+ *   out bf16 [n_rows, dim]: row r of the RANGE, stride out_stride >= dim.
+ * One call is one launch, a wave per row.  8-byte accesses when dim % 4 == 0, both strides % 4 == 0 and h, out 8-byte aligned;
+ * one feature per lane otherwise (same bits).  A row whose batch does not lie inside [edge0, edge0 + n_edges) is left untouched.
+ * n_rows == 0 returns 0.
+ * BLISS_EINVAL before any launch: args, indptr, indices, h or out NULL; n_nodes <= 0; batch_size < 1; row0 or n_rows negative or
+ * past n_nodes; a range that cuts a batch; edge0 or n_edges negative, n_edges >= 2^31; reduce not 0 or 1; dim <= 0; a stride
+ * below dim; a misaligned indptr or indices (h or out at an odd address). */
+#define BLISS_SAGE_INFER_MEAN 0
+#define BLISS_SAGE_INFER_MAX  1
+typedef struct {
+  const int64_t* indptr; const int32_t* indices; int32_t n_nodes; int32_t batch_size;
+  int32_t row0; int32_t n_rows; int64_t edge0; int64_t n_edges;   /* a range of whole batches, as bliss_gcn_infer_t */
+  int32_t reduce;
+  const void* h; int64_t h_stride; int32_t dim;                   /* bf16 [n_nodes, dim] */
+  void* out; int64_t out_stride;                                  /* bf16 [n_rows, dim]: row r of the RANGE */
+} bliss_sage_infer_t;
+int bliss_sage_infer_spmm(const bliss_sage_infer_t* args, void* stream);
+
 /* Per-kernel timing with HIP events recorded on the launching stream (bench.py's roofline object).
  * bliss_prof_enable(id): -2 off (default), -1 every kernel, >= 0 one kernel id; names via
  * bliss_prof_kernel_name(id), id < bliss_prof_kernel_count().  bliss_prof_read synchronises on the
