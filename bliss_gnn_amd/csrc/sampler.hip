@@ -964,9 +964,12 @@ __device__ __forceinline__ double block_sum_f64(double v, double* shd) {
 template <bool COHERENT>
 __device__ __forceinline__ void poisson_scale_body(int* hist, LayerCounts* cnt, int C, int num, double eps, int* rng_ctl,
                                                    int* layer_off, int is_last, int rng_cap_total, int* __restrict__ sel_state,
-                                                   double* shd) {
-  // ticket + one status word per 1024-candidate chunk for k_select_fused's look-back
-  for (int i = threadIdx.x; i < (C + CHUNK - 1) / CHUNK + 2; i += 1024) sel_state[i] = 0;
+                                                   int state_words, double* shd) {
+  // ticket + one status word per 1024-candidate chunk for k_select_fused's look-back, and one spare -- but never past the
+  // `state_words` the caller's array holds: ws->chunk_cnt is documented as cap_c / 1024 + 2 words, which covers the 1 +
+  // ceil(C / CHUNK) words in use for every C <= cap_c, and ceil(C / CHUNK) + 2 is one more than that whenever C is no multiple of CHUNK
+  const int n_state = min((C + CHUNK - 1) / CHUNK + 2, state_words);
+  for (int i = threadIdx.x; i < n_state; i += 1024) sel_state[i] = 0;
   // the random numbers of this layer come from the streaming generator: one lane waits for them while the others work
   if (rng_ctl && threadIdx.x == 1023) rng_stream_acquire(rng_ctl, C, layer_off, is_last, rng_cap_total);
   // every thread owns 32 bins; load the counts and leave the histogram zero for the next layer
@@ -1013,14 +1016,15 @@ __device__ __forceinline__ void poisson_scale_body(int* hist, LayerCounts* cnt, 
 }
 
 __global__ void __launch_bounds__(1024) k_poisson_scale(int* hist, LayerCounts* cnt, int num, double eps, int* rng_ctl,
-                                                        int* layer_off, int is_last, int rng_cap_total, int* __restrict__ sel_state) {
+                                                        int* layer_off, int is_last, int rng_cap_total, int* __restrict__ sel_state,
+                                                        int state_words) {
   __shared__ double shd[16];
-  poisson_scale_body<false>(hist, cnt, cnt->C, num, eps, rng_ctl, layer_off, is_last, rng_cap_total, sel_state, shd);
+  poisson_scale_body<false>(hist, cnt, cnt->C, num, eps, rng_ctl, layer_off, is_last, rng_cap_total, sel_state, state_words, shd);
 }
 
 // the Poisson scale in k_cand_number's launch: the last workgroup to have flushed its histogram runs it (one launch less on
 // the sampler's critical chain, ~4.5 us per layer)
-struct FusedScale { int* ticket; int num; double eps; int* rng_ctl; int* layer_off; int is_last; int rng_cap_total; int* sel_state; };
+struct FusedScale { int* ticket; int num; double eps; int* rng_ctl; int* layer_off; int is_last; int rng_cap_total; int* sel_state; int state_words; };
 __global__ void __launch_bounds__(FIN_TPB) k_cand_number(const int* __restrict__ seeds, LayerCounts* cnt, int* __restrict__ cand_nid,
                                                          int* local_id, const unsigned long long* __restrict__ seed_p2,
                                                          const unsigned long long* __restrict__ touched_key,
@@ -1046,7 +1050,13 @@ __global__ void __launch_bounds__(FIN_TPB) k_cand_number(const int* __restrict__
     run += total;
   }
   int C = S + run;
-  if (C > cap_c) { C = cap_c; if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(&cnt->err, BLISS_ERR_CAP_CAND); }
+  if (C > cap_c) {
+    // k_bin_reduce has cut the touched list at cap_c entries in no particular order: numbering what is left would leave holes
+    // below cap_c, entries of cand_nid / p that nobody writes and that the select, the block passes and the cleanup index the
+    // node maps with.  The flagged layer keeps its seeds only: every entry below C is written, the maps stay clean.
+    C = min(S, cap_c);
+    if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(&cnt->err, BLISS_ERR_CAP_CAND);
+  }
   if (blockIdx.x == 0 && threadIdx.x == 0) cnt->C = C;
   if (blockIdx.x != 0 && (int)blockIdx.x * FIN_TPB >= C) return;      // surplus workgroups (workgroup 0 always takes part)
   {
@@ -1109,7 +1119,7 @@ __global__ void __launch_bounds__(FIN_TPB) k_cand_number(const int* __restrict__
     }
     __syncthreads();
     if (sh_is_last)
-      poisson_scale_body<true>(hist, cnt, C, fs.num, fs.eps, fs.rng_ctl, fs.layer_off, fs.is_last, fs.rng_cap_total, fs.sel_state, shd);
+      poisson_scale_body<true>(hist, cnt, C, fs.num, fs.eps, fs.rng_ctl, fs.layer_off, fs.is_last, fs.rng_cap_total, fs.sel_state, fs.state_words, shd);
   }
 }
 
@@ -1750,7 +1760,7 @@ int bliss_frontier_prob(const bliss_graph_t* g, const bliss_node_maps_t* m, cons
     PROF_LAUNCH(BK_CAND_NUMBER, st, k_cand_number<<<gf, FIN_TPB, 0, st>>>(
         seeds, cnt, ws->cand_nid, m->local_id, seed_p2, (const unsigned long long*)ws->touched_key,
         (const unsigned long long*)ws->touched_sum, ws->bitmap, word_prefix, tile_sum, (bf16_t*)ws->p, ws->hist, ws->cap_c, uniform_nodes,
-        FusedScale{ws->fs_ticket, ws->fs_fanout, ws->fs_eps, ws->fs_rng_ctl, ws->fs_layer_off, ws->fs_is_last, ws->fs_rng_cap, ws->chunk_cnt}));
+        FusedScale{ws->fs_ticket, ws->fs_fanout, ws->fs_eps, ws->fs_rng_ctl, ws->fs_layer_off, ws->fs_is_last, ws->fs_rng_cap, ws->chunk_cnt, ws->cap_c / CHUNK + 2}));
     return (int)hipGetLastError();
   }
   if (mode == BLISS_MODE_BANDIT) {
@@ -1784,7 +1794,7 @@ int bliss_poisson_select(const bliss_layer_ws_t* ws, int32_t fanout, double eps,
   if (cand_bound < 1) cand_bound = 1;
   if (cand_bound > ws->cap_c) cand_bound = ws->cap_c;
   if (!ws->fs_ticket)                                  // (else k_cand_number's last workgroup has computed the scale)
-    PROF_LAUNCH(BK_POISSON_SCALE, st, k_poisson_scale<<<1, 1024, 0, st>>>(ws->hist, cnt, fanout, eps, rng_ctl, uniforms_offset_dev, is_last, rng_cap_total, ws->chunk_cnt));
+    PROF_LAUNCH(BK_POISSON_SCALE, st, k_poisson_scale<<<1, 1024, 0, st>>>(ws->hist, cnt, fanout, eps, rng_ctl, uniforms_offset_dev, is_last, rng_cap_total, ws->chunk_cnt, ws->cap_c / CHUNK + 2));
   PROF_LAUNCH(BK_SELECT2, st, k_select_fused<<<grid_for(cand_bound, CHUNK, 1 << 20), TPB, 0, st>>>(
       (const bf16_t*)ws->p, uniforms, uniforms_offset_dev, cnt, (bf16_t*)ws->P, ws->chunk_cnt, ws->cand_nid, ws->new_id, ws->kept_nid,
       (bf16_t*)ws->node_prob, ws->cap_c, ws->cap_k, ws->kept_map));
@@ -1799,17 +1809,19 @@ int bliss_poisson_select_keyed(const bliss_layer_ws_t* ws, int32_t fanout, doubl
   if (cand_bound < 1) cand_bound = 1;
   if (cand_bound > ws->cap_c) cand_bound = ws->cap_c;
   if (!ws->fs_ticket)                                  // (else k_cand_number's last workgroup has computed the scale)
-    PROF_LAUNCH(BK_POISSON_SCALE, st, k_poisson_scale<<<1, 1024, 0, st>>>(ws->hist, cnt, fanout, eps, nullptr, nullptr, 0, 0, ws->chunk_cnt));
+    PROF_LAUNCH(BK_POISSON_SCALE, st, k_poisson_scale<<<1, 1024, 0, st>>>(ws->hist, cnt, fanout, eps, nullptr, nullptr, 0, 0, ws->chunk_cnt, ws->cap_c / CHUNK + 2));
   PROF_LAUNCH(BK_SELECT2, st, k_select_keyed<<<grid_for(cand_bound, CHUNK, 1 << 20), TPB, 0, st>>>(
       (const bf16_t*)ws->p, KeyedDraw{(unsigned long long)seed, (long long*)step_dev, (int)layer, bump_step ? 1 : 0}, cnt, (bf16_t*)ws->P,
       ws->chunk_cnt, ws->cand_nid, ws->new_id, ws->kept_nid, (bf16_t*)ws->node_prob, ws->cap_c, ws->cap_k, ws->kept_map));
   return (int)hipGetLastError();
 }
 
+// (the scratch has no capacity beside it: the caller sizes it from counts->C, (C + 1023) / 1024 + 2 words, and all of them are zeroed)
+constexpr int SCRATCH_UNBOUNDED = 0x7fffffff;
 int bliss_poisson_scale(int32_t* hist, void* counts, int32_t fanout, double eps, int32_t* scratch, void* stream_) {
   if (!hist || !counts || !scratch || fanout < 0) return BLISS_EINVAL;
   hipStream_t st = (hipStream_t)stream_;
-  PROF_LAUNCH(BK_POISSON_SCALE, st, k_poisson_scale<<<1, 1024, 0, st>>>(hist, (LayerCounts*)counts, fanout, eps, nullptr, nullptr, 0, 0, scratch));
+  PROF_LAUNCH(BK_POISSON_SCALE, st, k_poisson_scale<<<1, 1024, 0, st>>>(hist, (LayerCounts*)counts, fanout, eps, nullptr, nullptr, 0, 0, scratch, SCRATCH_UNBOUNDED));
   return (int)hipGetLastError();
 }
 

@@ -150,7 +150,8 @@ int bliss_flag_raise(int32_t* flag, void* stream);
  * exp3_weights row (BANDIT) or g.edata['w'] (LADIES).  eta_f = (float)eta,
  * one_minus_eta_f = (float)(1.0 - eta).  frontier_bound >= number of in-edges of the seeds
  * (num_edges is always valid).  Out (in ws): counts{S,E,C}, seg_ptr, cand_nid, p; the node maps
- * hold local ids of all candidates until bliss_build_block cleans them. */
+ * hold local ids of all candidates until bliss_build_block cleans them.  More than cap_c candidates: error bit 2 and a list that
+ * is invalid but complete below counts.C -- the seeds only (binned pipeline) or the first cap_c candidates (atomic passes). */
 int bliss_frontier_prob(const bliss_graph_t* g, const bliss_node_maps_t* maps, const void* w_pos,
                         const int32_t* seeds, int32_t n_seeds, const int32_t* n_seeds_dev, int32_t cap_s, int mode,
                         float eta_f, float one_minus_eta_f, int64_t frontier_bound, const bliss_layer_ws_t* ws,
@@ -464,7 +465,7 @@ int64_t bliss_rng_stream_handle(void);
  *   bliss_cand_importance: p_j = sqrt(bf16(exact sum)) (:75) from the summed Q.44 partials (uniform_nodes: [sum != 0], :79-81);
  *   bliss_poisson_scale:   the fixed point c of :391-401 from the GLOBAL histogram of p's bit patterns (hist int32[32768],
  *                          left zeroed) and the global candidate count counts->C; writes counts->{c, iters, all_one};
- *                          scratch: int32[counts->C / 1024 + 2];
+ *                          scratch: int32[(counts->C + 1023) / 1024 + 2], left zeroed;
  *   bliss_keyed_select:    P_j = seed ? 1 : min(c p_j, 1) (:403-406) and the Poisson draw u < P (:422-424) with the
  *                          counter-based uniform of (seed, step, layer, node id) -- SplitMix64 finaliser, top 24 bits -- since
  *                          shards cannot share torch's serial stream; keep[j] = 1 iff drawn. */
