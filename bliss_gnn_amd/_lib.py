@@ -293,6 +293,8 @@ SIGNATURES = {
     "bliss_spmm_max_fwd": [_P, _P, _P, _P, _P, _I64, _I32, _P, _I32, _I32, _P, _I64, _P, _I64, _P, _P],
     "bliss_spmm_max_bwd": [_P, _P, _P, _P, _P, _P, _I64, _P, _I64, _I32, _P, _I32, _I32, _P, _I64, _P, _P],
     "bliss_spmm_max_bwd_relu": [_P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _I32, _P, _I32, _I32, _P, _I64, _P, _P],
+    "bliss_spmm_self_fwd": [_P, _P, _P, _P, _P, _I64, _P, _I64, _I32, _P, _P, _I32, _I32, _P, _I64, _P, _P],
+    "bliss_spmm_self_bwd": [_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P, _P, _I32, _I32, _P, _I64, _P, _P],
     "bliss_block_transpose": [_P, _P, _I32, _I32, _I32, _P, _P, _P, _I64, _P],
     "bliss_spmm_chunk_edges": [_I32],
     "bliss_sage_epilogue_fwd": [_P, _I64, _P, _I64, _I32, _I32, _F, C.c_uint32, _P, _P, _I64, _P, _P],

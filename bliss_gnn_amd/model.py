@@ -7,7 +7,7 @@ runs the SAGEConv layers with the sampler's edge weights (model.py:321-329).
 import torch
 import torch.nn as nn
 
-from .nn import TILE_KINDS, SAGEConv, embed_norm, sage_epilogue
+from .nn import TILE_KINDS, SAGEConv, SAGEGCNConv, embed_norm, sage_epilogue
 
 
 def _gathered_norm(blocks, x):
@@ -27,8 +27,9 @@ class SAGE(nn.Module):
     # for "mean" the MFMA path of "auto" (same launches and bits, in_feats <= 1024), for "pool" nn.sage_pool_tile per layer.
     SAGE_TRANSFORMS = ("auto", "wide", "tile")
     # "pool" (DESIGN.md section 30): SAGEConv(..., "pool") layers on library GEMMs and the max-reduce kernels of csrc/spmm_max.hip
-    # under "auto"; on the tile kernels under "tile" (section 32).
-    SAGE_AGGREGATORS = ("mean", "pool")
+    # under "auto"; on the tile kernels under "tile" (section 32).  "gcn" (section 34): nn.SAGEGCNConv layers -- library GEMMs
+    # and the self-inclusive normalised sum of csrc/spmm_self.hip under "auto", nn.sage_gcn_tile per layer under "tile".
+    SAGE_AGGREGATORS = ("mean", "pool", "gcn")
 
     def __init__(self, in_feats, n_hidden, n_classes, n_layers, activation, dropout, transforms="auto", aggregator_type="mean"):
         super().__init__()
@@ -42,13 +43,14 @@ class SAGE(nn.Module):
         self.transforms, self.aggregator_type = transforms, aggregator_type
         self.n_layers, self.n_hidden, self.n_classes = n_layers, n_hidden, n_classes
         self.layers = nn.ModuleList()
+        mk = (lambda i, o: SAGEGCNConv(i, o)) if aggregator_type == "gcn" else (lambda i, o: SAGEConv(i, o, aggregator_type))
         if n_layers > 1:
-            self.layers.append(SAGEConv(in_feats, n_hidden, aggregator_type))
+            self.layers.append(mk(in_feats, n_hidden))
             for _ in range(1, n_layers - 1):
-                self.layers.append(SAGEConv(n_hidden, n_hidden, aggregator_type))
-            self.layers.append(SAGEConv(n_hidden, n_classes, aggregator_type))
+                self.layers.append(mk(n_hidden, n_hidden))
+            self.layers.append(mk(n_hidden, n_classes))
         else:
-            self.layers.append(SAGEConv(in_feats, n_classes, aggregator_type))
+            self.layers.append(mk(in_feats, n_classes))
         self.dropout = nn.Dropout(dropout)
         self.activation = activation
 
@@ -110,11 +112,15 @@ class SAGE(nn.Module):
     def _pool_tile(self):
         return self.transforms == "tile" and self.aggregator_type == "pool"
 
+    @property
+    def _gcn_tile(self):
+        return self.transforms == "tile" and self.aggregator_type == "gcn"
+
     def tile_refusal(self, x):
         """Why transforms="tile" cannot take ``x`` (a tensor or LazyRows of the input rows, or a parameter), or None."""
         import os
         from .nn import TILE_GEMM_MAX_K, TILE_GEMM_MAX_N, tile_gemm_ok
-        if not self._pool_tile:
+        if not (self._pool_tile or self._gcn_tile):
             return self.mfma_refusal(x)
         what = 'SAGE: transforms="tile"'
         for env in ("BLISS_SAGE_MFMA", "BLISS_SAGE_MFMA_BWD"):
@@ -129,7 +135,11 @@ class SAGE(nn.Module):
         if not isinstance(self.dropout, nn.Dropout):
             return "%s covers nn.Dropout (the tail's own counter-based stream), not %s" % (what, type(self.dropout).__name__)
         for l, layer in enumerate(self.layers):
-            if layer.norm is not None or layer.activation is not None or layer.feat_drop.p != 0 or layer.fc_self.bias is None:
+            if self._gcn_tile:                                                   # ('gcn' has no fc_self; its bias is optional)
+                if layer.norm is not None or layer.activation is not None or layer.feat_drop.p != 0:
+                    return ("SAGE layer %d: transforms=\"tile\" covers plain SAGEConv layers (no norm, activation or feat_drop of "
+                            "their own)" % l)
+            elif layer.norm is not None or layer.activation is not None or layer.feat_drop.p != 0 or layer.fc_self.bias is None:
                 return ("SAGE layer %d: transforms=\"tile\" covers plain SAGEConv layers with a bias (no norm, activation or feat_drop "
                         "of their own)" % l)
             if not tile_gemm_ok(layer._in_src_feats, layer._out_feats):
@@ -145,6 +155,11 @@ class SAGE(nn.Module):
             if why is not None:
                 raise NotImplementedError(why)
             return "pool"
+        if self._gcn_tile:
+            why = self.tile_refusal(x)
+            if why is not None:
+                raise NotImplementedError(why)
+            return "gcn"
         if self._mfma_ok(x):
             return True
         if self.transforms != "auto":
@@ -166,6 +181,31 @@ class SAGE(nn.Module):
             h, out_norm, in_norm = sage_pool_tile(block, h, ew, layer, not last, p, ctr, seed)
             block.srcdata["embed_norm"] = in_norm if norm is None else norm      # model.py:318-320 (same bits either way)
             norm = None if last else out_norm
+        return h, norm
+
+    def _gcn_drop_state(self, l, device):
+        """The keyed dropout stream of layer l's epilogue (nn.gat_drop_state: launch counter and seed)."""
+        from .nn import gat_drop_state
+        if not hasattr(self, "_gcn_dstate"):
+            self._gcn_dstate = {}
+        key = (l, str(device))
+        if key not in self._gcn_dstate:
+            self._gcn_dstate[key] = gat_drop_state(l + 1, device)
+        return self._gcn_dstate[key]
+
+    def _layers_gcn_tile(self, blocks, h, norm, lo, hi):
+        """model.py:312-333, layers lo..hi-1, for 'gcn' on bounded kernels: per layer one autograd node,
+        nn.sage_gcn_tile -- fc_neigh on the tile product, the self-inclusive normalised sum, and ONE epilogue launch with the bias,
+        ReLU, the model's dropout and the next layer's row norms."""
+        from .nn import sage_gcn_tile
+        n_layers = len(self.layers)
+        for l in range(lo, hi):
+            layer, block = self.layers[l], blocks[l]
+            last = l == n_layers - 1
+            block.srcdata["embed_norm"] = embed_norm(h) if norm is None else norm            # model.py:318-320
+            ew = block.edata["edge_weights"] if "edge_weights" in block.edata else None
+            p = float(self.dropout.p) if (self.training and not last) else 0.0
+            h, norm = sage_gcn_tile(block, h, ew, layer, not last, p, self._gcn_drop_state(l, h.device) if p > 0 else None, not last)
         return h, norm
 
     def _layers_mfma(self, blocks, h, norm, lo, hi, parts=False):
@@ -231,12 +271,14 @@ class SAGE(nn.Module):
         from .nn import LazyRows
         if mfma == "pool":
             return self._layers_pool_tile(blocks, x, norm, lo, hi)
-        if mfma:
+        if mfma is True:
             return self._layers_mfma(blocks, x, norm, lo, hi)
         if isinstance(x, LazyRows):
             x = x.materialize()
         if lo == 0 and norm is None:
             norm = _gathered_norm(blocks, x)
+        if mfma == "gcn":
+            return self._layers_gcn_tile(blocks, x, norm, lo, hi)
         return self._layers_plain(blocks, x, norm, lo, hi)
 
     def forward(self, blocks, x):
@@ -284,6 +326,9 @@ class SAGE(nn.Module):
         """Why ``inference(path="csc")`` cannot run on this graph, these features and this batch size, or None."""
         if int(batch_size) < 1:
             return "SAGE.inference: the CSC path takes batch_size >= 1, not %d" % int(batch_size)
+        if self.aggregator_type == "gcn":
+            return ('SAGE.inference: the CSC path covers aggregator_type "mean" and "pool", not "gcn" (DESIGN.md section 34); '
+                    'path="blocks" and "chunks" run it')
         if self.aggregator_type == "pool":
             if self.transforms != "tile":
                 return ('SAGE.inference: the CSC path of aggregator_type="pool" has the bits of the tile kernels; build the model '
@@ -377,7 +422,7 @@ class SAGE(nn.Module):
         one forward-only message-passing launch per range of rows straight off the graph's CSC -- the bits of "blocks" at the
         same ``batch_size``, no block built (``node_chunk`` is ignored).  Raises NotImplementedError naming the reason
         (``csc_refusal``) when it cannot run.
-        ``path="auto"``: "csc" when nothing refuses it, "chunks" otherwise."""
+        ``path="auto"``: "csc" when nothing refuses it, "chunks" otherwise ("blocks" for aggregator_type="gcn", which has no CSC path)."""
         if path not in self.INFERENCE_PATHS:
             raise ValueError("path must be one of %r, not %r" % (self.INFERENCE_PATHS, path))
         h = g.ndata["features"]                                              # :346
@@ -385,7 +430,7 @@ class SAGE(nn.Module):
             why = self.csc_refusal(g, h, batch_size)
             if path == "csc" and why is not None:
                 raise NotImplementedError(why)
-            path = "csc" if why is None else "chunks"
+            path = "csc" if why is None else ("blocks" if self.aggregator_type == "gcn" else "chunks")
         was_training = self.training
         self.eval()                                                          # :364
         try:
@@ -406,9 +451,9 @@ class SAGE(nn.Module):
         V = g.num_nodes()
         deg = g.indptr[1:] - g.indptr[:-1]
         dst_all = torch.repeat_interleave(torch.arange(V, device=g.device, dtype=torch.int32), deg)
-        pool = self.aggregator_type == "pool"
+        pool, gcn = self.aggregator_type == "pool", self.aggregator_type == "gcn"
         for l, layer in enumerate(self.layers):                              # :366
-            before = not pool and layer._in_src_feats > layer._out_feats     # SAGEConv 'mean': fc_neigh before aggregation iff in > out
+            before = not pool and layer._in_src_feats > layer._out_feats     # SAGEConv 'mean', 'gcn': fc_neigh before aggregation iff in > out
             if pool:                                                         # relu(fc_pool(h)) once over all nodes, fc_neigh after the max
                 src_feat = torch.relu(layer.fc_pool(h))
             else:
@@ -416,10 +461,13 @@ class SAGE(nn.Module):
             y = torch.empty(V, layer._out_feats, dtype=h.dtype, device=h.device)
             for b0 in range(0, V, node_chunk):
                 b1 = min(V, b0 + node_chunk)
-                neigh = _full_neighbor(g, src_feat, b0, b1, dst_all, pool)
+                neigh = _full_neighbor(g, src_feat, b0, b1, dst_all, pool, gcn)
                 if not before:
                     neigh = layer.fc_neigh(neigh)
-                out = layer.fc_self(h[b0:b1]) + neigh
+                if gcn:                                                      # (no fc_self: the node's own row rode in the aggregation)
+                    out = neigh if layer.bias is None else neigh + layer.bias
+                else:
+                    out = layer.fc_self(h[b0:b1]) + neigh
                 if l < len(self.layers) - 1:
                     out = self.dropout(self.activation(out))                 # :377-379 (dropout is the identity in eval mode)
                 y[b0:b1] = out
@@ -458,18 +506,21 @@ def _csc_groups(ranges, spmm_edges):
     return groups
 
 
-def _full_neighbor(g, h, b0, b1, dst_all, pool=False):
-    """mean (``pool``: max, no winning edge recorded) over ALL in-neighbours of nodes b0..b1-1 (a MultiLayerFullNeighborSampler(1)
+def _full_neighbor(g, h, b0, b1, dst_all, pool=False, gcn=False):
+    """mean (``pool``: max, no winning edge recorded; ``gcn``: the self-inclusive normalised sum, the destinations' rows h[b0:b1]
+    handed over as h_self since they are not the leading source rows) over ALL in-neighbours of nodes b0..b1-1 (a MultiLayerFullNeighborSampler(1)
     block without edge weights, model.py:347-349, 375-376): the CSC columns of a contiguous node range are one contiguous slice."""
     import torch
     from .graph import Block
-    from .nn import max_aggregate, weighted_aggregate
+    from .nn import gcn_aggregate, max_aggregate, weighted_aggregate
     e0, e1 = int(g.indptr[b0]), int(g.indptr[b1])
     indptr = (g.indptr[b0:b1 + 1] - e0).to(torch.int32)
     src = g.indices[e0:e1]
     dst = dst_all[e0:e1] - b0
     blk = Block(None, h.shape[0], b1 - b0, indptr, src, dst, src, src, torch.empty(0, dtype=torch.int32, device=h.device))
     blk._transposed = (None, None)
+    if gcn:
+        return gcn_aggregate(blk, h, None, h_self=h[b0:b1])
     return max_aggregate(blk, h, None) if pool else weighted_aggregate(blk, h, None, mean=True)
 
 

@@ -5,6 +5,8 @@
 fc_neigh (bias-free) is applied BEFORE aggregation iff in > out; fc_self carries the bias; both
 weights xavier-uniform with gain('relu').  The dense transforms are plain library GEMMs (hipBLASLt
 through torch.nn.functional.linear); the aggregation and its backward are ours.
+'pool' (max-reduce, csrc/spmm_max.hip) and 'gcn' (the self-inclusive normalised sum of csrc/spmm_self.hip: no fc_self, a
+plain bias) are the other two aggregators built: DESIGN.md sections 30 and 34.
 """
 import torch
 import torch.nn as nn
@@ -72,6 +74,29 @@ def max_aggregate(block, h, edge_weight=None, return_arg=False):
     out, arg = ops.spmm_max(block.indptr, block.src, block.dst, w, h, block.num_dst_nodes(), counts,
                             bool(return_arg or t_indptr is not None), t_indptr, t_edge)
     return (out, arg) if return_arg else out
+
+
+def gcn_aggregate(block, h, edge_weight=None, h_self=None):
+    """out[i] = (sum_{e -> i} w_e h[src_e] + h_self[i]) / (deg_i + 1) over a Block, ONE rounding -- ``torch.ops.bliss.spmm_self``
+    (csrc/spmm_self.hip, DESIGN.md section 34: the 'gcn' aggregator of dglnn.SAGEConv [DGL-recalled]).  ``h_self=None``: the
+    destinations are the leading rows of ``h``, and the gradient w.r.t. h carries the self term on those rows.  A distinct
+    ``h_self`` (the (feat_src, feat_dst) pair form) is forward-only: one that requires a gradient is refused."""
+    from . import ops
+    if h_self is h:
+        h_self = None
+    if h_self is not None:
+        assert h_self.is_cuda and h_self.dtype == torch.bfloat16, "bf16 features on the GPU (load_graph.py:7)"
+        if h_self.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError("gcn_aggregate: a distinct h_self that requires a gradient (the (feat_src, feat_dst) pair form under "
+                                      "training) is not built: DESIGN.md section 34")
+        if h_self.stride(1) != 1:
+            h_self = h_self.contiguous()
+        if h_self.shape[0] < block.num_dst_nodes() or h_self.shape[1] != h.shape[1]:
+            raise ValueError("gcn_aggregate: h_self is [num_dst_nodes, dim] like h")
+    elif h.shape[0] < block.num_dst_nodes():
+        raise ValueError("gcn_aggregate: the destinations are the leading rows of h; pass h_self for any other block")
+    h, w, counts, t_indptr, t_edge = _aggregate_operands(block, h, edge_weight)
+    return ops.spmm_self(block.indptr, block.src, block.dst, w, h, h_self, block.num_dst_nodes(), counts, t_indptr, t_edge)
 
 
 class _SageEpilogue(torch.autograd.Function):
@@ -754,13 +779,18 @@ def tile_gemm_ok(in_feats, out_feats, wide=False):
 class SAGEConv(nn.Module):
     """dglnn.SAGEConv(in_feats, out_feats, 'mean') as used at model.py:303-308, 321-329, and [DGL-recalled] the 'pool'
     aggregator: neigh = max over the in-edges of relu(fc_pool(feat_src))[src_e] * w_e, then fc_neigh --
-    never fc_neigh before the aggregation, which DGL has for 'mean' and 'gcn' only."""
+    never fc_neigh before the aggregation, which DGL has for 'mean' and 'gcn' only; and [DGL-recalled] the 'gcn' aggregator, which SAGEGCNConv below constructs (DESIGN.md
+    section 34): rst = fc_neigh o agg + bias, agg[i] = (sum_e w_e z[src_e] + z_dst[i]) / (deg_i + 1), fc_neigh first iff in > out, no
+    fc_self, a plain ``bias`` parameter."""
+
+    _AGGREGATORS = ("mean", "pool")              # what this class's constructor takes; SAGEGCNConv below: ("gcn",)
 
     def __init__(self, in_feats, out_feats, aggregator_type="mean", feat_drop=0.0, bias=True, norm=None, activation=None):
         super().__init__()
-        if aggregator_type not in ("mean", "pool"):
-            raise NotImplementedError("SAGEConv: aggregator_type 'mean' (model.py:303-308) and 'pool' are built, not %r "
-                                      "('gcn' and 'lstm' are not: DESIGN.md section 30)" % (aggregator_type,))
+        if aggregator_type not in self._AGGREGATORS:
+            raise NotImplementedError("SAGEConv: aggregator_type 'mean' (model.py:303-308) and 'pool' are built here and 'gcn' as "
+                                      "nn.SAGEGCNConv(in_feats, out_feats, ...), not %r ('lstm' is not built: DESIGN.md section 34)"
+                                      % (aggregator_type,))
         self._aggre_type = aggregator_type
         self._in_src_feats = self._in_dst_feats = in_feats
         self._out_feats = out_feats
@@ -769,23 +799,53 @@ class SAGEConv(nn.Module):
         if aggregator_type == "pool":
             self.fc_pool = nn.Linear(in_feats, in_feats)
         self.fc_neigh = nn.Linear(in_feats, out_feats, bias=False)
-        self.fc_self = nn.Linear(in_feats, out_feats, bias=bias)
+        if aggregator_type == "gcn":                 # no fc_self: the destination's own row rides in the aggregation; a plain bias
+            if bias:
+                self.bias = nn.Parameter(torch.zeros(out_feats))
+            else:
+                self.register_parameter("bias", None)
+        else:
+            self.fc_self = nn.Linear(in_feats, out_feats, bias=bias)
         self.reset_parameters()
 
     def reset_parameters(self):
         gain = nn.init.calculate_gain("relu")
         if self._aggre_type == "pool":
             nn.init.xavier_uniform_(self.fc_pool.weight, gain=gain)
-        nn.init.xavier_uniform_(self.fc_self.weight, gain=gain)
+        if self._aggre_type == "gcn":
+            if self.bias is not None:
+                nn.init.zeros_(self.bias)
+        else:
+            nn.init.xavier_uniform_(self.fc_self.weight, gain=gain)
         nn.init.xavier_uniform_(self.fc_neigh.weight, gain=gain)
 
+    def _forward_gcn(self, graph, feat_src, feat_dst, edge_weight):
+        """rst = fc_neigh o agg, agg[i] = (sum_e w_e z[src_e] + z_dst[i]) / (deg_i + 1); ``feat_dst`` None: the
+        destinations are the leading source rows."""
+        lin_first = self._in_src_feats > self._out_feats
+        z = self.fc_neigh(feat_src) if lin_first else feat_src
+        z_dst = None
+        if feat_dst is not None:
+            z_dst = self.fc_neigh(feat_dst) if lin_first else feat_dst
+        agg = gcn_aggregate(graph, z, edge_weight, z_dst)
+        rst = agg if lin_first else self.fc_neigh(agg)
+        return rst if self.bias is None else rst + self.bias
+
     def forward(self, graph, feat, edge_weight=None, parts=False):
-        """``parts=True`` returns (fc_self(h_dst), h_neigh) un-added, for a caller that fuses the sum with what follows."""
+        """``parts=True`` returns (fc_self(h_dst), h_neigh) un-added, for a caller that fuses the sum with what follows ('gcn' has no
+        two parts: the finished tensor)."""
         if isinstance(feat, tuple):                  # (feat_src, feat_dst) like dglnn.SAGEConv: destinations that are not the
             feat_src, feat_dst = self.feat_drop(feat[0]), self.feat_drop(feat[1])      # leading source rows (shard blocks)
         else:
             feat_src = self.feat_drop(feat)
             feat_dst = feat_src[: graph.num_dst_nodes()]
+        if self._aggre_type == "gcn":
+            rst = self._forward_gcn(graph, feat_src, feat_dst if isinstance(feat, tuple) else None, edge_weight)
+            if self.activation is not None:
+                rst = self.activation(rst)
+            if self.norm is not None:
+                rst = self.norm(rst)
+            return rst
         if self._aggre_type == "pool":
             h_neigh = self.fc_neigh(max_aggregate(graph, torch.relu(self.fc_pool(feat_src)), edge_weight))
         elif self._in_src_feats > self._out_feats:   # fc_neigh before the aggregation
@@ -800,6 +860,17 @@ class SAGEConv(nn.Module):
         if self.norm is not None:
             rst = self.norm(rst)
         return rst
+
+
+class SAGEGCNConv(SAGEConv):
+    """[DGL-recalled] dglnn.SAGEConv(in_feats, out_feats, 'gcn'), a class of its own because
+    ``SAGEConv(in, out, "gcn")`` keeps refusing, as it always has: rst = fc_neigh o agg + bias, agg[i] = (sum_e w_e z[src_e] +
+    z_dst[i]) / (deg_i + 1), fc_neigh first iff in > out; parameters ``fc_neigh.weight`` and a plain ``bias``, no ``fc_self``.
+    ``forward(graph, feat, edge_weight=None)`` is SAGEConv's, both orders of fc_neigh and the (feat_src, feat_dst) pair form."""
+    _AGGREGATORS = ("gcn",)
+
+    def __init__(self, in_feats, out_feats, feat_drop=0.0, bias=True, norm=None, activation=None):
+        super().__init__(in_feats, out_feats, "gcn", feat_drop=feat_drop, bias=bias, norm=norm, activation=activation)
 
 
 # transforms="tile" (DESIGN.md section 26): GraphConv(norm='both') on bounded kernels -- the degree-normalised SpMM of csrc/gcn.hip,
@@ -926,6 +997,131 @@ class _GcnLayer(torch.autograd.Function):
         if dx is not None and x_rows > n_src:
             dx = torch.cat([dx, _zero_rows(x_rows - n_src, dx)])
         return (dx, dw, db) + (None,) * 10
+
+
+# transforms="tile" for SAGEConv 'gcn' (DESIGN.md section 34): fc_neigh on bliss_tile_gemm, the self-inclusive normalised sum of
+# csrc/spmm_self.hip and GraphConv's row-wise epilogue; every loop that crosses rows or edges is bounded by the block's device-side counts.
+def _spmm_self_launch(backward, idx, w, h, n_src, n_dst, words):
+    """bliss_spmm_self_fwd (out [n_dst, dim] from h [n_src, dim], the self rows = h's leading rows) or _bwd (gh [n_src, dim] from
+    gout [n_dst, dim], the self term folded in) over ``idx`` = (indptr, src, dst, t_indptr, t_edge)."""
+    indptr, src, dst, t_indptr, t_edge = idx
+    dst_dev, _src_dev, nnz_dev = words
+    B, D = int(src.numel()), h.shape[1]
+    out = torch.empty(n_src if backward else n_dst, D, dtype=torch.bfloat16, device=h.device)
+    part = spmm_partials(B, D, h.device, floor=4)
+    wp = 0 if w is None else w.data_ptr()
+    if backward:
+        _lib.check(_lib.lib.bliss_spmm_self_bwd(t_indptr.data_ptr(), t_edge.data_ptr(), src.data_ptr(), dst.data_ptr(), indptr.data_ptr(), wp,
+                                                h.data_ptr(), h.stride(0), n_src, n_dst, dst_dev, nnz_dev, B, D, out.data_ptr(), out.stride(0),
+                                                part.data_ptr(), _stream()), "bliss_spmm_self_bwd")
+    else:
+        _lib.check(_lib.lib.bliss_spmm_self_fwd(indptr.data_ptr(), src.data_ptr(), dst.data_ptr(), wp, h.data_ptr(), h.stride(0), h.data_ptr(),
+                                                h.stride(0), n_dst, dst_dev, nnz_dev, B, D, out.data_ptr(), out.stride(0), part.data_ptr(),
+                                                _stream()), "bliss_spmm_self_fwd")
+    return out
+
+
+def _linear_tile(x, w, m_bound, m_dev):
+    """x[m, in] . W^T -> [m, out] for an nn.Linear weight W = [out, in] on bliss_tile_gemm: output-column blocks of at most 256, two
+    per launch; zero rows at or past the count."""
+    out = torch.empty(m_bound, w.shape[0], dtype=torch.bfloat16, device=x.device)
+    sets = [_tg_args(x, w[c0:c1], out[:, c0:c1], m_bound, m_dev=m_dev) for c0, c1 in _col_blocks(w.shape[0])]
+    for i in range(0, len(sets), 2):
+        _tile_gemm(sets[i], sets[i + 1] if i + 1 < len(sets) else None)
+    return out
+
+
+class _SageGcnTile(torch.autograd.Function):
+    """One SAGEGCNConv layer (SAGEConv 'gcn') on the bounded kernels, ONE autograd node: fc_neigh (``weight`` [out, in], an
+    nn.Linear weight) on bliss_tile_gemm before (in > out) or behind the self-inclusive normalised sum (bliss_spmm_self_fwd), and
+    GraphConv's epilogue (bias, ReLU, keyed dropout, the row norms of the stored rows).  Backward: the epilogue's mirror with the bias
+    gradient, bliss_spmm_self_bwd, dX on bliss_gat_dgrad, dW = dY^T X on bliss_sage_wgrad -- all bound by the block's device-side
+    counts."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, idx, ew, n_src, n_dst, words, relu, p, state, want_norm):
+        import ctypes as C
+        ctx.set_materialize_grads(False)
+        x, w = _bf16c(x), _bf16c(weight)
+        dev = x.device
+        dst_dev, src_dev, _nnz_dev = words
+        lin_first = w.shape[1] > w.shape[0]
+        if lin_first:
+            kept = x
+            a = _spmm_self_launch(False, idx, ew, _linear_tile(x, w, n_src, src_dev), n_src, n_dst, words)
+        else:
+            kept = _spmm_self_launch(False, idx, ew, x, n_src, n_dst, words)
+            a = _linear_tile(kept, w, n_dst, dst_dev)
+        width = w.shape[0]
+        out = torch.empty(n_dst, width, dtype=torch.bfloat16, device=dev)
+        norm = torch.empty(n_dst, dtype=torch.bfloat16, device=dev) if want_norm else None
+        ctr_used = torch.empty(1, dtype=torch.int32, device=dev) if p > 0 else None
+        t = _gcn_epilogue_args(n_dst, dst_dev, width, relu, p, state, ctr_used)
+        t.a, t.a_stride, t.bias = a.data_ptr(), a.stride(0), 0 if bias is None else bias.data_ptr()
+        t.out, t.out_stride, t.norm_out = out.data_ptr(), out.stride(0), 0 if norm is None else norm.data_ptr()
+        _lib.check(_lib.lib.bliss_gcn_epilogue_fwd(C.byref(t), _stream()), "bliss_gcn_epilogue_fwd")
+        ctx.save_for_backward(kept, w, out if relu else None, ew, ctr_used, *idx)
+        ctx.cfg = (lin_first, n_src, n_dst, words, bool(relu), float(p), state, bias is not None, x.shape[0])
+        if norm is not None:
+            ctx.mark_non_differentiable(norm)
+        return out, norm
+
+    @staticmethod
+    def backward(ctx, dout, _dnorm):
+        import ctypes as C
+        kept, w, out, ew, ctr_used = ctx.saved_tensors[:5]
+        idx = tuple(ctx.saved_tensors[5:])
+        lin_first, n_src, n_dst, words, relu, p, state, has_bias, x_rows = ctx.cfg
+        if dout is None:
+            return (None,) * 12
+        dst_dev, src_dev, _nnz_dev = words
+        dout = _bf16c(dout)
+        dev, width = dout.device, w.shape[0]
+        g = torch.empty(n_dst, width, dtype=torch.bfloat16, device=dev)
+        db = torch.empty(width, dtype=torch.bfloat16, device=dev) if has_bias else None
+        t = _gcn_epilogue_args(n_dst, dst_dev, width, relu, p, state, ctr_used)
+        t.dout, t.dout_stride, t.din, t.din_stride = dout.data_ptr(), dout.stride(0), g.data_ptr(), g.stride(0)
+        if relu:
+            t.out, t.out_stride = out.data_ptr(), out.stride(0)
+        if has_bias:
+            rows = int(_lib.lib.bliss_gcn_db_chunk_rows())
+            part = torch.empty(max(((n_dst + rows - 1) // rows) * width, 4), dtype=torch.float32, device=dev)
+            t.db, t.db_partials = db.data_ptr(), part.data_ptr()
+        _lib.check(_lib.lib.bliss_gcn_epilogue_bwd(C.byref(t), _stream()), "bliss_gcn_epilogue_bwd")
+        dx = None
+        if lin_first:
+            dz = _spmm_self_launch(True, idx, ew, g, n_src, n_dst, words)                  # [n_src, out]
+            dw = _wgrad_blocks([(dz, kept, n_src, src_dev, False)])[0][0]
+            if ctx.needs_input_grad[0]:
+                dx = gat_dgrad(dz, w, n_src, src_dev)
+        else:
+            dw = _wgrad_blocks([(g, kept, n_dst, dst_dev, False)])[0][0]
+            if ctx.needs_input_grad[0]:
+                dx = _spmm_self_launch(True, idx, ew, gat_dgrad(g, w, n_dst, dst_dev), n_src, n_dst, words)
+        if dx is not None and x_rows > n_src:
+            dx = torch.cat([dx, _zero_rows(x_rows - n_src, dx)])
+        return (dx, dw, db) + (None,) * 9
+
+
+def sage_gcn_tile(block, h, edge_weight, layer, relu, p, state, want_norm):
+    """``layer`` = SAGEGCNConv(in, out) on ``block`` through _SageGcnTile: (out [n_dst, out_feats], its bf16 row norms or None).
+    ``h``: bf16 [>= num_src_nodes, in_feats] on the GPU.  Rows at or past the block's live destination count come out as zeros."""
+    K, S = block.num_src_nodes(), block.num_dst_nodes()
+    if not (torch.is_tensor(h) and h.is_cuda and h.dtype == torch.bfloat16 and h.dim() == 2):
+        raise NotImplementedError('SAGEConv "gcn": transforms="tile" takes bf16 features [rows, in_feats] on the GPU')
+    if h.shape[0] < K or h.shape[1] != layer._in_src_feats or S > K:
+        raise ValueError('SAGEConv "gcn": %d x %d input rows for a block of %d sources, %d destinations and in_feats %d'
+                         % (h.shape[0], h.shape[1], K, S, layer._in_src_feats))
+    _wait_block(block)
+    ew = None
+    if edge_weight is not None:
+        ew = _bf16c(edge_weight.detach().reshape(-1))
+        if ew.numel() != block.num_edges():
+            raise ValueError('SAGEConv "gcn": %d edge weights for %d edges' % (ew.numel(), block.num_edges()))
+    need_t = torch.is_grad_enabled() and (h.requires_grad or any(q.requires_grad for q in layer.parameters()))
+    t_indptr, t_edge = block.transposed() if need_t else (None, None)      # (the backward's index; evaluation builds none)
+    return _SageGcnTile.apply(h, layer.fc_neigh.weight, layer.bias, (block.indptr, block.src, block.dst, t_indptr, t_edge), ew, K, S,
+                              _block_words(block), bool(relu), float(p), state if p > 0 else None, bool(want_norm))
 
 
 # Full-neighbour inference of GraphConv(norm='both') straight off the graph's CSC (csrc/gcn_infer.hip, DESIGN.md section 27): the

@@ -1,7 +1,7 @@
 """The message-passing kernels as ``torch.library`` custom ops (last row): ``torch.ops.bliss.spmm``
 (the weighted g-SpMM of dglnn.SAGEConv / GraphConv, [DGL-recalled] SURVEY m3, with its transposed backward m6 registered as
-the op's autograd formula) and ``torch.ops.bliss.embed_norm`` (model.py:318-320).  Device tensors in, device tensors out,
-no host sync; fake (meta) implementations make them traceable (FakeTensor / torch.compile shape propagation); the real
+the op's autograd formula), ``spmm_max`` ('pool') and ``spmm_self`` ('gcn': the sum with the destination's own row, over deg + 1)
+and ``torch.ops.bliss.embed_norm`` (model.py:318-320).  Device tensors in, device tensors out, no host sync; fake (meta) implementations make them traceable (FakeTensor / torch.compile shape propagation); the real
 implementations are the C ABI calls of include/bliss_gnn.h -- there is no other backend.
 
 ``counts`` (optional int32[10] = a bliss_layer_counts_t on the device) marks capacity-padded blocks: the true edge count is
@@ -171,6 +171,71 @@ def _spmm_max_backward(ctx, gout, _garg):
 
 
 spmm_max.register_autograd(_spmm_max_backward, setup_context=_spmm_max_setup)
+
+
+@torch.library.custom_op("bliss::spmm_self", mutates_args=())
+def spmm_self(indptr: Tensor, src: Tensor, dst: Tensor, w: Optional[Tensor], h: Tensor, h_self: Optional[Tensor], n_dst: int,
+              counts: Optional[Tensor], t_indptr: Optional[Tensor], t_edge: Optional[Tensor]) -> Tensor:
+    """out[i] = (sum_{e -> i} w_e h[src_e] + h_self[i]) / (deg_i + 1), one rounding -- CSR by destination (csrc/spmm_self.hip,
+    DESIGN.md section 34).  ``h_self=None``: the destinations are the leading rows of ``h`` (a block)."""
+    assert h.is_cuda and h.dtype == torch.bfloat16 and h.stride(1) == 1, "bf16 features on the GPU (load_graph.py:7)"
+    hs = h if h_self is None else h_self
+    assert hs.is_cuda and hs.dtype == torch.bfloat16 and hs.stride(1) == 1 and hs.shape[0] >= n_dst and hs.shape[1] == h.shape[1]
+    B, D = int(src.numel()), h.shape[1]
+    out = torch.empty(n_dst, D, dtype=torch.bfloat16, device=h.device)
+    part = spmm_partials(B, D, h.device)
+    _lib.check(_lib.lib.bliss_spmm_self_fwd(indptr.data_ptr(), src.data_ptr(), dst.data_ptr(), _p(w), h.data_ptr(), h.stride(0),
+                                            hs.data_ptr(), hs.stride(0), n_dst, _p(counts), _nnz_ptr(counts), B, D, out.data_ptr(),
+                                            out.stride(0), _p(part), _stream()), "bliss_spmm_self_fwd")
+    return out
+
+
+@spmm_self.register_fake
+def _(indptr, src, dst, w, h, h_self, n_dst, counts, t_indptr, t_edge):
+    return h.new_empty((n_dst, h.shape[1]), dtype=torch.bfloat16)
+
+
+@torch.library.custom_op("bliss::spmm_self_t", mutates_args=())
+def spmm_self_t(t_indptr: Tensor, t_edge: Tensor, src: Tensor, dst: Tensor, indptr: Tensor, w: Optional[Tensor], gout: Tensor, n_src: int,
+                n_dst: int, counts: Optional[Tensor], fold_self: bool) -> Tensor:
+    """gh[j] = sum_{e : src_e = j} w_e / (deg_{dst_e} + 1) gout[dst_e] (+ gout[j] / (deg_j + 1) on the live destination rows when
+    ``fold_self``: the destinations are the leading source rows)  -- by-source index t_*."""
+    B, D = int(src.numel()), gout.shape[1]
+    gh = torch.empty(n_src, D, dtype=torch.bfloat16, device=gout.device)
+    part = spmm_partials(B, D, gout.device)
+    # without the fold no row counts as a destination: n_dst = 0 (the degrees come from indptr either way)
+    _lib.check(_lib.lib.bliss_spmm_self_bwd(t_indptr.data_ptr(), t_edge.data_ptr(), src.data_ptr(), dst.data_ptr(), indptr.data_ptr(), _p(w),
+                                            gout.data_ptr(), gout.stride(0), n_src, n_dst if fold_self else 0,
+                                            _p(counts) if fold_self else 0, _nnz_ptr(counts), B, D, gh.data_ptr(), gh.stride(0),
+                                            _p(part), _stream()), "bliss_spmm_self_bwd")
+    return gh
+
+
+@spmm_self_t.register_fake
+def _(t_indptr, t_edge, src, dst, indptr, w, gout, n_src, n_dst, counts, fold_self):
+    return gout.new_empty((n_src, gout.shape[1]), dtype=torch.bfloat16)
+
+
+def _spmm_self_setup(ctx, inputs, output):
+    indptr, src, dst, w, h, h_self, n_dst, counts, t_indptr, t_edge = inputs
+    ctx.save_for_backward(indptr, src, dst, w, counts, t_indptr, t_edge)
+    ctx.n_src, ctx.n_dst, ctx.fold = h.shape[0], n_dst, h_self is None
+
+
+def _spmm_self_backward(ctx, gout):
+    indptr, src, dst, w, counts, t_indptr, t_edge = ctx.saved_tensors
+    if ctx.needs_input_grad[5]:
+        raise NotImplementedError("bliss::spmm_self: no gradient w.r.t. a distinct h_self (the pair form under training)")
+    if t_indptr is None or t_edge is None:
+        raise RuntimeError("bliss::spmm_self needs the block's by-source index (Block.transposed()) to differentiate w.r.t. h")
+    g = gout.contiguous()
+    if g.dtype != torch.bfloat16:
+        g = g.bfloat16()
+    gh = spmm_self_t(t_indptr, t_edge, src, dst, indptr, w, g, ctx.n_src, ctx.n_dst, counts, ctx.fold)
+    return (None, None, None, None, gh, None, None, None, None, None)             # the sampler's edge weights carry no grad (m6)
+
+
+spmm_self.register_autograd(_spmm_self_backward, setup_context=_spmm_self_setup)
 
 
 @torch.library.custom_op("bliss::embed_norm", mutates_args=())

@@ -478,6 +478,13 @@ def sharded_sage_forward(model, blocks, x_owned_rows_fn, world, group=None):
     return h
 
 
+def refuse_unsharded_aggregator(model, what):
+    """The sharded steps hand a layer (feat_src, feat_dst) pairs and split it into fc_neigh / fc_self: SAGEConv 'gcn' has no fc_self,
+    and its pair form carries no gradient w.r.t. the destinations' rows -- refused by name, at construction."""
+    if any(getattr(layer, "_aggre_type", None) == "gcn" for layer in getattr(model, "layers", ())):
+        raise NotImplementedError('%s: SAGEConv aggregator_type="gcn" is not built on the sharded step (DESIGN.md section 34)' % what)
+
+
 def allreduce_gradients_sum(model, scale, group=None):
     """Sum the gradients over ranks (each rank's loss covers its own output seeds) and scale by 1 / global batch."""
     grads = [p.grad for p in model.parameters() if p.grad is not None]
@@ -499,6 +506,7 @@ class ShardedTrainStep:
 
     def __init__(self, shard, sampler, model, lr=0.002, multilabel=False, group=None):
         import torch.nn as nn
+        refuse_unsharded_aggregator(model, type(self).__name__)
         self.g, self.sampler, self.model, self.group = shard, sampler, model, group
         self.loss_fn = nn.BCEWithLogitsLoss(reduction="sum") if multilabel else nn.CrossEntropyLoss(reduction="sum")   # :77-79
         self.opt = torch.optim.Adam(model.parameters(), lr=lr)                                                       # :206

@@ -529,7 +529,9 @@ class StaticShardedTrainStep:
 
     def __init__(self, shard, sampler, model, batch, lr=0.002, multilabel=False, group=None):
         import torch.nn as nn
+        from .shard import refuse_unsharded_aggregator
         from .train import make_adam
+        refuse_unsharded_aggregator(model, type(self).__name__)
         if not sampler.static:
             raise ValueError("StaticShardedTrainStep needs a DenseShardedSampler on its static HIP path (ops=None)")
         self.g, self.sampler, self.model, self.group, self.batch = shard, sampler, model, group, int(batch)

@@ -149,6 +149,8 @@ def _live_refusal(model):
     ps = list(model.parameters())
     if ps and model._pool_tile:                  # 'pool' on the tile kernels: bounded like the MFMA path
         return model.tile_refusal(ps[0])
+    if ps and model._gcn_tile:                   # 'gcn' on the tile kernels: every row and edge loop bounded
+        return model.tile_refusal(ps[0])
     if not ps or not model._mfma_ok(ps[0]) or not _mfma_bwd_on():
         return ("SAGE runs live on its MFMA path only (bf16 on the GPU, ReLU, layers within the tile kernel's limits, "
                 "BLISS_SAGE_MFMA / BLISS_SAGE_MFMA_BWD not 0): the library-GEMM path multiplies stale capacity rows into the "

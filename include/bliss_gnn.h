@@ -853,6 +853,33 @@ int bliss_spmm_max_bwd_relu(const int32_t* t_indptr, const int32_t* t_edge, cons
                             int64_t act_stride, int32_t n_src, const int32_t* nnz_dev, int32_t nnz, int32_t dim, void* gh,
                             int64_t gh_stride, void* partials, void* stream);
 
+/* SAGEConv 'gcn' message passing [DGL-recalled: update_all(u_mul_e | copy_u, sum), then (neigh + h_dst) / (in_degrees + 1)],
+ * csrc/spmm_self.hip, DESIGN.md section 34 -- one rounding where DGL keeps three bf16 intermediates:
+ *   out[i, :] = bf16( (sum_{e in row i} float(w_e) * float(h[src_e, :]) + float(h_self[i, :])) * (1.0f / (float)(deg_i + 1)) )
+ * deg_i = indptr[i + 1] - indptr[i] (edges with multiplicity, never a sum of weights); w == NULL: w_e = 1.  The messages are
+ * summed in fp32 by edge inside a work chunk, chunk partials in chunk order; the self row is added LAST, in fp32; one rounding
+ * at the store.  A live row without in-edges: out[i] = h_self[i] bit for bit.  n_dst_dev (optional): the live destination count
+ * on the device (bliss_layer_counts_t word 0), n_dst an upper bound -- rows at or past it are stored as +0 WITHOUT reading
+ * their self row, which may hold anything; nnz_dev / nnz as for bliss_spmm_fwd (edges at or past *nnz_dev do not exist).
+ * h bf16 [n_src, dim], h_self bf16 [n_dst, dim] (may alias h: the destinations of a block are its leading source rows), out
+ * bf16 [n_dst, dim] (aliases neither); strides in elements.
+ * bliss_spmm_self_bwd, w.r.t. h with the self term folded into the leading rows (h_self aliasing h):
+ *   gh[j, :] = bf16( sum_{e : src_e = j} (float(w_e) / (float)(deg_{dst_e} + 1)) * float(gout[dst_e, :])
+ *                    + (j < live n_dst ? (1.0f / (float)(deg_j + 1)) * float(gout[j, :]) : 0) )
+ * fp32 sums in by-source order inside a work chunk, chunk partials in chunk order, the self term added last where the finished
+ * row is rounded and stored (never to the fp32 partials).  gh bf16 [n_src, dim]; sources that receive nothing and rows past the
+ * live source count are zeros; t_indptr / t_edge as for bliss_spmm_bwd, indptr = the block's CSR by destination (the degrees).
+ * No float atomics: both calls are bitwise reproducible.
+ * partials (both calls): as for bliss_spmm_fwd, fp32 [2 * ceil(nnz / EC) * dim]; may be NULL when nnz is at most one chunk.
+ * BLISS_EINVAL before any launch: a NULL required pointer (indptr, t_indptr, h / gout, h_self, out / gh; the edge arrays when
+ * nnz > 0), a negative count, dim <= 0, a stride below dim, partials NULL with more than one chunk; the backward: n_dst > n_src. */
+int bliss_spmm_self_fwd(const int32_t* indptr, const int32_t* src, const int32_t* dst, const void* w, const void* h, int64_t h_stride,
+                        const void* h_self, int64_t h_self_stride, int32_t n_dst, const int32_t* n_dst_dev, const int32_t* nnz_dev,
+                        int32_t nnz, int32_t dim, void* out, int64_t out_stride, float* partials, void* stream);
+int bliss_spmm_self_bwd(const int32_t* t_indptr, const int32_t* t_edge, const int32_t* src, const int32_t* dst, const int32_t* indptr,
+                        const void* w, const void* gout, int64_t gout_stride, int32_t n_src, int32_t n_dst, const int32_t* n_dst_dev,
+                        const int32_t* nnz_dev, int32_t nnz, int32_t dim, void* gh, int64_t gh_stride, float* partials, void* stream);
+
 /* The element-wise tail of a hidden SAGE layer in one pass (model.py:321-333 and :318-320 of the next layer):
  * out = dropout_p(relu(a + b)) row by row, norm_out[row] = ||out[row,:]||_2 (bf16, may be NULL).  a, b, out: bf16
  * [n_rows, dim].  p_drop = 0 (evaluation) makes it deterministic.  ctr: device uint64[66], zero-initialised once: the
