@@ -2,7 +2,7 @@
 // csrc/labor_is.hip): the kernels behind the one that wrote pos / dst / eid and marked the kept edges' sources in the |V|-bit bitmap.
 //   k_nb_count   popcount per bitmap tile; the last workgroup (a ticket, k_md_pass's hand-over) scans the tile counts and writes K
 //   k_nb_number  ordered numbering: new sources get kept_nid[S + rank] and kept_map; every bitmap word read here is left ZERO
-//   k_nb_tail    src = kept_map[indices[pos]], unit weights
+//   k_nb_tail    src = kept_map[indices[pos]] (0 where a clamped K left the source without a number), unit weights
 //   k_nb_clean   kept_map back to -1 at kept_nid[0 .. K); kept_nid[K .. cap_k) = 0 (capacity padding), node_prob = 1
 //   k_nb_scan / k_nb_select: the head of the per-column draws (csrc/neighbor.hip; csrc/neighbor_w.hip selects over its own keys)
 // Scratch layout of these samplers: [0, NB_HDR) tickets ([0] step ticket, [1] tile ticket), the bitmap (whole tiles), one count per tile.
@@ -131,7 +131,10 @@ __global__ void __launch_bounds__(NB_TPB) k_nb_tail(const int* __restrict__ indi
   const int B = min(cnt->B, cap_b);
   for (int j = blockIdx.x * NB_TPB + threadIdx.x; j < B; j += gridDim.x * NB_TPB) {
     const int u = indices[b_pos[j]];
-    b_src[j] = (unsigned)u < (unsigned)V ? kept_map[u] : -1;
+    // a source that k_nb_number could not number (K clamped at cap_k) has no kept_map entry: its edges stand at source 0, a seed,
+    // which exists wherever an edge does -- invalid like the rest of the flagged step, but inside [0, K) for whoever walks the block
+    const int k = (unsigned)u < (unsigned)V ? kept_map[u] : -1;
+    b_src[j] = k < 0 ? 0 : k;
     b_w[j] = NB_ONE_BF16;
     b_q[j] = NB_ONE_BF16;
   }

@@ -134,7 +134,9 @@ __device__ __forceinline__ void seg_scan_body(const int64_t* __restrict__ indptr
   // long_list (optional): the columns of more than COL_BIG edges as ColEnt records, longest class first (no order inside a
   // class): k_col_sums gives each of them a workgroup without walking over the short ones, and starts the longest ones first
   __shared__ int sh_long[2];
+  __shared__ int sh_bad;
   if (long_list && threadIdx.x < 2) sh_long[threadIdx.x] = 0;     // (appended to behind the first block_excl_scan's barriers)
+  if (threadIdx.x == 0) sh_bad = 0;
   int S = S_host >= 0 ? S_host : *S_dev;
   int bad = 0;
   if (S > cap_s) { S = cap_s; bad |= BLISS_ERR_CAP_SEEDS; }         // clamp: results invalid but in bounds
@@ -217,7 +219,11 @@ __device__ __forceinline__ void seg_scan_body(const int64_t* __restrict__ indptr
       if (run > frontier_cap) bad |= BLISS_ERR_CAP_FRONTIER;
     }
   }
-  int any_bad = __syncthreads_or(bad);
+  // the error BITS of all threads (__syncthreads_or reduces a predicate: it returned 1, BLISS_ERR_CAP_FRONTIER, for any of them)
+  __syncthreads();
+  if (bad) atomicOr(&sh_bad, bad);
+  __syncthreads();
+  const int any_bad = sh_bad;
   if (threadIdx.x == 0) {
     if (long_list) { int* n_long = (int*)(long_list + cap_s); n_long[0] = sh_long[0]; n_long[1] = sh_long[1]; }
     seg_ptr[S] = (int)run;
@@ -1453,7 +1459,8 @@ __global__ void __launch_bounds__(1024) k_block_scans(int* __restrict__ chunk_cn
       int j = base + threadIdx.x;
       int v = j < cap_k ? src_cnt[j] : 0;
       int tot, ex = block_excl_scan(v, sh, &tot);
-      if (j <= cap_k) { t_indptr[j] = run + ex; if (j < cap_k) src_cnt[j] = run + ex; }
+      // (past cap_b only when B overflowed: k_tr_sort_lists then builds the index anew from the cap_b edges that exist)
+      if (j <= cap_k) { t_indptr[j] = min(run + ex, cap_b); if (j < cap_k) src_cnt[j] = run + ex; }
       run += tot;
     }
     return;
@@ -1480,11 +1487,11 @@ __global__ void __launch_bounds__(1024) k_block_scans(int* __restrict__ chunk_cn
     int k = base + threadIdx.x;
     int v = k < S ? deg_blk[k] : 0;
     int tot, ex = block_excl_scan(v, sh, &tot);
-    if (k < S) blk_indptr[k] = run + ex;
+    if (k < S) blk_indptr[k] = min(run + ex, cap_b);      // (a B overflow: the rows end where the edge arrays do)
     run += tot;
   }
   // rows S .. cap_s are empty: capacity-padded consumers (static shapes, HIP-graph replay) may walk them
-  for (int k = S + threadIdx.x; k <= cap_s; k += blockDim.x) blk_indptr[k] = run;
+  for (int k = S + threadIdx.x; k <= cap_s; k += blockDim.x) blk_indptr[k] = min(run, cap_b);
 }
 
 // ---------------------------------------------------------------- K_n: emit the block's edges in frontier order
@@ -1543,7 +1550,10 @@ __global__ void __launch_bounds__(TPB) k_block_pass2(const int64_t* __restrict__
         out = wt * d;                                                // ladies_sampler.py:97
       }
       out_src[idx] = r.nid;
-      if (src_cursor) t_unsorted[atomicAdd(src_cursor + r.nid, 1)] = idx;   // its source's list, arbitrary order for now
+      if (src_cursor) {                                              // its source's list, arbitrary order for now
+        const int at = atomicAdd(src_cursor + r.nid, 1);             // (the cursors count ALL kept edges: past cap_b only when B
+        if (at < cap_b) t_unsorted[at] = idx;                        //  overflowed, and k_tr_sort_lists then starts anew)
+      }
       out_dst[idx] = k;
       out_pos[idx] = r.pos;
       out_eid[idx] = eid_map ? eid_map[r.pos] : r.pos;               // :335-337
@@ -1573,17 +1583,48 @@ __device__ __forceinline__ void maps_cleanup(LayerCounts* cnt, const int* __rest
 // rank, so a long list in which a destination bit was already set is ranked by edge index like the short ones, in rounds
 // of 64 -- O(len^2 / 64), exact for any list; lists without a repeat never take that branch.
 #define TSORT_MAX_S 32768
-__global__ void __launch_bounds__(TPB) k_tr_sort_lists(const int* __restrict__ t_indptr, const int* __restrict__ t_unsorted,
+// A B overflow (BLISS_ERR_CAP_EDGES, raised by k_block_scans): k_block_pass1 sized the lists for every kept edge, k_block_pass2 wrote
+// only the first cap_b of them, so the lists have holes.  The step is invalid, but the index must still be one of the block that
+// exists (include/bliss_gnn.h, "clamped blocks": whoever walks it stays inside cap_b).  One workgroup builds it anew from src[0, B):
+// counts, list starts, fill; the caller then sorts every list.  Never taken by a step within its capacities.
+__device__ __noinline__ void tr_rebuild(const int* __restrict__ src, int B, int cap_k, int* src_cnt, int* t_indptr, int* t_unsorted) {
+  __shared__ int sh[17];
+  for (int j = threadIdx.x; j <= cap_k; j += TPB) src_cnt[j] = 0;
+  __syncthreads();
+  for (int e = threadIdx.x; e < B; e += TPB) atomicAdd(src_cnt + src[e], 1);
+  __syncthreads();
+  int run = 0;
+  for (int base = 0; base <= cap_k; base += TPB) {
+    const int j = base + threadIdx.x;
+    const int v = j < cap_k ? src_cnt[j] : 0;
+    int tot;
+    const int ex = block_excl_scan(v, sh, &tot);
+    if (j <= cap_k) { t_indptr[j] = run + ex; src_cnt[j] = run + ex; }
+    run += tot;
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < B; e += TPB) t_unsorted[atomicAdd(src_cnt + src[e], 1)] = e;
+  __syncthreads();
+}
+
+__global__ void __launch_bounds__(TPB) k_tr_sort_lists(int* t_indptr, int* t_unsorted,
                                                        const int* __restrict__ dst, LayerCounts* cnt, int cap_k, int cap_s,
                                                        int* __restrict__ t_edge, const int* __restrict__ cand_nid, int* local_id,
-                                                       int cap_c, const int* __restrict__ kept_nid, int* kept_map, int do_cleanup) {
+                                                       int cap_c, const int* __restrict__ kept_nid, int* kept_map, int do_cleanup,
+                                                       const int* __restrict__ src, int* src_cnt, int cap_b) {
   extern __shared__ unsigned bm_all[];
   if (do_cleanup) maps_cleanup(cnt, cand_nid, local_id, cap_c, kept_nid, kept_map, cap_k);   // independent of the lists below
   const int lane = lane_id(), wave = threadIdx.x >> 6;
   const int words = (cap_s + 31) / 32;
   unsigned* bm = bm_all + (size_t)wave * (words + 1);
   const int K = min(cnt->K, cap_k);
-  for (int j = blockIdx.x * (TPB / 64) + wave; j < K; j += gridDim.x * (TPB / 64)) {
+  int j0 = blockIdx.x * (TPB / 64) + wave, j_step = gridDim.x * (TPB / 64);
+  if (cnt->err & BLISS_ERR_CAP_EDGES) {                  // (uniform over the grid: the bit was raised two launches ago)
+    if (blockIdx.x != 0) return;
+    tr_rebuild(src, min(cnt->B, cap_b), cap_k, src_cnt, t_indptr, t_unsorted);
+    j0 = wave; j_step = TPB / 64;
+  }
+  for (int j = j0; j < K; j += j_step) {
     const int beg = t_indptr[j], len = t_indptr[j + 1] - beg;
     if (len <= 0) continue;
     if (len <= 64) {
@@ -1890,10 +1931,10 @@ int bliss_build_block(const bliss_graph_t* g, const bliss_node_maps_t* m, const 
     PROF_LAUNCH(BK_CLEANUP, st, k_cleanup<<<grid_for(ws->cap_c, TPB), TPB, 0, st>>>(cnt, ws->cand_nid, m->local_id, ws->cap_c, ws->kept_nid, ws->kept_map, ws->cap_k));
     k_flag_raise<<<1, 64, 0, st>>>(ws->block_ready_flag);
     const size_t lds = (size_t)(TPB / 64) * ((cap_s + 31) / 32 + 1) * sizeof(unsigned);
-    PROF_LAUNCH(BK_TRANSPOSE, st, k_tr_sort_lists<<<grid_for(ws->cap_k, TPB / 64), TPB, lds, st>>>(out->t_indptr, out->t_scratch, out->dst, cnt, ws->cap_k, cap_s, out->t_edge, ws->cand_nid, m->local_id, ws->cap_c, ws->kept_nid, ws->kept_map, 0));
+    PROF_LAUNCH(BK_TRANSPOSE, st, k_tr_sort_lists<<<grid_for(ws->cap_k, TPB / 64), TPB, lds, st>>>(out->t_indptr, out->t_scratch, out->dst, cnt, ws->cap_k, cap_s, out->t_edge, ws->cand_nid, m->local_id, ws->cap_c, ws->kept_nid, ws->kept_map, 0, out->src, src_cnt, out->cap_b));
   } else if (want_t) {        // the by-source lists, and (same launch) the dense maps back to -1
     const size_t lds = (size_t)(TPB / 64) * ((cap_s + 31) / 32 + 1) * sizeof(unsigned);
-    PROF_LAUNCH(BK_TRANSPOSE, st, k_tr_sort_lists<<<grid_for(ws->cap_k, TPB / 64), TPB, lds, st>>>(out->t_indptr, out->t_scratch, out->dst, cnt, ws->cap_k, cap_s, out->t_edge, ws->cand_nid, m->local_id, ws->cap_c, ws->kept_nid, ws->kept_map, 1));
+    PROF_LAUNCH(BK_TRANSPOSE, st, k_tr_sort_lists<<<grid_for(ws->cap_k, TPB / 64), TPB, lds, st>>>(out->t_indptr, out->t_scratch, out->dst, cnt, ws->cap_k, cap_s, out->t_edge, ws->cand_nid, m->local_id, ws->cap_c, ws->kept_nid, ws->kept_map, 1, out->src, src_cnt, out->cap_b));
     if (ws->block_ready_flag) k_flag_raise<<<1, 64, 0, st>>>(ws->block_ready_flag);
   } else {
     PROF_LAUNCH(BK_CLEANUP, st, k_cleanup<<<grid_for(ws->cap_c, TPB), TPB, 0, st>>>(cnt, ws->cand_nid, m->local_id, ws->cap_c, ws->kept_nid, ws->kept_map, ws->cap_k));

@@ -208,6 +208,29 @@ int bliss_multinomial_draw(const int32_t* cand_nid, const void* p_bf16, const vo
  * P = p (:309), union(drawn, seeds) numbered as block sources, kept_nid / node_prob / K.  No host-side count. */
 int bliss_multinomial_select_marked(const bliss_layer_ws_t* ws, void* stream);
 
+/* CLAMPED BLOCKS.  A static-shape step reads its error words only after its consumers (SpMM, GCN, GATv2, the EXP3 update, the
+ * by-source index) have walked the block, so "clamped" must still mean "a block": invalid numbers, valid plumbing.  The following
+ * holds for the outputs of every layer entry point below (bliss_neighbor_layer, bliss_wneighbor_layer, bliss_neighbor_replace_layer,
+ * bliss_labor_layer, bliss_labor_is_layer, bliss_wlabor_layer), of the select calls above followed by bliss_build_block, and of
+ * bliss_block_transpose on such a block -- WHETHER OR NOT an error bit is set.  (S, K, B, C) are the counts record.
+ *   I1  0 <= S <= cap_s, 0 <= K <= cap_k, 0 <= B <= cap_b, C <= cap_c; BLISS_ERR_CAP_SEEDS / _KEPT / _EDGES / _CAND is set exactly
+ *       when the unclamped count was larger, and the clamped count then equals its capacity.
+ *   I2  indptr[0] = 0, indptr non-decreasing over [0, cap_s], indptr[S] = B, indptr[r] = B for S <= r <= cap_s.
+ *   I3  for every e < B: dst[e] is the row r with indptr[r] <= e < indptr[r + 1]; 0 <= src[e] < K; 0 <= pos[e] < num_edges;
+ *       eid[e] = g->eid[pos[e]] (pos[e] when g->eid == NULL).
+ *   I4  kept_nid[0, K) are valid, pairwise distinct node ids, the first min(S, K) the layer's seeds in order; kept_nid[K, cap_k) = 0.
+ *   I5  an edge is CONSISTENT if kept_nid[src[e]] = g->indices[pos[e]].  Only S, B or C clamped: every edge is.  K clamped: every
+ *       edge whose true source is in kept_nid[0, K) is; the node-wise layers keep the others at source 0 (a seed: it exists wherever
+ *       an edge does), the select + bliss_build_block chain does not emit them.  They need I3 only.
+ *   I6  by-source index: t_indptr[0] = 0, non-decreasing over [0, cap_k], t_indptr[j] = B for K <= j <= cap_k; t_edge[0, B) is a
+ *       permutation of 0 .. B-1; list j holds exactly the edges with src = j, in ascending edge index.
+ *   I7  edge_weights[0, B), q_ij[0, B), p_ij[0, B) where the layer writes it, node_prob[0, cap_k): no NaN, no infinity.
+ *   I8  what the next call (a replayed graph) relies on is as an unclamped call leaves it: kept_map and local_id all -1, the
+ *       node-wise tickets and node bitmap, fs_ticket and (after a Poisson select, which consumes it) hist zero, the draw step
+ *       bumped exactly once (bump_step) / the generator state advanced by the numbers the call's candidates took.
+ * Nothing is written beyond a capacity.  tests/block_invariants.py states I1 - I7 in NumPy; tests/test_gpu_clamped_blocks.py holds
+ * every kind of layer to them with each capacity of each layer one below the truth. */
+
 /* dgl.dataloading.NeighborSampler(fanouts) ON THE DEVICE, one layer (fit.NeighborSampler with draw="device"; a defined-mode keyed
  * draw like bliss_multinomial_draw with the key on the EDGE, restated on the CPU by tests/neighbor_ref.py):
  *   key(pos) = (uint32)(z >> 32), z = SplitMix64 finaliser of mix(seed, *step_dev, layer) ^ (uint64)pos  -- bliss_multinomial_draw's
@@ -223,7 +246,8 @@ int bliss_multinomial_select_marked(const bliss_layer_ws_t* ws, void* stream);
  * (the by-source index is not built here: bliss_block_transpose on out->src with the record's B).  Every other field is ignored.
  * Out: counts{S, E = sum d, C = K, K, B, err}, seg_ptr, kept_nid, the block arrays; capacity padding as bliss_build_block leaves it
  * (indptr rows S .. cap_s empty, kept_nid[K .. cap_k) = 0); ws->node_prob, when not NULL, = 1 for all cap_k entries.  A count beyond cap_s / cap_k / cap_b raises
- * the matching BLISS_ERR_CAP_* bit and is clamped; nothing is written beyond a capacity.  ws->kept_map: [num_nodes], -1 everywhere
+ * the matching BLISS_ERR_CAP_* bit and is clamped; nothing is written beyond a capacity, and what is written is still a block
+ * ("clamped blocks" above, I1 - I8).  ws->kept_map: [num_nodes], -1 everywhere
  * on entry and on exit.  bump_step: the last workgroup of the select kernel increments *step_dev once, after every workgroup has
  * read it.  scratch: bliss_neighbor_scratch_bytes(num_nodes, cap_s) bytes (cap_s > 0 is checked; nothing is sized by it), 16-byte aligned, zero-initialised ONCE; its words are
  * [0, 16) tickets, then the node bitmap (ceil(num_nodes / 32) words rounded up to a multiple of 1024) -- both left zero by every
@@ -414,7 +438,8 @@ int bliss_wlabor_layer(const bliss_graph_t* g, const int32_t* seeds, int32_t n_s
 
 /* generate_block    bandit_sampler.py:269-339 (BANDIT: Hajek weights) / ladies_sampler.py:71-107.
  * Same g, maps, w_pos, seeds, eta as the matching bliss_frontier_prob call.  Out: counts{B}, the block;
- * leaves the node maps clean. */
+ * leaves the node maps clean.  More than cap_b kept edges: BLISS_ERR_CAP_EDGES, B = cap_b, the block is the first cap_b kept edges
+ * in frontier order -- indptr ends at cap_b, the by-source index is the index of those edges ("clamped blocks" above). */
 int bliss_build_block(const bliss_graph_t* g, const bliss_node_maps_t* maps, const void* w_pos,
                       const int32_t* seeds, int32_t cap_s, int mode, float eta_f, float one_minus_eta_f,
                       int64_t frontier_bound, const bliss_layer_ws_t* ws, const bliss_block_out_t* out, void* stream);

@@ -14,6 +14,7 @@ import pytest
 import torch
 
 import labor_is_ref as ref
+from block_invariants import check_index
 import test_labor_is_ref as cpu
 from test_gpu_labor import GUARD, HUB, SEED, V, Layer as Layer0, graph_np, seeds67, seeds_all
 
@@ -324,6 +325,7 @@ def test_edge_capacity_below_the_true_count(cuda, graph_dev):
     short = want["B"] - 40
     c = lay(seeds, 3, 2, cap_b=short)
     assert c.err == 8 and c.B == short and c.S == 67
+    check_index(lay.src.cpu(), lay.t_indptr.cpu(), lay.t_edge.cpu(), c.K, c.B, lay.cap_k)             # clamped, and still walkable
     lay.assert_guards(cap_b=short)                                                # (the words [short, B) of the arrays are guards too)
     lay.assert_clean()
     t = lambda x: torch.from_numpy(np.asarray(x)).to(cuda)
@@ -342,11 +344,13 @@ def test_edge_capacity_below_the_true_count(cuda, graph_dev):
     assert c.err == 4 and c.K == want["K"] - 1 and c.B == want["B"]
     short_k.assert_guards()
     short_k.assert_clean()
+    check_index(short_k.src.cpu(), short_k.t_indptr.cpu(), short_k.t_edge.cpu(), c.K, c.B, short_k.cap_k)     # clamped, and still walkable
     short_s = Layer(cuda, graph_dev, 66, want["K"], want["B"])
     c = short_s(seeds, 3, 2)
     assert c.err & 64 and c.S == 66
     short_s.assert_guards()
     short_s.assert_clean()
+    check_index(short_s.src.cpu(), short_s.t_indptr.cpu(), short_s.t_edge.cpu(), c.K, c.B, short_s.cap_k)     # clamped, and still walkable
 
 
 def test_two_runs_of_twenty_launches_are_bit_equal(cuda, graph_dev, layer67):

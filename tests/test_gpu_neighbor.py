@@ -14,6 +14,7 @@ import pytest
 import torch
 
 import neighbor_ref as ref
+from block_invariants import check_index
 from test_neighbor_ref import check_inclusion, inclusion_counts
 
 pytestmark = pytest.mark.gpu
@@ -195,11 +196,13 @@ def test_capacity_overflows_raise_their_bit_and_write_nothing_beyond(cuda, graph
     assert c.err == 4 and c.K == want["K"] - 1 and c.B == want["B"]
     short_k.assert_guards()
     short_k.assert_clean()
+    check_index(short_k.src.cpu(), short_k.t_indptr.cpu(), short_k.t_edge.cpu(), c.K, c.B, short_k.cap_k)     # clamped, and still walkable
     short_b = Layer(cuda, graph_dev, 67, want["K"], want["B"] - 1)
     c = short_b(seeds, 7)
     assert c.err == 8 and c.B == want["B"] - 1
     short_b.assert_guards()
     short_b.assert_clean()
+    check_index(short_b.src.cpu(), short_b.t_indptr.cpu(), short_b.t_edge.cpu(), c.K, c.B, short_b.cap_k)     # clamped, and still walkable
     exact = Layer(cuda, graph_dev, 67, want["K"], want["B"])                      # the exact capacities hold everything
     exact.assert_equals(exact(seeds, 7), want)
     short_s = Layer(cuda, graph_dev, 66, want["K"], want["B"])
@@ -207,6 +210,7 @@ def test_capacity_overflows_raise_their_bit_and_write_nothing_beyond(cuda, graph
     assert c.err & 64 and c.S == 66
     short_s.assert_guards()
     short_s.assert_clean()
+    check_index(short_s.src.cpu(), short_s.t_indptr.cpu(), short_s.t_edge.cpu(), c.K, c.B, short_s.cap_k)     # clamped, and still walkable
 
 
 def test_inclusion_frequencies_on_the_device(cuda):

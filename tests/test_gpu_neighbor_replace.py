@@ -14,6 +14,7 @@ import torch
 
 import replace_ref as ref
 import wneighbor_ref as wref
+from block_invariants import check_index
 from bounds import SPMM_K, assert_within, spmm_terms
 from test_gpu_neighbor import GUARD, SEED, Layer
 from test_replace_ref import CASES, check_counts
@@ -273,6 +274,7 @@ def test_capacity_overflows_raise_their_bit_and_leave_the_scratch_idle(cuda, gra
         assert c.K <= cap_k and c.B <= cap_b and c.S <= cap_s
         short.assert_guards()
         short.assert_clean()
+        check_index(short.src.cpu(), short.t_indptr.cpu(), short.t_edge.cpu(), c.K, c.B, cap_k)       # clamped, and still walkable
         roomy = RLayer(cuda, graphs_dev["hand"], 31, want["K"], want["B"])       # the exact capacities hold everything
         roomy.scratch, roomy.kept_map = shared, short.kept_map
         roomy.assert_equals(roomy(seeds, 64, prob), want)

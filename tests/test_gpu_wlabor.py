@@ -17,6 +17,7 @@ import torch
 
 import test_wlabor_ref as cpu
 import wlabor_ref as ref
+from block_invariants import check_index
 from test_gpu_labor import SEED, Layer as Layer0
 from test_labor_is_ref import lognormal_graph
 
@@ -315,6 +316,7 @@ def test_edge_capacity_below_the_true_count(cuda):
         short = want["B"] - 40
         c = lay(seeds, 3, mode, cap_b=short)
         assert c.err == 8 and c.B == short and c.S == 64
+        check_index(lay.src.cpu(), lay.t_indptr.cpu(), lay.t_edge.cpu(), c.K, c.B, lay.cap_k)         # clamped, and still walkable
         lay.assert_guards(cap_b=short)                                            # (the words [short, B) of the arrays are guards too)
         lay.assert_clean()
         t = lambda x: torch.from_numpy(np.asarray(x)).to(cuda)
@@ -330,11 +332,13 @@ def test_edge_capacity_below_the_true_count(cuda):
         assert c.err == 4 and c.K == want["K"] - 1 and c.B == want["B"]
         short_k.assert_guards()
         short_k.assert_clean()
+        check_index(short_k.src.cpu(), short_k.t_indptr.cpu(), short_k.t_edge.cpu(), c.K, c.B, short_k.cap_k) # clamped, and still walkable
         short_s = Layer(cuda, "log", 63, want["K"], want["B"])
         c = short_s(seeds, 3, mode)
         assert c.err & 64 and c.S == 63
         short_s.assert_guards()
         short_s.assert_clean()
+        check_index(short_s.src.cpu(), short_s.t_indptr.cpu(), short_s.t_edge.cpu(), c.K, c.B, short_s.cap_k) # clamped, and still walkable
 
 
 def test_a_non_finite_exp3_weight_is_flagged_and_the_scratch_left_idle(cuda, log_layer):

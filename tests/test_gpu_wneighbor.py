@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import wneighbor_ref as ref
+from block_invariants import check_index
 from oracle import bliss_oracle as bo
 from test_gpu_neighbor import GUARD, HUB, SEED, V, Layer, graph_dev, graph_np, seeds67  # noqa: F401  (graph_dev: a fixture)
 from test_wneighbor_ref import COLUMNS, check_inclusion
@@ -231,6 +232,7 @@ def test_capacity_overflows_raise_their_bit_and_leave_the_scratch_idle(cuda, gra
         assert c.K <= cap_k and c.B <= cap_b and c.S <= cap_s
         short.assert_guards()
         short.assert_clean()
+        check_index(short.src.cpu(), short.t_indptr.cpu(), short.t_edge.cpu(), c.K, c.B, cap_k)       # clamped, and still walkable
         # the same scratch and kept_map serve a call with enough room: bitmap, tickets and kept_map were left idle
         roomy = WLayer(cuda, graph_dev, 67, want["K"], want["B"])                 # (the exact capacities hold everything)
         roomy.scratch, roomy.kept_map = shared, short.kept_map
