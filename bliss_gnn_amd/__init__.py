@@ -10,4 +10,5 @@ from .graph import Block, Graph, NID, EID  # noqa: F401
 from .bandit_sampler import BanditLadiesSampler, PoissonBanditLadiesSampler, normalized_edata  # noqa: F401
 from .ladies_sampler import LadiesSampler, PoissonLadiesSampler  # noqa: F401
 from .metrics import MicroF1  # noqa: F401
+from .explain import edge_gradients  # noqa: F401
 from .fit import BanditLaborSampler, BanditNeighborSampler, ImportanceLaborSampler, LaborSampler, WeightedLaborSampler  # noqa: F401

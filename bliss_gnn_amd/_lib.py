@@ -174,6 +174,7 @@ class AdamTensors(C.Structure):                        # bliss_adam_t
 LEDGER_MAX_LAYERS = 8                                  # BLISS_LEDGER_MAX_LAYERS
 LEDGER_STEP, LEDGER_RESET_EPOCH, LEDGER_REARM = 0, 1, 2
 LEDGER_LOSS_BF16, LEDGER_LOSS_F32 = 0, 1
+SDDMM_SUM, SDDMM_MEAN, SDDMM_SELF, SDDMM_MAX = 0, 1, 2, 3     # BLISS_SDDMM_*
 _LEDGER_STRUCTS = {}
 
 
@@ -295,6 +296,7 @@ SIGNATURES = {
     "bliss_spmm_max_bwd_relu": [_P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _I32, _P, _I32, _I32, _P, _I64, _P, _P],
     "bliss_spmm_self_fwd": [_P, _P, _P, _P, _P, _I64, _P, _I64, _I32, _P, _P, _I32, _I32, _P, _I64, _P, _P],
     "bliss_spmm_self_bwd": [_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P, _P, _I32, _I32, _P, _I64, _P, _P],
+    "bliss_sddmm_dot": [_P, _P, _P, _P, _I32, _P, _I64, _P, _I64, _P, _I64, _I32, _I32, _P, _I32, _P],
     "bliss_block_transpose": [_P, _P, _I32, _I32, _I32, _P, _P, _P, _I64, _P],
     "bliss_spmm_chunk_edges": [_I32],
     "bliss_sage_epilogue_fwd": [_P, _I64, _P, _I64, _I32, _I32, _F, C.c_uint32, _P, _P, _I64, _P, _P],

@@ -18,6 +18,12 @@ def u_add_v(lhs_field, rhs_field, out):
     return _Message("u_add_v", lhs_field, rhs_field, out)
 
 
+def u_dot_v(lhs_field, rhs_field, out):
+    """edge[out] = src[lhs_field] . dst[rhs_field], shape [B, 1] (dgl.function.u_dot_v): the per-edge dot product kernel
+    (csrc/sddmm.hip), forward-only."""
+    return _Message("u_dot_v", lhs_field, rhs_field, out)
+
+
 def u_mul_e(lhs_field, rhs_field, out):
     """message[out] = src[lhs_field] * edge[rhs_field]   (model.py:98)."""
     return _Message("u_mul_e", lhs_field, rhs_field, out)

@@ -267,8 +267,21 @@ class Block:
     def apply_edges(self, func):
         """``graph.apply_edges(fn.u_add_v('el', 'er', 'e'))`` (model.py:82): materialises the per-edge tensor, as DGL does
         (bliss_gnn_amd.nn.GATv2Conv fuses this step away; this entry exists so that layer code written against DGL runs)."""
-        if getattr(func, "kind", None) != "u_add_v":
-            raise NotImplementedError("apply_edges: only fn.u_add_v is used by the reference (model.py:82)")
+        kind = getattr(func, "kind", None)
+        if kind == "u_dot_v":
+            # edata[out][e] = srcdata[lhs][src_e] . dstdata[rhs][dst_e], bf16 [B, 1], forward-only: bliss::sddmm in SUM mode
+            # (csrc/sddmm.hip, DESIGN.md section 36); entries past a capacity-padded block's live edge count are +0
+            from . import _lib, ops
+            b, a = self.srcdata[func.lhs], self.dstdata[func.rhs]
+            if not (a.is_cuda and a.dtype == b.dtype == torch.bfloat16 and a.shape[1:] == b.shape[1:]):
+                raise NotImplementedError("apply_edges(fn.u_dot_v): bf16 node features of one width on the GPU")
+            a, b = a.detach().reshape(a.shape[0], -1), b.detach().reshape(b.shape[0], -1)
+            a, b = (a if a.stride(1) == 1 else a.contiguous()), (b if b.stride(1) == 1 else b.contiguous())
+            counts = getattr(self, "_counts_dev", None) if self._nnz_ptr else None
+            self.edata[func.out] = ops.sddmm(self.src, self.dst, None, a, b, None, counts, _lib.SDDMM_SUM, False).view(-1, 1)
+            return
+        if kind != "u_add_v":
+            raise NotImplementedError("apply_edges: fn.u_add_v (model.py:82) and fn.u_dot_v are built, not %r" % (kind,))
         self.edata[func.out] = self.srcdata[func.lhs][self.src.long()] + self.dstdata[func.rhs][self.dst.long()]
 
     def update_all(self, message_func, reduce_func):

@@ -36,8 +36,9 @@ def _wait_block(block):
 
 
 def _aggregate_operands(block, h, edge_weight):
-    """What weighted_aggregate and max_aggregate hand to their op: h with unit column stride, w bf16 contiguous or None, the
-    device-side counts of a capacity-padded block, and the by-source index when a gradient w.r.t. h is needed (else None, None)."""
+    """What weighted_aggregate and max_aggregate hand to their op: h with unit column stride, w bf16 contiguous or None (the cast
+    is autograd's, so an fp32 leaf gets its gradient through it), the device-side counts of a capacity-padded block, and the
+    by-source index when a gradient w.r.t. h is needed (else None, None)."""
     assert h.is_cuda and h.dtype == torch.bfloat16, "bf16 features on the GPU (load_graph.py:7)"
     _wait_block(block)
     if h.stride(1) != 1:
@@ -57,8 +58,8 @@ def _aggregate_operands(block, h, edge_weight):
 
 def weighted_aggregate(block, h, edge_weight=None, mean=True, out_fp32=False):
     """out[i] = (1/deg_i if mean) * sum_{e -> i} w_e h[src_e] over a Block -- ``torch.ops.bliss.spmm`` (bliss_gnn_amd/ops.py: a
-    torch.library custom op with a fake kernel and the transposed SpMM as its autograd formula); gradient w.r.t. h only
-    (the sampler's edge weights carry no grad)."""
+    torch.library custom op with a fake kernel and the transposed SpMM as its autograd formula).  Edge weights that require a
+    gradient get gw_e = (1/deg_{dst_e} if mean) * d out[dst_e] . h[src_e] from ``torch.ops.bliss.sddmm``."""
     from . import ops
     h, w, counts, t_indptr, t_edge = _aggregate_operands(block, h, edge_weight)
     return ops.spmm(block.indptr, block.src, block.dst, w, h, block.num_dst_nodes(), counts, bool(mean), bool(out_fp32), t_indptr, t_edge)
@@ -67,19 +68,22 @@ def weighted_aggregate(block, h, edge_weight=None, mean=True, out_fp32=False):
 def max_aggregate(block, h, edge_weight=None, return_arg=False):
     """out[i, c] = max_{e -> i} bf16(w_e h[src_e, c]) over a Block, 0 for a row without edges -- ``torch.ops.bliss.spmm_max``
     (csrc/spmm_max.hip, DESIGN.md section 30: DGL's ``update_all(u_mul_e | copy_u, fn.max)``, the lowest edge wins a tie);
-    gradient w.r.t. h only, routed to the recorded edge of every element.  ``return_arg=True`` also returns arg int32 [S, dim]
-    (the winning edge, -1 for a row without edges)."""
+    the gradient w.r.t. h is routed to the recorded edge of every element, and edge weights that require a gradient get the
+    dot product of d out and h over the columns their edge won.  ``return_arg=True`` also returns arg
+    int32 [S, dim] (the winning edge, -1 for a row without edges)."""
     from . import ops
     h, w, counts, t_indptr, t_edge = _aggregate_operands(block, h, edge_weight)
+    w_grad = w is not None and w.requires_grad and torch.is_grad_enabled()
     out, arg = ops.spmm_max(block.indptr, block.src, block.dst, w, h, block.num_dst_nodes(), counts,
-                            bool(return_arg or t_indptr is not None), t_indptr, t_edge)
+                            bool(return_arg or t_indptr is not None or w_grad), t_indptr, t_edge)
     return (out, arg) if return_arg else out
 
 
 def gcn_aggregate(block, h, edge_weight=None, h_self=None):
     """out[i] = (sum_{e -> i} w_e h[src_e] + h_self[i]) / (deg_i + 1) over a Block, ONE rounding -- ``torch.ops.bliss.spmm_self``
     (csrc/spmm_self.hip, DESIGN.md section 34: the 'gcn' aggregator of dglnn.SAGEConv [DGL-recalled]).  ``h_self=None``: the
-    destinations are the leading rows of ``h``, and the gradient w.r.t. h carries the self term on those rows.  A distinct
+    destinations are the leading rows of ``h``, and the gradient w.r.t. h carries the self term on those rows.  Edge weights that
+    require a gradient get gw_e = d out[dst_e] . h[src_e] / (deg_{dst_e} + 1).  A distinct
     ``h_self`` (the (feat_src, feat_dst) pair form) is forward-only: one that requires a gradient is refused."""
     from . import ops
     if h_self is h:
@@ -706,7 +710,9 @@ class _SageDualLinear(torch.autograd.Function):
 class _SageAggDual(torch.autograd.Function):
     """Aggregation + _SageDualLinear as ONE autograd node: the layer input h feeds both the SpMM and (its first rows) fc_self, and
     two nodes made autograd zero-pad the slice's gradient and add the two (fill + copy + add kernels, 5 K x 256 each); here the
-    fc_self product accumulates straight into the transposed SpMM's result."""
+    fc_self product accumulates straight into the transposed SpMM's result.  Edge weights that require a gradient get
+    gw_e = (d W_neigh)[dst_e] . h[src_e] / deg_{dst_e} (bliss::sddmm, DESIGN.md section 36): one more dense launch for d W_neigh on
+    the destination rows, issued in that case only."""
 
     @staticmethod
     def forward(ctx, h, indptr, src, dst, w, counts, t_indptr, t_edge, n_dst, w_neigh, w_self, bias, relu, p, ctr, seed, rows_dev):
@@ -736,8 +742,11 @@ class _SageAggDual(torch.autograd.Function):
                                                         out.shape[1], ctx.p, din.data_ptr(), din.stride(0), _stream()),
                        "bliss_sage_epilogue_bwd")
             d = din
-        gh = None
+        gh = gw = None
         mfma = _mfma_bwd_on() and w1.shape[0] <= 256 and _bwd_ok(d, agg, h, w1, w2)
+        if w is not None and ctx.needs_input_grad[4]:
+            dn = sage_dgrad(d, w1, ctx.n_dst, ctx.rows_dev) if mfma else d @ w1
+            gw = ops.sddmm(src, dst, indptr, dn, h, None, counts, _lib.SDDMM_MEAN, False)
         if ctx.needs_input_grad[0]:
             if t_indptr is None or t_edge is None:
                 raise RuntimeError("the block's by-source index (Block.transposed()) is needed to differentiate w.r.t. h")
@@ -748,12 +757,12 @@ class _SageAggDual(torch.autograd.Function):
                 src_dev = counts.data_ptr() + 12 if counts is not None else 0
                 gh = sage_dgrad(t, w1, h.shape[0], src_dev, a2=d, w2=w2, m2_bound=ctx.n_dst, m2_dev=ctx.rows_dev)
             else:
-                gh = ops.spmm_t(t_indptr, t_edge, src, dst, indptr, w, d @ w1, h.shape[0], counts, True)
+                gh = ops.spmm_t(t_indptr, t_edge, src, dst, indptr, w, d @ w1 if gw is None else dn, h.shape[0], counts, True)
                 gh[: ctx.n_dst].addmm_(d, w2)
         if mfma:
             (dw1, _), (dw2, db) = sage_wgrad([(d, agg, ctx.n_dst, ctx.rows_dev, False), (d, h, ctx.n_dst, ctx.rows_dev, ctx.has_bias)])
-            return (gh, None, None, None, None, None, None, None, None, dw1, dw2, db, None, None, None, None, None)
-        return (gh, None, None, None, None, None, None, None, None, d.t() @ agg, d.t() @ h[: ctx.n_dst],
+            return (gh, None, None, None, gw, None, None, None, None, dw1, dw2, db, None, None, None, None, None)
+        return (gh, None, None, None, gw, None, None, None, None, d.t() @ agg, d.t() @ h[: ctx.n_dst],
                 _bias_grad(d) if ctx.has_bias else None, None, None, None, None, None)
 
 

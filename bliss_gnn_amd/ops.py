@@ -1,7 +1,8 @@
 """The message-passing kernels as ``torch.library`` custom ops (last row): ``torch.ops.bliss.spmm``
 (the weighted g-SpMM of dglnn.SAGEConv / GraphConv, [DGL-recalled] SURVEY m3, with its transposed backward m6 registered as
 the op's autograd formula), ``spmm_max`` ('pool') and ``spmm_self`` ('gcn': the sum with the destination's own row, over deg + 1)
-and ``torch.ops.bliss.embed_norm`` (model.py:318-320).  Device tensors in, device tensors out, no host sync; fake (meta) implementations make them traceable (FakeTensor / torch.compile shape propagation); the real
+and ``torch.ops.bliss.embed_norm`` (model.py:318-320).  Edge weights that require a gradient get one from the three aggregation ops:
+``torch.ops.bliss.sddmm``, the per-edge dot product of d out and h (csrc/sddmm.hip).  Device tensors in, device tensors out, no host sync; fake (meta) implementations make them traceable (FakeTensor / torch.compile shape propagation); the real
 implementations are the C ABI calls of include/bliss_gnn.h -- there is no other backend.
 
 ``counts`` (optional int32[10] = a bliss_layer_counts_t on the device) marks capacity-padded blocks: the true edge count is
@@ -21,6 +22,45 @@ def _p(t):
 
 def _nnz_ptr(counts):
     return 0 if counts is None else counts.data_ptr() + 16          # bliss_layer_counts_t::B
+
+
+def _wants_grad(w):
+    """setup_context only (it runs when autograd records the op): do the edge weights want a gradient?"""
+    return w is not None and w.requires_grad
+
+
+@torch.library.custom_op("bliss::sddmm", mutates_args=())
+def sddmm(src: Tensor, dst: Tensor, indptr: Optional[Tensor], a: Tensor, b: Tensor, arg: Optional[Tensor], counts: Optional[Tensor],
+          mode: int, out_fp32: bool) -> Tensor:
+    """out[e] = coef_e * sum_c a[dst_e, c] b[src_e, c], one rounding (csrc/sddmm.hip) -- the per-edge dot
+    product of a destination-indexed and a source-indexed bf16 matrix.  ``mode`` (_lib.SDDMM_*): SUM coef 1; MEAN 1 / max(deg, 1)
+    and SELF 1 / (deg + 1) of the destination (``indptr``); MAX coef 1 over the columns ``arg[dst_e, c] == e`` only.  bf16
+    [len(src)] (fp32 with ``out_fp32``); entries past a padded block's live edge count are +0.  Rows may be strided and
+    unaligned (a column slice).  Forward-only."""
+    assert a.is_cuda and b.is_cuda and a.dtype == b.dtype == torch.bfloat16 and a.dim() == b.dim() == 2, "bf16 matrices on the GPU"
+    assert a.shape[1] == b.shape[1] and a.stride(1) == 1 and b.stride(1) == 1
+    B, D = int(src.numel()), a.shape[1]
+    assert dst.numel() == B
+    if arg is not None:
+        assert arg.dtype == torch.int32 and arg.dim() == 2 and arg.shape[1] == D and arg.stride(1) == 1
+    out = torch.empty(B, dtype=torch.float32 if out_fp32 else torch.bfloat16, device=a.device)
+    _lib.check(_lib.lib.bliss_sddmm_dot(src.data_ptr(), dst.data_ptr(), _p(indptr), _nnz_ptr(counts), B, a.data_ptr(), a.stride(0),
+                                        b.data_ptr(), b.stride(0), _p(arg), 0 if arg is None else arg.stride(0), D, int(mode),
+                                        out.data_ptr(), int(out_fp32), _stream()), "bliss_sddmm_dot")
+    return out
+
+
+@sddmm.register_fake
+def _(src, dst, indptr, a, b, arg, counts, mode, out_fp32):
+    return a.new_empty((src.numel(),), dtype=torch.float32 if out_fp32 else torch.bfloat16)
+
+
+def _sddmm_no_grad(ctx, g):
+    raise NotImplementedError("bliss::sddmm is forward-only: no gradient through the per-edge dot product (no second derivative "
+                              "of the aggregation ops w.r.t. their edge weights; DESIGN.md section 36)")
+
+
+sddmm.register_autograd(_sddmm_no_grad)
 
 
 @torch.library.custom_op("bliss::spmm", mutates_args=())
@@ -62,19 +102,24 @@ def _(t_indptr, t_edge, src, dst, indptr, w, gout, n_src, counts, mean):
 
 def _spmm_setup(ctx, inputs, output):
     indptr, src, dst, w, h, n_dst, counts, mean, out_fp32, t_indptr, t_edge = inputs
-    ctx.save_for_backward(indptr, src, dst, w, counts, t_indptr, t_edge)
+    ctx.need_w = _wants_grad(w)                                 # (then h is saved too: gw = the per-edge dot of d out and h)
+    ctx.save_for_backward(indptr, src, dst, w, counts, t_indptr, t_edge, *((h,) if ctx.need_w else ()))
     ctx.n_src, ctx.mean = h.shape[0], mean
 
 
 def _spmm_backward(ctx, gout):
-    indptr, src, dst, w, counts, t_indptr, t_edge = ctx.saved_tensors
-    if t_indptr is None or t_edge is None:
-        raise RuntimeError("bliss::spmm needs the block's by-source index (Block.transposed()) to differentiate w.r.t. h")
+    indptr, src, dst, w, counts, t_indptr, t_edge = ctx.saved_tensors[:7]
     g = gout.contiguous()
     if g.dtype != torch.bfloat16:
         g = g.bfloat16()
-    gh = spmm_t(t_indptr, t_edge, src, dst, indptr, w, g, ctx.n_src, counts, ctx.mean)
-    return (None, None, None, None, gh, None, None, None, None, None, None)       # the sampler's edge weights carry no grad (m6)
+    gh = gw = None
+    if ctx.needs_input_grad[4] or not ctx.need_w:
+        if t_indptr is None or t_edge is None:
+            raise RuntimeError("bliss::spmm needs the block's by-source index (Block.transposed()) to differentiate w.r.t. h")
+        gh = spmm_t(t_indptr, t_edge, src, dst, indptr, w, g, ctx.n_src, counts, ctx.mean)
+    if ctx.need_w:
+        gw = sddmm(src, dst, indptr, g, ctx.saved_tensors[7], None, counts, _lib.SDDMM_MEAN if ctx.mean else _lib.SDDMM_SUM, False)
+    return (None, None, None, gw, gh, None, None, None, None, None, None)
 
 
 spmm.register_autograd(_spmm_backward, setup_context=_spmm_setup)
@@ -150,24 +195,31 @@ def _(t_indptr, t_edge, src, dst, w, gout, arg, act, n_src, counts):
 
 def _spmm_max_setup(ctx, inputs, output):
     indptr, src, dst, w, h, n_dst, counts, want_arg, t_indptr, t_edge = inputs
-    ctx.save_for_backward(src, dst, w, counts, t_indptr, t_edge, output[1])
+    ctx.need_w = _wants_grad(w)
+    ctx.save_for_backward(src, dst, w, counts, t_indptr, t_edge, output[1], *((h,) if ctx.need_w else ()))
     ctx.n_src, ctx.want_arg = h.shape[0], want_arg
     ctx.mark_non_differentiable(output[1])
     ctx.set_materialize_grads(False)
 
 
 def _spmm_max_backward(ctx, gout, _garg):
-    src, dst, w, counts, t_indptr, t_edge, arg = ctx.saved_tensors
+    src, dst, w, counts, t_indptr, t_edge, arg = ctx.saved_tensors[:7]
     if gout is None:
         return (None,) * 10
-    if t_indptr is None or t_edge is None or not ctx.want_arg:
-        raise RuntimeError("bliss::spmm_max needs the block's by-source index (Block.transposed()) and want_arg=True to "
-                           "differentiate w.r.t. h")
     g = gout.contiguous()
     if g.dtype != torch.bfloat16:
         g = g.bfloat16()
-    gh = spmm_max_t(t_indptr, t_edge, src, dst, w, g, arg, ctx.n_src, counts)
-    return (None, None, None, None, gh, None, None, None, None, None)             # the sampler's edge weights carry no grad (m6)
+    gh = gw = None
+    if ctx.needs_input_grad[4] or not ctx.need_w:
+        if t_indptr is None or t_edge is None or not ctx.want_arg:
+            raise RuntimeError("bliss::spmm_max needs the block's by-source index (Block.transposed()) and want_arg=True to "
+                               "differentiate w.r.t. h")
+        gh = spmm_max_t(t_indptr, t_edge, src, dst, w, g, arg, ctx.n_src, counts)
+    if ctx.need_w:
+        if not ctx.want_arg:
+            raise RuntimeError("bliss::spmm_max needs want_arg=True to differentiate w.r.t. w")
+        gw = sddmm(src, dst, None, g, ctx.saved_tensors[7], arg, counts, _lib.SDDMM_MAX, False)
+    return (None, None, None, gw, gh, None, None, None, None, None)
 
 
 spmm_max.register_autograd(_spmm_max_backward, setup_context=_spmm_max_setup)
@@ -218,21 +270,26 @@ def _(t_indptr, t_edge, src, dst, indptr, w, gout, n_src, n_dst, counts, fold_se
 
 def _spmm_self_setup(ctx, inputs, output):
     indptr, src, dst, w, h, h_self, n_dst, counts, t_indptr, t_edge = inputs
-    ctx.save_for_backward(indptr, src, dst, w, counts, t_indptr, t_edge)
+    ctx.need_w = _wants_grad(w)
+    ctx.save_for_backward(indptr, src, dst, w, counts, t_indptr, t_edge, *((h,) if ctx.need_w else ()))
     ctx.n_src, ctx.n_dst, ctx.fold = h.shape[0], n_dst, h_self is None
 
 
 def _spmm_self_backward(ctx, gout):
-    indptr, src, dst, w, counts, t_indptr, t_edge = ctx.saved_tensors
+    indptr, src, dst, w, counts, t_indptr, t_edge = ctx.saved_tensors[:7]
     if ctx.needs_input_grad[5]:
         raise NotImplementedError("bliss::spmm_self: no gradient w.r.t. a distinct h_self (the pair form under training)")
-    if t_indptr is None or t_edge is None:
-        raise RuntimeError("bliss::spmm_self needs the block's by-source index (Block.transposed()) to differentiate w.r.t. h")
     g = gout.contiguous()
     if g.dtype != torch.bfloat16:
         g = g.bfloat16()
-    gh = spmm_self_t(t_indptr, t_edge, src, dst, indptr, w, g, ctx.n_src, ctx.n_dst, counts, ctx.fold)
-    return (None, None, None, None, gh, None, None, None, None, None)             # the sampler's edge weights carry no grad (m6)
+    gh = gw = None
+    if ctx.needs_input_grad[4] or not ctx.need_w:
+        if t_indptr is None or t_edge is None:
+            raise RuntimeError("bliss::spmm_self needs the block's by-source index (Block.transposed()) to differentiate w.r.t. h")
+        gh = spmm_self_t(t_indptr, t_edge, src, dst, indptr, w, g, ctx.n_src, ctx.n_dst, counts, ctx.fold)
+    if ctx.need_w:                                              # (a distinct h_self does not enter gw)
+        gw = sddmm(src, dst, indptr, g, ctx.saved_tensors[7], None, counts, _lib.SDDMM_SELF, False)
+    return (None, None, None, gw, gh, None, None, None, None, None)
 
 
 spmm_self.register_autograd(_spmm_self_backward, setup_context=_spmm_self_setup)

@@ -905,6 +905,31 @@ int bliss_spmm_self_bwd(const int32_t* t_indptr, const int32_t* t_edge, const in
                         const void* w, const void* gout, int64_t gout_stride, int32_t n_src, int32_t n_dst, const int32_t* n_dst_dev,
                         const int32_t* nnz_dev, int32_t nnz, int32_t dim, void* gh, int64_t gh_stride, float* partials, void* stream);
 
+/* Per-edge dot product of two gathered rows (SDDMM), csrc/sddmm.hip, DESIGN.md section 36: the gradient of the aggregation ops
+ * above w.r.t. their per-edge weights (a = d out, b = h) and fn.u_dot_v.  For live edge e with s = src[e], d = dst[e]:
+ *   dot_e  = sum_c float(a[d, c]) * float(b[s, c])            (BLISS_SDDMM_MAX: only the columns c with arg[d, c] == e)
+ *   out[e] = round(dot_e * coef_e)                             one rounding, to bf16, or none when out_fp32 (out is then float)
+ *   coef_e = 1                              BLISS_SDDMM_SUM, BLISS_SDDMM_MAX
+ *            1.0f / (float)max(deg_d, 1)    BLISS_SDDMM_MEAN      deg_d = indptr[d + 1] - indptr[d]
+ *            1.0f / (float)(deg_d + 1)      BLISS_SDDMM_SELF
+ * a bf16 [>= n_dst, dim] by destination, b bf16 [>= n_src, dim] by source, arg int32 [>= n_dst, dim] the winner table of
+ * bliss_spmm_max_fwd; strides in elements; any alignment (16-byte, 8-byte and scalar loads give the same bits).
+ * Sum order, fp32, never contracted: the columns are cut into groups of 8; group g belongs to lane g % 16 of the edge's 16 lanes;
+ * a lane starts from +0 and adds its products one by one in ascending column order (a masked-out column adds +0); the 16 lane
+ * sums are added as a balanced tree of neighbours ((p15 + p14) + (p13 + p12)) + ... (four steps: distance 1, 2, 4, 8); then
+ * the coefficient, then the rounding.  No float atomics: bitwise reproducible.
+ * nnz_dev (optional): the live edge count on the device, nnz an upper bound: live = min(*nnz_dev, nnz).  out[live .. nnz) is
+ * written as +0 and nothing -- no endpoint, row, degree or arg entry -- is read for an edge at or past the live count.
+ * nnz == 0 returns 0 without a launch.  BLISS_EINVAL before any launch: a NULL required pointer (src, dst, a, b, out when
+ * nnz > 0; indptr for MEAN and SELF; arg for MAX), nnz < 0, dim <= 0, a stride below dim, an unknown mode. */
+#define BLISS_SDDMM_SUM  0
+#define BLISS_SDDMM_MEAN 1
+#define BLISS_SDDMM_SELF 2
+#define BLISS_SDDMM_MAX  3
+int bliss_sddmm_dot(const int32_t* src, const int32_t* dst, const int32_t* indptr, const int32_t* nnz_dev, int32_t nnz, const void* a,
+                    int64_t a_stride, const void* b, int64_t b_stride, const int32_t* arg, int64_t arg_stride, int32_t dim, int32_t mode,
+                    void* out, int32_t out_fp32, void* stream);
+
 /* The element-wise tail of a hidden SAGE layer in one pass (model.py:321-333 and :318-320 of the next layer):
  * out = dropout_p(relu(a + b)) row by row, norm_out[row] = ||out[row,:]||_2 (bf16, may be NULL).  a, b, out: bf16
  * [n_rows, dim].  p_drop = 0 (evaluation) makes it deterministic.  ctr: device uint64[66], zero-initialised once: the
