@@ -11,4 +11,5 @@ from .bandit_sampler import BanditLadiesSampler, PoissonBanditLadiesSampler, nor
 from .ladies_sampler import LadiesSampler, PoissonLadiesSampler  # noqa: F401
 from .metrics import MicroF1  # noqa: F401
 from .explain import edge_gradients  # noqa: F401
+from .model import SAGELSTM  # noqa: F401
 from .fit import BanditLaborSampler, BanditNeighborSampler, ImportanceLaborSampler, LaborSampler, WeightedLaborSampler  # noqa: F401

@@ -175,6 +175,7 @@ LEDGER_MAX_LAYERS = 8                                  # BLISS_LEDGER_MAX_LAYERS
 LEDGER_STEP, LEDGER_RESET_EPOCH, LEDGER_REARM = 0, 1, 2
 LEDGER_LOSS_BF16, LEDGER_LOSS_F32 = 0, 1
 SDDMM_SUM, SDDMM_MEAN, SDDMM_SELF, SDDMM_MAX = 0, 1, 2, 3     # BLISS_SDDMM_*
+LSTM_MAX_DIM = 256                     # BLISS_LSTM_MAX_DIM: the widest hidden state of bliss_lstm_agg_fwd / bwd
 _LEDGER_STRUCTS = {}
 
 
@@ -297,6 +298,10 @@ SIGNATURES = {
     "bliss_spmm_self_fwd": [_P, _P, _P, _P, _P, _I64, _P, _I64, _I32, _P, _P, _I32, _I32, _P, _I64, _P, _P],
     "bliss_spmm_self_bwd": [_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P, _P, _I32, _I32, _P, _I64, _P, _P],
     "bliss_sddmm_dot": [_P, _P, _P, _P, _I32, _P, _I64, _P, _I64, _P, _I64, _I32, _I32, _P, _I32, _P],
+    "bliss_lstm_tile_rows": [],
+    "bliss_lstm_agg_fwd": [_P, _P, _P, _P, _I64, _P, _I64, _P, _P, _I32, _P, _P, _I32, _I32, _P, _I64, _P, _P, _P, _P],
+    "bliss_lstm_agg_bwd": [_P, _P, _I64, _P, _I64, _P, _P, _I32, _P, _P, _I32, _I32, _P, _P],
+    "bliss_lstm_edge_reduce": [_P, _P, _P, _P, _I32, _P, _I32, _I32, _P, _I64, _P],
     "bliss_block_transpose": [_P, _P, _I32, _I32, _I32, _P, _P, _P, _I64, _P],
     "bliss_spmm_chunk_edges": [_I32],
     "bliss_sage_epilogue_fwd": [_P, _I64, _P, _I64, _I32, _I32, _F, C.c_uint32, _P, _P, _I64, _P, _P],

@@ -9,6 +9,7 @@ enum BlissKernelId {
   BK_EXP3_APPLY, BK_NORMALIZE, BK_ROW_SUM, BK_NORM_EDATA, BK_TRANSPOSE, BK_SPMM_FIXUP, BK_SPMM_MAX_FWD, BK_SPMM_MAX_FIXUP,
   BK_SPMM_MAX_BWD, BK_SPMM_MAX_BWD_FIXUP, BK_COL_SUMS, BK_BIN_SCATTER, BK_BIN_REDUCE, BK_BITMAP_SCAN, BK_CAND_NUMBER,
   BK_SPMM_SELF_FWD, BK_SPMM_SELF_FIXUP, BK_SPMM_SELF_BWD, BK_SPMM_SELF_BWD_FIXUP,       // (ids are looked up by name; the two below stay last)
+  BK_LSTM_AGG_FWD, BK_LSTM_AGG_BWD, BK_LSTM_EDGE_REDUCE,
   BK_SDDMM_DOT,
   BK_SPMM_MAX_BWD_RELU, BK_SPMM_MAX_BWD_RELU_FIXUP, BK_COUNT
 };

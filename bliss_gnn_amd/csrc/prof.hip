@@ -18,7 +18,8 @@ const char* kNames[BK_COUNT] = {
   "k_spmm_fwd", "k_spmm_bwd", "k_embed_norm", "k_exp3_update", "k_exp3_apply", "k_normalize_row", "k_row_sum",
   "k_normalized_edata", "k_block_transpose", "k_spmm_fixup", "k_spmm_max", "k_spmm_max_fixup", "k_spmm_max_bwd",
   "k_spmm_max_bwd_fixup", "k_col_sums", "k_bin_scatter", "k_bin_reduce", "k_bitmap_scan", "k_cand_number",
-  "k_spmm_self", "k_spmm_self_fixup", "k_spmm_self_bwd", "k_spmm_self_bwd_fixup", "k_sddmm_dot",
+  "k_spmm_self", "k_spmm_self_fixup", "k_spmm_self_bwd", "k_spmm_self_bwd_fixup",
+  "k_lstm_agg_fwd", "k_lstm_agg_bwd", "k_lstm_edge_reduce", "k_sddmm_dot",
   "k_spmm_max_bwd_relu", "k_spmm_max_bwd_relu_fixup"};
 thread_local Pair t_cur;
 

@@ -7,7 +7,7 @@ runs the SAGEConv layers with the sampler's edge weights (model.py:321-329).
 import torch
 import torch.nn as nn
 
-from .nn import TILE_KINDS, SAGEConv, SAGEGCNConv, embed_norm, sage_epilogue
+from .nn import TILE_KINDS, SAGEConv, SAGEGCNConv, SAGELSTMConv, embed_norm, sage_epilogue
 
 
 def _gathered_norm(blocks, x):
@@ -36,14 +36,16 @@ class SAGE(nn.Module):
         if transforms not in self.SAGE_TRANSFORMS:
             raise ValueError("transforms must be one of %r, not %r" % (self.SAGE_TRANSFORMS, transforms))
         if aggregator_type not in self.SAGE_AGGREGATORS:
-            raise NotImplementedError("SAGE: aggregator_type must be one of %r, not %r" % (self.SAGE_AGGREGATORS, aggregator_type))
+            raise NotImplementedError("SAGE: aggregator_type must be one of %r, not %r%s" % (
+                self.SAGE_AGGREGATORS, aggregator_type,
+                " (the 'lstm' aggregator is the model SAGELSTM: DESIGN.md section 37)" if aggregator_type == "lstm" else ""))
         if aggregator_type != "mean" and transforms == "wide":
             raise NotImplementedError('SAGE: transforms="wide" runs the MFMA tile path, which covers aggregator_type="mean", not %r'
                                       % (aggregator_type,))
         self.transforms, self.aggregator_type = transforms, aggregator_type
         self.n_layers, self.n_hidden, self.n_classes = n_layers, n_hidden, n_classes
         self.layers = nn.ModuleList()
-        mk = (lambda i, o: SAGEGCNConv(i, o)) if aggregator_type == "gcn" else (lambda i, o: SAGEConv(i, o, aggregator_type))
+        mk = {"gcn": SAGEGCNConv, "lstm": SAGELSTMConv}.get(aggregator_type) or (lambda i, o: SAGEConv(i, o, aggregator_type))
         if n_layers > 1:
             self.layers.append(mk(in_feats, n_hidden))
             for _ in range(1, n_layers - 1):
@@ -326,6 +328,9 @@ class SAGE(nn.Module):
         """Why ``inference(path="csc")`` cannot run on this graph, these features and this batch size, or None."""
         if int(batch_size) < 1:
             return "SAGE.inference: the CSC path takes batch_size >= 1, not %d" % int(batch_size)
+        if self.aggregator_type == "lstm":
+            return ('SAGE.inference: the CSC path covers aggregator_type "mean" and "pool", not "lstm" (DESIGN.md section 37); '
+                    'path="blocks" runs it')
         if self.aggregator_type == "gcn":
             return ('SAGE.inference: the CSC path covers aggregator_type "mean" and "pool", not "gcn" (DESIGN.md section 34); '
                     'path="blocks" and "chunks" run it')
@@ -422,7 +427,8 @@ class SAGE(nn.Module):
         one forward-only message-passing launch per range of rows straight off the graph's CSC -- the bits of "blocks" at the
         same ``batch_size``, no block built (``node_chunk`` is ignored).  Raises NotImplementedError naming the reason
         (``csc_refusal``) when it cannot run.
-        ``path="auto"``: "csc" when nothing refuses it, "chunks" otherwise ("blocks" for aggregator_type="gcn", which has no CSC path)."""
+        ``path="auto"``: "csc" when nothing refuses it, "chunks" otherwise ("blocks" for aggregator_type="gcn" and "lstm", which have no CSC path;
+        "lstm" has no chunk path either)."""
         if path not in self.INFERENCE_PATHS:
             raise ValueError("path must be one of %r, not %r" % (self.INFERENCE_PATHS, path))
         h = g.ndata["features"]                                              # :346
@@ -430,7 +436,10 @@ class SAGE(nn.Module):
             why = self.csc_refusal(g, h, batch_size)
             if path == "csc" and why is not None:
                 raise NotImplementedError(why)
-            path = "csc" if why is None else ("blocks" if self.aggregator_type == "gcn" else "chunks")
+            path = "csc" if why is None else ("blocks" if self.aggregator_type in ("gcn", "lstm") else "chunks")
+        if path == "chunks" and self.aggregator_type == "lstm":
+            raise NotImplementedError('SAGE.inference: path="chunks" covers aggregator_type "mean", "pool" and "gcn", not "lstm" '
+                                      '(DESIGN.md section 37); path="blocks" runs it')
         was_training = self.training
         self.eval()                                                          # :364
         try:
@@ -473,6 +482,21 @@ class SAGE(nn.Module):
                 y[b0:b1] = out
             h = y
         return h
+
+
+class SAGELSTM(SAGE):
+    """SAGE with the 'lstm' aggregator [DGL-recalled: dglnn.SAGEConv(in, out, 'lstm')], a model of its own because
+    ``SAGE(..., aggregator_type="lstm")`` keeps refusing: nn.SAGELSTMConv layers on library GEMMs and the
+    recurrent aggregation of csrc/lstm.hip, every layer's input norms as in SAGE.  Every layer's input width is at most 256."""
+    SAGE_AGGREGATORS = ("lstm",)
+
+    def __init__(self, in_feats, n_hidden, n_classes, n_layers, activation, dropout):
+        super().__init__(in_feats, n_hidden, n_classes, n_layers, activation, dropout, transforms="auto", aggregator_type="lstm")
+
+    def inference(self, g, device=None, batch_size=128, use_uva=False, num_workers=0, node_chunk=16384, path="auto"):
+        """SAGE.inference with ``path="auto"`` as the default, which resolves to "blocks" -- the only path this model has:
+        "chunks" and "csc" raise NotImplementedError naming the aggregator."""
+        return super().inference(g, device, batch_size, use_uva, num_workers, node_chunk, path)
 
 
 def _csc_ranges(g, batch_size, max_edges, what):

@@ -5,8 +5,9 @@
 fc_neigh (bias-free) is applied BEFORE aggregation iff in > out; fc_self carries the bias; both
 weights xavier-uniform with gain('relu').  The dense transforms are plain library GEMMs (hipBLASLt
 through torch.nn.functional.linear); the aggregation and its backward are ours.
-'pool' (max-reduce, csrc/spmm_max.hip) and 'gcn' (the self-inclusive normalised sum of csrc/spmm_self.hip: no fc_self, a
-plain bias) are the other two aggregators built: DESIGN.md sections 30 and 34.
+'pool' (max-reduce, csrc/spmm_max.hip), 'gcn' (the self-inclusive normalised sum of csrc/spmm_self.hip: no fc_self, a
+plain bias) and 'lstm' (a recurrent cell over each destination's in-edges, csrc/lstm.hip) are the other aggregators built:
+DESIGN.md sections 30, 34 and 37.
 """
 import torch
 import torch.nn as nn
@@ -101,6 +102,46 @@ def gcn_aggregate(block, h, edge_weight=None, h_self=None):
         raise ValueError("gcn_aggregate: the destinations are the leading rows of h; pass h_self for any other block")
     h, w, counts, t_indptr, t_edge = _aggregate_operands(block, h, edge_weight)
     return ops.spmm_self(block.indptr, block.src, block.dst, w, h, h_self, block.num_dst_nodes(), counts, t_indptr, t_edge)
+
+
+LSTM_MAX_DIM = _lib.LSTM_MAX_DIM            # the widest hidden state of csrc/lstm.hip's tile
+
+
+def lstm_refusal(lstm, h=None, what="lstm_aggregate"):
+    """Why the recurrent aggregation cannot take this nn.LSTM (and these features), or None."""
+    if not isinstance(lstm, nn.LSTM) or lstm.num_layers != 1 or lstm.bidirectional or lstm.proj_size != 0 or lstm.input_size != lstm.hidden_size:
+        return "%s takes a one-layer, one-direction nn.LSTM(D, D) without a projection" % what
+    if lstm.hidden_size > LSTM_MAX_DIM:
+        return "%s: in_feats <= %d (the tile of csrc/lstm.hip, DESIGN.md section 37), not %d" % (what, LSTM_MAX_DIM, lstm.hidden_size)
+    bad = [q for q in list(lstm.parameters()) + ([] if h is None else [h]) if not (q.is_cuda and q.dtype == torch.bfloat16)]
+    if bad:
+        return ("%s takes bf16 features and LSTM parameters on the GPU, not %s on %s: there is no other path"
+                % (what, bad[0].dtype, bad[0].device))
+    if h is not None and (h.dim() != 2 or h.shape[1] != lstm.hidden_size):
+        return "%s: features [n_src, %d] for this LSTM, not %r" % (what, lstm.hidden_size, tuple(h.shape))
+    return None
+
+
+def lstm_aggregate(block, h, lstm, edge_weight=None):
+    """out[i] = the last hidden state of ``lstm`` (an nn.LSTM(D, D)) run over w_e h[src_e] for the in-edges e of i in the block's row
+    order from h = c = 0, +0 for a row without in-edges -- ``torch.ops.bliss.lstm_agg`` (csrc/lstm.hip, DESIGN.md section 37: the
+    'lstm' aggregator of dglnn.SAGEConv [DGL-recalled]).  The input projection runs once per source row as a library GEMM,
+    P = h @ W_ih^T, rounded to bf16; the recurrence takes P.  Differentiates w.r.t. h, the four LSTM parameters and, when they
+    require it, the edge weights (gw_e = dgate[e] . P[src_e]).  Raises NotImplementedError, before any launch, for anything but
+    bf16 on the GPU and D <= 256."""
+    from . import ops
+    why = lstm_refusal(lstm, h)
+    if why is not None:
+        raise NotImplementedError(why)
+    h, w, counts, t_indptr, t_edge = _aggregate_operands(block, h, edge_weight)
+    p = torch.nn.functional.linear(h, lstm.weight_ih_l0)        # [n_src, 4 D]; its autograd gives d h and d W_ih from d P
+    grad = torch.is_grad_enabled()
+    if grad and p.requires_grad and t_indptr is None:           # (h itself may need nothing: the input layer's W_ih still does)
+        t_indptr, t_edge = block.transposed()
+    b_ih, b_hh = (lstm.bias_ih_l0, lstm.bias_hh_l0) if lstm.bias else (None, None)
+    save = grad and any(q is not None and q.requires_grad for q in (p, w, lstm.weight_hh_l0, b_ih, b_hh))
+    return ops.lstm_agg(block.indptr, block.src, w, p, lstm.weight_hh_l0, b_ih, b_hh, block.num_dst_nodes(), counts, save,
+                        t_indptr, t_edge)[0]
 
 
 class _SageEpilogue(torch.autograd.Function):
@@ -792,14 +833,17 @@ class SAGEConv(nn.Module):
     section 34): rst = fc_neigh o agg + bias, agg[i] = (sum_e w_e z[src_e] + z_dst[i]) / (deg_i + 1), fc_neigh first iff in > out, no
     fc_self, a plain ``bias`` parameter."""
 
-    _AGGREGATORS = ("mean", "pool")              # what this class's constructor takes; SAGEGCNConv below: ("gcn",)
+    _AGGREGATORS = ("mean", "pool")              # what this class's constructor takes; SAGEGCNConv below: ("gcn",), SAGELSTMConv: ("lstm",)
 
     def __init__(self, in_feats, out_feats, aggregator_type="mean", feat_drop=0.0, bias=True, norm=None, activation=None):
         super().__init__()
         if aggregator_type not in self._AGGREGATORS:
-            raise NotImplementedError("SAGEConv: aggregator_type 'mean' (model.py:303-308) and 'pool' are built here and 'gcn' as "
-                                      "nn.SAGEGCNConv(in_feats, out_feats, ...), not %r ('lstm' is not built: DESIGN.md section 34)"
-                                      % (aggregator_type,))
+            raise NotImplementedError("SAGEConv: aggregator_type 'mean' (model.py:303-308) and 'pool' are built here, 'gcn' as "
+                                      "nn.SAGEGCNConv(in_feats, out_feats, ...) and 'lstm' as nn.SAGELSTMConv(in_feats, out_feats, ...) "
+                                      "(DESIGN.md sections 34 and 37), not %r" % (aggregator_type,))
+        if aggregator_type == "lstm" and in_feats > LSTM_MAX_DIM:
+            raise NotImplementedError("SAGELSTMConv: in_feats <= %d (the tile of csrc/lstm.hip, DESIGN.md section 37), not %d"
+                                      % (LSTM_MAX_DIM, in_feats))
         self._aggre_type = aggregator_type
         self._in_src_feats = self._in_dst_feats = in_feats
         self._out_feats = out_feats
@@ -807,6 +851,8 @@ class SAGEConv(nn.Module):
         self.norm, self.activation = norm, activation
         if aggregator_type == "pool":
             self.fc_pool = nn.Linear(in_feats, in_feats)
+        if aggregator_type == "lstm":
+            self.lstm = nn.LSTM(in_feats, in_feats, batch_first=True)
         self.fc_neigh = nn.Linear(in_feats, out_feats, bias=False)
         if aggregator_type == "gcn":                 # no fc_self: the destination's own row rides in the aggregation; a plain bias
             if bias:
@@ -821,6 +867,8 @@ class SAGEConv(nn.Module):
         gain = nn.init.calculate_gain("relu")
         if self._aggre_type == "pool":
             nn.init.xavier_uniform_(self.fc_pool.weight, gain=gain)
+        if self._aggre_type == "lstm":
+            self.lstm.reset_parameters()             # uniform +-1 / sqrt(in_feats), as DGL leaves it
         if self._aggre_type == "gcn":
             if self.bias is not None:
                 nn.init.zeros_(self.bias)
@@ -857,6 +905,8 @@ class SAGEConv(nn.Module):
             return rst
         if self._aggre_type == "pool":
             h_neigh = self.fc_neigh(max_aggregate(graph, torch.relu(self.fc_pool(feat_src)), edge_weight))
+        elif self._aggre_type == "lstm":             # never fc_neigh before the recurrence
+            h_neigh = self.fc_neigh(lstm_aggregate(graph, feat_src, self.lstm, edge_weight))
         elif self._in_src_feats > self._out_feats:   # fc_neigh before the aggregation
             h_neigh = weighted_aggregate(graph, self.fc_neigh(feat_src), edge_weight, mean=True)
         else:
@@ -880,6 +930,19 @@ class SAGEGCNConv(SAGEConv):
 
     def __init__(self, in_feats, out_feats, feat_drop=0.0, bias=True, norm=None, activation=None):
         super().__init__(in_feats, out_feats, "gcn", feat_drop=feat_drop, bias=bias, norm=norm, activation=activation)
+
+
+class SAGELSTMConv(SAGEConv):
+    """[DGL-recalled] dglnn.SAGEConv(in_feats, out_feats, 'lstm'), a class of its own for SAGEGCNConv's
+    reason (``SAGEConv(in, out, "lstm")`` keeps refusing): rst = fc_self(h_dst) + fc_neigh(neigh), neigh[d] = the last hidden state
+    of ``lstm = nn.LSTM(in, in, batch_first=True)`` run over w_e h[src_e] for d's in-edges in row order (nn.lstm_aggregate).
+    Parameters ``lstm.weight_ih_l0``, ``lstm.weight_hh_l0`` (4 in, in), ``lstm.bias_ih_l0``, ``lstm.bias_hh_l0`` (4 in,),
+    ``fc_neigh.weight``, ``fc_self.weight``, ``fc_self.bias``.  ``forward(graph, feat, edge_weight=None, parts=False)`` is
+    SAGEConv's.  in_feats <= 256; bf16 on the GPU or NotImplementedError."""
+    _AGGREGATORS = ("lstm",)
+
+    def __init__(self, in_feats, out_feats, feat_drop=0.0, bias=True, norm=None, activation=None):
+        super().__init__(in_feats, out_feats, "lstm", feat_drop=feat_drop, bias=bias, norm=norm, activation=activation)
 
 
 # transforms="tile" (DESIGN.md section 26): GraphConv(norm='both') on bounded kernels -- the degree-normalised SpMM of csrc/gcn.hip,

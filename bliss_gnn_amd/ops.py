@@ -1,6 +1,7 @@
 """The message-passing kernels as ``torch.library`` custom ops (last row): ``torch.ops.bliss.spmm``
 (the weighted g-SpMM of dglnn.SAGEConv / GraphConv, [DGL-recalled] SURVEY m3, with its transposed backward m6 registered as
-the op's autograd formula), ``spmm_max`` ('pool') and ``spmm_self`` ('gcn': the sum with the destination's own row, over deg + 1)
+the op's autograd formula), ``spmm_max`` ('pool'), ``spmm_self`` ('gcn': the sum with the destination's own row, over deg + 1) and ``lstm_agg`` ('lstm': a recurrent
+cell over each destination's in-edges, csrc/lstm.hip)
 and ``torch.ops.bliss.embed_norm`` (model.py:318-320).  Edge weights that require a gradient get one from the three aggregation ops:
 ``torch.ops.bliss.sddmm``, the per-edge dot product of d out and h (csrc/sddmm.hip).  Device tensors in, device tensors out, no host sync; fake (meta) implementations make them traceable (FakeTensor / torch.compile shape propagation); the real
 implementations are the C ABI calls of include/bliss_gnn.h -- there is no other backend.
@@ -22,6 +23,11 @@ def _p(t):
 
 def _nnz_ptr(counts):
     return 0 if counts is None else counts.data_ptr() + 16          # bliss_layer_counts_t::B
+
+
+def _rs(t):
+    """Row stride in elements of a matrix with unit column stride (torch leaves the stride of a one-row matrix arbitrary)."""
+    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
 
 
 def _wants_grad(w):
@@ -293,6 +299,106 @@ def _spmm_self_backward(ctx, gout):
 
 
 spmm_self.register_autograd(_spmm_self_backward, setup_context=_spmm_self_setup)
+
+
+@torch.library.custom_op("bliss::lstm_agg", mutates_args=())
+def lstm_agg(indptr: Tensor, src: Tensor, w: Optional[Tensor], p: Tensor, w_hh: Tensor, b_ih: Optional[Tensor], b_hh: Optional[Tensor],
+             n_dst: int, counts: Optional[Tensor], save: bool, t_indptr: Optional[Tensor],
+             t_edge: Optional[Tensor]) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """out[i] = the last hidden state of an LSTM cell run over row i's in-edges in row order, its input projection handed over
+    as ``p = bf16(h @ W_ih^T)`` [n_src, 4 D] and scaled per edge by ``w`` (csrc/lstm.hip).  Returns (out bf16
+    [n_dst, D], gates fp32 [B, 4 D], cell fp32 [B, D], hprev bf16 [B, D]); the last three are the backward's state, empty unless
+    ``save``.  Rows without live in-edges, and rows past a padded block's live destination count, are +0."""
+    assert p.is_cuda and p.dtype == torch.bfloat16 and p.dim() == 2 and p.stride(1) == 1, "bf16 projections on the GPU"
+    assert w_hh.is_cuda and w_hh.dtype == torch.bfloat16 and w_hh.dim() == 2 and w_hh.stride(1) == 1
+    D, B = w_hh.shape[1], int(src.numel())
+    assert w_hh.shape[0] == 4 * D and p.shape[1] == 4 * D and 1 <= D <= _lib.LSTM_MAX_DIM
+    for b in (b_ih, b_hh):
+        assert b is None or (b.is_cuda and b.dtype == torch.bfloat16 and b.numel() == 4 * D and b.is_contiguous())
+    dev = p.device
+    out = torch.empty(n_dst, D, dtype=torch.bfloat16, device=dev)
+    Bs = B if save else 0
+    gates = torch.empty(Bs, 4 * D, dtype=torch.float32, device=dev)
+    cell = torch.empty(Bs, D, dtype=torch.float32, device=dev)
+    hprev = torch.empty(Bs, D, dtype=torch.bfloat16, device=dev)
+    _lib.check(_lib.lib.bliss_lstm_agg_fwd(indptr.data_ptr(), src.data_ptr(), _p(w), p.data_ptr(), _rs(p), w_hh.data_ptr(),
+                                           _rs(w_hh), _p(b_ih), _p(b_hh), n_dst, _p(counts), _nnz_ptr(counts), B, D, out.data_ptr(),
+                                           _rs(out), gates.data_ptr(), cell.data_ptr(), hprev.data_ptr(), _stream()),
+               "bliss_lstm_agg_fwd")
+    return out, gates, cell, hprev
+
+
+@lstm_agg.register_fake
+def _(indptr, src, w, p, w_hh, b_ih, b_hh, n_dst, counts, save, t_indptr, t_edge):
+    D, Bs = w_hh.shape[1], (src.numel() if save else 0)
+    return (p.new_empty((n_dst, D), dtype=torch.bfloat16), p.new_empty((Bs, 4 * D), dtype=torch.float32),
+            p.new_empty((Bs, D), dtype=torch.float32), p.new_empty((Bs, D), dtype=torch.bfloat16))
+
+
+@torch.library.custom_op("bliss::lstm_agg_t", mutates_args=())
+def lstm_agg_t(indptr: Tensor, t_indptr: Optional[Tensor], t_edge: Optional[Tensor], w: Optional[Tensor], gout: Tensor, w_hh: Tensor,
+               gates: Tensor, cell: Tensor, n_src: int, counts: Optional[Tensor]) -> Tuple[Tensor, Tensor]:
+    """The backward of lstm_agg: dgate bf16 [B, 4 D], the gradient at the gate pre-activations of every live edge (+0 past them),
+    and -- with the by-source index -- dp[s] = sum_{e : src_e = s} w_e dgate[e], bf16 [n_src, 4 D] (else empty)."""
+    D, B, n_dst = w_hh.shape[1], gates.shape[0], gout.shape[0]
+    dev = gout.device
+    dgate = torch.empty(B, 4 * D, dtype=torch.bfloat16, device=dev)
+    wt = w_hh.t().contiguous()                                  # [D, 4 D]: the product's B operand, K-contiguous
+    _lib.check(_lib.lib.bliss_lstm_agg_bwd(indptr.data_ptr(), gout.data_ptr(), _rs(gout), wt.data_ptr(), _rs(wt),
+                                           gates.data_ptr(), cell.data_ptr(), n_dst, _p(counts), _nnz_ptr(counts), B, D,
+                                           dgate.data_ptr(), _stream()), "bliss_lstm_agg_bwd")
+    if t_indptr is None or t_edge is None:
+        return dgate, torch.empty(0, 4 * D, dtype=torch.bfloat16, device=dev)
+    dp = torch.empty(n_src, 4 * D, dtype=torch.bfloat16, device=dev)
+    _lib.check(_lib.lib.bliss_lstm_edge_reduce(t_indptr.data_ptr(), t_edge.data_ptr(), _p(w), dgate.data_ptr(), n_src, _nnz_ptr(counts),
+                                               B, D, dp.data_ptr(), _rs(dp), _stream()), "bliss_lstm_edge_reduce")
+    return dgate, dp
+
+
+@lstm_agg_t.register_fake
+def _(indptr, t_indptr, t_edge, w, gout, w_hh, gates, cell, n_src, counts):
+    D = w_hh.shape[1]
+    return (gout.new_empty((gates.shape[0], 4 * D), dtype=torch.bfloat16),
+            gout.new_empty((n_src if t_indptr is not None and t_edge is not None else 0, 4 * D), dtype=torch.bfloat16))
+
+
+def _lstm_setup(ctx, inputs, output):
+    indptr, src, w, p, w_hh, b_ih, b_hh, n_dst, counts, save, t_indptr, t_edge = inputs
+    ctx.need_w = _wants_grad(w)
+    ctx.save_for_backward(indptr, src, w, w_hh, counts, t_indptr, t_edge, output[1], output[2], output[3], *((p,) if ctx.need_w else ()))
+    ctx.n_src, ctx.saved_state = p.shape[0], save
+    ctx.mark_non_differentiable(output[1], output[2], output[3])
+    ctx.set_materialize_grads(False)
+
+
+def _lstm_backward(ctx, gout, _g1, _g2, _g3):
+    indptr, src, w, w_hh, counts, t_indptr, t_edge, gates, cell, hprev = ctx.saved_tensors[:10]
+    if gout is None:
+        return (None,) * 12
+    if not ctx.saved_state:
+        raise RuntimeError("bliss::lstm_agg was run with save=False: the backward's state was not kept")
+    need_p = ctx.needs_input_grad[3]
+    if need_p and (t_indptr is None or t_edge is None):
+        raise RuntimeError("bliss::lstm_agg needs the block's by-source index (Block.transposed()) to differentiate w.r.t. p")
+    g = gout.contiguous()
+    if g.dtype != torch.bfloat16:
+        g = g.bfloat16()
+    dgate, dp = lstm_agg_t(indptr, t_indptr if need_p else None, t_edge if need_p else None, w, g, w_hh, gates, cell, ctx.n_src, counts)
+    gw = g_hh = gb_ih = gb_hh = None
+    if ctx.need_w:                                              # gw_e = dgate[e] . p[src_e]: the per-edge dot with the edge as its own row
+        rows = torch.arange(src.numel(), dtype=torch.int32, device=src.device)
+        gw = sddmm(src, rows, None, dgate, ctx.saved_tensors[10], None, counts, _lib.SDDMM_SUM, False)
+    if ctx.needs_input_grad[4]:
+        g_hh = dgate.t() @ hprev                                # [4 D, B] x [B, D]: zeros past the live edges on both sides
+    if ctx.needs_input_grad[5] or ctx.needs_input_grad[6]:
+        from .nn import _bias_grad
+        gb = _bias_grad(dgate)
+        gb_ih = gb if ctx.needs_input_grad[5] else None
+        gb_hh = gb if ctx.needs_input_grad[6] else None
+    return (None, None, gw, dp if need_p else None, g_hh, gb_ih, gb_hh, None, None, None, None, None)
+
+
+lstm_agg.register_autograd(_lstm_backward, setup_context=_lstm_setup)
 
 
 @torch.library.custom_op("bliss::embed_norm", mutates_args=())

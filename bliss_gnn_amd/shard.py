@@ -483,6 +483,9 @@ def refuse_unsharded_aggregator(model, what):
     and its pair form carries no gradient w.r.t. the destinations' rows -- refused by name, at construction."""
     if any(getattr(layer, "_aggre_type", None) == "gcn" for layer in getattr(model, "layers", ())):
         raise NotImplementedError('%s: SAGEConv aggregator_type="gcn" is not built on the sharded step (DESIGN.md section 34)' % what)
+    if any(getattr(layer, "_aggre_type", None) == "lstm" for layer in getattr(model, "layers", ())):
+        raise NotImplementedError('%s: SAGEConv aggregator_type="lstm" (SAGELSTM) is not built on the sharded step (DESIGN.md section 37)'
+                                  % what)
 
 
 def allreduce_gradients_sum(model, scale, group=None):

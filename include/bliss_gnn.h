@@ -930,6 +930,42 @@ int bliss_sddmm_dot(const int32_t* src, const int32_t* dst, const int32_t* indpt
                     int64_t a_stride, const void* b, int64_t b_stride, const int32_t* arg, int64_t arg_stride, int32_t dim, int32_t mode,
                     void* out, int32_t out_fp32, void* stream);
 
+/* Recurrent neighbour aggregation, SAGEConv 'lstm' [DGL-recalled: the mailbox of each destination through nn.LSTM(D, D), the last
+ * hidden state kept], csrc/lstm.hip, DESIGN.md section 37.  The input projection is the caller's: p = bf16(h @ W_ih^T), bf16
+ * [>= n_src, 4 dim] (gate order i, f, g, o; column k dim + u).  For destination d with live in-edges e_0 .. e_{L-1} in row order:
+ *   pre_k = ((float(w_e) * float(p[src_e, k dim + u])) + (float(b_ih) + float(b_hh))) + bf16(h_{t-1}) . w_hh[k dim + u, :]
+ *   i, f, o = sigmoid(pre), g = tanh(pre_g); c_t = f c_{t-1} + i g; h_t = o tanh(c_t)      fp32; h_{-1} = c_{-1} = 0
+ *   out[d] = bf16(h_{L-1}); +0 for a row without live in-edges and for rows at or past the live destination count
+ * The recurrent product runs on MFMA (bf16 operands, fp32 accumulation); the operand h_{t-1} is h rounded to bf16, c and the
+ * gates stay fp32.  A workgroup owns bliss_lstm_tile_rows() consecutive destinations and walks to the tile's largest degree; a
+ * row whose degree is at or below the step is frozen.  w (bf16 [nnz]) NULL: w_e = 1; b_ih, b_hh (bf16 [4 dim]) NULL: zeros.
+ * w_hh bf16 [4 dim, dim]; strides in elements.  1 <= dim <= BLISS_LSTM_MAX_DIM, any dim (padded internally with zero weights).
+ * gates (fp32 [nnz, 4 dim]), cell (fp32 [nnz, dim]), hprev (bf16 [nnz, dim]): all three NULL (inference) or all three given
+ * (training): per live edge the gate activations, c_t and the operand bf16(h_{t-1}) (+0 at a row's first edge), 22 dim bytes
+ * per edge; hprev[live, nnz) is written as +0, gates and cell past the live count are left unwritten and are never read.
+ * Live counts: n_dst_dev ? min(*n_dst_dev, n_dst) : n_dst and nnz_dev ? min(*nnz_dev, nnz) : nnz; nothing is read for a row or
+ * edge at or past them.  nnz == 0 still writes the +0 rows.
+ * bliss_lstm_agg_bwd: the same tiles, t descending; dgate bf16 [nnz, 4 dim] = the gradient at the gate pre-activations per live
+ * edge (+0 on [live, nnz)), from gout bf16 [n_dst, dim] = d out and the saved state; d h_{t-1} = dgate_t . w_hh on MFMA, read
+ * from w_hh_t = w_hh^T, bf16 [dim, 4 dim].
+ * bliss_lstm_edge_reduce: dp[s] = bf16(sum over the out-edges e of s, ascending in the by-source index, float(w_e) *
+ * float(dgate[e])), dp bf16 [n_src, 4 dim], fp32 from +0, one wave per source row; sources without a live entry get +0.
+ * No float atomics: all three are bitwise reproducible.
+ * BLISS_EINVAL before any launch: a NULL required pointer (indptr, w_hh / w_hh_t, out / gout, t_indptr, dp; src and p, the saved
+ * state and dgate, t_edge when nnz > 0), a negative count, dim outside 1 .. BLISS_LSTM_MAX_DIM, a stride below the width, one or
+ * two of gates / cell / hprev. */
+#define BLISS_LSTM_MAX_DIM 256
+int bliss_lstm_tile_rows(void);
+int bliss_lstm_agg_fwd(const int32_t* indptr, const int32_t* src, const void* w, const void* p, int64_t p_stride, const void* w_hh,
+                       int64_t w_hh_stride, const void* b_ih, const void* b_hh, int32_t n_dst, const int32_t* n_dst_dev,
+                       const int32_t* nnz_dev, int32_t nnz, int32_t dim, void* out, int64_t out_stride, float* gates, float* cell,
+                       void* hprev, void* stream);
+int bliss_lstm_agg_bwd(const int32_t* indptr, const void* gout, int64_t gout_stride, const void* w_hh_t, int64_t w_hh_t_stride,
+                       const float* gates, const float* cell, int32_t n_dst, const int32_t* n_dst_dev, const int32_t* nnz_dev,
+                       int32_t nnz, int32_t dim, void* dgate, void* stream);
+int bliss_lstm_edge_reduce(const int32_t* t_indptr, const int32_t* t_edge, const void* w, const void* dgate, int32_t n_src,
+                           const int32_t* nnz_dev, int32_t nnz, int32_t dim, void* dp, int64_t dp_stride, void* stream);
+
 /* The element-wise tail of a hidden SAGE layer in one pass (model.py:321-333 and :318-320 of the next layer):
  * out = dropout_p(relu(a + b)) row by row, norm_out[row] = ||out[row,:]||_2 (bf16, may be NULL).  a, b, out: bf16
  * [n_rows, dim].  p_drop = 0 (evaluation) makes it deterministic.  ctr: device uint64[66], zero-initialised once: the
