@@ -130,10 +130,13 @@ __device__ __forceinline__ void rows_norm(const bf16_t* tile, int stride, int di
   }
 }
 
-// Stage the 64 rows of one operand in LDS.  The loads of all rows are independent and issued together: wave w takes rows
-// w, w + 8, ... (8 rounds), a lane the dwords lane, lane + 64, ... of its row, so ~40 loads per lane are in flight before
-// the first LDS store -- the gather is latency-bound (a random 1.2 KB row per id), not bandwidth-bound.  row_id[lr] = the
-// source row of tile row lr or -1 (beyond the true row count: zeros).  Optional copy-out of the staged rows.
+// Stage the TG_M rows of one operand in LDS.  Wave w takes rows w, w + 8, ... (4 of them), a lane the dwords lane,
+// lane + 64, ... of its row (8 at the largest K; beyond the row they repeat its last dword).  Even path: the 32 loads of a
+// lane are independent and leave as one batch before the first LDS store (see the opaque step below for what makes that
+// hold in the compiled code) -- the gather is latency-bound (a random 1.2 KB row per id), not bandwidth-bound, so one round
+// trip per operand instead of one per load is what counts.  The odd path (odd K, stride or base) loads under its masks, one
+// wait per load.  row_id[lr] = the source row of tile row lr or -1 (beyond the true row count: zeros).  Optional copy-out of
+// the staged rows.
 __device__ __forceinline__ void stage_rows(const bf16_t* __restrict__ a, long long a_stride, const int* row_id, int k,
                                            int row0, int m_bound, bf16_t* tile, int stride, bf16_t* __restrict__ copy, long long copy_stride,
                                            int wave, int lane) {
@@ -147,19 +150,31 @@ __device__ __forceinline__ void stage_rows(const bf16_t* __restrict__ a, long lo
 #pragma unroll
     for (int hb = 0; hb < 1; ++hb) {
       uint32_t v[HALF][MAXC];
+      int ids[HALF];
 #pragma unroll
       for (int q = 0; q < HALF; ++q) {
         const int id = row_id[(hb * HALF + q) * TG_WAVES + wave];
         const uint32_t* src = reinterpret_cast<const uint32_t*>(a + (long long)(id < 0 ? 0 : id) * a_stride);
+        ids[q] = id;
 #pragma unroll
         for (int j = 0; j < MAXC; ++j) {
-          // unconditional loads from clamped (always valid) addresses, masked afterwards: a load under a branch costs a full
-          // wait for everything outstanding, and these are meant to be in flight together
+          // raw loads from clamped (always valid) addresses; the mask comes in a loop of its own below
           const int c = lane + 64 * j;
-          const uint32_t x = src[c < dw ? c : dw - 1];
-          v[q][j] = (id >= 0 && c < dw) ? x : 0u;
+          v[q][j] = src[c < dw ? c : dw - 1];
         }
       }
+      // Every loaded register is made opaque here, after the last load has been issued.  Written as one expression
+      // (load, then select on the mask), the select became a branch, the load sank under it and every load was waited
+      // for alone: 32 dependent round trips per operand.  A load cannot sink below a statement that reads its result,
+      // so all HALF * MAXC loads leave back to back and the uses below wait for them in order, with counted waits.
+#pragma unroll
+      for (int q = 0; q < HALF; ++q)
+#pragma unroll
+        for (int j = 0; j < MAXC; ++j) asm volatile("" : "+v"(v[q][j]));
+#pragma unroll
+      for (int q = 0; q < HALF; ++q)
+#pragma unroll
+        for (int j = 0; j < MAXC; ++j) v[q][j] = (ids[q] >= 0 && lane + 64 * j < dw) ? v[q][j] : 0u;
 #pragma unroll
       for (int q = 0; q < HALF; ++q) {
         const int lr = (hb * HALF + q) * TG_WAVES + wave, r = row0 + lr;
@@ -199,11 +214,12 @@ __device__ __forceinline__ void stage_rows(const bf16_t* __restrict__ a, long lo
 #define TG_WROWS 256
 typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
 
-struct WRegs { uint4 v[TG_WROWS * TG_SLAB / 8 / TG_TPB]; };      // 8 x 16 bytes per thread
+struct WRegs { uint4 v[TG_WROWS * TG_SLAB / 8 / TG_TPB]; };      // 4 x 16 bytes per thread
 
 // full slab (all 64 k inside K, rows 4-byte aligned): no branch, no mask -- rows beyond N are CLAMPED to a real row (their
-// columns are computed from it and never stored), so every lane issues its eight 16-byte loads unconditionally and the
-// compiler can count them (a load under a branch made it wait for ALL outstanding loads at every use)
+// columns are computed from it and never stored), so every lane issues its four 16-byte loads unconditionally.  That alone
+// lets the compiler count them only where the loads outstanding are the same on every path into the use: w_first_slabs and
+// mma_product are written for that.
 __device__ __forceinline__ void w_slab_load_full(WRegs& g, const bf16_t* __restrict__ w, long long w_stride, int N, int slab, int tid) {
   const int part = tid & 7, k = slab * TG_SLAB + 8 * part;
 #pragma unroll
@@ -214,7 +230,37 @@ __device__ __forceinline__ void w_slab_load_full(WRegs& g, const bf16_t* __restr
     g.v[i] = make_uint4(q[0], q[1], q[2], q[3]);
   }
 }
-// the last, partial slab (or odd alignment): element-wise with masks
+// the last, partial slab where the full path's predicate holds and K is even (rows are whole dwords): every lane loads its
+// 4 x 4 dwords unconditionally, from element indices clamped into [0, K - 2] of its (clamped) row, and what lies at or
+// past K is zeroed afterwards.  One batch of 16 loads: the opaque step between the loads and the masks keeps the compiler
+// from sinking a load under its mask (as in stage_rows).
+__device__ __forceinline__ void w_slab_load_tail_even(WRegs& g, const bf16_t* __restrict__ w, long long w_stride, int N, int K, int slab, int tid) {
+  constexpr int NV = (int)(sizeof(g.v) / sizeof(g.v[0]));
+  const int part = tid & 7, k = slab * TG_SLAB + 8 * part;
+  uint32_t x[NV][4];
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    int n = i * (TG_TPB / 8) + (tid >> 3);
+    n = n < N ? n : N - 1;
+    const bf16_t* p = w + (long long)n * w_stride;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+      const int e = k + 2 * d;
+      x[i][d] = *reinterpret_cast<const uint32_t*>(p + (e < K ? e : K - 2));
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < NV; ++i)
+#pragma unroll
+    for (int d = 0; d < 4; ++d) asm volatile("" : "+v"(x[i][d]));
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+#pragma unroll
+    for (int d = 0; d < 4; ++d) x[i][d] = k + 2 * d < K ? x[i][d] : 0u;
+    g.v[i] = make_uint4(x[i][0], x[i][1], x[i][2], x[i][3]);
+  }
+}
+// the partial last slab of an odd K, or any slab of an oddly aligned W: element-wise under masks, one wait per load
 __device__ __forceinline__ void w_slab_load_tail(WRegs& g, const bf16_t* __restrict__ w, long long w_stride, int N, int K, int slab, int tid) {
   const int part = tid & 7, k = slab * TG_SLAB + 8 * part;
   for (int i = 0; i < (int)(sizeof(g.v) / sizeof(g.v[0])); ++i) {
@@ -231,6 +277,16 @@ __device__ __forceinline__ void w_slab_load_tail(WRegs& g, const bf16_t* __restr
 __device__ __forceinline__ int w_full_slabs(const bf16_t* w, long long w_stride, int K) {
   return ((w_stride % 2 == 0) && (((uintptr_t)w) % 4 == 0)) ? K / TG_SLAB : 0;
 }
+// The first two slabs of a product: requested by the caller before mma_product so that they arrive behind other work.  Both
+// sets are requested on one path, ga before gb (a W of a single full slab asks for slab 0 twice): mma_product's counted
+// waits rest on gb's loads being the younger ones on EVERY path that reaches them.
+__device__ __forceinline__ void w_first_slabs(WRegs& ga, WRegs& gb, const bf16_t* __restrict__ w, long long w_stride, int N, int K, int tid) {
+  const int nf = w_full_slabs(w, w_stride, K);
+  if (nf > 0) {
+    w_slab_load_full(ga, w, w_stride, N, 0, tid);
+    w_slab_load_full(gb, w, w_stride, N, nf > 1 ? 1 : 0, tid);
+  }
+}
 __device__ __forceinline__ void w_slab_store(const WRegs& g, bf16_t* wl, int tid) {
   const int part = tid & 7;
 #pragma unroll
@@ -245,12 +301,14 @@ __device__ __forceinline__ void mma_product(WRegs& ga, WRegs& gb, const bf16_t* 
                                             long long w_stride, int n0, int N, bf16_t* wl, int tid, int lane, f32x16_t acc[TG_NB]) {
   const int kp = k_pad16(k), r = lane & 31, h = lane >> 5;
   const int nslab = (kp + TG_SLAB - 1) / TG_SLAB;
-  auto multiply = [&](int sl) {
+  // full: all four 16-steps of the slab lie inside K (a literal at every call, so the test folds away and the four steps'
+  // LDS reads are issued together instead of one read, one wait, one MFMA at a time)
+  auto multiply = [&](int sl, bool full) {
     if (n0 < N) {
 #pragma unroll
       for (int st = 0; st < TG_SLAB / 16; ++st) {
         const int ks = sl * TG_SLAB + 16 * st;
-        if (ks < kp) {
+        if (full || ks < kp) {
           const bf16x8_t a = *reinterpret_cast<const bf16x8_t*>(tile + (size_t)r * stride + ks + 8 * h);
 #pragma unroll
           for (int nb = 0; nb < TG_NB; ++nb) {
@@ -262,31 +320,53 @@ __device__ __forceinline__ void mma_product(WRegs& ga, WRegs& gb, const bf16_t* 
     }
   };
   // Two register sets (ga: even slabs, gb: odd), two slabs in flight beside the one being multiplied; the caller has
-  // requested slabs 0 and 1.  Only full slabs run through this pipeline: their loads are unconditional, so the compiler's
-  // wait before a set's LDS store counts exactly that set's (older) loads.
+  // requested slabs 0 and 1.  Only full slabs run through this pipeline.  The wait before a set's LDS store must count
+  // that set's loads and leave the other set's younger ones outstanding, and the compiler can only count what is the
+  // same on every path into the store: with the prefetches under `if (sl + 2 < nfull)` it was not, and each store waited
+  // for everything.  So the steady loop refills both sets on every trip, without a condition, and the last one to three
+  // slabs, which refill less, are written out after it.
   const int nfull = w_full_slabs(w, w_stride, k);
-  for (int sl = 0; sl < nfull; sl += 2) {
+  auto step = [&](WRegs& g, int sl, int next) {           // next < 0: nothing left to request for this set
     __syncthreads();                                      // the previous slab has been consumed
-    w_slab_store(ga, wl, tid);
-    if (sl + 2 < nfull) w_slab_load_full(ga, w, w_stride, N, sl + 2, tid);
+    w_slab_store(g, wl, tid);
+    if (next >= 0) w_slab_load_full(g, w, w_stride, N, next, tid);
     __syncthreads();
-    multiply(sl);
-    if (sl + 1 < nfull) {
-      __syncthreads();
-      w_slab_store(gb, wl, tid);
-      if (sl + 3 < nfull) w_slab_load_full(gb, w, w_stride, N, sl + 3, tid);
-      __syncthreads();
-      multiply(sl + 1);
-    }
+    multiply(sl, true);
+  };
+  int sl = 0;
+  for (; sl + 3 < nfull; sl += 2) {
+    step(ga, sl, sl + 2);
+    step(gb, sl + 1, sl + 3);
   }
-  // the partial last slab (K not a multiple of 64) or an oddly aligned W: one slab at a time, masked element loads
-  for (int sl = nfull; sl < nslab; ++sl) {
+  const int left = nfull - sl;
+  if (left == 3) {
+    step(ga, sl, sl + 2);
+    step(gb, sl + 1, -1);
+    step(ga, sl + 2, -1);
+  } else if (left == 2) {
+    step(ga, sl, -1);
+    step(gb, sl + 1, -1);
+  } else if (left == 1) {
+    step(ga, sl, -1);
+  }
+  // the partial last slab (K not a multiple of 64) or an oddly aligned W: one slab at a time
+  const bool dword_tail = nfull * TG_SLAB < kp && (k % 2 == 0) && (w_stride % 2 == 0) && (((uintptr_t)w) % 4 == 0);
+  if (dword_tail) {
     WRegs t;
-    w_slab_load_tail(t, w, w_stride, N, k, sl, tid);
+    w_slab_load_tail_even(t, w, w_stride, N, k, nfull, tid);
     __syncthreads();
     w_slab_store(t, wl, tid);
     __syncthreads();
-    multiply(sl);
+    multiply(nfull, false);
+  } else {
+    for (int s = nfull; s < nslab; ++s) {
+      WRegs t;
+      w_slab_load_tail(t, w, w_stride, N, k, s, tid);
+      __syncthreads();
+      w_slab_store(t, wl, tid);
+      __syncthreads();
+      multiply(s, false);
+    }
   }
 }
 
@@ -347,9 +427,7 @@ __device__ __forceinline__ void tile_gemm_body(const TileGemm& p, bf16_t* lds, i
       for (int c0 = 0; c0 < K; c0 += TG_PANEL) {
         // every fast-path predicate below is taken on the panel's own base pointer and width
         const int pw = K - c0 < TG_PANEL ? K - c0 : TG_PANEL, st = lds_stride(pw);
-        const int nf = w_full_slabs(w + c0, w_stride, pw);
-        if (nf > 0) w_slab_load_full(ga, w + c0, w_stride, N, 0, tid);
-        if (nf > 1) w_slab_load_full(gb, w + c0, w_stride, N, 1, tid);
+        w_first_slabs(ga, gb, w + c0, w_stride, N, pw, tid);
         __syncthreads();                                    // every wave has multiplied the previous panel (first panel: row_id is set)
         stage_rows(a + c0, a_stride, row_id + op * TG_M, pw, row0, p.m_bound, lds, st, (op == 0 && p.a_copy) ? p.a_copy + c0 : nullptr,
                    p.copy_stride, wave, lane);
@@ -366,9 +444,7 @@ __device__ __forceinline__ void tile_gemm_body(const TileGemm& p, bf16_t* lds, i
     bf16_t* wl = lds + (size_t)TG_M * (s1 + s2);              // the W slab behind the staged rows
     // the first two W slabs depend on nothing: requested now, they arrive while the rows are gathered
     {
-      const int nf = w_full_slabs(p.w1, p.w1_stride, p.k1);
-      if (nf > 0) w_slab_load_full(ga, p.w1, p.w1_stride, N, 0, tid);
-      if (nf > 1) w_slab_load_full(gb, p.w1, p.w1_stride, N, 1, tid);
+      w_first_slabs(ga, gb, p.w1, p.w1_stride, N, p.k1, tid);
     }
     if (tid < TG_M) {
       const int r = row0 + tid;
@@ -386,9 +462,7 @@ __device__ __forceinline__ void tile_gemm_body(const TileGemm& p, bf16_t* lds, i
       for (int i = 0; i < 16; ++i) acc[m][i] = 0.f;
     if (!(dbg & 2)) mma_product(ga, gb, t1, s1, p.k1, p.w1, p.w1_stride, n0, N, wl, tid, lane, acc);
     if (p.k2) {
-      const int nf = w_full_slabs(p.w2, p.w2_stride, p.k2);
-      if (nf > 0) w_slab_load_full(ga, p.w2, p.w2_stride, N, 0, tid);
-      if (nf > 1) w_slab_load_full(gb, p.w2, p.w2_stride, N, 1, tid);
+      w_first_slabs(ga, gb, p.w2, p.w2_stride, N, p.k2, tid);
       mma_product(ga, gb, t2, s2, p.k2, p.w2, p.w2_stride, n0, N, wl, tid, lane, acc);
     }
   }
@@ -441,7 +515,9 @@ __device__ __forceinline__ void bump_drop_counter(const TileGemm& p0, const Tile
   }
 }
 
-__global__ void __launch_bounds__(TG_TPB) k_tile_gemm(TileGemm p0, TileGemm p1, int n_sets, int dbg) {
+// (waves_per_eu(4): two workgroups per CU is what the 330-workgroup input layer needs to run in one round, so the register
+// allocator is held to the 128 VGPRs of that occupancy step instead of drifting one past it; it does so without scratch)
+__global__ void __launch_bounds__(TG_TPB) __attribute__((amdgpu_waves_per_eu(4))) k_tile_gemm(TileGemm p0, TileGemm p1, int n_sets, int dbg) {
   extern __shared__ __attribute__((aligned(16))) bf16_t tg_lds[];
   __shared__ int row_id[2 * TG_M];
   if (dbg & 8) return;
